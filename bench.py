@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the GCG hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--rehearse]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--rehearse] [--dump-outputs DIR]
 
 With --gpus N > 1 and no RANK in the environment bench.py starts the N ranks ITSELF — fresh child processes running
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, spawned before torch or the GPU is touched — relays
@@ -37,6 +37,9 @@ torch.distributed only hands rank 0's RCCL id to the other ranks and synchronise
              under OPS_USE_OMP), all host cores, on BASELINE config 1 (Lap3D 50^3, nev 20, block 20) — with the
              GPU's time on that SAME config beside it (gpu_same_config); kind "port" = our C restatement when the
              compiled reference is absent.
+  ms_per_step = milliseconds per timed step (elapsed / K).
+With --dump-outputs DIR the last timed solve's result is written to DIR/*.npy (dump_outputs); the inputs are fixed by the
+arguments (generated matrix, seeded device start blocks), so two builds can be compared output for output.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -85,7 +88,11 @@ def parse():
     ap.add_argument("--amg-smooth", default=None, help="CG smoothing iterations before and after the coarse correction: finest level, coarser levels "
                                                        "(default 3,4; config c5: 8,24 — the coarse levels carry the projected atoms, 2000 outlying eigenvalues, "
                                                        "and must be smoothed long enough to resolve them: profiles/r05_amg/13_...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed solve returned to DIR/<name>.npy (float64; see dump_outputs)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.config == "c4":
         a.nev, a.block, a.nevmax = 200, 128, 400
     if a.config == "c5":
@@ -460,6 +467,40 @@ def cpu_like_for_like(args, hip):
                                 "max_rel_diff_vs_cpu_reference": float(np.max(np.abs(ev_g[:k] - ev[:k]) / np.abs(ev[:k]))) if k > 0 else None}}
 
 
+def dump_outputs(path, hip, last, nloc, rank, world, dist):
+    """--dump-outputs DIR: what the last timed solve handed its caller (run_gcg: eigenvalues, eigenvector block, counts), written
+    by rank 0 as float64 arrays, a few MB in all:
+      eigenvalues.npy       the nevConv converged eigenvalues
+      eigenvectors.npy      the converged eigenvectors at a fixed, seeded sample of at most 4096 global rows (rows x nevConv,
+                            the matrix's own row order whatever the back-end reordered)
+      eigenvector_rows.npy  the global indices of those rows, ascending
+      counts.npy            [nevConv, numIter]
+    Collective over the ranks (each contributes its own rows of the sample)."""
+    import numpy as np
+    ev, res, evec = last[0], last[1], last[2]
+    k = int(res.nevConv)
+    sizes = [int(nloc)]
+    if world > 1:
+        sizes = [None] * world
+        dist.all_gather_object(sizes, int(nloc))
+    r0, n = sum(sizes[:rank]), sum(sizes)
+    rows = np.sort(np.random.default_rng(20240601).choice(n, min(n, 4096, max(1, (32 << 20) // (8 * max(1, k)))), replace=False))
+    mine = rows[(rows >= r0) & (rows < r0 + nloc)] - r0
+    X = np.zeros((mine.size, k))
+    for c in range(0, k, 4):                  # four columns of every local row at a time through the host
+        X[:, c:c + 4] = hip.mv_to_numpy(evec, nloc, c, min(k, c + 4))[mine]
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, X)
+        X = np.concatenate(parts)             # ranks hold ascending row ranges
+    if rank == 0:
+        os.makedirs(path, exist_ok=True)
+        np.save(os.path.join(path, "eigenvalues.npy"), np.array(ev[:k], dtype=np.float64))
+        np.save(os.path.join(path, "eigenvectors.npy"), X)
+        np.save(os.path.join(path, "eigenvector_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, "counts.npy"), np.array([k, res.numIter], dtype=np.float64))
+
+
 def slab_cut_planes(planes, world, levels):
     """Planes per cut unit for row slabs of a grid matrix behind BlockAMG with `levels` levels (1 without it)."""
     unit = 1
@@ -688,8 +729,9 @@ def main():
     barrier()
     t0 = time.perf_counter()
     conv_total, iters, last = 0, 0, None
+    keep_last = c5 or c3 or args.dump_outputs is not None
     for step in range(args.steps):
-        if (c5 or c3) and step == args.steps - 1:      # keep the last solve's vectors: the parity guard recomputes their residuals
+        if keep_last and step == args.steps - 1:       # keep the last solve's vectors: the parity guard recomputes their residuals
             if last is not None and len(last) > 2:
                 hip.ops.mv_destroy(last[2], args.nevmax)
             last = run_gcg(hip.ops_handle, mat, matB, solver_args, flag=1, keep_evec=True)
@@ -704,6 +746,10 @@ def main():
         t = torch.tensor([elapsed], device="cpu" if rehearse else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, hip, last, A.nrows, rank, world, dist)
+        if not (c5 or c3):
+            hip.ops.mv_destroy(last[2], args.nevmax)
 
     # HIP-event intervals the back-end recorded on its own stream, by kind: 0 = MatDotMultiVec products (K1, plain or
     # with the column sums), 2 / 3 = first / second pass of a block-CG iteration (the product recomputed, never stored)
