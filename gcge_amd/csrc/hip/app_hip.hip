@@ -1272,7 +1272,7 @@ extern "C" int gcge_hip_cg_start_scaled_mv(void* mat, void** x, int xc0, const d
   return 0;
 }
 
-// ---- two steps of a V-cycle in one sweep each (GCGE_SetBlockAMGFusions, include/gcge_solver.h; csrc/host/lin_sol.c) ------------
+// ---- two steps of a V-cycle in one sweep each (GCGE_BACKEND.amg_residual / amg_prolong_add; csrc/host/lin_sol.c) ----------
 // r[:, rc0:rc0+m) = b[:, bc0:bc0+m) - A x[:, xc0:xc0+m): the start sweep of the block CG (kernel MODE 5) with ONE store — the
 // product is rounded on its own and then subtracted from b, exactly what MatDotMultiVec + MultiVecAxpby(1, b, -1, r) leave
 // (reference src/ops_lin_sol.c:596-606): 3 block streams instead of 5.  Pattern matrices only; 0 = declined, nothing touched.
@@ -1342,7 +1342,7 @@ static int HIP_AmgProlongAdd(void* matP, void** xc, int c0, void** xf, int f0, i
 }
 
 // b[:, bc0:bc0+m) = x[:, xc0:xc0+m) diag(scale): the right-hand sides (lambda_j + sigma) x_j of the GCG driver's W systems for a
-// BlockAMG that takes them as scale factors (GCGE_SetBlockAMGFormRhs) — one read, one write, each product rounded once like the
+// BlockAMG that takes them as scale factors (GCGE_BACKEND.amg_form_rhs) — one read, one write, each product rounded once like the
 // column scaling after a copy (MatDotMultiVec(B = NULL) + MultiVecLinearComb: reference src/ops_eig_sol_gcg.c:560-577)
 __global__ __launch_bounds__(256) void scaled_copy_kernel(long nrows, const double* __restrict__ x, long ldx, double* __restrict__ b, long ldb,
     int m2, const double* __restrict__ scale, int tpr) {
@@ -1537,19 +1537,22 @@ extern "C" void OPS_HIP_Set(struct OPS_* ops) {
   ops->MultiVecAxpby            = HIP_MultiVecAxpby;
   ops->MultiVecLinearComb       = HIP_MultiVecLinearComb;
   ops->MatDotMultiVec           = HIP_MatDotMultiVec;
-  GCGE_SetResidualHook(HIP_ResidualSq, (void*)HIP_MatDotMultiVec);   /* used by our GCG driver for this table only */
-  // panel updates work row by row on the row-major blocks (lincomb_mfma.hip: a block / wave reads only the rows it
-  // writes, and writes them after its last read): one panel of <= 128 output columns may be updated in place
-  GCGE_SetInplaceLinearComb((void*)HIP_MultiVecLinearComb, 128);
-  {   // K7 on the device for the projected matrices where the host solver dominates an outer iteration (eig_device.hip)
-    GCGE_SetSymEigHook(gcge_hip_symeig, 192, (void*)HIP_MultiVecLinearComb);
-  }
   ops->MatTransDotMultiVec      = HIP_MatTransDotMultiVec;
   ops->MultiVecQtAP             = HIP_MultiVecQtAP;
-  // the hierarchy behind BlockAMG (src/ops.h:134-139; multigrid.hip) and the fused device CG as its smoother for THIS table
+  // the hierarchy behind BlockAMG (src/ops.h:134-139; multigrid.hip)
   ops->MultiGridCreate          = gcge_hip_multigrid_create;
   ops->MultiGridDestroy         = gcge_hip_multigrid_destroy;
-  GCGE_SetBlockAMGSmoother(gcge_hip_amg_smoother_setup, gcge_hip_amg_smoother_residual, (void*)HIP_MatDotMultiVec);
-  GCGE_SetBlockAMGFusions(HIP_AmgResidual, HIP_AmgProlongAdd, (void*)HIP_MatDotMultiVec);   // r = b - A x and x += P e as one sweep each
-  GCGE_SetBlockAMGFormRhs(HIP_AmgFormRhs, (void*)HIP_MatDotMultiVec);                         // b = x diag(scale) in one sweep
+  // what this table offers the solver stack beyond its slots (GCGE_BACKEND, include/gcge_ops.h)
+  GCGE_BACKEND be = {};
+  be.residual_sq = HIP_ResidualSq;
+  // panel updates work row by row on the row-major blocks (lincomb_mfma.hip: a block / wave reads only the rows it
+  // writes, and writes them after its last read): one panel of <= 128 output columns may be updated in place
+  be.inplace_lincomb_cols = 128;
+  // K7 on the device for the projected matrices where the host solver dominates an outer iteration (eig_device.hip)
+  be.symeig = gcge_hip_symeig; be.symeig_min_n = 192;
+  be.amg_residual = HIP_AmgResidual;          // r = b - A x and x += P e as one sweep each
+  be.amg_prolong_add = HIP_AmgProlongAdd;
+  be.amg_form_rhs = HIP_AmgFormRhs;           // b = x diag(scale) in one sweep
+  gcge_hip_bpcg_backend(&be);                 // the fused device CG: BlockAMG's smoother, and the solver of unformed b = x diag(scale)
+  GCGE_SetBackend(ops, &be);
 }

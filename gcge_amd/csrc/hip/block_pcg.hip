@@ -29,7 +29,7 @@
 // ops_lin_sol.c:317,365 happens); retired columns get alpha = 0 / keep-flag so their
 // x, r, p are bit-for-bit untouched, as if they had been skipped.
 //
-// A shift published by the caller (GCGE_SetLinearSolverShift: our GCG does it for -gcge_compW_cg_shift, the
+// A shift published by the caller (GCGE_LINSOL_ARGS: our GCG does it for -gcge_compW_cg_shift, the
 // reference leaves sigma to a user-defined solver, ops_eig_sol_gcg.c:584-618) turns the operator into
 // A + sigma B (second SpMM + axpy per application; B == NULL: + sigma I).
 //
@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256) void cg_update_p_implicit(long nrows, const do
   }
 }
 
-// Start of a solve whose right-hand sides are b = x diag(scale) (GCGE_SetLinearSolverRhsScale) on a matrix whose product is stored:
+// Start of a solve whose right-hand sides are b = x diag(scale) (GCGE_LINSOL_ARGS.rhs_scale) on a matrix whose product is stored:
 // after w = A x, ONE sweep forms r = x diag(scale) - w, writes it as r and as p0 and sums r.r per column — instead of copying x to b,
 // scaling b, r = b - w, the column sums and the copy p0 = r (10 block streams; here 4).
 template <int UNR>
@@ -567,9 +567,9 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
   const int n = gcge_hip_mv_nrows(mv_x);
   if (gcge_hip_mv_nrows(mv_b) != n) { fprintf(stderr, "HIP_BlockPCG: b and x have different row counts\n"); abort(); }
   bpcg_shape(s, n, nrhs, mv_x, ops);
-  // operator: A, or A + sigma B when the caller published a shift (GCGE_SetLinearSolverShift)
-  double sigma = 0.0; void* matB = nullptr;
-  GCGE_GetLinearSolverShift(&sigma, &matB);
+  // what the caller published for this call (include/gcge_ops.h); operator: A, or A + sigma B when it published a shift
+  const GCGE_LINSOL_ARGS args = *GCGE_GetLinearSolverArgs();
+  const double sigma = args.sigma; void* const matB = args.matB;
   if (sigma != 0.0 && matB != nullptr && s->mv_ws[3] == nullptr) ops->MultiVecCreateByMultiVec(&s->mv_ws[3], s->ws_cols, mv_x, ops);
   // y[:, ys:ys+k) = (A + sigma B) x[:, xs:xs+k); dots != NULL: dots[j] = x_j . y_j (local part)
   auto apply = [&](void** xin, int xs, void** yout, int ys, int k, double* dots, double* yy = nullptr) {
@@ -609,10 +609,10 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
   std::vector<double> norm_b(nrhs), rho1(nrhs), rho2(nrhs), pTw(nrhs), init_res(nrhs), last_res(nrhs), coef(nrhs);
   std::vector<int> active(nrhs), flag(nrhs);
   int st2[2], en2[2];
-  // The caller may have declared b = x diag(scale) without forming it (GCGE_SetLinearSolverRhsScale: our GCG driver's
-  // systems A w = (lambda + sigma) x, started from w = x).  The one-sweep start below then takes the scale factors
+  // The caller may have declared b = x diag(scale) without forming it (args.rhs_scale: our GCG driver's systems
+  // A w = (lambda + sigma) x, started from w = x).  The one-sweep start below then takes the scale factors
   // and neither reads nor needs b; every other route forms b first, here, on the device.
-  const double* rhs_scale = GCGE_GetLinearSolverRhsScale();
+  const double* rhs_scale = args.rhs_scale;
   bool p0_done = false;
   // Will the iteration rebuild its residual from the directions (device-scalar loop of the recompute form, MODE 7 below)?  Then the
   // block r is never read, and the one-sweep starts store p0 alone (r and p0 name the same block: single store, 3 block streams
@@ -671,12 +671,12 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
     ops->MultiVecInnerProd('D', mv_b, mv_b, 0, st2, en2, norm_b.data(), 1, ops);
     for (int i = 0; i < nrhs; ++i) norm_b[i] = sqrt(norm_b[i]);
   } else if (0 == strcmp(s->tol_type, "user")) {
-    // src/ops_lin_sol.c:186-192: the caller's scales, |lambda_j + sigma| from the GCG driver (GCGE_SetLinearSolverUserScale)
-    int nsc = 0;
-    const double* usc = GCGE_GetLinearSolverUserScale(&nsc);
+    // src/ops_lin_sol.c:186-192: the caller's scales, |lambda_j + sigma| from the GCG driver (args.user_scale)
+    const int nsc = args.user_scale != nullptr ? args.n_user_scale : 0;
+    const double* usc = args.user_scale;
     if (usc == nullptr || nsc < nrhs) {
       fprintf(stderr, "HIP_BlockPCG: tol_type \"user\" but the caller published %d scales for %d right-hand sides "
-                      "(GCGE_SetLinearSolverUserScale, include/gcge_ops.h)\n", nsc, nrhs);
+                      "(GCGE_LINSOL_ARGS.user_scale, include/gcge_ops.h)\n", nsc, nrhs);
       abort();
     }
     for (int i = 0; i < nrhs; ++i) norm_b[i] = fabs(usc[i]);
@@ -738,10 +738,10 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
     void** slots[17]; int R = R0;                            // ring slots; 1: x is updated in every iteration
     for (int q = 0; q < R0; ++q) slots[q] = R0 > 1 ? s->ring[q] : s->mv_ws[1];
     if (recompute && R < 16 && getenv("GCGE_CG_NO_W_SLOT") == nullptr) slots[R++] = s->mv_ws[2];
-    // ... and the blocks the caller declared idle for the duration of the solve (GCGE_SetLinearSolverIdleBlocks), where
+    // ... and the blocks the caller declared idle for the duration of the solve (args.idle_blocks), where
     // they have the shape of the ring's own blocks (same rows, same leading dimension, 16-byte aligned, room for the halo)
     if (recompute && getenv("GCGE_CG_NO_IDLE_SLOTS") == nullptr) {
-      int nidle = 0; void*** idle = GCGE_GetLinearSolverIdleBlocks(&nidle);
+      const int nidle = args.idle_blocks != nullptr ? args.n_idle : 0; void*** idle = args.idle_blocks;
       for (int q = 0; q < nidle && R < 16; ++q) {
         void** hb = idle[q];
         if (hb == nullptr || hb == mv_x || hb == mv_b || gcge_hip_mv_nrows(hb) != n || gcge_hip_mv_ncols(hb) < nrhs) continue;
@@ -1063,7 +1063,7 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
 // C-ABI: install the fused solver (GCG: pass flag = 1 to the harness / -gcge_user_defined_multi_lin_sol 1)
 extern "C" void gcge_hip_bpcg_setup(struct OPS_* ops, int max_iter, double rate, double tol, const char* tol_type) {
   // "user": the column scales BlockPCG finds in its scalar scratch (src/ops_lin_sol.c:186-192) are read from
-  // GCGE_GetLinearSolverUserScale at solve time (the GCG driver publishes lambda_j + sigma there); anything else is refused
+  // GCGE_LINSOL_ARGS.user_scale at solve time (the GCG driver publishes lambda_j + sigma there); anything else is refused
   if (tol_type != nullptr && strcmp(tol_type, "abs") != 0 && strcmp(tol_type, "rel") != 0 && strcmp(tol_type, "user") != 0) {
     fprintf(stderr, "gcge_hip_bpcg_setup: tol_type \"%s\" is not one of \"abs\", \"rel\", \"user\"\n", tol_type);
     abort();
@@ -1072,7 +1072,6 @@ extern "C" void gcge_hip_bpcg_setup(struct OPS_* ops, int max_iter, double rate,
   strncpy(g_bpcg.tol_type, tol_type ? tol_type : "abs", 7); g_bpcg.tol_type[7] = 0;
   ops->multi_linear_solver_workspace = (void*)&g_bpcg;
   ops->MultiLinearSolver = HIP_BlockPCG;
-  GCGE_SetRhsScaleCapability((void*)HIP_BlockPCG);   // b = x diag(scale) need not be formed (see HIP_BlockPCG_run)
 }
 // Optional: create the solver's blocks (r, p, w and the ring of direction slots) NOW, for systems with the rows of `mv_like` and up
 // to `ncols` right-hand sides, instead of inside the first solve.  The counterpart of the reference's EigenSolverCreateWorkspace /
@@ -1082,10 +1081,8 @@ extern "C" void gcge_hip_bpcg_setup(struct OPS_* ops, int max_iter, double rate,
 extern "C" int gcge_hip_bpcg_prepare(struct OPS_* ops, void* mat, void** mv_like, int ncols) {
   if (ops == nullptr || ops->MultiLinearSolver != HIP_BlockPCG || mv_like == nullptr || ncols <= 0) return -1;
   HipBpcg* s = (HipBpcg*)ops->multi_linear_solver_workspace;
-  double sigma = 0.0; void* matB = nullptr;
-  GCGE_GetLinearSolverShift(&sigma, &matB);
   bpcg_shape(s, gcge_hip_mv_nrows(mv_like), ncols, mv_like, ops);
-  bpcg_ring(s, mat, mv_like, sigma, ops);
+  bpcg_ring(s, mat, mv_like, GCGE_GetLinearSolverArgs()->sigma, ops);
   GCGE_HIP_CHECK(hipStreamSynchronize((hipStream_t)gcge_hip_stream()));
   return s->ring_len;
 }
@@ -1109,12 +1106,19 @@ extern "C" void gcge_hip_bpcg_column_stats(long* col_iters, long* active_col_ite
   if (active_col_iters) *active_col_iters = g_bpcg.active_col_iters;
 }
 extern "C" long gcge_hip_bpcg_surplus_iters(void) { return g_bpcg.surplus_iters; }
-// the fused CG as the smoother of BlockAMG for the HIP table (GCGE_SetBlockAMGSmoother, registered by OPS_HIP_Set): same stopping
-// rules as MultiLinearSolverSetup_BlockPCG, its own blocks per level (parked sets above)
-extern "C" void gcge_hip_amg_smoother_setup(int max_iter, double rate, double tol, const char* tol_type, struct OPS_* ops) {
+// the fused CG as the smoother of BlockAMG for the HIP table: same stopping rules as MultiLinearSolverSetup_BlockPCG, its own
+// blocks per level (parked sets above)
+static void amg_smoother_setup(int max_iter, double rate, double tol, const char* tol_type, struct OPS_* ops) {
   gcge_hip_bpcg_setup(ops, max_iter, rate, tol, tol_type);
 }
-extern "C" double gcge_hip_amg_smoother_residual(struct OPS_* ops) { (void)ops; return g_bpcg.residual; }
+static double amg_smoother_residual(struct OPS_* ops) { (void)ops; return g_bpcg.residual; }
+// this file's part of the HIP table's back-end record (OPS_HIP_Set): the smoother above, and the solver itself as the one that
+// takes b = x diag(scale) unformed (see HIP_BlockPCG_run)
+extern "C" void gcge_hip_bpcg_backend(GCGE_BACKEND* be) {
+  be->amg_smoother_setup = amg_smoother_setup;
+  be->amg_smoother_residual = amg_smoother_residual;
+  be->scaled_rhs_solver = HIP_BlockPCG;
+}
 extern "C" void gcge_hip_bpcg_release(struct OPS_* ops) {
   for (int i = 0; i < g_nparked; ++i) bpcg_destroy_set(&g_parked[i], ops);
   g_nparked = 0;

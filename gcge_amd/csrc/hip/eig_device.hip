@@ -15,8 +15,8 @@
 //      independent, one lane per row carries the running column through a whole sweep (1 load + 1 store per rotation,
 //      the (c, s) pairs arrive through scalar loads).
 //   5. Ascending sort on the host, columns gathered while they are copied back.
-// Hooked into the GCG driver of libgcge_host.so through GCGE_SetSymEigHook (include/gcge_ops.h); OPS_HIP_Set registers
-// it for N >= 192 (below that the launch count, ~4 N, costs more than the host solver).  The reference's own stack
+// Hooked into the GCG driver of libgcge_host.so through the back-end record (GCGE_BACKEND.symeig, include/gcge_ops.h); OPS_HIP_Set
+// offers it for N >= 192 (below that the launch count, ~4 N, costs more than the host solver).  The reference's own stack
 // keeps calling its LAPACK.
 #include <hip/hip_runtime.h>
 #include <float.h>

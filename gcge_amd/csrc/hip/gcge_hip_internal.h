@@ -89,11 +89,11 @@ struct GcgePerm { int n; int* perm; int* iperm; int identity; long refs; unsigne
 extern "C" struct GcgePerm* gcge_hip_perm_acquire(struct GcgePerm* p);      // ++refs (NULL passes through)
 extern "C" void gcge_hip_perm_release(struct GcgePerm* p);
 extern "C" void gcge_hip_halo_native_free(struct GCGE_HIP_MAT_* A);
-// multigrid.hip: the MultiGridCreate / MultiGridDestroy slots of OPS_HIP_Set and the block-CG smoother it registers for BlockAMG
+// multigrid.hip: the MultiGridCreate / MultiGridDestroy slots of OPS_HIP_Set
 extern "C" void gcge_hip_multigrid_create(void*** A_array, void*** B_array, void*** P_array, int* num_levels, void* A, void* B, struct OPS_* ops);
 extern "C" void gcge_hip_multigrid_destroy(void*** A_array, void*** B_array, void*** P_array, int* num_levels, struct OPS_* ops);
-extern "C" void gcge_hip_amg_smoother_setup(int max_iter, double rate, double tol, const char* tol_type, struct OPS_* ops);
-extern "C" double gcge_hip_amg_smoother_residual(struct OPS_* ops);
+// block_pcg.hip: the fused CG's part of the back-end record OPS_HIP_Set registers (the BlockAMG smoother, the scaled-rhs solver)
+extern "C" void gcge_hip_bpcg_backend(GCGE_BACKEND* be);
 // A column scaling the slots hold back (column-wise Gram-Schmidt, app_hip.hip) is applied now.  First statement of every EXPORTED
 // raw kernel that takes device pointers: the caller may have fetched its pointer before the scaling was held back.
 extern "C" void gcge_hip_apply_pending(void);

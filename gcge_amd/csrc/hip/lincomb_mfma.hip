@@ -23,7 +23,7 @@
 // clamped X row only feeds output rows that are never stored.
 //
 // In-place use is safe, with disjoint column ranges (ops_orth.c:70,90,253) and with the output columns INSIDE the
-// input range (X = X R^-1, P = V[:, N..W) coef; declared to the solver stack by GCGE_SetInplaceLinearComb): a block /
+// input range (X = X R^-1, P = V[:, N..W) coef; declared to the solver stack by GCGE_BACKEND.inplace_lincomb_cols): a block /
 // wave reads only the rows it writes (rows past the end are clamped to the last row, but feed output rows that are
 // never stored) and stores them after its last read of them; x is therefore NOT __restrict__.
 // Roofline: 2 n k m flops (FP64 MFMA) vs 8 n (k + m [+ m]) bytes.

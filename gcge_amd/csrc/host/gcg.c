@@ -108,9 +108,8 @@ static int CheckConvergence(Ctx *c, int numCheck, int *offset)
 	struct OPS_ *ops = c->ops; GCGSolver *p = c->p;
 	double *res = c->scratch, *tol = p->tol, *ev = c->ss_eval + c->startN;
 	int s[2], e[2], idx, state, nun, nevConv; double t0 = ops->GetWtime();
-	GCGE_RESIDUAL_FN hook = GCGE_GetResidualHook((void*)ops->MatDotMultiVec);
-	if (numCheck > 0 && hook != NULL && getenv("GCGE_NO_RESIDUAL_HOOK") == NULL &&
-			hook(c->A, c->B, c->ritz, c->startN, c->startN + numCheck, ev, res)) {
+	GCGE_RESIDUAL_FN hook = GCGE_BackendOf(ops).residual_sq;
+	if (numCheck > 0 && hook != NULL && hook(c->A, c->B, c->ritz, c->startN, c->startN + numCheck, ev, res)) {
 		GCGE_COMM *comm = GCGE_GetComm();          /* the back-end summed over its own rows */
 		if (comm != NULL) comm->allreduce_sum(res, numCheck, comm->ctx);
 		for (idx = 0; idx < numCheck; ++idx) res[idx] = sqrt(res[idx]);
@@ -197,7 +196,7 @@ static void ComputeP(Ctx *c, int *offset)
 	c->startP = sP + c->sizeC; c->endP = eP + c->sizeC; c->sizeP = c->endP - c->startP;
 	/* P = V[:, N..W) * coef, staged through a work block */
 	coef = evec + (size_t)N * (c->sizeX - c->sizeC);
-	if (c->sizeP <= GCGE_InplaceLinearCombCols((void*)ops->MultiVecLinearComb) &&
+	if (c->sizeP <= GCGE_BackendOf(ops).inplace_lincomb_cols &&
 			c->startP >= c->startN && c->endP <= c->endW) {
 		/* the P columns lie inside [N, W): a back-end that works row by row writes them in place */
 		s[0] = c->startN; e[0] = c->endW; s[1] = c->startP; e[1] = c->endP;
@@ -231,14 +230,14 @@ static void ComputeW(Ctx *c, int *offset)
 		sigma = -c->ss_eval[c->sizeC] + (c->ss_eval[c->sizeC + 1] - c->ss_eval[c->sizeC]) * 0.01;
 	p->sigma = sigma = p->compW_cg_shift + sigma;
 	/* (the reference asserts here that auto-shift and a user-defined solver are not combined, ops_eig_sol_gcg.c:497: its
-	 *  hook hands the solver A only.  Ours publishes sigma and B through GCGE_SetLinearSolverShift below, so a solver
+	 *  hook hands the solver A only.  Ours publishes sigma and B with the solver call below (GCGE_LINSOL_ARGS), so a solver
 	 *  installed behind flag 1 that reads them — the fused device CG does — takes the automatic shift like a fixed one;
 	 *  flag 2 solvers still get A alone and are refused) */
 	assert(p->compW_cg_auto_shift == 0 || p->user_defined_multi_linear_solver != 2);
 
-	/* B == NULL and a solver that takes "b = x diag(scale)" (GCGE_SetRhsScaleCapability): b is not formed */
-	const int scaled_rhs = p->user_defined_multi_linear_solver == 1 && c->B == NULL &&
-			GCGE_HasRhsScaleCapability((void*)ops->MultiLinearSolver);
+	/* B == NULL and a solver that takes "b = x diag(scale)": b is not formed */
+	const int scaled_rhs = p->user_defined_multi_linear_solver == 1 && c->B == NULL && GCGE_SolverTakesScaledRhs(ops);
+	GCGE_LINSOL_ARGS args = {0};
 	c->startW = c->endP;
 	for (idx = 0; idx < offset[0]; ++idx) {
 		int lo = offset[idx * 2 + 1], hi = offset[idx * 2 + 2], len = hi - lo;
@@ -274,20 +273,18 @@ static void ComputeW(Ctx *c, int *offset)
 					sigma != 0.0 ? MatDotMultiVecShift : NULL, ops);
 		}
 	}
-	if (p->user_defined_multi_linear_solver == 1) GCGE_SetLinearSolverShift(sigma, c->B);
-	/* the column scales (lambda_j + sigma): what BlockPCG finds at the start of its scalar scratch for the "user"
-	 * tolerance type (ops_lin_sol.c:186-192); a solver behind flag 1 has no such scratch and reads them here */
-	if (p->user_defined_multi_linear_solver == 1) GCGE_SetLinearSolverUserScale(scales, blk);
-	if (scaled_rhs) GCGE_SetLinearSolverRhsScale(scales);
-	if (p->user_defined_multi_linear_solver == 1) {   /* the work blocks are idle until the orthonormalisation below */
+	/* a solver behind flag 1 gets the shift, the column scales (lambda_j + sigma: what BlockPCG finds at the start of its
+	 * scalar scratch for the "user" tolerance type, ops_lin_sol.c:186-192) and the work blocks, idle until the
+	 * orthonormalisation below */
+	if (p->user_defined_multi_linear_solver == 1) {
 		cg_ws[0] = c->ws0; cg_ws[1] = c->ws1; cg_ws[2] = c->ws2;
-		GCGE_SetLinearSolverIdleBlocks(cg_ws, 3);
+		args.sigma = sigma; args.matB = c->B; args.user_scale = scales; args.n_user_scale = blk;
+		args.idle_blocks = cg_ws; args.n_idle = 3;
 	}
+	if (scaled_rhs) args.rhs_scale = scales;
+	GCGE_SetLinearSolverArgs(&args);
 	ops->MultiLinearSolver(c->A, b, c->V, s, e, ops);
-	GCGE_SetLinearSolverIdleBlocks(NULL, 0);
-	GCGE_SetLinearSolverUserScale(NULL, 0);
-	if (scaled_rhs) GCGE_SetLinearSolverRhsScale(NULL);
-	if (p->user_defined_multi_linear_solver == 1) GCGE_SetLinearSolverShift(0.0, NULL);
+	GCGE_SetLinearSolverArgs(NULL);
 	if (sigma != 0.0 && c->B != NULL && ops->MatAxpby != NULL
 			&& p->user_defined_multi_linear_solver != 1)
 		ops->MatAxpby(-sigma, c->B, 1.0, c->A, ops);
@@ -315,6 +312,7 @@ static void ComputeW12(Ctx *c, int *offset)
 	void (*saved_solver)(void*, void**, void**, int*, int*, struct OPS_*) = ops->MultiLinearSolver;
 	void *saved_ws = ops->multi_linear_solver_workspace;
 	void **cg_ws[3];
+	GCGE_LINSOL_ARGS args = {0};
 	int use_axpby;
 	if (p->compW_cg_auto_shift == 1)
 		sigma = -c->ss_eval[c->sizeC] + (c->ss_eval[c->sizeC + 1] - c->ss_eval[c->sizeC]) * 0.01;
@@ -324,6 +322,9 @@ static void ComputeW12(Ctx *c, int *offset)
 
 	for (idx = 0; idx < offset[0]; ++idx) total += offset[idx * 2 + 2] - offset[idx * 2 + 1];
 	half = total / 2;
+	if (p->user_defined_multi_linear_solver == 1) {      /* as in ComputeW, without idle blocks */
+		args.sigma = sigma; args.matB = c->B; args.user_scale = scales; args.n_user_scale = half;
+	}
 	c->startW = c->endP;
 	for (pass = 0; pass < 2; ++pass) {
 		/* x (first pass only) and the right-hand side (lambda + sigma) B x for the first `half` unconverged columns;
@@ -353,7 +354,7 @@ static void ComputeW12(Ctx *c, int *offset)
 						p->compW_cg_tol_type, cg_ws, c->scratch, c->iscratch, NULL,
 						(sigma != 0.0 && !use_axpby) ? MatDotMultiVecShift : NULL, ops);
 			}
-			if (p->user_defined_multi_linear_solver == 1) { GCGE_SetLinearSolverShift(sigma, c->B); GCGE_SetLinearSolverUserScale(scales, half); }
+			GCGE_SetLinearSolverArgs(&args);
 			s[0] = offset[1]; e[0] = s[0] + half; s[1] = c->startW; e[1] = s[1] + half;
 			ops->MultiLinearSolver(c->A, b, c->V, s, e, ops);
 			g_timing.linsol += ops->GetWtime() - t1;
@@ -367,7 +368,7 @@ static void ComputeW12(Ctx *c, int *offset)
 	s[0] = offset[1]; e[0] = s[0] + half; s[1] = c->endW; e[1] = s[1] + half;
 	ops->MultiLinearSolver(c->A, b, c->V, s, e, ops);
 	g_timing.linsol += ops->GetWtime() - t1;
-	if (p->user_defined_multi_linear_solver == 1) { GCGE_SetLinearSolverShift(0.0, NULL); GCGE_SetLinearSolverUserScale(NULL, 0); }
+	GCGE_SetLinearSolverArgs(NULL);
 	c->endW += half;
 	assert(c->endW - c->startW <= total);
 	if (use_axpby) ops->MatAxpby(-sigma, c->B, 1.0, c->A, ops);
@@ -433,7 +434,7 @@ static void ComputeRayleighRitz(Ctx *c, int nevConv)
 
 	t1 = ops->GetWtime();
 	work = c->scratch + (size_t)c->sizeP * c->sizeP;
-	info = GCGE_SymEigFor((void*)ops->MultiVecLinearComb, 'U', N, c->ss_matA, N, c->ss_eval + c->sizeC, c->ss_evec, N, work);
+	info = GCGE_SymEigFor(ops, 'U', N, c->ss_matA, N, c->ss_eval + c->sizeC, c->ss_evec, N, work);
 	assert(info == 0); (void)info;
 	g_timing.dsyevx += ops->GetWtime() - t1;
 

@@ -34,7 +34,7 @@ GCGE_AMG *GCGE_AMGCreate(void *A, void *B, int max_levels, int block_size, int c
 	amg->int_ws = (int*)calloc(2 * (size_t)block_size, sizeof(int));
 	/* blocks: right-hand side and solution of every coarse level, the residual block of every level; the CG's p and w blocks
 	 * only where the smoother is the solver stack's own BlockPCG (a back-end's smoother brings its blocks) */
-	amg->own_smoother = GCGE_HasBlockAMGSmoother(ops);
+	amg->own_smoother = GCGE_BackendOf(ops).amg_smoother_setup != NULL;
 	for (i = 0; i < 5; ++i) amg->mv_ws[i] = (void***)calloc(L, sizeof(void**));
 	for (l = 0; l < L; ++l) {
 		for (i = 0; i < 5; ++i) {

@@ -131,136 +131,115 @@ void MultiLinearSolverSetup_BlockPCG(int max_iter, double rate, double tol, cons
 	ops->MultiLinearSolver = BlockPCG;
 }
 
-/* ---- V-cycle multigrid with block CG as the smoother: the reference's BlockAlgebraicMultiGrid / BlockAMG
+/* ---- V-cycle multigrid with block CG as the smoother: the reference's BlockAMG
  * (src/ops_lin_sol.c:466-715; set up as in test/test_eig_sol_SiO2_MAT.c:96-180, test/test_multi_grid.c:97-129).
- * The hierarchy A_array / P_array comes from the back-end's MultiGridCreate slot.  One cycle on level l:
- *   max_iter[2l + 1] CG iterations on A_l x = b from the current x (pre-smoothing; on the coarsest level that is all),
- *   r = b - A_l x, restricted by P_l^T to the right-hand side of level l + 1, zero start there, the cycle on level l + 1,
- *   x += P_l (coarse x), max_iter[2l + 2] CG iterations (post-smoothing).
+ * The hierarchy A_array / P_array comes from the back-end's MultiGridCreate slot.  One cycle over L levels:
+ *   down, l = 0 .. L-2:  max_iter[2l + 1] CG iterations on A_l x_l = b_l from the current x_l (pre-smoothing),
+ *                        r = b_l - A_l x_l, b_{l+1} = P_l^T r, x_{l+1} = 0;
+ *   coarsest level:      max_iter[2L - 1] CG iterations (its solve);
+ *   up, l = L-2 .. 0:    x_l += P_l x_{l+1}, max_iter[2l + 2] CG iterations (post-smoothing).
  * max_iter[0] cycles at most, stopping once the residual the last smoothing call reports is below tol[0].
- * Workspace per level (mv_array_ws[i][level], as the reference): 0 coarse right-hand side, 1 coarse x, 2 / 3 / 4 the CG's
- * r / p / w — 2 doubles as the residual / correction block, 4 as the scratch of MultiVecFromItoJ.
+ * Level 0 is the caller's b / x and column ranges, level l >= 1 is mv_array_ws[0 / 1][l] over columns [0, m); mv_array_ws[2 / 3 / 4][l]
+ * are the CG's r / p / w (2 doubles as the residual / correction block, 4 as the scratch of MultiVecFromItoJ), as the reference.
  *
- * The smoother is installed through a hook: by default MultiLinearSolverSetup_BlockPCG (the reference's choice,
- * :482-486,:626-629); a back-end may register its own block CG for ITS table (owner = the table's MatDotMultiVec slot) —
- * the HIP back-end's fused device CG — with the same stopping rules. */
-static GCGE_SMOOTHER_SETUP_FN g_smoother_fn = NULL; static GCGE_SMOOTHER_RESIDUAL_FN g_smoother_res = NULL;
-static void *g_smoother_owner = NULL;
-void GCGE_SetBlockAMGSmoother(GCGE_SMOOTHER_SETUP_FN setup, GCGE_SMOOTHER_RESIDUAL_FN residual, void *owner)
+ * The smoother is installed in ops->MultiLinearSolver and called through it (BlockPCG and a back-end's block CG both find their
+ * state in ops->multi_linear_solver_workspace): the back-end's amg_smoother_* where its record offers them (GCGE_BACKEND,
+ * gcge_ops.h), the solver stack's BlockPCG otherwise (the reference's choice, :482-486,:626-629); likewise the residual and the
+ * correction as one sweep each where the record offers amg_residual / amg_prolong_add. */
+struct amg_level { void **b, **x; int start[2], end[2]; };
+static struct amg_level amg_level(const BlockAMGSolver *bamg, int l, void **mv_b, void **mv_x, const int *start_bx, const int *end_bx)
 {
-	g_smoother_fn = setup; g_smoother_res = residual; g_smoother_owner = owner;
+	const int m = end_bx[1] - start_bx[1];
+	struct amg_level v = {mv_b, mv_x, {start_bx[0], start_bx[1]}, {end_bx[0], end_bx[1]}};
+	if (l > 0) { v.b = bamg->mv_array_ws[0][l]; v.x = bamg->mv_array_ws[1][l]; v.start[0] = v.start[1] = 0; v.end[0] = v.end[1] = m; }
+	return v;
 }
-static int own_smoother(struct OPS_ *ops)
+static void smooth(const GCGE_BACKEND *be, const BlockAMGSolver *bamg, int l, int max_iter, struct amg_level *v, struct OPS_ *ops)
 {
-	return g_smoother_fn != NULL && g_smoother_res != NULL && g_smoother_owner == (void*)ops->MatDotMultiVec &&
-	       getenv("GCGE_AMG_HOST_SMOOTHER") == NULL;
-}
-int GCGE_HasBlockAMGSmoother(struct OPS_ *ops) { return own_smoother(ops); }
-/* residual and prolongation + correction as one sweep each where the back-end of this table offers them (include/gcge_solver.h) */
-static GCGE_AMG_RESIDUAL_FN g_fuse_residual = NULL; static GCGE_AMG_PROLONG_ADD_FN g_fuse_prolong = NULL;
-static void *g_fuse_owner = NULL;
-void GCGE_SetBlockAMGFusions(GCGE_AMG_RESIDUAL_FN residual, GCGE_AMG_PROLONG_ADD_FN prolong_add, void *owner)
-{
-	g_fuse_residual = residual; g_fuse_prolong = prolong_add; g_fuse_owner = owner;
-}
-static GCGE_AMG_FORM_RHS_FN g_fuse_rhs = NULL; static void *g_fuse_rhs_owner = NULL;
-void GCGE_SetBlockAMGFormRhs(GCGE_AMG_FORM_RHS_FN form_rhs, void *owner) { g_fuse_rhs = form_rhs; g_fuse_rhs_owner = owner; }
-static int own_fusions(struct OPS_ *ops)
-{
-	return g_fuse_owner != NULL && g_fuse_owner == (void*)ops->MatDotMultiVec && getenv("GCGE_AMG_NO_FUSIONS") == NULL;
-}
-static void smoother_setup(int max_iter, double rate, double tol, const char *tol_type, void **mv_ws[3], double *dbl_ws,
-		int *int_ws, struct OPS_ *ops)
-{
-	if (own_smoother(ops)) g_smoother_fn(max_iter, rate, tol, tol_type, ops);
-	else MultiLinearSolverSetup_BlockPCG(max_iter, rate, tol, tol_type, mv_ws, dbl_ws, int_ws, NULL, NULL, ops);
-}
-/* residual of the smoothing call that ran last (src/ops_lin_sol.c:643: read from the BlockPCG struct behind the table) */
-static double smoother_residual(struct OPS_ *ops)
-{
-	if (own_smoother(ops)) return g_smoother_res(ops);
-	return ((BlockPCGSolver*)ops->multi_linear_solver_workspace)->residual;
+	void **mv_ws[3] = {bamg->mv_array_ws[2][l], bamg->mv_array_ws[3][l], bamg->mv_array_ws[4][l]};
+	if (be->amg_smoother_setup != NULL) be->amg_smoother_setup(max_iter, bamg->rate[l], bamg->tol[l], bamg->tol_type, ops);
+	else MultiLinearSolverSetup_BlockPCG(max_iter, bamg->rate[l], bamg->tol[l], bamg->tol_type, mv_ws, bamg->dbl_ws, bamg->int_ws,
+			NULL, NULL, ops);
+	ops->MultiLinearSolver(bamg->A_array[l], v->b, v->x, v->start, v->end, ops);
 }
 
-static void BlockAlgebraicMultiGrid(int current_level, void **mv_b, void **mv_x, int *start_bx, int *end_bx, struct OPS_ *ops)
+static void BlockAlgebraicMultiGrid(const GCGE_BACKEND *be, BlockAMGSolver *bamg, void **mv_b, void **mv_x, int *start_bx,
+		int *end_bx, struct OPS_ *ops)
 {
-	BlockAMGSolver *bamg = (BlockAMGSolver*)ops->multi_linear_solver_workspace;
-	void (*multi_linear_sol)(void*, void**, void**, int*, int*, struct OPS_*) = ops->MultiLinearSolver;
-	const int coarsest_level = bamg->num_levels - 1, block_size = end_bx[1] - start_bx[1];
-	const int fused = own_fusions(ops);
-	void *A = bamg->A_array[current_level];
-	void **mv_ws[3], **mv_r, **coarse_b, **coarse_x;
-	int start[2], end[2];
-	assert(end_bx[0] - start_bx[0] == end_bx[1] - start_bx[1]);
-	mv_ws[0] = bamg->mv_array_ws[2][current_level];
-	mv_ws[1] = bamg->mv_array_ws[3][current_level];
-	mv_ws[2] = bamg->mv_array_ws[4][current_level];
-	/* pre-smoothing (the coarsest level's "solve") */
-	smoother_setup(bamg->max_iter[current_level * 2 + 1], bamg->rate[current_level], bamg->tol[current_level],
-			bamg->tol_type, mv_ws, bamg->dbl_ws, bamg->int_ws, ops);
-	ops->MultiLinearSolver(A, mv_b, mv_x, start_bx, end_bx, ops);
-	if (current_level < coarsest_level) {
-		const int coarse_level = current_level + 1;
-		/* r = b - A x */
-		start[0] = start_bx[1]; end[0] = end_bx[1]; start[1] = 0; end[1] = block_size;
-		mv_r = bamg->mv_array_ws[2][current_level];
-		if (!(fused && g_fuse_residual != NULL &&
-				g_fuse_residual(A, mv_b, start_bx[0], mv_x, start_bx[1], mv_r, 0, block_size, ops))) {
-			ops->MatDotMultiVec(A, mv_x, mv_r, start, end, ops);
-			start[0] = start_bx[0]; end[0] = end_bx[0]; start[1] = 0; end[1] = block_size;
-			ops->MultiVecAxpby(1.0, mv_b, -1.0, mv_r, start, end, ops);
+	GCGE_LINSOL_FN solver = ops->MultiLinearSolver;
+	void *solver_ws = ops->multi_linear_solver_workspace;
+	const int L = bamg->num_levels, m = end_bx[1] - start_bx[1];
+	int l, cs[2] = {0, 0}, ce[2] = {m, m};          /* the column range of a coarse level's blocks */
+	struct amg_level f, c;
+	assert(end_bx[0] - start_bx[0] == m);
+	for (l = 0; l < L - 1; ++l) {
+		void *A = bamg->A_array[l], **r = bamg->mv_array_ws[2][l];
+		f = amg_level(bamg, l, mv_b, mv_x, start_bx, end_bx);
+		c = amg_level(bamg, l + 1, mv_b, mv_x, start_bx, end_bx);
+		smooth(be, bamg, l, bamg->max_iter[2 * l + 1], &f, ops);
+		if (!(be->amg_residual != NULL && be->amg_residual(A, f.b, f.start[0], f.x, f.start[1], r, 0, m, ops))) {
+			int s[2] = {f.start[1], 0}, e[2] = {f.end[1], m};
+			ops->MatDotMultiVec(A, f.x, r, s, e, ops);                 /* r = b - A x */
+			s[0] = f.start[0]; e[0] = f.end[0];
+			ops->MultiVecAxpby(1.0, f.b, -1.0, r, s, e, ops);
 		}
-		/* restrict, zero start, recurse */
-		coarse_b = bamg->mv_array_ws[0][coarse_level];
-		coarse_x = bamg->mv_array_ws[1][coarse_level];
-		start[0] = 0; end[0] = block_size; start[1] = 0; end[1] = block_size;
-		ops->MultiVecFromItoJ(bamg->P_array, current_level, coarse_level, mv_r, coarse_b, start, end, bamg->mv_array_ws[4], ops);
-		ops->MultiVecAxpby(0.0, NULL, 0.0, coarse_x, start, end, ops);
-		ops->multi_linear_solver_workspace = (void*)bamg;
-		BlockAlgebraicMultiGrid(coarse_level, coarse_b, coarse_x, start, end, ops);
-		/* prolongate and correct */
-		if (!(fused && g_fuse_prolong != NULL &&
-				g_fuse_prolong(bamg->P_array[current_level], coarse_x, 0, mv_x, start_bx[1], block_size, ops))) {
-			ops->MultiVecFromItoJ(bamg->P_array, coarse_level, current_level, coarse_x, mv_r, start, end, bamg->mv_array_ws[4], ops);
-			start[0] = 0; end[0] = block_size; start[1] = start_bx[1]; end[1] = end_bx[1];
-			ops->MultiVecAxpby(1.0, mv_r, 1.0, mv_x, start, end, ops);
-		}
-		/* post-smoothing */
-		smoother_setup(bamg->max_iter[current_level * 2 + 2], bamg->rate[current_level], bamg->tol[current_level],
-				bamg->tol_type, mv_ws, bamg->dbl_ws, bamg->int_ws, ops);
-		ops->MultiLinearSolver(A, mv_b, mv_x, start_bx, end_bx, ops);
+		ops->MultiVecFromItoJ(bamg->P_array, l, l + 1, r, c.b, cs, ce, bamg->mv_array_ws[4], ops);
+		ops->MultiVecAxpby(0.0, NULL, 0.0, c.x, cs, ce, ops);
 	}
-	bamg->residual = smoother_residual(ops);
-	/* the table's solver is BlockAMG again */
-	ops->multi_linear_solver_workspace = (void*)bamg;
-	ops->MultiLinearSolver = multi_linear_sol;
+	f = amg_level(bamg, L - 1, mv_b, mv_x, start_bx, end_bx);
+	smooth(be, bamg, L - 1, bamg->max_iter[2 * L - 1], &f, ops);
+	for (l = L - 2; l >= 0; --l) {
+		void **r = bamg->mv_array_ws[2][l];
+		f = amg_level(bamg, l, mv_b, mv_x, start_bx, end_bx);
+		c = amg_level(bamg, l + 1, mv_b, mv_x, start_bx, end_bx);
+		if (!(be->amg_prolong_add != NULL && be->amg_prolong_add(bamg->P_array[l], c.x, 0, f.x, f.start[1], m, ops))) {
+			int s[2] = {0, f.start[1]}, e[2] = {m, f.end[1]};
+			ops->MultiVecFromItoJ(bamg->P_array, l + 1, l, c.x, r, cs, ce, bamg->mv_array_ws[4], ops);
+			ops->MultiVecAxpby(1.0, r, 1.0, f.x, s, e, ops);
+		}
+		smooth(be, bamg, l, bamg->max_iter[2 * l + 2], &f, ops);
+	}
+	/* residual of the smoothing call that ran last (src/ops_lin_sol.c:643: read from the solver behind the table) */
+	bamg->residual = be->amg_smoother_setup != NULL ? be->amg_smoother_residual(ops) :
+			((BlockPCGSolver*)ops->multi_linear_solver_workspace)->residual;
+	ops->MultiLinearSolver = solver;
+	ops->multi_linear_solver_workspace = solver_ws;
 }
 
 static void BlockAMG(void *mat, void **mv_b, void **mv_x, int *start_bx, int *end_bx, struct OPS_ *ops)
 {
 	BlockAMGSolver *bamg = (BlockAMGSolver*)ops->multi_linear_solver_workspace;
+	const GCGE_BACKEND be = GCGE_BackendOf(ops);
+	const GCGE_LINSOL_ARGS args = *GCGE_GetLinearSolverArgs();
 	int idx;
-	/* systems declared as b = x diag(scale) (only to a BlockAMG that registered for them: MultiLinearSolverSetup_BlockAMG):
-	 * b is formed here, once, from the initial guess; the smoothing calls then see an ordinary right-hand side */
-	const double *rhs_scale = GCGE_GetLinearSolverRhsScale();
 	(void)mat;      /* level 0 of the hierarchy IS the matrix (src/ops_lin_sol.c:477) */
-	if (rhs_scale != NULL) {
+	/* systems published as b = x diag(scale) (GCGE_SolverTakesScaledRhs): b is formed here, once, from the initial guess;
+	 * the smoothing calls then see an ordinary right-hand side */
+	if (args.rhs_scale != NULL) {
+		GCGE_LINSOL_ARGS formed = args;
 		const int ncols = end_bx[1] - start_bx[1];
-		if (!(g_fuse_rhs != NULL && g_fuse_rhs_owner == (void*)ops->MatDotMultiVec &&
-				g_fuse_rhs(mv_b, start_bx[0], mv_x, start_bx[1], rhs_scale, ncols, ops))) {
+		if (!(be.amg_form_rhs != NULL && be.amg_form_rhs(mv_b, start_bx[0], mv_x, start_bx[1], args.rhs_scale, ncols, ops))) {
 			int s[2], e[2];
 			s[0] = start_bx[1]; e[0] = end_bx[1]; s[1] = start_bx[0]; e[1] = end_bx[0];
 			ops->MultiVecAxpby(1.0, mv_x, 0.0, mv_b, s, e, ops);
-			ops->MultiVecLinearComb(NULL, mv_b, 0, s, e, NULL, 0, (double*)rhs_scale, 1, ops);
+			ops->MultiVecLinearComb(NULL, mv_b, 0, s, e, NULL, 0, (double*)args.rhs_scale, 1, ops);
 		}
-		GCGE_SetLinearSolverRhsScale(NULL);
+		formed.rhs_scale = NULL;
+		GCGE_SetLinearSolverArgs(&formed);
 	}
 	for (idx = 0; idx < bamg->max_iter[0]; ++idx) {
-		BlockAlgebraicMultiGrid(0, mv_b, mv_x, start_bx, end_bx, ops);
+		BlockAlgebraicMultiGrid(&be, bamg, mv_b, mv_x, start_bx, end_bx, ops);
 		bamg->niter = idx + 1;
 		if (bamg->residual < bamg->tol[0]) break;
 	}
-	if (rhs_scale != NULL) GCGE_SetLinearSolverRhsScale(rhs_scale);   /* (the caller clears it) */
+	if (args.rhs_scale != NULL) GCGE_SetLinearSolverArgs(&args);   /* (the caller clears it) */
+}
+
+int GCGE_SolverTakesScaledRhs(struct OPS_ *ops)
+{
+	const GCGE_BACKEND be = GCGE_BackendOf(ops);
+	return ops->MultiLinearSolver != NULL &&
+			(ops->MultiLinearSolver == be.scaled_rhs_solver || (ops->MultiLinearSolver == BlockAMG && be.amg_form_rhs != NULL));
 }
 
 void MultiLinearSolverSetup_BlockAMG(int *max_iter, double *rate, double *tol, const char *tol_type,
@@ -278,7 +257,4 @@ void MultiLinearSolverSetup_BlockAMG(int *max_iter, double *rate, double *tol, c
 	bamg.niter = 0; bamg.residual = -1.0;
 	ops->multi_linear_solver_workspace = (void*)&bamg;
 	ops->MultiLinearSolver = BlockAMG;
-	/* over a back-end that forms b = x diag(scale) in one sweep, BlockAMG takes the GCG driver's scaled right-hand sides */
-	GCGE_SetRhsScaleCapabilityOfBlockAMG((g_fuse_rhs != NULL && g_fuse_rhs_owner == (void*)ops->MatDotMultiVec &&
-			getenv("GCGE_AMG_NO_FUSIONS") == NULL) ? (void*)BlockAMG : NULL);
 }

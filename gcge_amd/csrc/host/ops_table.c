@@ -42,38 +42,42 @@ static int g_local_ip_reduces = 0;
 void GCGE_SetLocalInnerProdReduces(int on) { g_local_ip_reduces = on != 0; }
 int  GCGE_GetLocalInnerProdReduces(void) { return g_local_ip_reduces && g_comm != NULL; }
 
-static GCGE_RESIDUAL_FN g_res_hook = NULL; static void *g_res_owner = NULL;
-void GCGE_SetResidualHook(GCGE_RESIDUAL_FN fn, void *owner) { g_res_hook = fn; g_res_owner = owner; }
-GCGE_RESIDUAL_FN GCGE_GetResidualHook(void *owner) { return (g_res_hook != NULL && owner == g_res_owner) ? g_res_hook : NULL; }
-/* (two owners: a back-end's block CG and, over it, BlockAMG where the back-end forms b in one sweep — lin_sol.c) */
-static void *g_rhs_scale_owner[2] = {NULL, NULL}; static const double *g_rhs_scale = NULL;
-void GCGE_SetRhsScaleCapability(void *owner) { g_rhs_scale_owner[0] = owner; }
-void GCGE_SetRhsScaleCapabilityOfBlockAMG(void *owner) { g_rhs_scale_owner[1] = owner; }
-int GCGE_HasRhsScaleCapability(void *owner)
+static GCGE_LINSOL_ARGS g_linsol_args;
+void GCGE_SetLinearSolverArgs(const GCGE_LINSOL_ARGS *args)
 {
-	return owner != NULL && (owner == g_rhs_scale_owner[0] || owner == g_rhs_scale_owner[1]) && getenv("GCGE_NO_RHS_SCALE") == NULL;
+	if (args != NULL) g_linsol_args = *args;
+	else memset(&g_linsol_args, 0, sizeof(g_linsol_args));
 }
-void GCGE_SetLinearSolverRhsScale(const double *scale) { g_rhs_scale = scale; }
-const double *GCGE_GetLinearSolverRhsScale(void) { return g_rhs_scale; }
-static void ***g_idle_blocks = NULL; static int g_idle_count = 0;
-void GCGE_SetLinearSolverIdleBlocks(void ***blocks, int count) { g_idle_blocks = blocks; g_idle_count = blocks != NULL ? count : 0; }
-void ***GCGE_GetLinearSolverIdleBlocks(int *count) { if (count != NULL) *count = g_idle_count; return g_idle_blocks; }
-static void *g_inplace_owner = NULL; static int g_inplace_cols = 0;
-void GCGE_SetInplaceLinearComb(void *owner, int max_cols) { g_inplace_owner = owner; g_inplace_cols = max_cols; }
-int GCGE_InplaceLinearCombCols(void *owner)
-{
-	return (g_inplace_owner != NULL && owner == g_inplace_owner && getenv("GCGE_NO_INPLACE_LINCOMB") == NULL) ? g_inplace_cols : 0;
-}
+const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs(void) { return &g_linsol_args; }
 
-static double g_ls_sigma = 0.0; static void *g_ls_matB = NULL;
-void GCGE_SetLinearSolverShift(double sigma, void *matB) { g_ls_sigma = sigma; g_ls_matB = matB; }
-static const double *g_user_scale = NULL; static int g_user_scale_n = 0;
-void GCGE_SetLinearSolverUserScale(const double *scale, int n) { g_user_scale = scale; g_user_scale_n = scale != NULL ? n : 0; }
-const double *GCGE_GetLinearSolverUserScale(int *n) { if (n != NULL) *n = g_user_scale_n; return g_user_scale; }
-void GCGE_GetLinearSolverShift(double *sigma, void **matB)
+/* The back-end record and the two slots that identify its table.  The lookup applies the opt-out switches, read at every
+ * call (the tests flip them inside a running process); each turns off what it names:
+ *   GCGE_NO_RESIDUAL_HOOK    residual_sq                                    (CheckConvergence through the slots)
+ *   GCGE_NO_INPLACE_LINCOMB  inplace_lincomb_cols                           (panel updates staged through a work block)
+ *   GCGE_EIG_HOST            symeig                                         (projected eigenproblems on the host)
+ *   GCGE_AMG_HOST_SMOOTHER   amg_smoother_setup, amg_smoother_residual      (BlockAMG smooths with BlockPCG over the slots)
+ *   GCGE_AMG_NO_FUSIONS      amg_residual, amg_prolong_add, amg_form_rhs    (the V-cycle's slot calls)
+ *   GCGE_NO_RHS_SCALE        scaled_rhs_solver, amg_form_rhs                (the GCG driver forms b = (lambda + sigma) x) */
+static GCGE_BACKEND g_backend; static void *g_backend_matvec = NULL, *g_backend_lincomb = NULL;
+void GCGE_SetBackend(struct OPS_ *ops, const GCGE_BACKEND *backend)
 {
-	if (sigma) *sigma = g_ls_sigma;
-	if (matB) *matB = g_ls_matB;
+	g_backend = *backend;
+	g_backend_matvec = (void*)ops->MatDotMultiVec; g_backend_lincomb = (void*)ops->MultiVecLinearComb;
+}
+GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
+{
+	GCGE_BACKEND b;
+	memset(&b, 0, sizeof(b));
+	if (ops == NULL || g_backend_matvec == NULL || (void*)ops->MatDotMultiVec != g_backend_matvec ||
+			(void*)ops->MultiVecLinearComb != g_backend_lincomb) return b;
+	b = g_backend;
+	if (getenv("GCGE_NO_RESIDUAL_HOOK") != NULL) b.residual_sq = NULL;
+	if (getenv("GCGE_NO_INPLACE_LINCOMB") != NULL) b.inplace_lincomb_cols = 0;
+	if (getenv("GCGE_EIG_HOST") != NULL) b.symeig = NULL;
+	if (getenv("GCGE_AMG_HOST_SMOOTHER") != NULL) { b.amg_smoother_setup = NULL; b.amg_smoother_residual = NULL; }
+	if (getenv("GCGE_AMG_NO_FUSIONS") != NULL) { b.amg_residual = NULL; b.amg_prolong_add = NULL; b.amg_form_rhs = NULL; }
+	if (getenv("GCGE_NO_RHS_SCALE") != NULL) { b.scaled_rhs_solver = NULL; b.amg_form_rhs = NULL; }
+	return b;
 }
 
 /* ---------------------------------------------------------------- services */

@@ -24,6 +24,15 @@ class OPS(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in OPS_FIELDS]
 
 
+class LINSOL_ARGS(C.Structure):
+    """ctypes mirror of GCGE_LINSOL_ARGS (include/gcge_ops.h): what one MultiLinearSolver call carries beyond its arguments,
+    published through GCGE_SetLinearSolverArgs."""
+    _fields_ = [("sigma", C.c_double), ("matB", C.c_void_p),
+                ("user_scale", C.POINTER(C.c_double)), ("n_user_scale", C.c_int),
+                ("rhs_scale", C.POINTER(C.c_double)),
+                ("idle_blocks", C.c_void_p), ("n_idle", C.c_int)]
+
+
 _vp, _i, _d, _c = C.c_void_p, C.c_int, C.c_double, C.c_char
 _ip, _dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
 

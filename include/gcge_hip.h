@@ -79,7 +79,7 @@ void gcge_hip_mat_destroy (GCGE_HIP_MAT *A);
  * src/ops.h:134-139; what app/app_slepc.c:648-728 gets from PETSc GAMG): the CSR arrays come back from the device, the
  * aggregation hierarchy of include/gcge_multigrid.h is built on the host (2 x 2 x 2 cells of a detected grid, greedy aggregates
  * otherwise, A_{l+1} = scale P^T A_l P; gcge_mg_set_defaults), every level is uploaded like any other matrix, and the fused
- * block CG is registered as the smoother of BlockAMG for this table (GCGE_SetBlockAMGSmoother, include/gcge_solver.h).
+ * block CG is the smoother of BlockAMG for this table (GCGE_BACKEND.amg_smoother_setup, include/gcge_ops.h).
  * One rank only.  A prolongation is a RECTANGULAR matrix handle: MatDotMultiVec applies P (rows of level l x rows of level
  * l + 1), MatTransDotMultiVec its transpose (the restriction of src/ops_multi_grid.c:95-113); MultiVecCreateByMat of it gives
  * blocks with its COLUMN count of rows (app_ccs.c:43).                                                                      */
@@ -163,7 +163,7 @@ void gcge_hip_bpcg_stats (long *spmm_calls, long *spmm_cols, int *last_niter);
  * from EigenSolverCreateWorkspace_GCG, before the harness starts its timer (test/test_eig_sol_gcg.c:89-143).  Returns the ring
  * length (>= 1), -1 when ops->MultiLinearSolver is not this solver.  Collective when a communicator exists.                    */
 int  gcge_hip_bpcg_prepare (struct OPS_ *ops, void *mat, void **mv_like, int ncols);
-/*     tol_type: "abs", "rel" or "user" (src/ops_lin_sol.c:175-197; "user": scales from GCGE_GetLinearSolverUserScale).
+/*     tol_type: "abs", "rel" or "user" (src/ops_lin_sol.c:175-197; "user": scales from GCGE_LINSOL_ARGS.user_scale).
  *     Residual of the recompute form: 0 automatic (not stored where rate >= 1e-4 and max_iter <= 100), 1 never stored
  *     (r_k = p_k - beta_{k-1} p_{k-1} rebuilt from the ring), 2 always stored                                         */
 void gcge_hip_bpcg_residual_form (int form);
@@ -177,7 +177,7 @@ long gcge_hip_bpcg_device_scalar_iters (void);
 /* iterations of that device-scalar loop with the product STORED (matrices without a pattern form, no shift: product + column sums
  * left on the device by gcge_hip_spmm_dot2_dev, then one sweep over w and the directions); GCGE_CG_STORED_HOST=1: host scalars */
 long gcge_hip_bpcg_stored_dev_iters (void);
-/* solves with right-hand sides b = x diag(scale) (GCGE_SetLinearSolverRhsScale) on such a matrix that started as product + ONE sweep
+/* solves with right-hand sides b = x diag(scale) (GCGE_LINSOL_ARGS.rhs_scale) on such a matrix that started as product + ONE sweep
  * (r = x diag(scale) - A x, p0 = r, r.r) instead of forming b; GCGE_CG_NO_FUSED_START=1 switches it off */
 long gcge_hip_bpcg_fused_starts (void);
 /*     y[:, cy : cy + m) = A x[:, cx : cx + m) with d_out[0, m) = x.y and d_out[m, 2m) = y.y (local rows) left on the device, nothing
@@ -205,7 +205,7 @@ long gcge_hip_profile_kind_rows (int kind, int ncols, long nrows, double *total_
  * z (HOST, ld ldz) orthonormal eigenvectors.  Householder tridiagonalisation and the accumulation of Q on the device,
  * implicit QL on the host with recorded rotations, replayed on the device (csrc/hip/eig_device.hip).  0 on success.  */
 int gcge_hip_symeig (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
-long gcge_hip_symeig_calls (void);   /* calls so far: the hook is keyed to the HIP table (GCGE_SetSymEigHook owner), the CPU oracle never gets here */
+long gcge_hip_symeig_calls (void);   /* calls so far: offered by the HIP table's back-end record only: the CPU oracle never gets here */
 
 /* ---- raw kernels (what the slots launch; exposed for micro-benchmarks) --------- */
 /* K1  Y[:,0:m) = A X[:,0:m);  x/y point at (row 0, first column); see csrc/hip/spmm*.hip */

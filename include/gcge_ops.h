@@ -151,51 +151,64 @@ GCGE_COMM *GCGE_GetComm (void);
  * OPS_HIP_Set's slot; libgcge_host.so's own BlockPCG skips its reduction while it is on.  Get: 1 only while a communicator exists. */
 void       GCGE_SetLocalInnerProdReduces (int on);
 int        GCGE_GetLocalInnerProdReduces (void);
-/* Shift of the W systems for a user-defined MultiLinearSolver (flag 1): the reference calls such a solver with A
- * only (ops_eig_sol_gcg.c:584-618) and leaves sigma to it; our GCG publishes (sigma, B) here before every call so
- * that a shift-aware solver (the fused block CG of the HIP back-end) can apply A + sigma B.  An application that
- * drives the REFERENCE's GCG sets a fixed shift itself.  sigma == 0: no shift. */
-void       GCGE_SetLinearSolverShift (double sigma, void *matB);
-void       GCGE_GetLinearSolverShift (double *sigma, void **matB);
-/*     the column scales of the "user" tolerance type of BlockPCG (src/ops_lin_sol.c:186-192: a column has converged when
- *     its residual is below tol * |scale_j|; the reference's GCG leaves lambda_j + sigma at the start of BlockPCG's scalar
- *     scratch).  A solver installed behind flag 1 has no such scratch: the GCG driver publishes the n scales here for the
- *     duration of the call, NULL otherwise.                                                                              */
-void       GCGE_SetLinearSolverUserScale (const double *scale, int n);
-const double *GCGE_GetLinearSolverUserScale (int *n);
-/* Optional fast path of CheckConvergence (src/ops_eig_sol_gcg.c:195-315 forms A x, B x, lambda B x, the difference and
- * its column norms through five slots = 11 block streams).  A back-end may offer the squared residual norms
- *   res_sq[j] = sum over its LOCAL rows of ((A x_j) - lambda_j (B x_j))^2 ,  j = start .. end-1  (columns of x)
- * in one go; it returns 1 if it did, 0 to decline (the driver then takes the slots).  `owner` ties the hook to one
- * operator table: it is only used when ops->MatDotMultiVec == owner.  The driver sums over ranks (GCGE_COMM). */
-typedef int (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
-void       GCGE_SetResidualHook (GCGE_RESIDUAL_FN fn, void *owner);
-GCGE_RESIDUAL_FN GCGE_GetResidualHook (void *owner);
-/* Optional capability of a user-defined MultiLinearSolver: the driver's systems A w = (lambda + sigma) B x are started
- * from w = x, so for B == NULL the right-hand side is the initial guess scaled column by column.  A solver that
- * declared the capability (owner = its function pointer, as installed in ops->MultiLinearSolver) is called with the x
- * block holding the initial guess, GCGE_GetLinearSolverRhsScale() returning the factors and the b block NOT filled in
- * (it may use that block as scratch).  The reference forms b through MatDotMultiVec + MultiVecLinearComb
- * (src/ops_eig_sol_gcg.c:560-577): two block sweeps and a third read at the start of the solve. */
-void       GCGE_SetRhsScaleCapability (void *owner);
-void       GCGE_SetRhsScaleCapabilityOfBlockAMG (void *owner);   /* second owner: BlockAMG over a back-end that forms b in one sweep (NULL: none) */
-int        GCGE_HasRhsScaleCapability (void *owner);
-void       GCGE_SetLinearSolverRhsScale (const double *scale);   /* NULL: b is an ordinary right-hand side */
-const double *GCGE_GetLinearSolverRhsScale (void);
-/* Blocks of vectors the driver does not need while MultiLinearSolver runs (its orthonormalisation / residual work
- * blocks: contents dead across the call).  A solver may use them as scratch — the fused HIP solver takes those that
- * match its own work blocks as additional slots of its direction ring, which is what limits it when HBM is nearly
- * full (BASELINE config 4's shape: 244 of 288 GB are the solver stack's own blocks).  Valid only during the call. */
-void       GCGE_SetLinearSolverIdleBlocks (void ***blocks, int count);
-void    ***GCGE_GetLinearSolverIdleBlocks (int *count);
-/* Optional capability: a back-end whose MultiVecLinearComb works ROW BY ROW (row-major blocks: every output row is
- * formed from the same row of x and written after that row has been read) may declare panel updates IN PLACE safe:
- * y == x with the output columns inside the input column range, at most `max_cols` output columns per call.  The
- * block orthonormalisation and ComputeP of this solver stack then skip the work block + copy back the reference's
- * LAPACKVEC layout needs (src/ops_orth.c, src/ops_eig_sol_gcg.c:624-640): same arithmetic, same results, two block
- * streams less per update.  `owner` = the table's MultiVecLinearComb; 0 columns: not declared. */
-void       GCGE_SetInplaceLinearComb (void *owner, int max_cols);
-int        GCGE_InplaceLinearCombCols (void *owner);
+/* What one call of ops->MultiLinearSolver carries beyond the slot's arguments: published by the caller before the call,
+ * cleared after it (our GCG driver around its W solves; BlockAMG republishes it without rhs_scale for its smoothing calls).
+ *   sigma, matB   shift of the W systems (sigma == 0: none).  The reference calls a user-defined solver (flag 1) with A only
+ *                 (ops_eig_sol_gcg.c:584-618); a shift-aware solver (the HIP back-end's fused block CG) applies A + sigma B.
+ *   user_scale    n_user_scale column scales of the "user" tolerance type of BlockPCG (src/ops_lin_sol.c:186-192: a column has
+ *                 converged below tol * |scale_j|; the reference's GCG leaves lambda_j + sigma in BlockPCG's scalar scratch,
+ *                 which a solver behind flag 1 does not have).
+ *   rhs_scale     b = x diag(rhs_scale) with x holding the initial guess and b NOT filled in (the solver may use it as scratch):
+ *                 the driver's systems A w = (lambda + sigma) x for B == NULL, published only to a solver that takes them
+ *                 (GCGE_SolverTakesScaledRhs, gcge_solver.h).  The reference forms b through MatDotMultiVec + MultiVecLinearComb
+ *                 (src/ops_eig_sol_gcg.c:560-577).  NULL: b is an ordinary right-hand side.
+ *   idle_blocks   n_idle blocks the driver does not need during the call (its work blocks): scratch for the solver — the fused
+ *                 HIP solver takes those that match its own blocks as further slots of its direction ring.                     */
+typedef struct GCGE_LINSOL_ARGS_ {
+	double sigma; void *matB;
+	const double *user_scale; int n_user_scale;
+	const double *rhs_scale;
+	void ***idle_blocks; int n_idle;
+} GCGE_LINSOL_ARGS;
+void       GCGE_SetLinearSolverArgs (const GCGE_LINSOL_ARGS *args);   /* copied; NULL clears */
+const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs (void);              /* never NULL; all zero when nothing is published */
+
+/* What a back-end offers beyond the slots of struct OPS_ (NULL / 0: not offered).  Registered once by the back-end
+ * (GCGE_SetBackend; OPS_HIP_Set does it), it applies to every table whose MatDotMultiVec AND MultiVecLinearComb are the ones
+ * `ops` held then; GCGE_BackendOf returns a copy — all zero for other tables — minus what the opt-out switches of the
+ * environment turn off at the time of the call (listed in ops_table.c).
+ *   residual_sq   res_sq[j] = sum over the LOCAL rows of ((A x_j) - lambda_j (B x_j))^2, j = start .. end-1, in one go for
+ *                 CheckConvergence (the slots take 11 block streams: src/ops_eig_sol_gcg.c:195-315); 0 declines.
+ *   inplace_lincomb_cols   MultiVecLinearComb works ROW BY ROW (every output row written after its input row was read), so a
+ *                 panel update y == x with the output columns inside the input range and at most this many of them is safe: the
+ *                 orthonormalisation and ComputeP skip the reference's work block + copy back (src/ops_orth.c,
+ *                 src/ops_eig_sol_gcg.c:624-640).
+ *   symeig        the small dense eigensolver (contract of GCGE_SymEig) on the device, for n >= symeig_min_n (GCGE_SymEigFor).
+ *   amg_smoother_setup / _residual   the back-end's block CG as BlockAMG's smoother (both or neither): setup(max_iter, rate,
+ *                 tol, tol_type, ops) installs it in ops->MultiLinearSolver, residual(ops) returns what BlockPCGSolver.residual
+ *                 would hold after the call.  Default: BlockPCG over the slots (src/ops_lin_sol.c:482-486,626-629).
+ *   amg_residual  r[:, r0..) = b[:, b0..) - A x[:, x0..)  and  amg_prolong_add  xf[:, f0..) += P xc[:, c0..)  as one sweep each,
+ *                 bit for bit the slot calls they replace (src/ops_lin_sol.c:596-606, :626-640); 0 declines.
+ *   amg_form_rhs  b[:, b0..) = x[:, x0..) diag(scale) in one sweep: BlockAMG then takes rhs_scale systems; 0 declines.
+ *   scaled_rhs_solver   the back-end's solver that takes rhs_scale systems, as installed in ops->MultiLinearSolver.        */
+typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
+typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
+typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
+typedef double (*GCGE_SMOOTHER_RESIDUAL_FN) (struct OPS_ *ops);
+typedef int    (*GCGE_AMG_RESIDUAL_FN) (void *A, void **b, int b0, void **x, int x0, void **r, int r0, int ncols, struct OPS_ *ops);
+typedef int    (*GCGE_AMG_PROLONG_ADD_FN) (void *P, void **xc, int c0, void **xf, int f0, int ncols, struct OPS_ *ops);
+typedef int    (*GCGE_AMG_FORM_RHS_FN) (void **b, int b0, void **x, int x0, const double *scale, int ncols, struct OPS_ *ops);
+typedef void   (*GCGE_LINSOL_FN) (void *mat, void **b, void **x, int *start, int *end, struct OPS_ *ops);
+typedef struct GCGE_BACKEND_ {
+	GCGE_RESIDUAL_FN residual_sq;
+	int inplace_lincomb_cols;
+	GCGE_SYMEIG_FN symeig; int symeig_min_n;
+	GCGE_SMOOTHER_SETUP_FN amg_smoother_setup; GCGE_SMOOTHER_RESIDUAL_FN amg_smoother_residual;
+	GCGE_AMG_RESIDUAL_FN amg_residual; GCGE_AMG_PROLONG_ADD_FN amg_prolong_add; GCGE_AMG_FORM_RHS_FN amg_form_rhs;
+	GCGE_LINSOL_FN scaled_rhs_solver;
+} GCGE_BACKEND;
+void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
+GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);
 void       GCGE_SetQuiet (OPS *ops, int quiet);   /* silence ops->Printf (and the dense table's) */
 
 #ifdef __cplusplus

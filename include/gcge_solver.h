@@ -23,13 +23,9 @@ int GCGE_SymEig (char uplo, int n, const double *a, int lda, double *w,
 /*     the host implementation itself (GCGE_SymEig is this; kept under both names) */
 int GCGE_SymEigHost (char uplo, int n, const double *a, int lda, double *w,
 		double *z, int ldz, double *work /* >= 2n */);
-/*     a back-end's own solver with the same contract (host pointers in and out, 0 on success), registered for ONE
- *     operator table: owner = that table's MultiVecLinearComb slot.  GCGE_SymEigFor(owner, ...) — what the GCG driver and
- *     the orthonormalisation call with their table's slot — takes it for n >= min_n when the owners match, the host solver
- *     otherwise.  The HIP back-end registers gcge_hip_symeig (csrc/hip/eig_device.hip) in OPS_HIP_Set.                  */
-typedef int (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
-void GCGE_SetSymEigHook (GCGE_SYMEIG_FN fn, int min_n, void *owner);
-int GCGE_SymEigFor (void *owner, char uplo, int n, const double *a, int lda, double *w,
+/*     ... or through the back-end of the table (GCGE_BackendOf(ops).symeig, gcge_ops.h) for n >= its symeig_min_n: what the
+ *     GCG driver and the orthonormalisation call.  The host solver where the back-end offers none or its solver fails.   */
+int GCGE_SymEigFor (struct OPS_ *ops, char uplo, int n, const double *a, int lda, double *w,
 		double *z, int ldz, double *work /* >= 2n */);
 
 /* ---- block orthonormalisation (sets ops->MultiVecOrth + orth_workspace) ---- */
@@ -86,29 +82,10 @@ typedef struct BlockAMGSolver_ {
 void MultiLinearSolverSetup_BlockAMG (int *max_iter, double *rate, double *tol, const char *tol_type,
 		void **A_array, void **P_array, int num_levels, void ***mv_array_ws[5], double *dbl_ws, int *int_ws,
 		void *pc, struct OPS_ *ops);
-/*     The smoother of BlockAMG.  Default: MultiLinearSolverSetup_BlockPCG on the level's r / p / w blocks, as the reference
- *     (src/ops_lin_sol.c:482-486,626-629).  A back-end may register its own block CG for ITS table (owner = the table's
- *     MatDotMultiVec slot): setup(max_iter, rate, tol, tol_type, ops) installs it in ops->MultiLinearSolver (it brings its own
- *     work blocks), residual(ops) returns what BlockPCGSolver.residual would hold after the call.  The HIP back-end
- *     registers its fused device CG in OPS_HIP_Set; GCGE_AMG_HOST_SMOOTHER=1 keeps the default.                          */
-typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
-typedef double (*GCGE_SMOOTHER_RESIDUAL_FN) (struct OPS_ *ops);
-void GCGE_SetBlockAMGSmoother (GCGE_SMOOTHER_SETUP_FN setup, GCGE_SMOOTHER_RESIDUAL_FN residual, void *owner);
-int  GCGE_HasBlockAMGSmoother (struct OPS_ *ops);      /* 1: a smoother is registered for THIS table and not switched off */
-/*     Two steps of a V-cycle that a back-end may do in one sweep each for ITS table (owner as above), with the arithmetic
- *     of the slot calls they replace (src/ops_lin_sol.c:596-606, :626-640) — results identical bit for bit:
- *       residual(A, b, b0, x, x0, r, r0, ncols, ops):  r[:, r0..) = b[:, b0..) - A x[:, x0..)   (MatDotMultiVec + MultiVecAxpby)
- *       prolong_add(P, xc, c0, xf, f0, ncols, ops):    xf[:, f0..) += P xc[:, c0..)             (MultiVecFromItoJ + MultiVecAxpby)
- *     each returns 1 when it did the work and 0 to decline (the V-cycle then issues the slot calls).
- *     GCGE_AMG_NO_FUSIONS=1 in the environment keeps the slot calls.
- *       form_rhs(b, b0, x, x0, scale, ncols, ops):  b[:, b0..) = x[:, x0..) diag(scale) — with it BlockAMG takes the GCG driver's
- *     "b = x diag(scale)" systems (GCGE_SetRhsScaleCapability, include/gcge_ops.h) and forms b itself in one sweep (the driver's
- *     MatDotMultiVec(B = NULL) + MultiVecLinearComb are two: reference src/ops_eig_sol_gcg.c:560-577); NULL: b comes formed.     */
-typedef int (*GCGE_AMG_RESIDUAL_FN) (void *A, void **b, int b0, void **x, int x0, void **r, int r0, int ncols, struct OPS_ *ops);
-typedef int (*GCGE_AMG_PROLONG_ADD_FN) (void *P, void **xc, int c0, void **xf, int f0, int ncols, struct OPS_ *ops);
-typedef int (*GCGE_AMG_FORM_RHS_FN) (void **b, int b0, void **x, int x0, const double *scale, int ncols, struct OPS_ *ops);
-void GCGE_SetBlockAMGFusions (GCGE_AMG_RESIDUAL_FN residual, GCGE_AMG_PROLONG_ADD_FN prolong_add, void *owner);
-void GCGE_SetBlockAMGFormRhs (GCGE_AMG_FORM_RHS_FN form_rhs, void *owner);
+/*     1: ops->MultiLinearSolver takes systems published as b = x diag(rhs_scale) (GCGE_LINSOL_ARGS, gcge_ops.h) — it is the
+ *     back-end's scaled_rhs_solver, or BlockAMG over a back-end with amg_form_rhs (GCGE_BACKEND).  BlockAMG smooths with the
+ *     back-end's amg_smoother_* and takes its amg_residual / amg_prolong_add where the back-end offers them.              */
+int GCGE_SolverTakesScaledRhs (struct OPS_ *ops);
 /*     BlockAMG as the solver of GCG's W systems, the way the reference's SiO2 driver sets it up under OPS_USE_AMG
  *     (test/test_eig_sol_SiO2_MAT.c:96-128,160-170): hierarchy from ops->MultiGridCreate (at most max_levels), work blocks of
  *     block_size columns per level, max_iter = {cycles, smooth0, smooth0, smooth, smooth, ...} (reference: {1, 5, 5, 4, 4, ...}),

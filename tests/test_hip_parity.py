@@ -9,6 +9,7 @@ from helpers import OracleBackend, csr_to_scipy, gcg_on, lap3d_exact, load_golde
 from slot_cases import run_bpcg_case, run_orth_cases, run_slot_cases, _close
 from solver_setup import bpcg_setup, orth_setup
 from gcge_amd.lib import make_problem
+from gcge_amd.ops_struct import LINSOL_ARGS
 
 pytestmark = pytest.mark.gpu
 
@@ -849,7 +850,7 @@ def test_lincomb_row_fragment_variants_vs_oracle(both, rf):
             hip.ops.lincomb(yh, yh, (0, kk), (kk, kk + 64), coef, kk, one, 0)
             ora.ops.lincomb(yo, yo, (0, kk), (kk, kk + 64), coef, kk, one, 0)
             _close(hip.mv_to_numpy(yh, n, 0, 264), ora.mv_to_numpy(yo, n, 0, 264), tol=1e-12, what="lincomb W -= V C in place k=%d rf=%d" % (kk, rf))
-        # output columns INSIDE the input range (what GCGE_SetInplaceLinearComb declares safe: X = X R^-1 of the block
+        # output columns INSIDE the input range (what GCGE_BACKEND.inplace_lincomb_cols declares safe: X = X R^-1 of the block
         # orthonormalisation, P = V[:, N..W) coef): bit-identical to the same update staged through another block
         for (x0, kk, y0, mm) in [(4, 64, 4, 64), (0, 192, 64, 64), (2, 128, 2, 128), (6, 48, 22, 16), (0, 131, 100, 31), (1, 33, 1, 33)]:
             Y0 = uniform(55, (n, 200)) - 0.5
@@ -869,7 +870,7 @@ def test_lincomb_row_fragment_variants_vs_oracle(both, rf):
 
 def test_gcg_inplace_panel_updates_equal_staged_ones(hip):
     """The solver stack skips the work block + copy back of X = X R^-1 (block orthonormalisation) and of ComputeP when the
-    back-end declares row-wise panel updates in place safe (GCGE_SetInplaceLinearComb): same arithmetic, so the
+    back-end declares row-wise panel updates in place safe (GCGE_BACKEND.inplace_lincomb_cols): same arithmetic, so the
     eigensolve is identical bit for bit to the staged form (GCGE_NO_INPLACE_LINCOMB=1)."""
     import os
     hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
@@ -1110,7 +1111,7 @@ def test_fused_cg_small_direction_ring(hip):
 
 def test_gcg_small_ring_takes_the_idle_blocks(hip):
     """With the ring capped at 3 (GCGE_CG_RING: what memory leaves at BASELINE config 4's shape) the fused solver adds its
-    never-written w block and the blocks the driver declares idle (GCGE_SetLinearSolverIdleBlocks) as further slots: x is
+    never-written w block and the blocks the driver declares idle (GCGE_LINSOL_ARGS.idle_blocks) as further slots: x is
     then brought up to date every 6th instead of every 2nd iteration — same eigensolve; with those extras switched off
     (GCGE_CG_NO_W_SLOT, GCGE_CG_NO_IDLE_SLOTS) likewise."""
     import os
@@ -1239,7 +1240,7 @@ def test_cg_start_from_scale_factors_equals_start_from_formed_rhs(hip, size, m):
 @pytest.mark.parametrize("extra_env", [{}, {"GCGE_CG_NO_RECOMPUTE": "1"}])
 def test_gcg_scaled_rhs_start_equals_formed_rhs(hip, extra_env):
     """B == NULL: the driver hands the fused solver b = x diag(lambda + sigma) as scale factors instead of forming it
-    (GCGE_SetLinearSolverRhsScale).  Same eigensolve: counts equal, Ritz values to rounding (where the formed b sits on
+    (GCGE_LINSOL_ARGS.rhs_scale).  Same eigensolve: counts equal, Ritz values to rounding (where the formed b sits on
     an odd column the old start took the unfused route, so the two runs are not bit-identical); with the product stored
     (here: recompute form switched off — what matrices without a pattern form get) the start is product + ONE sweep for
     r = x diag(scale) - w, p0 = r and r.r (round 4: cg_start_scaled_stored) instead of forming b."""
@@ -1825,9 +1826,9 @@ def test_fused_cg_tight_tolerances(hip, size):
     hip.free_matrix(mat)
 
 
-def test_fused_cg_user_tolerance_and_active_column_statistics(hip):
+def test_fused_cg_user_tolerance_from_solver_args_and_active_column_statistics(hip):
     """tol_type "user" of BlockPCG (src/ops_lin_sol.c:186-192: a column stops at tol * |scale_j|, the scales published
-    through GCGE_SetLinearSolverUserScale as the GCG driver does with lambda_j + sigma) against the host-scalar BlockPCG
+    through GCGE_LINSOL_ARGS.user_scale as the GCG driver does with lambda_j + sigma) against the host-scalar BlockPCG
     of libgcge_host on the same operands; and the column statistics of the device-scalar loop (they were a
     constant): columns that retire early lower the active share, surplus iterations are counted apart."""
     from solver_setup import bpcg_setup
@@ -1835,7 +1836,7 @@ def test_fused_cg_user_tolerance_and_active_column_statistics(hip):
     g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     g.gcge_hip_bpcg_column_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
     g.gcge_hip_bpcg_surplus_iters.restype = C.c_long
-    h.GCGE_SetLinearSolverUserScale.argtypes = [C.POINTER(C.c_double), C.c_int]
+    h.GCGE_SetLinearSolverArgs.argtypes = [C.POINTER(LINSOL_ARGS)]
     A, _ = make_problem("lap3d", 16)
     S = csr_to_scipy(A); n = A.nrows
     mat = hip.matrix(A)
@@ -1846,11 +1847,11 @@ def test_fused_cg_user_tolerance_and_active_column_statistics(hip):
     ci0, ai0 = C.c_long(), C.c_long(); g.gcge_hip_bpcg_column_stats(C.byref(ci0), C.byref(ai0)); sp0 = g.gcge_hip_bpcg_surplus_iters()
     g.gcge_hip_bpcg_setup(hip.ops_handle, 400, 1e-30, 1e-6, b"user")
     b = hip.mv_from_numpy(mat, Bm); x = hip.mv_from_numpy(mat, np.zeros((n, nrhs)))
-    h.GCGE_SetLinearSolverUserScale(sc, nrhs)
+    h.GCGE_SetLinearSolverArgs(C.byref(LINSOL_ARGS(user_scale=sc, n_user_scale=nrhs)))
     try:
         hip.ops.multi_linear_solver(mat, b, x, (0, 0), (nrhs, nrhs))
     finally:
-        h.GCGE_SetLinearSolverUserScale(None, 0)
+        h.GCGE_SetLinearSolverArgs(None)
     it = C.c_int(); g.gcge_hip_bpcg_stats(None, None, C.byref(it))
     X = hip.mv_to_numpy(x, n, 0, nrhs)
     true_res = np.linalg.norm(Bm - S @ X, axis=0)
@@ -1871,7 +1872,7 @@ def test_fused_cg_user_tolerance_and_active_column_statistics(hip):
 def test_gcg_auto_shift_with_the_fused_solver(hip, key):
     """f1: -gcge_compW_cg_auto_shift 1 together with the back-end's own solver behind flag 1 — the combination the
     reference asserts away (ops_eig_sol_gcg.c:497) because its hook hands the solver A only; here sigma (computed as
-    :483-492) travels through GCGE_SetLinearSolverShift and the fused CG solves (A + sigma B) w = (lambda + sigma) B x.
+    :483-492) travels through GCGE_LINSOL_ARGS and the fused CG solves (A + sigma B) w = (lambda + sigma) B x.
     Same converged count and Ritz values as the reference's run with its own BlockPCG."""
     g = hip.g
     g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]

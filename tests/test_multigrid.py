@@ -424,8 +424,8 @@ def test_gcg_with_block_amg_on_hip_matches_oracle(hip, oracle, kind, size, nev, 
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,size,m", [("lap3d", 16, 8), ("lap3d", 24, 22), ("fe3d", 12, 6), ("sio2", 14, 4)])
 def test_block_amg_fused_vcycle_steps_equal_the_slot_calls(hip, kind, size, m, monkeypatch):
-    """The V-cycle's residual r = b - A x and its correction x += P e as one sweep each on the HIP table (GCGE_SetBlockAMGFusions:
-    the CG's start sweep with a single store, a prolongation kernel that adds in place) against the slot calls they replace
+    """The V-cycle's residual r = b - A x and its correction x += P e as one sweep each on the HIP table (GCGE_BACKEND.amg_residual /
+    amg_prolong_add: the CG's start sweep with a single store, a prolongation kernel that adds in place) against the slot calls they replace
     (MatDotMultiVec + MultiVecAxpby, MultiVecFromItoJ + MultiVecAxpby; reference src/ops_lin_sol.c:596-640): the same x bit for
     bit, and the solve converges to the direct solution."""
     import scipy.sparse.linalg as sla
