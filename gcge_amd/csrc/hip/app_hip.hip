@@ -1519,6 +1519,22 @@ static void HIP_MultiVecQtAP(char ntsA, char ntsd, void** mvQ, void* matA, void*
   }
 }
 
+// PAS (csrc/host/pas.c): the bordered product of its composite table (pas_border.hip), the identity of a standard problem whose
+// hierarchy holds the coarse masses P^T P, and the row-order check of the levels (the prolongations are in the hierarchy's order)
+extern "C" int gcge_hip_pas_border(void** QX, int s, void** q, int q0, void** y, int y0, int m, double beta,
+                                   const double* t, int ldt, double* g, int ldg);
+static void* HIP_MatIdentity(void* like) {
+  const GCGE_HIP_MAT_* A = (const GCGE_HIP_MAT_*)like;
+  if (A == nullptr || A->rect_ncols > 0 || A->nghost > 0 || A->part_world > 1) return nullptr;   // whole matrices on one rank
+  const int n = A->nrows;
+  std::vector<int> rp((size_t)n + 1), ci((size_t)n); std::vector<double> va((size_t)n, 1.0);
+  for (int r = 0; r <= n; ++r) rp[r] = r;
+  for (int r = 0; r < n; ++r) ci[r] = r;
+  return (void*)gcge_hip_mat_create(n, n, 0, rp.data(), ci.data(), va.data());
+}
+static void HIP_MatFree(void* m) { gcge_hip_mat_destroy((GCGE_HIP_MAT*)m); }
+static int HIP_MatRowsAsGiven(void* m) { const GCGE_HIP_MAT_* A = (const GCGE_HIP_MAT_*)m; return A == nullptr || real_perm(A->perm) == nullptr; }
+
 extern "C" void OPS_HIP_Set(struct OPS_* ops) {
   if (gcge_hip_init(-1) != 0) {
     fprintf(stderr, "OPS_HIP_Set: HIP back-end unavailable (no GPU): aborting — there is no CPU fallback\n");
@@ -1554,5 +1570,7 @@ extern "C" void OPS_HIP_Set(struct OPS_* ops) {
   be.amg_prolong_add = HIP_AmgProlongAdd;
   be.amg_form_rhs = HIP_AmgFormRhs;           // b = x diag(scale) in one sweep
   gcge_hip_bpcg_backend(&be);                 // the fused device CG: BlockAMG's smoother, and the solver of unformed b = x diag(scale)
+  be.pas_border = gcge_hip_pas_border;        // PAS: y += QX t and g = QX^T q in one pass over QX
+  be.mat_identity = HIP_MatIdentity; be.mat_free = HIP_MatFree; be.mat_rows_as_given = HIP_MatRowsAsGiven;
   GCGE_SetBackend(ops, &be);
 }

@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include "gcge_solver.h"
+#include "gcge_pas.h"
 
 /* ---- BlockAMG as the solver of the W systems: what the reference's SiO2 driver does under OPS_USE_AMG
  * (test/test_eig_sol_SiO2_MAT.c:96-128,160-170): hierarchy from ops->MultiGridCreate, per-level work blocks, parameter arrays
@@ -177,4 +178,113 @@ int GCGE_RunGCGGiven(void *A, void *B, int flag, int argc, char *argv[], struct 
 int TestEigenSolverGCG(void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops)
 {
 	return GCGE_RunGCG(A, B, flag, argc, argv, ops, NULL, NULL, NULL);
+}
+
+/* ---- PAS, then GCG warm-started from its converged vectors: the flow of the reference's test/test_eig_sol_pas.c ------
+ * The hierarchy comes from ops->MultiGridCreate (levels 0 .. L-1, level_aux = L-1).  For a standard problem it is built from
+ * the back-end's identity (GCGE_PAS_MatIdentityOf): its Galerkin levels are the coarse masses P^T P that PAS needs; level 0
+ * stays B == NULL. */
+int GCGE_RunPAS(void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops,
+		double *eval_out, void ***evec_out, GCGE_PAS_RESULT *res)
+{
+	int nevConv = 30, multiMax = 1, block_size, nevMax, nevInit, L, l, i, rc = 0, pas_conv;
+	double gapMin = 1e-5, tol_pas[2] = {1e-1, 1e-8}, tol_rr[2] = {1e-1, 1e-8}, t0;
+	int pas_levels = 3, pas_max_iter = 50, pas_rr_max_iter = 100, pas_only = 0, sizeV;
+	void **A_array = NULL, **B_array = NULL, **P_array = NULL, ***mv_ws[7], **evec, *I0 = NULL;
+	GCGE_MAT_FREE_FN mat_free = NULL;
+	double *eval, *dbl_ws; int *int_ws; long ldbl, lint;
+	PASSolver *pas;
+
+	if (res != NULL) memset(res, 0, sizeof(*res));
+	ops->GetOptionFromCommandLine("-nevConv", 'i', &nevConv, argc, argv, ops);
+	nevMax = 2 * nevConv;
+	ops->GetOptionFromCommandLine("-nevMax", 'i', &nevMax, argc, argv, ops);
+	block_size = nevConv < 30 ? (nevMax - nevConv) : nevConv / 5;
+	ops->GetOptionFromCommandLine("-blockSize", 'i', &block_size, argc, argv, ops);
+	nevInit = nevMax;
+	ops->GetOptionFromCommandLine("-nevInit", 'i', &nevInit, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_pas_levels", 'i', &pas_levels, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_pas_max_iter", 'i', &pas_max_iter, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_pas_abs_tol", 'f', &tol_pas[0], argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_pas_rel_tol", 'f', &tol_pas[1], argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_pas_rr_max_iter", 'i', &pas_rr_max_iter, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_pas_only", 'i', &pas_only, argc, argv, ops);
+	if (ops->MultiGridCreate == NULL || pas_levels < 2) {
+		ops->Printf("-gcge_pas_levels: PAS needs the back-end's MultiGridCreate and at least 2 levels\n");
+		return -7;
+	}
+	if (B == NULL) {
+		GCGE_MAT_IDENTITY_FN identity = GCGE_PAS_MatIdentityOf(ops, &mat_free);
+		if (identity == NULL || (I0 = identity(A)) == NULL) {
+			ops->Printf("PAS: a standard problem needs the back-end's identity upload (GCGE_BACKEND.mat_identity)\n");
+			return -9;
+		}
+	}
+	L = pas_levels;
+	ops->MultiGridCreate(&A_array, &B_array, &P_array, &L, A, B != NULL ? B : I0, ops);
+	if (L < 2) {
+		ops->Printf("PAS: the hierarchy has %d level(s); PAS needs 2 or more\n", L);
+		ops->MultiGridDestroy(&A_array, &B_array, &P_array, &L, ops);
+		if (I0 != NULL && mat_free != NULL) mat_free(I0);
+		return -7;
+	}
+	if (B == NULL) B_array[0] = NULL;   /* level 0 of a standard problem: the identity is not applied */
+
+	sizeV = nevMax + 2 * block_size;
+	for (i = 0; i < 7; ++i) {
+		mv_ws[i] = (void***)calloc(L, sizeof(void**));
+		for (l = 0; l < L; ++l) {
+			int cols = i < 6 ? nevMax : sizeV;
+			ops->MultiVecCreateByMat(&mv_ws[i][l], cols, A_array[l], ops);
+			ops->MultiVecSetRandomValue(mv_ws[i][l], 0, cols, ops);
+		}
+	}
+	GCGE_PASWorkspaceSizes(nevMax, block_size, &ldbl, &lint);
+	dbl_ws = (double*)calloc(ldbl, sizeof(double)); int_ws = (int*)calloc(lint, sizeof(int));
+	if (nevMax < 1) nevMax = 1;
+	eval = (double*)calloc((size_t)nevMax, sizeof(double));
+	ops->MultiVecCreateByMat(&evec, nevMax, A, ops);
+
+	srand(0);
+	t0 = ops->GetWtime();
+	ops->Printf("===============================================\n");
+	ops->Printf("PAS Eigen Solver\n");
+	EigenSolverSetup_PAS(multiMax, gapMin, nevMax, block_size, tol_pas, pas_max_iter, block_size, tol_rr, pas_rr_max_iter,
+			A_array, B_array, P_array, L, mv_ws, dbl_ws, int_ws, ops);
+	pas = (PASSolver*)ops->eigen_solver_workspace;
+	pas_conv = nevConv;
+	ops->EigenSolver(A, B, eval, evec, 0, &pas_conv, ops);
+	if (pas->status != 0) rc = pas->status;
+	if (res != NULL) {
+		res->nevConv = pas_conv; res->numIter = pas->numIter; res->num_levels = L;
+		res->seconds = ops->GetWtime() - t0;
+	}
+	ops->Printf("PAS: numIter = %d, nevConv = %d, time %.3f\n", pas->numIter, pas_conv, ops->GetWtime() - t0);
+
+	for (i = 0; i < 7; ++i) {
+		for (l = 0; l < L; ++l) ops->MultiVecDestroy(&mv_ws[i][l], i < 6 ? nevMax : sizeV, ops);
+		free(mv_ws[i]);
+	}
+	if (B == NULL) B_array[0] = I0;
+	ops->MultiGridDestroy(&A_array, &B_array, &P_array, &L, ops);
+	if (I0 != NULL && mat_free != NULL) mat_free(I0);
+	free(dbl_ws); free(int_ws);
+
+	if (rc == 0 && !pas_only) {
+		int given = pas_conv < nevInit ? pas_conv : nevInit;
+		rc = GCGE_RunGCGGiven(A, B, flag, argc, argv, ops, eval, evec, given, res != NULL ? &res->gcg : NULL);
+	}
+	if (eval_out != NULL) memcpy(eval_out, eval, nevMax * sizeof(double));
+	if (evec_out != NULL) *evec_out = evec;
+	else ops->MultiVecDestroy(&evec, nevMax, ops);
+	free(eval);
+	return rc;
+}
+
+int TestEigenSolverPAS(void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops)
+{
+	GCGE_PAS_RESULT r; int rc = GCGE_RunPAS(A, B, flag, argc, argv, ops, NULL, NULL, &r);
+	ops->Printf("PAS: nevConv = %d, numIter = %d, levels = %d, %.3f s; GCG: nevConv = %d, numIter = %d, %.3f s (rc %d)\n",
+			r.nevConv, r.numIter, r.num_levels, r.seconds, r.gcg.nevConv, r.gcg.numIter, r.gcg.seconds, rc);
+	return rc;
 }

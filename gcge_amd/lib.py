@@ -30,6 +30,12 @@ class RunResult(C.Structure):
                 ("timing", Timing)]
 
 
+class PASResult(C.Structure):
+    """GCGE_PAS_RESULT (include/gcge_solver.h): PAS's converged pairs, iterations, levels and seconds, then the warm-started GCG."""
+    _fields_ = [("nevConv", C.c_int), ("numIter", C.c_int), ("num_levels", C.c_int), ("seconds", C.c_double),
+                ("gcg", RunResult)]
+
+
 def build_libs(hip=True, verbose=False):
     """make -C gcge_amd/csrc [host|all]  (hipcc cross-compiles gfx950 without a GPU)."""
     target = "all" if hip else "host"
@@ -179,6 +185,38 @@ def run_gcg(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False, given=No
     if keep_evec:
         return ev, res, evec
     return ev, res
+
+
+def run_pas(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False):
+    """GCGE_RunPAS through the operator table `ops`: PAS (the multigrid eigensolver over the back-end's hierarchy), then GCG
+    warm-started from PAS's converged vectors unless args hold -gcge_pas_only 1.  Returns (eval, pas_result, gcg_result)
+    (and the eigenvector block handle, nevMax columns, with keep_evec: the caller destroys it).  Raises on an error code
+    (-7: no MultiGridCreate or fewer than 2 levels, -8: a re-ordered level, -9: B is None and the back-end has no identity)."""
+    import numpy as np
+    h = host_lib()
+    args = ["gcge"] + [str(a) for a in args]
+    if quiet and "-gcge_print_usage" not in args:
+        args += ["-gcge_print_usage", "0"]
+    argc, argv = make_argv(args)
+    nev, nev_max = 30, None
+    for i, a in enumerate(args):
+        if a == "-nevConv":
+            nev = int(args[i + 1])
+        if a == "-nevMax":
+            nev_max = int(args[i + 1])
+    nev_max = nev_max or 2 * nev
+    ev = np.zeros(nev_max)
+    res = PASResult()
+    evec = C.c_void_p()
+    h.GCGE_RunPAS.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_void_p,
+                              C.POINTER(C.c_double), C.c_void_p, C.POINTER(PASResult)]
+    rc = h.GCGE_RunPAS(matA, matB, flag, argc, argv, ops, ev.ctypes.data_as(C.POINTER(C.c_double)),
+                       C.cast(C.byref(evec), C.c_void_p) if keep_evec else None, C.byref(res))
+    if rc != 0:
+        raise RuntimeError("GCGE_RunPAS rc=%d" % rc)
+    if keep_evec:
+        return ev, res, res.gcg, evec
+    return ev, res, res.gcg
 
 
 class HipBackend:

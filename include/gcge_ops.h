@@ -190,7 +190,11 @@ const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs (void);              /* never N
  *   amg_residual  r[:, r0..) = b[:, b0..) - A x[:, x0..)  and  amg_prolong_add  xf[:, f0..) += P xc[:, c0..)  as one sweep each,
  *                 bit for bit the slot calls they replace (src/ops_lin_sol.c:596-606, :626-640); 0 declines.
  *   amg_form_rhs  b[:, b0..) = x[:, x0..) diag(scale) in one sweep: BlockAMG then takes rhs_scale systems; 0 declines.
- *   scaled_rhs_solver   the back-end's solver that takes rhs_scale systems, as installed in ops->MultiLinearSolver.        */
+ *   scaled_rhs_solver   the back-end's solver that takes rhs_scale systems, as installed in ops->MultiLinearSolver.
+ *   pas_border    the bordered product of PAS's composite table in one pass over QX (GCGE_PAS_BORDER_FN, gcge_pas.h).
+ *   mat_identity / mat_free   the identity of the size of a (whole, one-rank) matrix through the back-end's normal upload, and its
+ *                 release: PAS's hierarchy of a standard problem takes its coarse masses P^T P from it (NULL: not offered).
+ *   mat_rows_as_given   1 when the device rows of a matrix are in the order the caller gave them (0: the back-end re-ordered). */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -206,6 +210,10 @@ typedef struct GCGE_BACKEND_ {
 	GCGE_SMOOTHER_SETUP_FN amg_smoother_setup; GCGE_SMOOTHER_RESIDUAL_FN amg_smoother_residual;
 	GCGE_AMG_RESIDUAL_FN amg_residual; GCGE_AMG_PROLONG_ADD_FN amg_prolong_add; GCGE_AMG_FORM_RHS_FN amg_form_rhs;
 	GCGE_LINSOL_FN scaled_rhs_solver;
+	int  (*pas_border) (void **QX, int s, void **q, int q0, void **y, int y0, int m, double beta,
+			const double *t, int ldt, double *g, int ldg);
+	void *(*mat_identity) (void *like); void (*mat_free) (void *mat);
+	int  (*mat_rows_as_given) (void *mat);
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

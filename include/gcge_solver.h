@@ -163,6 +163,82 @@ int GCGE_RunGCG (void *A, void *B, int flag, int argc, char *argv[], struct OPS_
 int GCGE_RunGCGGiven (void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops,
 		double *eval, void **evec, int nevGiven, GCGE_RunResult *res);
 
+/* ---- PAS eigensolver (sets ops->EigenSolver; reference src/ops_eig_sol_pas.h) -------------------------------------
+ * Rayleigh-Ritz on the coarsest level H = num_levels - 1, then per iteration: prolongate X one level (down to level 0),
+ * smooth A X = Lambda B X by BlockAMG from that level down, make X B-orthogonal to range(P_H) and B-orthonormal, solve the
+ * augmented problem (gcge_pas.h) with our GCG over the composite table, form the Ritz vectors P_H q + X x; on level 0 the
+ * residuals are checked (abs AND rel).  A_array / B_array / P_array: the back-end's hierarchy (ops->MultiGridCreate) built
+ * with the process-wide scale (gcge_mg_get_defaults: A_{l+1} = scale P^T A_l P); B_array[l] the Galerkin masses, B_array[0]
+ * NULL for a standard problem (then every B_array[l], l >= 1, must be P^T P: GCGE_RunPAS builds the hierarchy from the
+ * identity).  mv_ws[i][l]: blocks of level l — i = 0 .. 5 nevMax columns, i = 6 nevMax + 2 block_size_rr columns.
+ * dbl_ws / int_ws: at least what GCGE_PASWorkspaceSizes returns (the inner GCG's arenas are PAS's own).                 */
+typedef struct PASSolver_ {
+	void   **A; void **B; void **P;
+	double *eval; void **evec; int nevConv;
+	int    nevMax; int multiMax; double gapMin;
+	int    block_size; double tol[2]; int numIterMax;
+	int    num_levels; int level_aux;
+	int    numIter;
+	int    block_size_rr; double tol_rr[2]; int numIterMax_rr;
+	void   ***mv_ws[7]; double *dbl_ws; int *int_ws;
+	int    check_conv_max_num;
+	int    compN_user_defined_multi_linear_solver;
+	int    compN_bamg_max_iter[32]; double compN_bamg_rate[16]; double compN_bamg_tol[16]; char compN_bamg_tol_type[8];
+	int    orthX_user_defined_multi_linear_solver;
+	int    orthX_ls_max_iter; double orthX_ls_rate; double orthX_ls_tol; char orthX_ls_tol_type[8];
+	char   orthX_orth_method[8]; int orthX_orth_block_size; int orthX_orth_max_reorth; double orthX_orth_zero_tol;
+	int    compRR_gcg_check_conv_max_num;
+	char   compRR_gcg_initX_orth_method[8]; int compRR_gcg_initX_orth_block_size; int compRR_gcg_initX_orth_max_reorth;
+	double compRR_gcg_initX_orth_zero_tol;
+	char   compRR_gcg_compP_orth_method[8]; int compRR_gcg_compP_orth_block_size; int compRR_gcg_compP_orth_max_reorth;
+	double compRR_gcg_compP_orth_zero_tol;
+	char   compRR_gcg_compW_orth_method[8]; int compRR_gcg_compW_orth_block_size; int compRR_gcg_compW_orth_max_reorth;
+	double compRR_gcg_compW_orth_zero_tol;
+	int    compRR_gcg_compW_cg_max_iter; double compRR_gcg_compW_cg_rate; double compRR_gcg_compW_cg_tol;
+	char   compRR_gcg_compW_cg_tol_type[8];
+	int    compRR_gcg_compRR_min_num; double compRR_gcg_compRR_min_gap; double compRR_gcg_compRR_tol;
+	double scale;      /* the hierarchy's scale (A_{l+1} = scale P^T A_l P), read at set-up */
+	int    status;     /* 0, or < 0: the last solve stopped (-8: a level the back-end re-ordered) */
+} PASSolver;
+
+void EigenSolverSetup_PAS (int multiMax, double gapMin, int nevMax,
+		int block_size, double tol[2], int numIterMax,
+		int block_size_rr, double tol_rr[2], int numIterMax_rr,
+		void **A_array, void **B_array, void **P_array, int num_levels,
+		void ***mv_ws[7], double *dbl_ws, int *int_ws, struct OPS_ *ops);
+void EigenSolverSetParameters_PAS (int check_conv_max_num,
+		int compN_user_defined_multi_linear_solver,
+		int *compN_bamg_max_iter, double *compN_bamg_rate, double *compN_bamg_tol, const char *compN_bamg_tol_type,
+		int orthX_user_defined_multi_linear_solver,
+		int orthX_ls_max_iter, double orthX_ls_rate, double orthX_ls_tol, const char *orthX_ls_tol_type,
+		const char *orthX_orth_method, int orthX_orth_block_size, int orthX_orth_max_reorth, double orthX_orth_zero_tol,
+		int compRR_gcg_check_conv_max_num,
+		const char *compRR_gcg_initX_orth_method, int compRR_gcg_initX_orth_block_size,
+		int compRR_gcg_initX_orth_max_reorth, double compRR_gcg_initX_orth_zero_tol,
+		const char *compRR_gcg_compP_orth_method, int compRR_gcg_compP_orth_block_size,
+		int compRR_gcg_compP_orth_max_reorth, double compRR_gcg_compP_orth_zero_tol,
+		const char *compRR_gcg_compW_orth_method, int compRR_gcg_compW_orth_block_size,
+		int compRR_gcg_compW_orth_max_reorth, double compRR_gcg_compW_orth_zero_tol,
+		int compRR_gcg_compW_cg_max_iter, double compRR_gcg_compW_cg_rate, double compRR_gcg_compW_cg_tol,
+		const char *compRR_gcg_compW_cg_tol_type,
+		int compRR_gcg_compRR_min_num, double compRR_gcg_compRR_min_gap, double compRR_gcg_compRR_tol,
+		struct OPS_ *ops);
+void GCGE_PASWorkspaceSizes (int nevMax, int block_size_rr, long *length_dbl_ws, long *length_int_ws);
+
+/* PAS, then (unless -gcge_pas_only 1) GCG warm-started from PAS's nevConv vectors: test/test_eig_sol_pas.c.
+ * Options: -gcge_pas_levels (3), -gcge_pas_max_iter (50), -gcge_pas_abs_tol / -gcge_pas_rel_tol (1e-1 / 1e-8),
+ * -gcge_pas_rr_max_iter (100), -gcge_pas_only (0), plus GCG's.  eval: nevMax doubles (PAS's values with -gcge_pas_only).
+ * Returns 0; -7: the back-end has no MultiGridCreate or the hierarchy has fewer than 2 levels; -8: a level the back-end
+ * re-ordered (the prolongations are in the hierarchy's numbering); -9: B == NULL and no matrix upload (gcge_pas.h).     */
+typedef struct GCGE_PAS_RESULT_ {
+	int nevConv, numIter, num_levels;
+	double seconds;
+	GCGE_RunResult gcg;   /* the warm-started GCG (zero with -gcge_pas_only 1) */
+} GCGE_PAS_RESULT;
+int GCGE_RunPAS (void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops,
+		double *eval, void ***evec_out /* NULL: destroy */, GCGE_PAS_RESULT *res);
+int TestEigenSolverPAS (void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops);
+
 #ifdef __cplusplus
 }
 #endif
