@@ -92,6 +92,15 @@ extern "C" void gcge_hip_halo_native_free(struct GCGE_HIP_MAT_* A);
 // multigrid.hip: the MultiGridCreate / MultiGridDestroy slots of OPS_HIP_Set
 extern "C" void gcge_hip_multigrid_create(void*** A_array, void*** B_array, void*** P_array, int* num_levels, void* A, void* B, struct OPS_* ops);
 extern "C" void gcge_hip_multigrid_destroy(void*** A_array, void*** B_array, void*** P_array, int* num_levels, struct OPS_* ops);
+// mg_device.hip: the device side of MultiGridCreate's hierarchy (d2h: bytes copied device to host are added there; may be NULL)
+extern "C" int gcge_hip_mg_detect_grid_device(int n, const int* d_rowptr, const int* d_colidx, int dims[3], long* d2h);
+extern "C" void gcge_hip_mg_agg_grid_device(const int dims[3], int* d_agg, int* d_ptr, int* d_mem, int cdims[3]);
+extern "C" int gcge_hip_mg_galerkin_device(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
+                                           const int* d_ptr, const int* d_mem, double scale, int** d_rp_out, int** d_ci_out, double** d_va_out,
+                                           long* nnz_out, long* d2h);
+extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_rect_device(int nf, int nc, const int* d_agg, const int* d_ptr, const int* d_mem);
+extern "C" int gcge_hip_mg_download_csr(int nrows, int ncols, long nnz, const int* d_rp, const int* d_ci, const double* d_va, GCGE_CSR* out, long* d2h);
+void gcge_hip_mg_members_host(const int* agg, int nf, int nc, std::vector<int>& ptr, std::vector<int>& mem);
 // block_pcg.hip: the fused CG's part of the back-end record OPS_HIP_Set registers (the BlockAMG smoother, the scaled-rhs solver)
 extern "C" void gcge_hip_bpcg_backend(GCGE_BACKEND* be);
 // A column scaling the slots hold back (column-wise Gram-Schmidt, app_hip.hip) is applied now.  First statement of every EXPORTED

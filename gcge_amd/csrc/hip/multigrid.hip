@@ -14,6 +14,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <array>
 #include <vector>
 
 #include "gcge_hip.h"
@@ -73,6 +74,18 @@ static void download_csr(const GCGE_HIP_MAT_* A, GCGE_CSR* out, std::vector<int>
   out->rowptr = rp.data(); out->colidx = ci.data(); out->val = va.data();
 }
 
+// the last MultiGridCreate: seconds per phase and bytes copied device to host
+enum { MG_DETECT, MG_AGGREGATE, MG_GALERKIN, MG_TRANSFER, MG_COARSE, MG_OTHER, MG_NPHASE };
+static double g_mg_phase[MG_NPHASE]; static long g_mg_d2h = 0;
+static int g_mg_mode = 0;
+extern "C" void gcge_hip_multigrid_mode(int mode) { g_mg_mode = mode; }
+extern "C" int gcge_hip_multigrid_get_mode(void) { return g_mg_mode; }
+extern "C" void gcge_hip_multigrid_stats(double* seconds6, long* d2h_bytes) {
+  if (seconds6 != nullptr) for (int i = 0; i < MG_NPHASE; ++i) seconds6[i] = g_mg_phase[i];
+  if (d2h_bytes != nullptr) *d2h_bytes = g_mg_d2h;
+}
+static long csr_bytes(long nrows, long nnz) { return (nrows + 1) * (long)sizeof(int) + nnz * (long)(sizeof(int) + sizeof(double)); }
+
 static gcge_hip_slab_factory_fn g_slab_factory = nullptr; static void* g_slab_factory_ctx = nullptr;
 extern "C" void gcge_hip_set_slab_factory(gcge_hip_slab_factory_fn fn, void* ctx) { g_slab_factory = fn; g_slab_factory_ctx = ctx; }
 
@@ -131,20 +144,170 @@ static void multigrid_create_slab(void*** A_array, void*** B_array, void*** P_ar
   *num_levels = L;
 }
 
+// ------------------------------------------------------------------------------------------------------------ the device path
+// gcge_mg_build's hierarchy (same stopping rules, same defaults) from the device-resident CSR of A (and B), one level after the other:
+// grid detection from the sampled rows only, grid aggregates and their members on the device (graph levels: the unchanged host
+// aggregation on that level's CSR, which is then downloaded), the Galerkin products on the device (mg_device.hip), P / P^T built on
+// the device.  Every coarse level is downloaded (8 x smaller than its parent on a grid) for gcge_hip_mat_create, which analyses it
+// exactly as in the host path; the next level is coarsened from the Galerkin output, in hierarchy order — never from the coarse
+// handle, whose rows gcge_hip_mat_create may re-order.  Returns false with nothing left behind when a level is out of the kernels'
+// reach (a coarse row of more than 512 distinct columns, 2^31 entries): the caller then builds on the host.
+struct DevCsr { int n; long nnz; int* rp; int* ci; double* va; bool owned; };
+static void devcsr_free(DevCsr& c) { if (c.owned) { hipFree(c.rp); hipFree(c.ci); hipFree(c.va); } c = DevCsr{0, 0, nullptr, nullptr, nullptr, false}; }
+
+static bool multigrid_create_device(void*** A_array, void*** B_array, void*** P_array, int* num_levels, const GCGE_HIP_MAT_* mA,
+                                    const GCGE_HIP_MAT_* mB, void* A, void* B) {
+  double scale = 0.5, theta = 0.25; int min_rows = 64;
+  gcge_mg_get_defaults(&scale, &min_rows, &theta);
+  const int max_levels = *num_levels;
+  GCGE_HIP_CHECK(hipStreamSynchronize((hipStream_t)gcge_hip_stream()));
+  double t = mg_now();
+  int dims[3] = {0, 0, 0};
+  const int have_grid = gcge_hip_mg_detect_grid_device(mA->nrows, mA->d_rowptr, mA->d_colidx, dims, &g_mg_d2h);
+  g_mg_phase[MG_DETECT] += mg_now() - t;
+  std::vector<GCGE_HIP_MAT*> As, Bs, Ps;
+  std::vector<std::array<int, 3>> ldims;
+  DevCsr fa{mA->nrows, mA->nnz, mA->d_rowptr, mA->d_colidx, mA->d_val, false};
+  DevCsr fb{0, 0, nullptr, nullptr, nullptr, false};
+  if (mB != nullptr) fb = DevCsr{mB->nrows, mB->nnz, mB->d_rowptr, mB->d_colidx, mB->d_val, false};
+  GCGE_CSR hostA; memset(&hostA, 0, sizeof hostA);       // the current level's CSR on the host (graph aggregation), once downloaded
+  bool ok = true;
+  for (int l = 0; l + 1 < max_levels; ++l) {
+    const int nf = fa.n;
+    if (nf <= min_rows) break;
+    t = mg_now();
+    int nc = 0, cdims[3] = {0, 0, 0};
+    int *d_agg = nullptr, *d_ptr = nullptr, *d_mem = nullptr;
+    GCGE_HIP_CHECK(hipMalloc(&d_agg, (size_t)nf * sizeof(int)));
+    GCGE_HIP_CHECK(hipMalloc(&d_mem, (size_t)nf * sizeof(int)));
+    if (have_grid) {
+      nc = ((dims[0] + 1) / 2) * ((dims[1] + 1) / 2) * ((dims[2] + 1) / 2);
+      GCGE_HIP_CHECK(hipMalloc(&d_ptr, ((size_t)nc + 1) * sizeof(int)));
+      gcge_hip_mg_agg_grid_device(dims, d_agg, d_ptr, d_mem, cdims);
+      g_mg_phase[MG_AGGREGATE] += mg_now() - t;
+    } else {
+      if (hostA.rowptr == nullptr) {
+        if (gcge_hip_mg_download_csr(nf, nf, fa.nnz, fa.rp, fa.ci, fa.va, &hostA, &g_mg_d2h) != 0) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
+        g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
+      }
+      std::vector<int> agg((size_t)nf), ptr, mem;
+      nc = gcge_mg_aggregate_graph(&hostA, theta, agg.data());
+      if (nc >= 1) gcge_hip_mg_members_host(agg.data(), nf, nc, ptr, mem);
+      g_mg_phase[MG_AGGREGATE] += mg_now() - t; t = mg_now();
+      if (nc >= 1) {
+        GCGE_HIP_CHECK(hipMalloc(&d_ptr, ((size_t)nc + 1) * sizeof(int)));
+        GCGE_HIP_CHECK(hipMemcpy(d_agg, agg.data(), (size_t)nf * sizeof(int), hipMemcpyHostToDevice));
+        GCGE_HIP_CHECK(hipMemcpy(d_ptr, ptr.data(), ((size_t)nc + 1) * sizeof(int), hipMemcpyHostToDevice));
+        GCGE_HIP_CHECK(hipMemcpy(d_mem, mem.data(), (size_t)nf * sizeof(int), hipMemcpyHostToDevice));
+      }
+      g_mg_phase[MG_TRANSFER] += mg_now() - t;
+    }
+    if (nc < 1 || (long)nc * 3 > (long)nf * 2) { hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); break; }     // coarsening stalled
+    t = mg_now();
+    DevCsr ca{nc, 0, nullptr, nullptr, nullptr, true}, cb{0, 0, nullptr, nullptr, nullptr, false};
+    int rc = gcge_hip_mg_galerkin_device(nf, fa.rp, fa.ci, fa.va, d_agg, nc, d_ptr, d_mem, scale, &ca.rp, &ca.ci, &ca.va, &ca.nnz, &g_mg_d2h);
+    if (rc == 0 && mB != nullptr) {
+      cb = DevCsr{nc, 0, nullptr, nullptr, nullptr, true};
+      rc = gcge_hip_mg_galerkin_device(nf, fb.rp, fb.ci, fb.va, d_agg, nc, d_ptr, d_mem, 1.0, &cb.rp, &cb.ci, &cb.va, &cb.nnz, &g_mg_d2h);
+      if (rc != 0) cb.owned = false;
+    }
+    if (rc != 0) ca.owned = ca.rp != nullptr;
+    g_mg_phase[MG_GALERKIN] += mg_now() - t;
+    if (rc != 0) { devcsr_free(ca); devcsr_free(cb); hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); ok = false; break; }
+    t = mg_now();
+    GCGE_HIP_MAT* p = gcge_hip_mat_create_rect_device(nf, nc, d_agg, d_ptr, d_mem);
+    GCGE_REQUIRE(p != nullptr, "MultiGridCreate: a prolongation from device arrays");
+    Ps.push_back(p);
+    hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem);
+    g_mg_phase[MG_OTHER] += mg_now() - t; t = mg_now();
+    GCGE_CSR hc, hb; memset(&hb, 0, sizeof hb);
+    if (gcge_hip_mg_download_csr(nc, nc, ca.nnz, ca.rp, ca.ci, ca.va, &hc, &g_mg_d2h) != 0 ||
+        (mB != nullptr && gcge_hip_mg_download_csr(nc, nc, cb.nnz, cb.rp, cb.ci, cb.va, &hb, &g_mg_d2h) != 0)) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
+    g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
+    GCGE_HIP_MAT* a = gcge_hip_mat_create(nc, nc, 0, hc.rowptr, hc.colidx, hc.val);
+    GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
+    As.push_back(a);
+    if (B_array != nullptr && mB != nullptr) {
+      GCGE_HIP_MAT* b = gcge_hip_mat_create(nc, nc, 0, hb.rowptr, hb.colidx, hb.val);
+      GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
+      Bs.push_back(b);
+    }
+    g_mg_phase[MG_COARSE] += mg_now() - t;
+    gcge_csr_free(&hb);
+    gcge_csr_free(&hostA); hostA = hc;
+    devcsr_free(fa); fa = ca;
+    devcsr_free(fb); fb = cb;
+    ldims.push_back({dims[0], dims[1], dims[2]});
+    if (have_grid) { dims[0] = cdims[0]; dims[1] = cdims[1]; dims[2] = cdims[2]; }
+  }
+  t = mg_now();
+  devcsr_free(fa); devcsr_free(fb);
+  gcge_csr_free(&hostA);
+  if (!ok) {
+    for (GCGE_HIP_MAT* m : As) gcge_hip_mat_destroy(m);
+    for (GCGE_HIP_MAT* m : Bs) gcge_hip_mat_destroy(m);
+    for (GCGE_HIP_MAT* m : Ps) gcge_hip_mat_destroy(m);
+    if (getenv("GCGE_MG_TRACE") != nullptr) fprintf(stderr, "MultiGridCreate: a level is out of the device path's reach; built on the host\n");
+    return false;
+  }
+  const int L = (int)As.size() + 1;
+  ldims.push_back({dims[0], dims[1], dims[2]});
+  MgHold h;
+  *A_array = (void**)calloc(L, sizeof(void*));
+  *P_array = (void**)calloc(L > 1 ? L - 1 : 1, sizeof(void*));
+  if (B_array != nullptr) *B_array = (void**)calloc(L, sizeof(void*));
+  (*A_array)[0] = A;
+  if (B_array != nullptr) (*B_array)[0] = B;
+  for (int l = 1; l < L; ++l) {
+    (*A_array)[l] = As[l - 1]; h.owned.push_back(As[l - 1]);
+    if (B_array != nullptr && mB != nullptr) { (*B_array)[l] = Bs[l - 1]; h.owned.push_back(Bs[l - 1]); }
+  }
+  for (int l = 0; l + 1 < L; ++l) { (*P_array)[l] = Ps[l]; h.owned.push_back(Ps[l]); }
+  if (getenv("GCGE_MG_TRACE") != nullptr)
+    for (int l = 0; l < L; ++l) {
+      const GCGE_HIP_MAT* m = (const GCGE_HIP_MAT*)(*A_array)[l];
+      fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, grid %d x %d x %d, K1 form %s (device build)\n", l, m->nrows, m->nnz,
+              have_grid ? ldims[l][0] : 0, have_grid ? ldims[l][1] : 0, have_grid ? ldims[l][2] : 0, gcge_hip_mat_spmm_form(m));
+    }
+  h.A_array = *A_array;
+  g_mg.push_back(h);
+  *num_levels = L;
+  g_mg_phase[MG_OTHER] += mg_now() - t;
+  return true;
+}
+
+static void mg_report(double t0) {
+  if (getenv("GCGE_MG_TRACE") == nullptr) return;
+  fprintf(stderr, "MultiGridCreate (%s path): %.3f s = detect %.3f + aggregate %.3f + Galerkin %.3f + transfers %.3f + coarse upload %.3f + other %.3f; "
+          "%ld bytes device to host\n", g_mg_mode == 0 ? "device" : "host", mg_now() - t0, g_mg_phase[MG_DETECT], g_mg_phase[MG_AGGREGATE],
+          g_mg_phase[MG_GALERKIN], g_mg_phase[MG_TRANSFER], g_mg_phase[MG_COARSE], g_mg_phase[MG_OTHER], g_mg_d2h);
+}
+
 extern "C" void gcge_hip_multigrid_create(void*** A_array, void*** B_array, void*** P_array, int* num_levels, void* A, void* B, struct OPS_* ops) {
   const GCGE_HIP_MAT_* mA = (const GCGE_HIP_MAT_*)A; const GCGE_HIP_MAT_* mB = (const GCGE_HIP_MAT_*)B;
   const double t0 = mg_now();
   GCGE_REQUIRE(mA != nullptr && mA->rect_ncols == 0 && num_levels != nullptr && *num_levels >= 1, "MultiGridCreate: a square matrix and a level count");
+  for (int i = 0; i < MG_NPHASE; ++i) g_mg_phase[i] = 0.0;
+  g_mg_d2h = 0;
   if (mA->nghost > 0 || mA->part_world > 1) {
     multigrid_create_slab(A_array, B_array, P_array, num_levels, mA, A, B);
     g_mg_seconds = mg_now() - t0;
     return;
   }
+  if (g_mg_mode == 0 && multigrid_create_device(A_array, B_array, P_array, num_levels, mA, mB, A, B)) {
+    g_mg_seconds = mg_now() - t0;
+    mg_report(t0);
+    return;
+  }
+  double t = mg_now();
   GCGE_CSR cA, cB; std::vector<int> rpA, ciA, rpB, ciB; std::vector<double> vaA, vaB;
   download_csr(mA, &cA, rpA, ciA, vaA);
   if (mB != nullptr) download_csr(mB, &cB, rpB, ciB, vaB);
+  g_mg_d2h += csr_bytes(mA->nrows, mA->nnz) + (mB != nullptr ? csr_bytes(mB->nrows, mB->nnz) : 0);
+  g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
   GCGE_MG mg;
   if (gcge_mg_build(&cA, mB != nullptr ? &cB : nullptr, *num_levels, 0, 0.0, &mg) != 0) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
+  g_mg_phase[MG_OTHER] += mg_now() - t; t = mg_now();
   const int L = mg.num_levels;
   MgHold h;
   *A_array = (void**)calloc(L, sizeof(void*));
@@ -168,6 +331,7 @@ extern "C" void gcge_hip_multigrid_create(void*** A_array, void*** B_array, void
     GCGE_REQUIRE(p != nullptr, "MultiGridCreate: upload of a prolongation");
     (*P_array)[l] = p; h.owned.push_back(p);
   }
+  g_mg_phase[MG_COARSE] += mg_now() - t;
   if (getenv("GCGE_MG_TRACE") != nullptr) {
     for (int l = 0; l < L; ++l)
       fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, grid %d x %d x %d, K1 form %s\n", l, mg.A[l].nrows, (long)mg.A[l].nnz,
@@ -178,6 +342,7 @@ extern "C" void gcge_hip_multigrid_create(void*** A_array, void*** B_array, void
   g_mg.push_back(h);
   *num_levels = L;
   g_mg_seconds = mg_now() - t0;
+  mg_report(t0);
 }
 
 extern "C" void gcge_hip_multigrid_destroy(void*** A_array, void*** B_array, void*** P_array, int* num_levels, struct OPS_* ops) {

@@ -73,7 +73,62 @@ def hip_lib():
         if not os.path.exists(path):
             raise RuntimeError("libgcge_hip.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
         _hip = C.CDLL(path, mode=C.RTLD_GLOBAL)
+        _hip.gcge_hip_multigrid_mode.argtypes = [C.c_int]
+        _hip.gcge_hip_multigrid_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_long)]
+        _hip.gcge_hip_mg_galerkin.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_double, C.POINTER(CSR)]
+        _hip.gcge_hip_mat_to_csr.argtypes = [C.c_void_p, C.POINTER(CSR)]
+        _hip.gcge_hip_mat_to_csr_t.argtypes = [C.c_void_p, C.POINTER(CSR)]
     return _hip
+
+
+def csr_arrays(A):
+    """(rowptr, colidx, val) numpy copies of a host CSR struct."""
+    import numpy as np
+    n, nnz = A.nrows, int(A.nnz)
+    return (np.ctypeslib.as_array(A.rowptr, (n + 1,)).copy(),
+            np.ctypeslib.as_array(A.colidx, (max(nnz, 1),))[:nnz].copy(),
+            np.ctypeslib.as_array(A.val, (max(nnz, 1),))[:nnz].copy())
+
+
+def _take_csr(out):
+    arrs = csr_arrays(out)
+    host_lib().gcge_csr_free(C.byref(out))
+    return arrs
+
+
+def multigrid_mode(mode=None):
+    """Where the HIP back-end builds its multigrid hierarchy: 0 on the device (default), 1 on the host; returns the mode in force."""
+    h = hip_lib()
+    if mode is not None:
+        h.gcge_hip_multigrid_mode(int(mode))
+    return h.gcge_hip_multigrid_get_mode()
+
+
+def multigrid_stats():
+    """The last MultiGridCreate of the HIP back-end: (dict of seconds per phase, bytes copied device to host)."""
+    s, b = (C.c_double * 6)(), C.c_long()
+    hip_lib().gcge_hip_multigrid_stats(s, C.byref(b))
+    return dict(zip(("detect", "aggregate", "galerkin", "transfers", "coarse_upload", "other"), list(s))), b.value
+
+
+def mg_galerkin_device(mat, agg, nc, scale):
+    """scale P^T A P on the device for a HIP matrix handle and an aggregate map (numpy int32): (rowptr, colidx, val)."""
+    import numpy as np
+    agg = np.ascontiguousarray(agg, dtype=np.int32)
+    out = CSR()
+    rc = hip_lib().gcge_hip_mg_galerkin(mat, agg.ctypes.data_as(C.POINTER(C.c_int)), int(nc), float(scale), C.byref(out))
+    if rc != 0:
+        raise RuntimeError("gcge_hip_mg_galerkin failed: %d" % rc)
+    return _take_csr(out)
+
+
+def mat_to_csr(mat, transpose=False):
+    """A HIP matrix handle's device CSR (P^T of a rectangular handle with transpose=True) as numpy (rowptr, colidx, val)."""
+    out = CSR()
+    rc = (hip_lib().gcge_hip_mat_to_csr_t if transpose else hip_lib().gcge_hip_mat_to_csr)(mat, C.byref(out))
+    if rc != 0:
+        raise RuntimeError("gcge_hip_mat_to_csr failed: %d" % rc)
+    return _take_csr(out)
 
 
 def load_petsc_binary(path, row_begin=0, row_end=-1):

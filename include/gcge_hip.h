@@ -76,8 +76,8 @@ void gcge_hip_mat_set_halo_async (GCGE_HIP_MAT *A, gcge_halo_exchange_fn begin, 
 void gcge_hip_set_halo_overlap (int on);
 void gcge_hip_mat_destroy (GCGE_HIP_MAT *A);
 /* ---- multigrid (csrc/hip/multigrid.hip): OPS_HIP_Set fills ops->MultiGridCreate / MultiGridDestroy (reference slots
- * src/ops.h:134-139; what app/app_slepc.c:648-728 gets from PETSc GAMG): the CSR arrays come back from the device, the
- * aggregation hierarchy of include/gcge_multigrid.h is built on the host (2 x 2 x 2 cells of a detected grid, greedy aggregates
+ * src/ops.h:134-139; what app/app_slepc.c:648-728 gets from PETSc GAMG): the aggregation hierarchy of include/gcge_multigrid.h,
+ * built on the device by default (gcge_hip_multigrid_mode below; 2 x 2 x 2 cells of a detected grid, greedy aggregates
  * otherwise, A_{l+1} = scale P^T A_l P; gcge_mg_set_defaults), every level is uploaded like any other matrix, and the fused
  * block CG is the smoother of BlockAMG for this table (GCGE_BACKEND.amg_smoother_setup, include/gcge_ops.h).
  * One rank only.  A prolongation is a RECTANGULAR matrix handle: MatDotMultiVec applies P (rows of level l x rows of level
@@ -87,6 +87,22 @@ GCGE_HIP_MAT *gcge_hip_mat_create_rect (int nrows, int ncols, const int *rowptr,
 		const int *t_rowptr, const int *t_colidx, const double *t_val);      /* CSR of P and CSR of P^T */
 GCGE_HIP_MAT *gcge_hip_mat_create_rect_csr (const GCGE_CSR *P);              /* the transpose is formed here */
 double gcge_hip_multigrid_seconds (void);    /* host + upload time of the last MultiGridCreate */
+/*     Where the hierarchy is built (whole matrices, one rank; row slabs always coarsen as below).  mode 0 (default): on the device
+ *     (csrc/hip/mg_device.hip) from the handle's device CSR — grid detection from the sampled rows only, grid aggregates, members and
+ *     the Galerkin products A_{l+1} = scale P^T A_l P on the device, P / P^T built there; graph levels download their CSR for the
+ *     host aggregation; every coarse level is downloaded for gcge_hip_mat_create.  Bit-identical to mode 1, the host build
+ *     (gcge_mg_build on the downloaded CSR), which mode 0 also falls back to when a level is out of the kernels' reach.         */
+void gcge_hip_multigrid_mode (int mode);
+int  gcge_hip_multigrid_get_mode (void);
+/*     the last MultiGridCreate: seconds of its phases (detect, aggregate, Galerkin, transfers, coarse upload / analysis, other)
+ *     and the bytes copied device to host; GCGE_MG_TRACE prints them                                                           */
+void gcge_hip_multigrid_stats (double *seconds6, long *d2h_bytes);
+/*     the device Galerkin product scale P^T A P on A's device CSR for a host aggregate map agg[nrows] (0 <= agg < nc): a host CSR
+ *     (gcge_csr_free); 0 on success, 1 when it is out of the kernels' reach, < 0 bad arguments                                     */
+int  gcge_hip_mg_galerkin (const GCGE_HIP_MAT *A, const int *agg_host, int nc, double scale, GCGE_CSR *Ac_out);
+/*     a handle's device CSR (square, or P of a rectangular one) / the P^T triple of a rectangular one as a host copy (gcge_csr_free) */
+int  gcge_hip_mat_to_csr (const GCGE_HIP_MAT *A, GCGE_CSR *out);
+int  gcge_hip_mat_to_csr_t (const GCGE_HIP_MAT *A, GCGE_CSR *out);
 /*     Row slabs (one rank per GPU): a slab that is whole planes of a detected grid (cut on any plane boundary) coarsens by itself
  *     (gcge_mg_build_slab, include/gcge_multigrid.h: local prolongations, coarse slabs with global columns); every coarse slab goes
  *     through the slab constructor — gcge_hip_mat_create_slab over RCCL by default, or the function registered here (a transport of

@@ -1,0 +1,250 @@
+"""The multigrid hierarchy built on the device (csrc/hip/mg_device.hip, the device path of MultiGridCreate in csrc/hip/multigrid.hip)
+against the host build it replaces (csrc/host/multigrid.c): the Galerkin product byte for byte, whole hierarchies level by level,
+solves that use them bit for bit, and the fine matrix not copied back to the host."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from gcge_amd.lib import CSR, host_lib, hip_lib, make_problem, mat_to_csr, mg_galerkin_device, multigrid_mode, multigrid_stats, run_gcg, run_pas
+from helpers import csr_from_scipy, csr_to_scipy
+
+
+def _host_arrays(rp, ci, va):
+    n = len(rp) - 1
+    keep = (np.ascontiguousarray(rp, dtype=np.int32), np.ascontiguousarray(ci, dtype=np.int32), np.ascontiguousarray(va, dtype=np.float64))
+    A = CSR(n, n, 0, len(ci), keep[0].ctypes.data_as(C.POINTER(C.c_int)), keep[1].ctypes.data_as(C.POINTER(C.c_int)),
+            keep[2].ctypes.data_as(C.POINTER(C.c_double)))
+    return A, keep
+
+
+def host_galerkin(arrays, agg, nc, scale):
+    h = host_lib()
+    A, keep = _host_arrays(*arrays)
+    agg = np.ascontiguousarray(agg, dtype=np.int32)
+    out = CSR()
+    assert h.gcge_mg_galerkin(C.byref(A), agg.ctypes.data_as(C.POINTER(C.c_int)), C.c_int(nc), C.c_double(scale), C.byref(out)) == 0
+    n, nnz = out.nrows, int(out.nnz)
+    res = (np.ctypeslib.as_array(out.rowptr, (n + 1,)).copy(), np.ctypeslib.as_array(out.colidx, (max(nnz, 1),))[:nnz].copy(),
+           np.ctypeslib.as_array(out.val, (max(nnz, 1),))[:nnz].copy())
+    h.gcge_csr_free(C.byref(out))
+    return res
+
+
+def grid_agg(dims):
+    h = host_lib()
+    agg = np.zeros(dims[0] * dims[1] * dims[2], dtype=np.int32)
+    cd = (C.c_int * 3)()
+    nc = h.gcge_mg_aggregate_grid((C.c_int * 3)(*dims), agg.ctypes.data_as(C.POINTER(C.c_int)), cd)
+    return agg, nc
+
+
+def graph_agg(arrays, theta=0.25):
+    A, keep = _host_arrays(*arrays)
+    agg = np.zeros(A.nrows, dtype=np.int32)
+    host_lib().gcge_mg_aggregate_graph.argtypes = [C.POINTER(CSR), C.c_double, C.POINTER(C.c_int)]
+    nc = host_lib().gcge_mg_aggregate_graph(C.byref(A), theta, agg.ctypes.data_as(C.POINTER(C.c_int)))
+    return agg, nc
+
+
+def same_csr(a, b):
+    assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+    assert np.array_equal(a[2].view(np.int64), b[2].view(np.int64))
+
+
+def permuted_lap3d(size, seed=7):
+    A, _ = make_problem("lap3d", size)
+    S = csr_to_scipy(A)
+    p = np.random.default_rng(seed).permutation(S.shape[0])
+    return csr_from_scipy(S[p][:, p].tocsr())
+
+
+def empty_and_isolated():
+    import scipy.sparse as sp
+    A, _ = make_problem("lap3d", 6)
+    S = csr_to_scipy(A).tolil()
+    n = S.shape[0]
+    for r in (0, 17, 100, n - 1):            # empty rows (and columns)
+        S[r, :] = 0; S[:, r] = 0
+    for r in (5, 60, 150):                   # isolated rows: the diagonal only
+        d = S[r, r]; S[r, :] = 0; S[:, r] = 0; S[r, r] = d
+    S = sp.csr_matrix(S); S.eliminate_zeros(); S.sort_indices()
+    return csr_from_scipy(S)
+
+
+# ---------------------------------------------------------------------------------------------- 1. the Galerkin product
+def _galerkin_cases():
+    return ["lap3d20_grid_0.5", "lap3d20_grid_1.0", "fe3d12_A", "fe3d12_B", "sio2_24", "lap3d16_permuted_graph", "empty_isolated", "nc1"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", _galerkin_cases())
+def test_device_galerkin_is_the_host_galerkin_byte_for_byte(hip, case):
+    keep = None
+    if case.startswith("lap3d20"):
+        A, _ = make_problem("lap3d", 20); scale = float(case.split("_")[-1]); mode = "grid"; dims = (20, 20, 20)
+    elif case.startswith("fe3d12"):
+        A, B = make_problem("fe3d", 12); dims = (12, 12, 12); mode = "grid"
+        A, scale = (A, 0.5) if case.endswith("A") else (B, 1.0)
+    elif case == "sio2_24":
+        A, _ = make_problem("sio2", 24); scale = 0.5; mode = "grid"; dims = (24, 24, 24)
+    elif case == "lap3d16_permuted_graph":
+        A, keep = permuted_lap3d(16); scale = 0.5; mode = "graph"
+    elif case == "empty_isolated":
+        A, keep = empty_and_isolated(); scale = 0.5; mode = "graph"
+    else:
+        A, _ = make_problem("lap3d", 9); scale = 0.5; mode = "one"
+    m = hip.matrix(A)
+    dev = mat_to_csr(m)                      # the rows as the device holds them: what both builds coarsen
+    if mode == "grid":
+        agg, nc = grid_agg(dims)
+    elif mode == "graph":
+        agg, nc = graph_agg(dev)
+    else:
+        agg, nc = np.zeros(A.nrows, dtype=np.int32), 1
+    got = mg_galerkin_device(m, agg, nc, scale)
+    ref = host_galerkin(dev, agg, nc, scale)
+    same_csr(got, ref)
+    if case == "sio2_24":
+        assert np.bincount(agg, weights=np.diff(dev[0])).max() > 4 * 64   # long coarse rows: several chunks of entries per row
+    hip.free_matrix(m)
+
+
+# ---------------------------------------------------------------------------------------------- 2. whole hierarchies
+def slot_multigrid(backend, A_handle, B_handle, levels):
+    from gcge_amd.ops_struct import OPS
+    st = C.cast(backend.ops_handle, C.POINTER(OPS)).contents
+    A_arr, B_arr, P_arr, nl = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(levels)
+    create = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p)(st.MultiGridCreate)
+    destroy = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p)(st.MultiGridDestroy)
+    create(C.byref(A_arr), C.byref(B_arr) if B_handle is not None else None, C.byref(P_arr), C.byref(nl), A_handle, B_handle, backend.ops_handle)
+    L = nl.value
+    Ah = [C.c_void_p(v) for v in C.cast(A_arr, C.POINTER(C.c_void_p * L)).contents]
+    Bh = [C.c_void_p(v) for v in C.cast(B_arr, C.POINTER(C.c_void_p * L)).contents] if B_handle is not None else []
+    Ph = [C.c_void_p(v) for v in C.cast(P_arr, C.POINTER(C.c_void_p * max(1, L - 1))).contents][:L - 1]
+
+    def done():
+        destroy(C.byref(A_arr), C.byref(B_arr) if B_handle is not None else None, C.byref(P_arr), C.byref(nl), backend.ops_handle)
+    return Ah, Bh, Ph, done
+
+
+def hierarchy_snapshot(hip, mA, mB, levels):
+    g = hip_lib()
+    g.gcge_hip_mat_spmm_form.restype = C.c_char_p; g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
+    g.gcge_hip_mat_row_order.restype = C.c_char_p; g.gcge_hip_mat_row_order.argtypes = [C.c_void_p]
+    Ah, Bh, Ph, done = slot_multigrid(hip, mA, mB, levels)
+    snap = {"L": len(Ah),
+            "A": [mat_to_csr(a) for a in Ah[1:]], "B": [mat_to_csr(b) for b in Bh[1:]],
+            "P": [mat_to_csr(p) for p in Ph], "PT": [mat_to_csr(p, transpose=True) for p in Ph],
+            "form": [g.gcge_hip_mat_spmm_form(a) for a in Ah], "order": [g.gcge_hip_mat_row_order(a) for a in Ah]}
+    done()
+    return snap
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,levels,min_levels", [("lap3d32", 6, 4), ("fe3d12", 4, 3), ("sio2_24", 4, 3), ("lap3d16_permuted", 4, 3)])
+def test_device_hierarchy_equals_the_host_hierarchy(hip, case, levels, min_levels):
+    keep = None; B = None
+    if case == "lap3d32":
+        A, _ = make_problem("lap3d", 32)
+    elif case == "fe3d12":
+        A, B = make_problem("fe3d", 12)
+    elif case == "sio2_24":
+        A, _ = make_problem("sio2", 24)
+    else:
+        A, keep = permuted_lap3d(16)
+    mA = hip.matrix(A)
+    mB = hip.matrix(B) if B is not None else None
+    snaps = {}
+    try:
+        for mode in (0, 1):
+            multigrid_mode(mode)
+            snaps[mode] = hierarchy_snapshot(hip, mA, mB, levels)
+    finally:
+        multigrid_mode(0)
+    d, h = snaps[0], snaps[1]
+    assert d["L"] == h["L"] >= min_levels
+    assert d["form"] == h["form"] and d["order"] == h["order"]
+    for key in ("A", "B", "P", "PT"):
+        assert len(d[key]) == len(h[key])
+        for x, y in zip(d[key], h[key]):
+            same_csr(x, y)
+    hip.free_matrix(mA)
+    if mB is not None:
+        hip.free_matrix(mB)
+
+
+# ---------------------------------------------------------------------------------------------- 3. solves
+def _bpcg_counts():
+    calls, cols, it = C.c_long(), C.c_long(), C.c_int()
+    hip_lib().gcge_hip_bpcg_stats(C.byref(calls), C.byref(cols), C.byref(it))
+    return calls.value, cols.value
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kind,size,nev", [("lap3d", 24, 20), ("fe3d", 12, 10)])
+def test_gcg_with_block_amg_is_the_same_in_both_modes(hip, kind, size, nev):
+    A, B = make_problem(kind, size)
+    mA = hip.matrix(A)
+    mB = hip.matrix(B) if B is not None else None
+    out = {}
+    try:
+        for mode in (0, 1):
+            multigrid_mode(mode)
+            hip.set_random_mode(0)
+            C.CDLL(None).srand(0)
+            c0 = _bpcg_counts()
+            ev, res = run_gcg(hip.ops_handle, mA, mB, ["-nevConv", nev, "-gcge_amg_levels", 4])
+            c1 = _bpcg_counts()
+            out[mode] = (ev.copy(), res.nevConv, res.numIter, (c1[0] - c0[0], c1[1] - c0[1]))
+    finally:
+        multigrid_mode(0)
+    assert out[0][1] >= nev
+    assert np.array_equal(out[0][0].view(np.int64), out[1][0].view(np.int64))
+    assert out[0][1:] == out[1][1:]
+    hip.free_matrix(mA)
+    if mB is not None:
+        hip.free_matrix(mB)
+
+
+@pytest.mark.gpu
+def test_pas_is_the_same_in_both_modes(hip):
+    A, _ = make_problem("lap3d", 20)
+    mA = hip.matrix(A)
+    out = {}
+    try:
+        for mode in (0, 1):
+            multigrid_mode(mode)
+            hip.set_random_mode(0)
+            C.CDLL(None).srand(0)
+            ev, pres, gres = run_pas(hip.ops_handle, mA, None, ["-nevConv", 10])
+            out[mode] = (ev.copy(), pres.nevConv, pres.numIter, pres.num_levels, gres.nevConv, gres.numIter)
+    finally:
+        multigrid_mode(0)
+    assert out[0][4] >= 10
+    assert np.array_equal(out[0][0].view(np.int64), out[1][0].view(np.int64))
+    assert out[0][1:] == out[1][1:]
+    hip.free_matrix(mA)
+
+
+# ---------------------------------------------------------------------------------------------- 4. no full download
+@pytest.mark.gpu
+def test_device_build_does_not_download_the_fine_matrix(hip):
+    A, _ = make_problem("lap3d", 48)
+    fine = (A.nrows + 1) * 4 + int(A.nnz) * 12
+    mA = hip.matrix(A)
+    got = {}
+    try:
+        for mode in (0, 1):
+            multigrid_mode(mode)
+            Ah, Bh, Ph, done = slot_multigrid(hip, mA, None, 4)
+            secs, d2h = multigrid_stats()
+            got[mode] = (len(Ah), d2h, secs)
+            done()
+    finally:
+        multigrid_mode(0)
+    assert got[0][0] == got[1][0] == 4
+    assert got[0][1] < fine / 4, (got[0][1], fine)
+    assert got[1][1] >= fine
+    assert got[0][2]["galerkin"] > 0.0 and got[0][2]["detect"] > 0.0
+    hip.free_matrix(mA)
