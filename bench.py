@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the GCG hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--rehearse] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config c2|c3|c4|c5] [--rehearse] [--dump-outputs DIR] [--full]
 
 With --gpus N > 1 and no RANK in the environment bench.py starts the N ranks ITSELF — fresh child processes running
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, spawned before torch or the GPU is touched — relays
@@ -38,6 +38,11 @@ torch.distributed only hands rank 0's RCCL id to the other ranks and synchronise
              GPU's time on that SAME config beside it (gpu_same_config); kind "port" = our C restatement when the
              compiled reference is absent.
   ms_per_step = milliseconds per timed step (elapsed / K).
+A plain run sets up, warms up, times the K steps, writes its outputs (--dump-outputs) and prints the line: every figure above
+but cpu_baseline comes from the set-up and the timed steps themselves.  --full adds the legs that take runs of their own, after the timed
+steps and one rank only: cpu_baseline and cpu_baseline_like_for_like (--no-cpu drops them), and with --no-extra unset
+plain_block_cg, dropin_reference_stack, roofline_k1_c5 and roofline_k1_permuted (config 2) or roofline_k1_spmm_A / _B (config 3).
+A full run of config 2 spends about two minutes in them.
 With --dump-outputs DIR the last timed solve's result is written to DIR/*.npy (dump_outputs); the inputs are fixed by the
 arguments (generated matrix, seeded device start blocks), so two builds can be compared output for output.
 Prints ONE JSON line on rank 0.
@@ -70,15 +75,18 @@ def parse():
     ap.add_argument("--rehearse", action="store_true",
                     help="every rank on cuda:0, gloo transport staged through the host (multi-rank code path on a one-GPU box)")
     ap.add_argument("--atoms", default="2000,2.0,5.0", help="c5: K,R0,R1 of the SiO2-like generator (SURVEY 8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs that take runs of their own (CPU baselines, plain block CG, the "
+                         "reference's stack, K1 on other matrices); a plain run prints only what the timed steps measured")
     ap.add_argument("--cpu-size", type=int, default=50, help="grid size of the CPU baseline (50 = BASELINE config 1)")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--dense-shapes", action="store_true", help="after the timed steps, print the in-solve rate of the Gram / panel-update kernels per shape (k, m) on stderr")
     ap.add_argument("--orth", default="chol", help="block orthonormalisation scheme for X and W: chol | mgs | bgs")
     ap.add_argument("--plain-steps", type=int, default=2,
-                    help="with --amg: additional solves with the plain fused block CG (30 iterations) after the timed region -> plain_block_cg "
+                    help="with --full and --amg: additional solves with the plain fused block CG (30 iterations) after the timed region -> plain_block_cg "
                          "(the configuration rounds 1-4 reported as value)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the legs after the timed region (plain_block_cg, roofline_k1_c5, roofline_k1_permuted, dropin_reference_stack)")
-    ap.add_argument("--cpu-like-size", type=int, default=48, help="grid size of the like-for-like CPU sample (config 2's solver shape on the CPU reference)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the legs after the timed region other than the CPU baselines (plain_block_cg, roofline_k1_c5, roofline_k1_permuted, dropin_reference_stack)")
+    ap.add_argument("--cpu-like-size", type=int, default=48, help="with --full: grid size of the like-for-like CPU sample (config 2's solver shape on the CPU reference)")
     ap.add_argument("--amg", type=int, default=-1,
                     help="levels (>= 2) of the multigrid hierarchy: the W systems are solved by BlockAMG (one V-cycle, fused block CG as the "
                          "smoother; reference src/ops_lin_sol.c:466-715 set up as test/test_eig_sol_SiO2_MAT.c:96-128) instead of 30 block-CG "
@@ -912,7 +920,7 @@ def main():
             "pairs_wanted_per_s": args.nev * args.steps / elapsed,
             "upload_seconds": upload_seconds, "warmup_solve_seconds": warm_solve, "alarm_budget_seconds": alarm_budget,
             "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True,
-            "scaling": "strong" if c5 else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "scaling": "strong" if c5 else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": args.full,
             "config": cfg,
             # the dominant kernel of the step; the K1 product alone (the north-star figure) and the other CG pass follow
             "roofline": dominant,
@@ -936,7 +944,8 @@ def main():
             if r is not None:
                 out[name] = r
 
-        extra = world == 1 and not args.no_extra and args.config == "c2"
+        # the legs below take runs of their own (minutes at config 2): --full only
+        extra = args.full and world == 1 and not args.no_extra and args.config == "c2"
         if extra and amg is not None and args.plain_steps > 0:
             # the configuration rounds 1-4 reported as `value`: the same solves with the W systems through 30 iterations of the
             # fused block CG (no multigrid), so that the round-over-round record stays comparable
@@ -976,10 +985,10 @@ def main():
                 return k1_c5_leg(hip, args)
             leg("roofline_k1_c5", k1c5)
             leg("roofline_k1_permuted", lambda: k1_permuted_leg(hip, args))
-        if c3 and world == 1 and not args.no_extra:
+        if args.full and c3 and world == 1 and not args.no_extra:
             leg("roofline_k1_spmm_A", lambda: k1_plain_leg(hip, mat, A, args.block, "stiffness matrix A (7-point stencil x h), config 3"))
             leg("roofline_k1_spmm_B", lambda: k1_plain_leg(hip, matB, Bc, args.block, "consistent mass matrix B (15-point stencil x h^3), config 3"))
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             leg("cpu_baseline", lambda: cpu_baseline(args, hip))
             if extra:
                 leg("cpu_baseline_like_for_like", lambda: cpu_like_for_like(args, hip))

@@ -280,3 +280,21 @@ def test_pmc_traffic_file_matches_the_kernel_sources():
     t5, note5 = b.pmc_traffic_c5(171, "2000,2.0,5.0", 64)
     # round 5: every kernel of the product (sweep 10.2 GB + dense blocks 3.0 GB + listed rows 1.3 GB = 14.5 GB per 64 columns)
     assert t5 is not None and 10e9 < t5 < 18e9, (t5, note5)
+
+
+def test_bench_legs_only_with_full(monkeypatch):
+    """`--full`, which runs the legs after the timed steps, is off in a plain `bench.py --gpus 1 --steps N --warmup W`; given,
+    it drops none of them."""
+    import importlib.util
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_for_cli", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    plain = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+    monkeypatch.setattr(sys, "argv", plain)
+    assert b.parse().full is False
+    monkeypatch.setattr(sys, "argv", plain + ["--full"])
+    a = b.parse()
+    assert a.full is True and not a.no_cpu and not a.no_extra
