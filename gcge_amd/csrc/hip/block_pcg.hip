@@ -443,6 +443,7 @@ struct HipBpcg {
   long stored_dev_iters;    // iterations of the device-scalar loop with the product stored (matrices without a pattern form)
   long fused_starts;        // solves started by product + one sweep (cg_start_scaled_stored)
   long surplus_iters;       // iterations enqueued after the last column had retired (no-ops on the data, but they stream)
+  long trimmed_iters;       // last iterations of the device-scalar loop whose second pass ran over fewer columns or not at all
 };
 static HipBpcg g_bpcg = {30, 1e-2, 1e-14, "abs", {nullptr, nullptr, nullptr, nullptr}, {nullptr}, 0, 0, 0, 0, -1.0, 0, 0, nullptr, nullptr, nullptr, 0};
 
@@ -840,11 +841,24 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
         hipLaunchKernelGGL(cg_accum_x, dim3((unsigned)g), dim3(256), 0, st, (long)n, rp, npend, ldp, dx, ldx, nrhs, d_ahist2, tpr);
         first_slot = (first_slot + npend) % R; npend = 0;
       };
+      // The last iteration the loop can enqueue (max_iter - 1) needs its first pass and alpha — x takes alpha p from the pending
+      // coefficients — but its second pass only writes p_{k+1}, which nothing reads, and measures rho_{k+1}, which only the
+      // caller can read (the residual this call reports, column 0's).  A caller that reads no residual, or that of the leading
+      // columns only (GCGE_LINSOL_ARGS.final_residual_cols: BlockAMG's smoothing calls), gets no second pass in that
+      // iteration, or one over the 16-column passes that hold those columns: the kernel launches its column passes with the
+      // same blocks and partial sums whatever the column count (spmm_pattern.hip), so their rho are the full pass's bit for bit.
+      // The stored-product form has no such cut (its sweep's row split follows the column count): it skips the sweep for none.
+      // niter, the column statistics and the surplus count never look at the last iteration's active count (see below).
+      const int fin = args.final_residual_cols < 0 ? 0 : (args.final_residual_cols == 0 ? nrhs : std::min(args.final_residual_cols, nrhs));
+      const int last_cols = fin == nrhs ? nrhs : (recompute ? std::min(nrhs, (fin + 15) / 16 * 16) : (fin > 0 ? nrhs : 0));
       int enq = 0;            // iterations enqueued
       int done = -1;          // index of the last iteration whose active count the host has seen
       int stop_at = -1;       // first iteration that found no active column at its start
+      bool trimmed = false;   // the last iteration's second pass left columns out: its active count is not a count of all
       while (enq < s->max_iter && enq < 4096) {
         void** pcur = slots[cur];
+        const int m2 = enq == s->max_iter - 1 ? last_cols : nrhs;   // columns of this iteration's second pass
+        trimmed = m2 < nrhs;
         if (recompute) {
           if (gcge_hip_cg_pass1_dev(mat, pcur, 0, nrhs, d_sums) != 0) { fprintf(stderr, "HIP_BlockPCG: first CG pass refused operands it had accepted\n"); abort(); }
         } else if (gcge_hip_spmm_dot2_dev(mat, pcur, s->mv_ws[2], 0, 0, nrhs, d_sums) != 0) {
@@ -856,7 +870,10 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
         hipLaunchKernelGGL(cg_scalars_a, dim3(1), dim3(256), 0, st, nrhs, d_rho2, d_sums, d_active, d_alpha, bcur, d_flag2,
                            d_ahist2 + (size_t)npend * nrhs);
         int rc2 = 0;
-        if (!recompute) {     // w is stored: one sweep over w, the directions (and r where it is stored) — cg_update_p_implicit / cg_update_rp
+        if (m2 == 0) {        // no second pass: p_{k+1}, rho_{k+1} and the active flags are left as they are (counted as before)
+          if (implicit_r) ++s->implicit_r_iters;
+          if (!recompute) ++s->stored_dev_iters;
+        } else if (!recompute) {     // w is stored: one sweep over w, the directions (and r where it is stored) — cg_update_p_implicit / cg_update_rp
           long ldq;
           const double* pold = gcge_hip_mv_device_ptr(slots[cur], &ldq);
           double* pnew = gcge_hip_mv_device_ptr(slots[(cur + 1) % R], &ldq);
@@ -872,14 +889,17 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
           gcge_hip_reduce_partials(part, (int)nb, nrhs, d_newrho, st);
           ++s->stored_dev_iters;
         } else if (implicit_r) {
-          rc2 = gcge_hip_cg_pass2i_dev(mat, pcur, enq == 0 ? pcur : slots[(cur + R - 1) % R], slots[(cur + 1) % R], 0, nrhs, d_alpha, bcur,
+          rc2 = gcge_hip_cg_pass2i_dev(mat, pcur, enq == 0 ? pcur : slots[(cur + R - 1) % R], slots[(cur + 1) % R], 0, m2, d_alpha, bcur,
                                        d_flag2, bprev, d_newrho);
           ++s->implicit_r_iters;
-        } else rc2 = gcge_hip_cg_pass2_dev(mat, pcur, s->mv_ws[0], slots[(cur + 1) % R], 0, nrhs, d_alpha, d_beta, d_flag2, d_newrho);
+        } else rc2 = gcge_hip_cg_pass2_dev(mat, pcur, s->mv_ws[0], slots[(cur + 1) % R], 0, m2, d_alpha, d_beta, d_flag2, d_newrho);
         if (rc2 != 0) { fprintf(stderr, "HIP_BlockPCG: second CG pass refused operands it had accepted\n"); abort(); }
-        if (reduce) gcge_hip_comm_allreduce_device(d_newrho, nrhs);
-        hipLaunchKernelGGL(cg_scalars_b, dim3(1), dim3(256), 0, st, nrhs, d_newrho, s->rate, s->tol, d_normb, d_init, d_rho2, d_active,
-                           d_last, s->h_nact + enq);
+        if (m2 > 0) {   // (m2 is the same on every rank: max_iter and the caller's final_residual_cols are)
+          if (reduce) gcge_hip_comm_allreduce_device(d_newrho, m2);
+          hipLaunchKernelGGL(cg_scalars_b, dim3(1), dim3(256), 0, st, m2, d_newrho, s->rate, s->tol, d_normb, d_init, d_rho2, d_active,
+                             d_last, s->h_nact + enq);
+        }
+        if (trimmed) ++s->trimmed_iters;
         GCGE_HIP_CHECK(hipEventRecord(s->ev_it[enq & 1], st));
         ++npend; cur = (cur + 1) % R; if (recompute) ++s->recompute_iters; ++s->dev_scalar_iters; s->spmm_calls++; s->spmm_cols += nrhs;
         ++enq;
@@ -892,8 +912,8 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
       }
       GCGE_HIP_CHECK(hipStreamSynchronize(st));
       if (stop_at < 0) {      // the queue ran dry at max_iter (or the last iterations have not been looked at yet)
-        stop_at = enq;
-        for (int q = done + 1; q < enq; ++q) if (s->h_nact[q] == 0) { stop_at = q + 1; break; }
+        stop_at = enq;        // (a trimmed last iteration q = enq - 1 left no count of all columns; it would give q + 1 = enq anyway)
+        for (int q = done + 1; q < enq - (trimmed ? 1 : 0); ++q) if (s->h_nact[q] == 0) { stop_at = q + 1; break; }
       }
       niter = stop_at;        // iterations that started with at least one active column, as the reference counts them
       flush_x_dev();
@@ -1106,6 +1126,8 @@ extern "C" void gcge_hip_bpcg_column_stats(long* col_iters, long* active_col_ite
   if (active_col_iters) *active_col_iters = g_bpcg.active_col_iters;
 }
 extern "C" long gcge_hip_bpcg_surplus_iters(void) { return g_bpcg.surplus_iters; }
+extern "C" long gcge_hip_bpcg_trimmed_iters(void) { return g_bpcg.trimmed_iters; }
+extern "C" double gcge_hip_bpcg_last_residual(void) { return g_bpcg.residual; }   // what the last call reported (column 0)
 // the fused CG as the smoother of BlockAMG for the HIP table: same stopping rules as MultiLinearSolverSetup_BlockPCG, its own
 // blocks per level (parked sets above)
 static void amg_smoother_setup(int max_iter, double rate, double tol, const char* tol_type, struct OPS_* ops) {
@@ -1118,6 +1140,7 @@ extern "C" void gcge_hip_bpcg_backend(GCGE_BACKEND* be) {
   be->amg_smoother_setup = amg_smoother_setup;
   be->amg_smoother_residual = amg_smoother_residual;
   be->scaled_rhs_solver = HIP_BlockPCG;
+  be->amg_final_cols = 1;
 }
 extern "C" void gcge_hip_bpcg_release(struct OPS_* ops) {
   for (int i = 0; i < g_nparked; ++i) bpcg_destroy_set(&g_parked[i], ops);

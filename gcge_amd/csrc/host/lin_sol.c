@@ -145,7 +145,10 @@ void MultiLinearSolverSetup_BlockPCG(int max_iter, double rate, double tol, cons
  * The smoother is installed in ops->MultiLinearSolver and called through it (BlockPCG and a back-end's block CG both find their
  * state in ops->multi_linear_solver_workspace): the back-end's amg_smoother_* where its record offers them (GCGE_BACKEND,
  * gcge_ops.h), the solver stack's BlockPCG otherwise (the reference's choice, :482-486,:626-629); likewise the residual and the
- * correction as one sweep each where the record offers amg_residual / amg_prolong_add. */
+ * correction as one sweep each where the record offers amg_residual / amg_prolong_add.  Where the record says the smoother honours
+ * GCGE_LINSOL_ARGS.final_residual_cols (amg_final_cols), every smoothing call is told that its residual goes unread, except the
+ * cycle's last one, whose column 0 becomes the cycle's residual: the other calls skip the work of their last iteration that only
+ * measures it (x and the iteration counts stay bit for bit what they were). */
 struct amg_level { void **b, **x; int start[2], end[2]; };
 static struct amg_level amg_level(const BlockAMGSolver *bamg, int l, void **mv_b, void **mv_x, const int *start_bx, const int *end_bx)
 {
@@ -154,9 +157,15 @@ static struct amg_level amg_level(const BlockAMGSolver *bamg, int l, void **mv_b
 	if (l > 0) { v.b = bamg->mv_array_ws[0][l]; v.x = bamg->mv_array_ws[1][l]; v.start[0] = v.start[1] = 0; v.end[0] = v.end[1] = m; }
 	return v;
 }
-static void smooth(const GCGE_BACKEND *be, const BlockAMGSolver *bamg, int l, int max_iter, struct amg_level *v, struct OPS_ *ops)
+static void smooth(const GCGE_BACKEND *be, const BlockAMGSolver *bamg, int l, int max_iter, int last, struct amg_level *v,
+		struct OPS_ *ops)
 {
 	void **mv_ws[3] = {bamg->mv_array_ws[2][l], bamg->mv_array_ws[3][l], bamg->mv_array_ws[4][l]};
+	if (be->amg_final_cols) {      /* last: the cycle's residual is column 0 of this call's (see below) */
+		GCGE_LINSOL_ARGS a = *GCGE_GetLinearSolverArgs();
+		a.final_residual_cols = last ? 1 : -1;
+		GCGE_SetLinearSolverArgs(&a);
+	}
 	if (be->amg_smoother_setup != NULL) be->amg_smoother_setup(max_iter, bamg->rate[l], bamg->tol[l], bamg->tol_type, ops);
 	else MultiLinearSolverSetup_BlockPCG(max_iter, bamg->rate[l], bamg->tol[l], bamg->tol_type, mv_ws, bamg->dbl_ws, bamg->int_ws,
 			NULL, NULL, ops);
@@ -176,7 +185,7 @@ static void BlockAlgebraicMultiGrid(const GCGE_BACKEND *be, BlockAMGSolver *bamg
 		void *A = bamg->A_array[l], **r = bamg->mv_array_ws[2][l];
 		f = amg_level(bamg, l, mv_b, mv_x, start_bx, end_bx);
 		c = amg_level(bamg, l + 1, mv_b, mv_x, start_bx, end_bx);
-		smooth(be, bamg, l, bamg->max_iter[2 * l + 1], &f, ops);
+		smooth(be, bamg, l, bamg->max_iter[2 * l + 1], 0, &f, ops);
 		if (!(be->amg_residual != NULL && be->amg_residual(A, f.b, f.start[0], f.x, f.start[1], r, 0, m, ops))) {
 			int s[2] = {f.start[1], 0}, e[2] = {f.end[1], m};
 			ops->MatDotMultiVec(A, f.x, r, s, e, ops);                 /* r = b - A x */
@@ -187,7 +196,7 @@ static void BlockAlgebraicMultiGrid(const GCGE_BACKEND *be, BlockAMGSolver *bamg
 		ops->MultiVecAxpby(0.0, NULL, 0.0, c.x, cs, ce, ops);
 	}
 	f = amg_level(bamg, L - 1, mv_b, mv_x, start_bx, end_bx);
-	smooth(be, bamg, L - 1, bamg->max_iter[2 * L - 1], &f, ops);
+	smooth(be, bamg, L - 1, bamg->max_iter[2 * L - 1], L == 1, &f, ops);
 	for (l = L - 2; l >= 0; --l) {
 		void **r = bamg->mv_array_ws[2][l];
 		f = amg_level(bamg, l, mv_b, mv_x, start_bx, end_bx);
@@ -197,7 +206,7 @@ static void BlockAlgebraicMultiGrid(const GCGE_BACKEND *be, BlockAMGSolver *bamg
 			ops->MultiVecFromItoJ(bamg->P_array, l + 1, l, c.x, r, cs, ce, bamg->mv_array_ws[4], ops);
 			ops->MultiVecAxpby(1.0, r, 1.0, f.x, s, e, ops);
 		}
-		smooth(be, bamg, l, bamg->max_iter[2 * l + 2], &f, ops);
+		smooth(be, bamg, l, bamg->max_iter[2 * l + 2], l == 0, &f, ops);
 	}
 	/* residual of the smoothing call that ran last (src/ops_lin_sol.c:643: read from the solver behind the table) */
 	bamg->residual = be->amg_smoother_setup != NULL ? be->amg_smoother_residual(ops) :
@@ -232,7 +241,7 @@ static void BlockAMG(void *mat, void **mv_b, void **mv_x, int *start_bx, int *en
 		bamg->niter = idx + 1;
 		if (bamg->residual < bamg->tol[0]) break;
 	}
-	if (args.rhs_scale != NULL) GCGE_SetLinearSolverArgs(&args);   /* (the caller clears it) */
+	if (args.rhs_scale != NULL || be.amg_final_cols) GCGE_SetLinearSolverArgs(&args);   /* (the caller clears it) */
 }
 
 int GCGE_SolverTakesScaledRhs(struct OPS_ *ops)

@@ -56,7 +56,9 @@ const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs(void) { return &g_linsol_args; 
  *   GCGE_NO_INPLACE_LINCOMB  inplace_lincomb_cols                           (panel updates staged through a work block)
  *   GCGE_EIG_HOST            symeig                                         (projected eigenproblems on the host)
  *   GCGE_AMG_HOST_SMOOTHER   amg_smoother_setup, amg_smoother_residual      (BlockAMG smooths with BlockPCG over the slots)
- *   GCGE_AMG_NO_FUSIONS      amg_residual, amg_prolong_add, amg_form_rhs    (the V-cycle's slot calls)
+ *   GCGE_AMG_NO_FUSIONS      amg_residual, amg_prolong_add, amg_form_rhs,   (the V-cycle's slot calls;
+ *                            amg_final_cols                                  every smoothing call runs its last pass whole)
+ *   GCGE_AMG_FULL_LAST_PASS  amg_final_cols                                 (the same, alone)
  *   GCGE_NO_RHS_SCALE        scaled_rhs_solver, amg_form_rhs                (the GCG driver forms b = (lambda + sigma) x) */
 static GCGE_BACKEND g_backend; static void *g_backend_matvec = NULL, *g_backend_lincomb = NULL;
 void GCGE_SetBackend(struct OPS_ *ops, const GCGE_BACKEND *backend)
@@ -74,8 +76,9 @@ GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
 	if (getenv("GCGE_NO_RESIDUAL_HOOK") != NULL) b.residual_sq = NULL;
 	if (getenv("GCGE_NO_INPLACE_LINCOMB") != NULL) b.inplace_lincomb_cols = 0;
 	if (getenv("GCGE_EIG_HOST") != NULL) b.symeig = NULL;
-	if (getenv("GCGE_AMG_HOST_SMOOTHER") != NULL) { b.amg_smoother_setup = NULL; b.amg_smoother_residual = NULL; }
-	if (getenv("GCGE_AMG_NO_FUSIONS") != NULL) { b.amg_residual = NULL; b.amg_prolong_add = NULL; b.amg_form_rhs = NULL; }
+	if (getenv("GCGE_AMG_HOST_SMOOTHER") != NULL) { b.amg_smoother_setup = NULL; b.amg_smoother_residual = NULL; b.amg_final_cols = 0; }
+	if (getenv("GCGE_AMG_NO_FUSIONS") != NULL) { b.amg_residual = NULL; b.amg_prolong_add = NULL; b.amg_form_rhs = NULL; b.amg_final_cols = 0; }
+	if (getenv("GCGE_AMG_FULL_LAST_PASS") != NULL) b.amg_final_cols = 0;
 	if (getenv("GCGE_NO_RHS_SCALE") != NULL) { b.scaled_rhs_solver = NULL; b.amg_form_rhs = NULL; }
 	return b;
 }

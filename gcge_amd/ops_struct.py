@@ -30,7 +30,8 @@ class LINSOL_ARGS(C.Structure):
     _fields_ = [("sigma", C.c_double), ("matB", C.c_void_p),
                 ("user_scale", C.POINTER(C.c_double)), ("n_user_scale", C.c_int),
                 ("rhs_scale", C.POINTER(C.c_double)),
-                ("idle_blocks", C.c_void_p), ("n_idle", C.c_int)]
+                ("idle_blocks", C.c_void_p), ("n_idle", C.c_int),
+                ("final_residual_cols", C.c_int)]
 
 
 _vp, _i, _d, _c = C.c_void_p, C.c_int, C.c_double, C.c_char

@@ -163,12 +163,17 @@ int        GCGE_GetLocalInnerProdReduces (void);
  *                 (GCGE_SolverTakesScaledRhs, gcge_solver.h).  The reference forms b through MatDotMultiVec + MultiVecLinearComb
  *                 (src/ops_eig_sol_gcg.c:560-577).  NULL: b is an ordinary right-hand side.
  *   idle_blocks   n_idle blocks the driver does not need during the call (its work blocks): scratch for the solver — the fused
- *                 HIP solver takes those that match its own blocks as further slots of its direction ring.                     */
+ *                 HIP solver takes those that match its own blocks as further slots of its direction ring.
+ *   final_residual_cols   whose residual the caller reads after the call: 0 every column's (a direct call), k > 0 only that of
+ *                 the leading k columns, < 0 none.  A solver may then leave out the work of its LAST iteration that only measures
+ *                 the residual of the other columns; x, the iteration count and the column statistics stay as they are.  BlockAMG
+ *                 sets it for its smoothing calls where the back-end's record says its smoother honours it (amg_final_cols).   */
 typedef struct GCGE_LINSOL_ARGS_ {
 	double sigma; void *matB;
 	const double *user_scale; int n_user_scale;
 	const double *rhs_scale;
 	void ***idle_blocks; int n_idle;
+	int final_residual_cols;
 } GCGE_LINSOL_ARGS;
 void       GCGE_SetLinearSolverArgs (const GCGE_LINSOL_ARGS *args);   /* copied; NULL clears */
 const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs (void);              /* never NULL; all zero when nothing is published */
@@ -194,7 +199,9 @@ const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs (void);              /* never N
  *   pas_border    the bordered product of PAS's composite table in one pass over QX (GCGE_PAS_BORDER_FN, gcge_pas.h).
  *   mat_identity / mat_free   the identity of the size of a (whole, one-rank) matrix through the back-end's normal upload, and its
  *                 release: PAS's hierarchy of a standard problem takes its coarse masses P^T P from it (NULL: not offered).
- *   mat_rows_as_given   1 when the device rows of a matrix are in the order the caller gave them (0: the back-end re-ordered). */
+ *   mat_rows_as_given   1 when the device rows of a matrix are in the order the caller gave them (0: the back-end re-ordered).
+ *   amg_final_cols   1 when the smoother of amg_smoother_setup honours GCGE_LINSOL_ARGS.final_residual_cols: BlockAMG then tells each
+ *                 smoothing call that no residual is read (-1), except the cycle's last one, whose column 0 it reads (1). */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -214,6 +221,7 @@ typedef struct GCGE_BACKEND_ {
 			const double *t, int ldt, double *g, int ldg);
 	void *(*mat_identity) (void *like); void (*mat_free) (void *mat);
 	int  (*mat_rows_as_given) (void *mat);
+	int amg_final_cols;
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);
