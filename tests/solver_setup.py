@@ -25,7 +25,8 @@ class _BPCG(C.Structure):
                 ("MatDotMultiVec", C.c_void_p), ("niter", C.c_int), ("residual", C.c_double)]
 
 
-def bpcg_setup(ops_handle):
+def bpcg_setup(ops_handle, tol_type=b"abs"):
+    """Installs the host BlockPCG (libgcge_host) over the table's own slots; tol_type: b"abs", b"rel" or b"user"."""
     h = host_lib()
     from gcge_amd.ops_struct import OPS
 
@@ -35,7 +36,7 @@ def bpcg_setup(ops_handle):
         h.MultiLinearSolverSetup_BlockPCG.argtypes = [C.c_int, C.c_double, C.c_double, C.c_char_p, C.c_void_p,
                                                       C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p,
                                                       C.c_void_p, C.c_void_p]
-        h.MultiLinearSolverSetup_BlockPCG(max_iter, rate, tol, b"abs", arr, dbl.ctypes.data_as(C.POINTER(C.c_double)),
+        h.MultiLinearSolverSetup_BlockPCG(max_iter, rate, tol, tol_type, arr, dbl.ctypes.data_as(C.POINTER(C.c_double)),
                                           iw.ctypes.data_as(C.POINTER(C.c_int)), None, None, ops_handle)
         solve()
         st = C.cast(C.cast(ops_handle, C.POINTER(OPS)).contents.multi_linear_solver_workspace, C.POINTER(_BPCG)).contents

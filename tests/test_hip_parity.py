@@ -273,6 +273,69 @@ def test_fused_block_pcg_matches_reference(hip):
         hip.g.gcge_hip_bpcg_stats(None, None, C.byref(it))
         return it.value
     run_bpcg_case(hip, P, setup)
+    _fused_block_pcg_rel_cases(hip, P)
+
+
+def _cg_distance_to_thresholds(S, B, X0, max_iter, rate, tol):
+    """Plain CG per column in numpy with BlockPCG's "rel" stopping rule (src/ops_lin_sol.c:175-197, 372-380):
+    (iterations of the slowest column, the smallest |res / threshold - 1| any column saw at any iteration)."""
+    niter, closest = 0, np.inf
+    for j in range(B.shape[1]):
+        b, x = B[:, j], X0[:, j].copy()
+        r = b - S @ x
+        init, nb = np.linalg.norm(r), np.linalg.norm(b)
+        p, rho, k = r.copy(), r @ r, 0
+        while k < max_iter and (k > 0 or init > tol * nb):
+            w = S @ p
+            al = rho / (p @ w)
+            x += al * p; r -= al * w
+            rn = r @ r; res = np.sqrt(rn); k += 1
+            closest = min(closest, abs(res / (rate * init) - 1.0), abs(res / (tol * nb) - 1.0))
+            if not (res > rate * init and res > tol * nb):
+                break
+            p = r + (rn / rho) * p; rho = rn
+        niter = max(niter, k)
+    return niter, closest
+
+
+def _fused_block_pcg_rel_cases(hip, P):
+    """tol_type "rel" — the route that needs |b| — has no stored vectors: the reference is the host BlockPCG of libgcge_host
+    over the same HIP slots (solver_setup.bpcg_setup), same iteration count and x to the 1e-10 of the "abs" case.  Two sets of
+    operands: those of run_bpcg_case (4 columns out of wider blocks, b at an odd column) and an even-width block at column 0
+    with a start vector, where tol * |b| is the binding rule (rate * |r0| is still 50 x away when the columns stop).
+    rate 1e-8, tol 1e-5, 25 iterations: a float64 CG per column (above) stops every column at least 10 % away from both
+    thresholds, so a difference in rounding cannot move an iteration count; asserted here so that it stays true."""
+    c = load_golden("slots.json")["block_pcg"]
+    n, ops, S = P.n, hip.ops, csr_to_scipy(P.A5)
+    max_iter, rate, tol = 25, 1e-8, 1e-5
+    hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
+    cases = [(uniform(c["seed_b"], (n, 6)), np.zeros((n, 7)), c["start"], c["end"]),
+             (uniform(72, (n, 8)) - 0.5, uniform(73, (n, 8)) - 0.5, [0, 0], [8, 8])]
+    for Bm, X0, start, end in cases:
+        xs, xe = start[1], end[1]
+        it_np, closest = _cg_distance_to_thresholds(S, Bm[:, start[0]:end[0]], X0[:, xs:xe], max_iter, rate, tol)
+        assert closest > 0.1 and it_np < max_iter, (closest, it_np)
+        got = {}
+        for which in ("host", "fused"):
+            b, x = hip.mv_from_numpy(P.mA5, Bm), hip.mv_from_numpy(P.mA5, X0)
+            solve = lambda: ops.multi_linear_solver(P.mA5, b, x, start, end)
+            if which == "host":
+                ws = [ops.mv_create(end[0] - start[0], P.mA5) for _ in range(3)]
+                niter = bpcg_setup(hip.ops_handle, b"rel")(max_iter, rate, tol, ws, solve)
+            else:
+                ws = []
+                hip.g.gcge_hip_bpcg_setup(hip.ops_handle, max_iter, rate, tol, b"rel")
+                solve()
+                it = C.c_int(); hip.g.gcge_hip_bpcg_stats(None, None, C.byref(it)); niter = it.value
+            got[which] = (niter, hip.mv_to_numpy(x, n, 0, X0.shape[1]))
+            for h in [b, x] + ws:
+                ops.mv_destroy(h)
+        print("fused CG \"rel\": columns %s, iterations host %d fused %d numpy %d, nearest threshold %.3f away, max |dx| %.3e"
+              % (end[0] - start[0], got["host"][0], got["fused"][0], it_np, closest, np.max(np.abs(got["fused"][1] - got["host"][1]))))
+        assert got["fused"][0] == got["host"][0] == it_np, (got["fused"][0], got["host"][0], it_np)
+        _close(got["fused"][1], got["host"][1], tol=1e-10, what="block_pcg solution, tol_type rel")
+        assert np.array_equal(got["fused"][1][:, :xs], X0[:, :xs]) and np.array_equal(got["fused"][1][:, xe:], X0[:, xe:])
+    hip.g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
 
 
 @pytest.mark.parametrize("key", ["lap3d_20_nev20", "fe3d_12_nev10", "sio2_12_nev10"])
@@ -1233,6 +1296,45 @@ def test_cg_start_from_scale_factors_equals_start_from_formed_rhs(hip, size, m):
     np.testing.assert_allclose(R2, X * s - csr_to_scipy(A) @ X, rtol=0, atol=1e-13 * np.abs(X).max() * 8)
     for v in [x, b] + blk:
         hip.ops.mv_destroy(v, m)
+    hip.free_matrix(mat)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("size,m", [(32, 16), (16, 22)])
+def test_cg_scale_factors_with_relative_tolerance_equal_the_formed_rhs(hip, size, m):
+    """tol_type "rel" needs |b|, so the fused solver must form b = x diag(s) even where the caller published the scale factors
+    (GCGE_LINSOL_ARGS.rhs_scale) and the one-sweep start would not read b: the block b comes back as x0 diag(s), and the solve
+    is the one of a caller who formed b itself — same iterations, x bit for bit."""
+    A, _ = make_problem("lap3d", size)
+    mat = hip.matrix(A)
+    n = A.nrows
+    g, h = hip.g, hip.h
+    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
+    h.GCGE_SetLinearSolverArgs.argtypes = [C.POINTER(LINSOL_ARGS)]
+    X = uniform(61, (n, m)) - 0.5
+    s = uniform(62, (m,)) * 0.2 + 0.01
+    sc = (C.c_double * m)(*s)
+    out = {}
+    g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-3, b"rel")
+    try:
+        for published in (1, 0):
+            x = hip.mv_from_numpy(mat, X)
+            b = hip.mv_from_numpy(mat, np.full((n, m), 7.0) if published else X * s)
+            if published:
+                h.GCGE_SetLinearSolverArgs(C.byref(LINSOL_ARGS(rhs_scale=sc)))
+            try:
+                hip.ops.multi_linear_solver(mat, b, x, (0, 0), (m, m))
+            finally:
+                h.GCGE_SetLinearSolverArgs(None)
+            it = C.c_int(); g.gcge_hip_bpcg_stats(None, None, C.byref(it))
+            out[published] = (it.value, hip.mv_to_numpy(x, n, 0, m), hip.mv_to_numpy(b, n, 0, m))
+            hip.ops.mv_destroy(x, m); hip.ops.mv_destroy(b, m)
+    finally:
+        g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
+    assert np.array_equal(out[1][2], X * s) and np.array_equal(out[0][2], X * s)
+    assert 0 < out[1][0] == out[0][0], (out[1][0], out[0][0])
+    assert np.array_equal(out[1][1], out[0][1])
+    assert not np.array_equal(out[1][1], X)
     hip.free_matrix(mat)
 
 
