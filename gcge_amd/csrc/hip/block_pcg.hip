@@ -67,29 +67,6 @@
 #include "gcge_hip.h"
 #include "gcge_hip_internal.h"
 
-extern "C" double* gcge_hip_partial_ws(size_t len);
-extern "C" void gcge_hip_reduce_partials(const double* d_partial, int nblocks, int len, double* d_out, void* stream);
-extern "C" void gcge_hip_spmm_dot_mv(void* mat, void** x, void** y, int* start, int* end, double* host_dots, struct OPS_* ops);
-extern "C" void gcge_hip_spmm_dot2_mv(void* mat, void** x, void** y, int* start, int* end, double* host_dots, double* host_yy,
-                                      struct OPS_* ops);
-extern "C" void gcge_hip_local_inner_prod(char nsd, void** x, void** y, int* start, int* end, double* ip, int ldIP, struct OPS_* ops);
-extern "C" int gcge_hip_cg_fusable(void* mat, void** p, int ncols);
-extern "C" int gcge_hip_cg_recompute_pays(void* mat);
-extern "C" int gcge_hip_cg_pass2i_dev(void* mat, void** p, void** pprev, void** pnew, int c0, int m, const double* d_alpha,
-                                      const double* d_beta, const int* d_flag, const double* d_betaprev, double* d_rho);
-extern "C" int gcge_hip_cg_start_scaled_mv(void* mat, void** x, int xc0, const double* host_scale, void** r, void** p0, int rc0,
-                                           int m, double* host_rho);
-extern "C" int gcge_hip_cg_start_mv(void* mat, void** x, int xc0, void** b, int bc0, void** r, void** p0, int rc0, int m,
-                                    double* host_rho);
-extern "C" int gcge_hip_cg_pass1_mv(void* mat, void** p, int c0, int m, double* host_pw, double* host_ww);
-extern "C" int gcge_hip_cg_pass1_dev(void* mat, void** p, int c0, int m, double* d_out);
-extern "C" int gcge_hip_spmm_dot2_dev(void* mat, void** x, void** y, int cx, int cy, int m, double* d_out);
-extern "C" int gcge_hip_spmm_dot2_dev_ok(void* mat, void** x, void** y, int cx, int cy, int m);
-extern "C" int gcge_hip_cg_pass2_dev(void* mat, void** p, void** r, void** pnew, int c0, int m, const double* d_alpha,
-                                     const double* d_beta, const int* d_flag, double* d_rho);
-extern "C" int gcge_hip_cg_pass2_mv(void* mat, void** p, void** r, void** pnew, int c0, int m, const double* d_alpha,
-                                    const double* d_beta, const int* d_flag, double* host_rho);
-
 namespace gcge {
 
 // x_j += aprev_j p_j (flag bit 2: deferred x update of the previous step), then
@@ -494,7 +471,6 @@ static void reduce_over_ranks(double* v, int n) {
   if (c != nullptr && n > 0) c->allreduce_sum(v, n, c->ctx);
 }
 
-extern "C" unsigned gcge_hip_mv_row_order_id(void** mv);
 static BpcgBlocks g_parked[8]; static int g_nparked = 0;
 static void bpcg_destroy_set(BpcgBlocks* q, struct OPS_* ops) {
   for (int i = 1; i < q->ring_len; ++i) if (q->ring[i]) ops->MultiVecDestroy(&q->ring[i], q->ws_cols, ops);

@@ -46,7 +46,7 @@ static inline void gcge_parallel_chunks(long n, int nchunks, F fn) {
   fn(0, 0L, n / nchunks);
   for (auto& t : th) t.join();
 }
-// sparse matrix handle (CCSMAT counterpart): shared by app_hip.hip (the slots) and rccl_comm.hip (the halo plan)
+// sparse matrix handle (CCSMAT counterpart): built by mat_upload.hip, multiplied by mat_product.hip, halo plan by rccl_comm.hip
 struct GCGE_HIP_MAT_ {
   int nrows;      // local rows
   int nglobal;    // global dimension
@@ -106,6 +106,110 @@ extern "C" void gcge_hip_bpcg_backend(GCGE_BACKEND* be);
 // A column scaling the slots hold back (column-wise Gram-Schmidt, app_hip.hip) is applied now.  First statement of every EXPORTED
 // raw kernel that takes device pointers: the caller may have fetched its pointer before the scaling was held back.
 extern "C" void gcge_hip_apply_pending(void);
+
+// ---- app_hip.hip (runtime state, pool, multivector slots) and mat_product.hip (everything that multiplies a matrix handle) ----------
+#include <chrono>
+struct GcgeHipMV {
+  double* d;      // 16-byte aligned: a hipMalloc'd block of the pool (mv_new), never an offset into one
+  size_t bytes;   // size of the allocation behind d
+  long ld;
+  int nrows, nrows_alloc, ncols;
+  const GCGE_HIP_MAT_* mat;   // shape donor (row partition)
+  GcgePerm* perm;             // the row order of the matrix this block was created for (NULL / identity: the caller's order); see mat_upload.hip
+  // column-wise Gram-Schmidt over the slots (app_hip.hip "one sweep per column"): the state lives in the block it belongs to
+  int pend_col; double pend_fac;                       // a scaling of column pend_col held back (pend_col < 0: none)
+  int spec_c0, spec_c1; unsigned long spec_epoch;      // Gram column of [spec_c0, spec_c1) computed on the way by the call of epoch spec_epoch
+  std::vector<double>* spec_dots;                      // (NULL: none)
+};
+static inline const GcgePerm* real_perm(const GcgePerm* p) { return (p != nullptr && !p->identity) ? p : nullptr; }
+// per-slot wall time (gcge_hip_slot_timing, app_hip.hip): one flag test when it is off
+struct SlotTimer {
+  const char* name; int cols; std::chrono::steady_clock::time_point t0; bool on;
+  SlotTimer(const char* n, int c);
+  ~SlotTimer();
+};
+extern "C" {
+void gcge_hip_enter(void);                      // top of every entry point that touches block data: counts the call, applies a held-back scaling
+double* gcge_hip_stage_d(size_t len);           // device / second device / pinned host staging of at least len doubles
+double* gcge_hip_stage_d2(size_t len);
+double* gcge_hip_stage_h(size_t len);
+void* gcge_hip_pool_alloc(size_t bytes);
+void gcge_hip_pool_free(void* q, size_t bytes);
+int gcge_hip_spmm_path_get(void);
+int gcge_hip_offset_patterns_get(void);
+unsigned gcge_hip_mv_row_order_id(void** mv);
+void gcge_hip_local_inner_prod(char nsd, void** x, void** y, int* start, int* end, double* ip, int ldIP, struct OPS_* ops);
+// mat_product.hip: its slots and hooks of the table OPS_HIP_Set fills, and the fused CG's entry points gcge_hip.h does not name
+void gcge_hip_product_slots(struct OPS_* ops, GCGE_BACKEND* be);
+void gcge_hip_spmm_dot_mv(void* mat, void** x, void** y, int* start, int* end, double* host_dots, struct OPS_* ops);
+void gcge_hip_spmm_dot2_mv(void* mat, void** x, void** y, int* start, int* end, double* host_dots, double* host_yy, struct OPS_* ops);
+int gcge_hip_cg_start_scaled_mv(void* mat, void** x, int xc0, const double* host_scale, void** r, void** p0, int rc0, int m, double* host_rho);
+// pas_border.hip
+int gcge_hip_pas_border(void** QX, int s, void** q, int q0, void** y, int y0, int m, double beta, const double* t, int ldt, double* g, int ldg);
+
+// ---- kernel files: what other translation units launch or build through them and gcge_hip.h does not name --------------------------
+// vec_kernels.hip
+double* gcge_hip_partial_ws(size_t len);
+void gcge_hip_reduce_partials(const double* d_partial, int nblocks, int len, double* d_out, void* stream);
+void gcge_hip_reduce_partials16(const double* d_partial, int nblocks, long slab_stride, int ncols, double* d_out, void* stream);
+void gcge_hip_reduce_partials_slabs(const double* d_partial, int nblocks, long slab_stride, int cpp, int ncols, double* d_out, void* stream);
+int gcge_hip_resid_sq(int nrows, const double* d_w, long ldw, const double* d_x, long ldx, int m, const double* d_lambda, double* d_out, void* stream);
+int gcge_hip_colscale(int nrows, double* d_y, long ldy, int m, const double* d_s, void* stream);
+int gcge_hip_panel_dot1(int nrows, const double* d_x, long ldx, int k, const double* d_y, long ldy, double* d_out, void* stream);
+int gcge_hip_rank1_update(int nrows, const double* d_x, long ldx, const double* d_c, const double* d_beta, double* d_y, long ldy, int m, void* stream);
+int gcge_hip_colscale1(int nrows, double* d_y, long ldy, double s, void* stream);
+int gcge_hip_mgs_step(int nrows, double* d_xk, long ld, double s, const double* d_c, int w, double* d_dots, void* stream);
+int gcge_hip_fill_uniform(int nrows, long row_begin, long nglobal, double* d_y, long ldy, int c0, int m, unsigned long long seed, void* stream);
+int gcge_hip_colmajor_to_rowmajor(int nrows, int m, const double* d_src, long lds, double* d_dst, long ldd, void* stream);
+int gcge_hip_rowmajor_to_colmajor(int nrows, int m, const double* d_src, long lds, double* d_dst, long ldd, void* stream);
+// spmm_pad8.hip
+int gcge_hip_pad8_spmm_dot(int nrows, const int* d_orp, const int* d_pcol, const double* d_pval, const double* d_x, long ldx, double* d_y, long ldy,
+                           int ncols, double* d_dots, void* stream, long x_own_row0);
+void gcge_hip_spmm_pad8_auto(double avg_octets_per_row);
+void gcge_hip_spmm_pad8_row_map(const int* d_map);
+void gcge_hip_spmm_pad8_row_map_add(const int* d_map);
+// spmm_pattern.hip, spmm_ring.hip
+int gcge_hip_pattern_spmm_vals(int nrows, const unsigned short* d_pid, const void* d_tab, int npat, int lt, long span, long span2, const double* d_x,
+                               long ldx, double* d_y, long ldy, int ncols, double* d_dots, double* d_dots_yy, void* stream, long near,
+                               const double* d_rowval);
+int gcge_hip_pattern_cg_vals(int mode, int nrows, const unsigned short* d_pid, const void* d_tab, int npat, int lt, long span, long span2,
+                             const double* d_x, long ldx, double* d_r, long ldr, double* d_pnew, long ldp, int ncols, const double* d_alpha,
+                             const double* d_beta, const int* d_flag, double* d_dots, double* d_dots_yy, void* stream, const double* d_b, long ldb,
+                             long near, const double* d_rowval);
+int gcge_hip_ring_pass(int mode, int nrows, const unsigned short* d_pid, const void* d_tab, int npat, long L, int nw, long nb, const double* d_x,
+                       long ldx, int m, double* part, long yyo, const double* d_lambda, void* stream, long maxoff, double* d_y, long ldy, int gy);
+// spmm_tile.hip
+void* gcge_hip_tile_build(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val);
+void* gcge_hip_tile_build_for(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, int remainder);
+void gcge_hip_tile_free(void* tm);
+int gcge_hip_spmm_tile_mode_get(void);
+void gcge_hip_tile_stats(const void* tm, long* ntiles, long* ov_nnz, double* xrows_per_row, double* ell_per_nnz, int* brick, long* strides);
+int gcge_hip_tile_spmm(const void* tm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, void* stream);
+// spmm_dense.hip
+void* gcge_hip_dense_build(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val);
+void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed);
+void gcge_hip_dense_free(void* dm);
+int gcge_hip_dense_remainder_is_tiled(const void* dm);
+const void* gcge_hip_dense_remainder_tile(const void* dm);
+void gcge_hip_dense_stats(const void* dm, long* nblocks, long* items, long* dense_nnz, long* dense_entries, long* rem_nnz);
+int gcge_hip_dense_spmm(const void* dm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, void* stream, int which);
+const int* gcge_hip_dense_row_list(const void* dm, int* nlisted);
+// spmm_star.hip
+void gcge_hip_star_next_geometry(int nrows, int nx, int ny, int nz, const int* box_of_row);
+void* gcge_hip_star_build(int nrows, int ncols_local, long row_begin, long nglobal, const int* ghost, const int* rowptr, const int* colidx, const double* val,
+                          const int** rem_rowptr, const int** rem_col, const double** rem_val);
+void gcge_hip_star_release_remainder(void);
+void gcge_hip_star_free(void* sm);
+void gcge_hip_star_stats(const void* sm, long* out);
+const unsigned char* gcge_hip_star_host_mask(void);
+int gcge_hip_star_masked_form(const void* sm);
+int gcge_hip_star_interior(const void* sm, int* ilo, int* ihi);
+int gcge_hip_star_spmm(const void* sm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, void* stream);
+int gcge_hip_star_spmm_part(const void* sm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, double* d_dots, void* stream, int part);
+int gcge_hip_star_coldots2_rows(int nlist, const int* d_list, const double* d_x, long ldx, const double* d_y, long ldy, int m, double* d_out, void* stream);
+// reorder.hip
+double gcge_hip_mean_bandwidth(int n, const int* rowptr, const int* colidx, const int* iperm);
+}
 
 #endif
 

@@ -26,8 +26,6 @@
 #include <stdlib.h>
 #include "gcge_hip_internal.h"
 
-extern "C" double* gcge_hip_partial_ws(size_t len);
-
 namespace gcge {
 #include "agpr_tiles.inc"
 

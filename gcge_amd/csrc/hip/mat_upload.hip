@@ -1,6 +1,6 @@
 // Matrix handle of the HIP back-end (the CCSMAT counterpart, reference app/app_ccs.h:20-24): upload of the host CSR arrays,
 // their analysis into the forms the K1 kernels take (pad-8 copy, row patterns, star + remainder, dense blocks, tiles), the halo
-// plan of a row slab, destruction.  Split off app_hip.hip in round 4; the slots live there.
+// plan of a row slab, destruction.  Split off app_hip.hip in round 4; the multivector slots live there, the products in mat_product.hip.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -15,27 +15,6 @@
 #include "gcge_hip.h"
 #include "gcge_hip_internal.h"
 
-extern "C" {
-int gcge_hip_spmm_path_get(void);
-int gcge_hip_offset_patterns_get(void);
-int gcge_hip_pattern_width(int max_row_len);
-void* gcge_hip_tile_build(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val);
-void gcge_hip_tile_free(void* tm);
-int gcge_hip_spmm_tile_mode_get(void);
-void* gcge_hip_dense_build(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val);
-void gcge_hip_dense_free(void* dm);
-int gcge_hip_dense_remainder_is_tiled(const void* dm);
-const void* gcge_hip_dense_remainder_tile(const void* dm);
-void gcge_hip_dense_stats(const void* dm, long* nblocks, long* items, long* dense_nnz, long* dense_entries, long* rem_nnz);
-void gcge_hip_tile_stats(const void* tm, long* ntiles, long* ov_nnz, double* xrows_per_row, double* ell_per_nnz, int* brick, long* strides);
-void* gcge_hip_star_build(int nrows, int ncols_local, long row_begin, long nglobal, const int* ghost, const int* rowptr, const int* colidx, const double* val,
-                          const int** rem_rowptr, const int** rem_col, const double** rem_val);
-void gcge_hip_star_release_remainder(void);
-void gcge_hip_star_free(void* sm);
-void gcge_hip_star_stats(const void* sm, long* out);
-const unsigned char* gcge_hip_star_host_mask(void);
-void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed);
-}
 #define g_spmm_path (gcge_hip_spmm_path_get())
 #define g_offset_patterns (gcge_hip_offset_patterns_get())
 
@@ -318,10 +297,6 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local(int nrows, int ncols_local, i
 // handles are opaque, blocks of vectors created for the matrix live in the new order, gcge_hip_mv_to_host / from_host
 // and the reference-order random fill translate.  mode: 0 automatic (matrices of >= 65 536 rows without a fast form), 1 every matrix
 // without a fast form (tests), -1 never.
-extern "C" void gcge_hip_star_next_geometry(int nrows, int nx, int ny, int nz, const int* box_of_row);
-extern "C" long gcge_hip_reorder_star_grid(int n, const int* rowptr, const int* colidx, const double* val, int* dims, int* box_of_row);
-extern "C" int gcge_hip_reorder_rcm(int n, const int* rowptr, const int* colidx, int* perm);
-extern "C" double gcge_hip_mean_bandwidth(int n, const int* rowptr, const int* colidx, const int* iperm);
 static int g_reorder_mode = 0;
 extern "C" void gcge_hip_spmm_reorder_mode(int mode) { g_reorder_mode = mode; }
 static std::vector<GcgePerm*> g_perms;          // live orders, one per n
@@ -433,7 +408,6 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_beg
 // geometry named, the rows that are a star stencil on that grid take the plane sweep of spmm_star.hip (through a row map);
 // without it such a matrix is served by dense blocks + the pad-8 kernel.  The geometry only selects kernels: results are those
 // of gcge_hip_mat_create on the same arrays.
-extern "C" void gcge_hip_star_next_geometry(int nrows, int nx, int ny, int nz, const int* box_of_row);
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_grid(int nrows, const int* rowptr, const int* colidx, const double* val,
                                                   int nx, int ny, int nz, const int* box_of_row) {
   if (box_of_row != nullptr && nx > 0 && ny > 0 && nz > 0) gcge_hip_star_next_geometry(nrows, nx, ny, nz, box_of_row);
@@ -530,7 +504,6 @@ extern "C" int gcge_hip_mat_form_stats(const GCGE_HIP_MAT* A, double* out) {
   }
   return 1;
 }
-extern "C" int gcge_hip_star_masked_form(const void* sm);
 extern "C" int gcge_hip_mat_star_masked_form(const GCGE_HIP_MAT* A) { return A->star != nullptr ? gcge_hip_star_masked_form(A->star) : 0; }
 // the grid form (spmm_star.hip): out[0..5] = nx, ny, nz, arm length of the star, rows it multiplies, rows of the matrix.  0: none.
 extern "C" int gcge_hip_mat_star_stats(const GCGE_HIP_MAT* A, long* out) {

@@ -19,12 +19,6 @@
 #include <vector>
 #include "gcge_hip_internal.h"
 
-extern "C" double* gcge_hip_partial_ws(size_t len);
-extern "C" double* gcge_hip_mv_device_ptr(void** mv, long* ld);
-extern "C" int gcge_hip_mv_nrows(void** mv);
-extern "C" int gcge_hip_mv_ncols(void** mv);
-extern "C" void* gcge_hip_stream(void);
-
 namespace {
 typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr int SC = 128;   // border columns per pass: 8 tiles of 16, two per wave

@@ -11,7 +11,7 @@
 //                             need are packed by a kernel, moved by ONE grouped ncclSend/ncclRecv per product and
 //                             unpacked into the halo rows — ordered by events, no host or device-wide synchronisation;
 //                             in the split form the transfer runs on its own stream while the interior rows are
-//                             multiplied (app_hip.hip: spmm_halo).
+//                             multiplied (mat_product.hip: spmm_halo).
 // xGMI is point-to-point, a slab has two neighbours: the grouped send/recv uses exactly the two links involved.
 // Python (bench.py, gcge_amd/dist.py) keeps only the bootstrap: handing rank 0's 128-byte id to the other ranks.
 #include <hip/hip_runtime.h>
@@ -238,9 +238,7 @@ static void rccl_exchange_int(const int* sendbuf, const int* send_cnt, int* recv
 // ... of a matrix on a MASKED grid (gcge_hip_mat_create_grid on one rank): box_of_global_row[r] = x + nx (y + ny z) of global row r,
 // rows in scan order, the partition cut between grid LINES (gcge_dist_partition_lines) — the slab keeps the plane sweep, its halo rows
 // are found through the line table (spmm_star.hip).  NULL geometry: gcge_hip_mat_create_slab.
-extern "C" void gcge_hip_star_next_geometry_cols(int ncols_local, int nx, int ny, int nz, const int* box_of_local_col);
 static const int* g_slab_box = nullptr; static int g_slab_dims[3] = {0, 0, 0};
-extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_slab(const long* part, const int* rowptr, const int* colidx_global, const double* val, int buf_cols);
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_slab_grid(const long* part, const int* rowptr, const int* colidx_global, const double* val, int buf_cols,
                                                        int nx, int ny, int nz, const int* box_of_global_row) {
   g_slab_box = box_of_global_row; g_slab_dims[0] = nx; g_slab_dims[1] = ny; g_slab_dims[2] = nz;

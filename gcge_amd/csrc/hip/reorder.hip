@@ -22,6 +22,8 @@
 #include <unordered_map>
 #include <vector>
 
+#include "gcge_hip_internal.h"
+
 // ---------------------------------------------------------------------------------------------------------------- RCM
 // perm[new] = old.  Components in order of their lowest-degree node; inside a component: BFS from a pseudo-peripheral node (two
 // sweeps of the Gibbs-Poole-Stockmeyer kind), neighbours visited by ascending degree; the whole order reversed.

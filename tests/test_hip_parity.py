@@ -2288,3 +2288,49 @@ def test_dense_profile_reports_the_shapes_a_solve_used(hip):
     buf = C.create_string_buffer(256)
     assert g.gcge_hip_dense_profile_report(buf, 256) == 0
     assert res.nevConv >= 6
+
+
+def test_product_profile_counts_and_algorithmic_bytes(hip):
+    """gcge_hip_profile_kind (bench.py's roofline lines divide its bytes by its time): one MatDotMultiVec, one first pass and the
+    two second passes of the fused CG on a pattern matrix are recorded as 1 / 1 / 2 launches of kinds 0 / 2 / 3 with exactly
+    12 nnz + 4 (nrows + 1) + 8 streams nrows m bytes each — streams: 2 (x read, y written), 1 (p read), 4 (p, r read; r, p_new
+    written) and 3 (p, p_prev read; p_new written).  Every term is an integer far below 2^53, so the sums are exact doubles."""
+    import torch
+    A, _ = make_problem("lap3d", 16)
+    n, nnz, m = A.nrows, int(A.nnz), 16
+    mat = hip.matrix(A)
+    g = hip.g
+    g.gcge_hip_profile_enable.argtypes = [C.c_int]
+    g.gcge_hip_profile_kind.restype = C.c_long
+    g.gcge_hip_profile_kind.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    g.gcge_hip_cg_pass1_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    g.gcge_hip_cg_pass2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p]
+    g.gcge_hip_cg_pass2i_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    p, r, q, pn = (hip.mv_from_numpy(mat, uniform(81 + i, (n, m)) - 0.5) for i in range(4))
+    d_al, d_be, d_bp = (torch.from_numpy(uniform(91 + i, (m,)) + 0.1).cuda() for i in range(3))
+    d_fl = torch.ones(m, dtype=torch.int32).cuda()
+    pw, ww, rho = np.zeros(m), np.zeros(m), np.zeros(m)
+    g.gcge_hip_profile_enable(1)
+    try:
+        hip.ops.spmm(mat, p, pn, (0, 0), (m, m))
+        assert g.gcge_hip_cg_pass1_mv(mat, p, 0, m, pw.ctypes.data, ww.ctypes.data) == 0
+        assert g.gcge_hip_cg_pass2_mv(mat, p, r, pn, 0, m, d_al.data_ptr(), d_be.data_ptr(), d_fl.data_ptr(), rho.ctypes.data) == 0
+        assert g.gcge_hip_cg_pass2i_mv(mat, p, q, pn, 0, m, d_al.data_ptr(), d_be.data_ptr(), d_fl.data_ptr(), d_bp.data_ptr(),
+                                       rho.ctypes.data) == 0
+        matrix_bytes = 12.0 * nnz + 4.0 * (n + 1.0)
+        for kind, count, streams in ((0, 1, 2), (2, 1, 1), (3, 2, 4 + 3)):
+            ms, by = C.c_double(-1.0), C.c_double(-1.0)
+            got = g.gcge_hip_profile_kind(kind, m, C.byref(ms), C.byref(by))
+            print("kind %d: count %d, %.1f bytes, %.4f ms" % (kind, got, by.value, ms.value))
+            assert got == count, (kind, got)
+            assert by.value == count * matrix_bytes + 8.0 * streams * n * m, (kind, by.value)
+            assert ms.value > 0.0, (kind, ms.value)
+            assert g.gcge_hip_profile_kind(kind, m + 2, None, None) == 0      # (no launch of another width)
+    finally:
+        g.gcge_hip_profile_enable(0)
+    assert g.gcge_hip_profile_kind(0, 0, None, None) == 0                      # switching it off empties the record
+    for v in (p, r, q, pn):
+        hip.ops.mv_destroy(v, m)
+    hip.free_matrix(mat)
