@@ -81,6 +81,10 @@ struct GCGE_HIP_MAT_ {
   // round 5: the row order the back-end chose for itself (mat_upload.hip "row orders"): the device arrays hold P A P^T, every block of
   // vectors created for this matrix lives in the same order; NULL: the caller's order
   struct GcgePerm* perm;
+  // one rank, whole matrix: the masked grid its rows live on (mat_upload.hip "geometry"), whatever K1 form the matrix took — what
+  // MultiGridCreate coarsens by 2 x 2 x 2 cells.  geom_kind 0: none, 1: named by the caller (gcge_hip_mat_create_grid), 2: recovered
+  // at upload (the grid form of spmm_star.hip was built on it); row r is box point h_box[r] = x + nx (y + ny z) of geom_dims, strictly ascending
+  int geom_kind; int geom_dims[3]; int* h_box; int* d_box;
 };
 // One row order per problem size and process: every matrix of n rows (A, then B of a generalised problem) and every block of vectors
 // created for them share it.  perm[new] = old, iperm[old] = new; identity: a matrix of this size was uploaded in the caller's order and
@@ -98,6 +102,8 @@ extern "C" void gcge_hip_mg_agg_grid_device(const int dims[3], int* d_agg, int* 
 extern "C" int gcge_hip_mg_galerkin_device(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
                                            const int* d_ptr, const int* d_mem, double scale, int** d_rp_out, int** d_ci_out, double** d_va_out,
                                            long* nnz_out, long* d2h);
+extern "C" int gcge_hip_mg_agg_masked_device(const int dims[3], const int* d_box, int nf, int* d_agg, int* d_mem, int** d_ptr_out, int** d_cbox_out,
+                                             int cdims[3], long* d2h);
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_rect_device(int nf, int nc, const int* d_agg, const int* d_ptr, const int* d_mem);
 extern "C" int gcge_hip_mg_download_csr(int nrows, int ncols, long nnz, const int* d_rp, const int* d_ci, const double* d_va, GCGE_CSR* out, long* d2h);
 void gcge_hip_mg_members_host(const int* agg, int nf, int nc, std::vector<int>& ptr, std::vector<int>& mem);

@@ -197,6 +197,29 @@ static void build_patterns(GCGE_HIP_MAT* A, int nrows, int ncols_local, const in
   GCGE_HIP_CHECK(hipMemcpy(A->d_tab, tab.data(), tab.size() * sizeof(PatEntryH), hipMemcpyHostToDevice));
 }
 
+// ---------------------------------------------------------------------------------------------------------------- geometry
+// The masked grid a whole matrix lives on stays on the handle — named by the caller (kind 1) or recovered at upload (kind 2) —
+// independent of the K1 form: host and device copies of the box array.  A geometry that is not one (box indices out of the box or
+// not strictly ascending) is not recorded.
+static bool g_geometry_named = false;       // the upload in progress has its geometry from the caller (or from the row order search)
+static void mat_set_geometry(GCGE_HIP_MAT* A, int kind, int nx, int ny, int nz, const int* box) {
+  const long nbox = (long)nx * ny * nz;
+  if (A == nullptr || box == nullptr || nx < 1 || ny < 1 || nz < 1 || nbox > 2147483647L || A->nghost != 0 || A->row_begin != 0) return;
+  for (int r = 0; r < A->nrows; ++r) if (box[r] < 0 || box[r] >= nbox || (r > 0 && box[r] <= box[r - 1])) return;
+  free(A->h_box); if (A->d_box) hipFree(A->d_box);
+  A->h_box = (int*)malloc((size_t)(A->nrows ? A->nrows : 1) * sizeof(int));
+  memcpy(A->h_box, box, (size_t)A->nrows * sizeof(int));
+  GCGE_HIP_CHECK(hipMalloc(&A->d_box, (size_t)(A->nrows ? A->nrows : 1) * sizeof(int)));
+  GCGE_HIP_CHECK(hipMemcpy(A->d_box, box, (size_t)A->nrows * sizeof(int), hipMemcpyHostToDevice));
+  A->geom_kind = kind; A->geom_dims[0] = nx; A->geom_dims[1] = ny; A->geom_dims[2] = nz;
+}
+extern "C" int gcge_hip_mat_geometry(const GCGE_HIP_MAT* A, int* dims, int* box_of_row) {
+  if (A == nullptr || A->geom_kind == 0) return 0;
+  if (dims != nullptr) { dims[0] = A->geom_dims[0]; dims[1] = A->geom_dims[1]; dims[2] = A->geom_dims[2]; }
+  if (box_of_row != nullptr) memcpy(box_of_row, A->h_box, (size_t)A->nrows * sizeof(int));
+  return A->geom_kind;
+}
+
 // rows of one slab with LOCAL column indices in [0, ncols_local); columns >= nrows are halo rows.  ghost_global (may be NULL): the
 // global rows behind the halo columns, ascending — with it (and nglobal) a slab of a grid matrix cut on plane boundaries keeps the
 // plane sweep of spmm_star.hip: the planes below and above the slab are then found among the halo rows.
@@ -263,6 +286,13 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local_ghosts(int nrows, int ncols_l
     const bool slab = !whole && nglobal > 0 && (ncols_local == nrows || ghost_global != nullptr);
     void* S = (whole || slab) ? gcge_hip_star_build(nrows, ncols_local, row_begin, whole ? nrows : nglobal, ghost_global, rowptr, colidx, val, &rr, &rc, &rv) : nullptr;
     phase("star split");
+    if (S != nullptr && whole && !g_geometry_named && gcge_hip_star_masked_form(S) != 0) {
+      // a masked grid nobody named: the build recovered it from the rows.  The same recovery once more, for the handle — kept
+      // whatever becomes of the grid form below
+      std::vector<int> gbox((size_t)nrows); int gd[3] = {0, 0, 0};
+      if (gcge_hip_star_infer_grid(nrows, rowptr, colidx, gd, gbox.data())) mat_set_geometry(A, 2, gd[0], gd[1], gd[2], gbox.data());
+      phase("geometry for the handle");
+    }
     if (S != nullptr) {
       void* D = gcge_hip_dense_build_rows(nrows, ncols_local, rr, rc, rv, gcge_hip_star_host_mask());   // (its pad-8 part lists the other rows only)
       if (D != nullptr) { A->star = S; A->star_rem = D; } else gcge_hip_star_free(S);   // (no blocks among the other rows: the forms below)
@@ -394,7 +424,9 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_beg
     std::vector<int> bsorted((size_t)nrows);
     for (int i = 0; i < nrows; ++i) bsorted[i] = box[perm[i]];
     gcge_hip_star_next_geometry(nrows, dims[0], dims[1], dims[2], bsorted.data());
+    g_geometry_named = true;
     A = gcge_hip_mat_create_local(nrows, nrows, nglobal, 0, rp.data(), ci.data(), va.data());
+    g_geometry_named = false;
     gcge_hip_star_next_geometry(0, 0, 0, 0, nullptr);
   } else {
     A = gcge_hip_mat_create_local(nrows, nrows, nglobal, 0, rp.data(), ci.data(), va.data());
@@ -411,9 +443,12 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_beg
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_grid(int nrows, const int* rowptr, const int* colidx, const double* val,
                                                   int nx, int ny, int nz, const int* box_of_row) {
   if (box_of_row != nullptr && nx > 0 && ny > 0 && nz > 0) gcge_hip_star_next_geometry(nrows, nx, ny, nz, box_of_row);
+  g_geometry_named = true;
   GCGE_HIP_MAT* A = gcge_hip_mat_create_local(nrows, nrows, nrows, 0, rowptr, colidx, val);      // (the caller named the geometry: the rows stay as given)
+  g_geometry_named = false;
   if (A != nullptr) { GcgePerm* P = perm_find(nrows); if (P == nullptr) P = perm_register(nrows, nullptr); if (P->identity) A->perm = gcge_hip_perm_acquire(P); }
   gcge_hip_star_next_geometry(0, 0, 0, 0, nullptr);                   // (not consumed when the matrix took a pattern form)
+  if (A != nullptr && box_of_row != nullptr && nx > 0 && ny > 0 && nz > 0) mat_set_geometry(A, 1, nx, ny, nz, box_of_row);
   return A;
 }
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_csr(const GCGE_CSR* A) {
@@ -451,6 +486,7 @@ extern "C" void gcge_hip_mat_destroy(GCGE_HIP_MAT* A) {
   if (A->star != nullptr) gcge_hip_star_free(A->star);
   if (A->native_halo != nullptr) gcge_hip_halo_native_free(A);   // RCCL plan + the exchange buffers it owns (rccl_comm.hip)
   free(A->h_ghost_global); free(A->h_part);
+  free(A->h_box); if (A->d_box) hipFree(A->d_box);
   gcge_hip_perm_release(A->perm);
   free(A);
 }

@@ -2,7 +2,8 @@
 //
 // What csrc/host/multigrid.c does on host CSR arrays, done here on the device-resident CSR of a level, with the same results bit for
 // bit: grid aggregation (gcge_mg_aggregate_grid: 2 x 2 x 2 cells, the last cell of an odd direction one layer thick), the members of
-// every aggregate in ascending fine-row order (aggregate_members), the Galerkin product Ac = scale P^T A P for a piecewise-constant
+// every aggregate in ascending fine-row order (aggregate_members), the cells of a masked grid (gcge_mg_aggregate_masked: the occupied
+// cells counted, numbered by a sum, their members found in the sorted box array), the Galerkin product Ac = scale P^T A P for a piecewise-constant
 // P (gcge_mg_galerkin) and the two CSR triples of P / P^T (gcge_mg_prolongation).
 //
 // Galerkin product: one wave per coarse row I.  Its entries are the entries of its member rows, member rows ascending, each row in
@@ -45,6 +46,51 @@ __global__ void k_mg_members_grid(int nx, int ny, int nz, int cx, int cy, int nc
   for (int dz = 0; dz < wz; ++dz)
     for (int dy = 0; dy < wy; ++dy)
       for (int dx = 0; dx < wx; ++dx) mem[q++] = (2 * ix + dx) + nx * ((2 * iy + dy) + ny * (2 * iz + dz));
+}
+
+// ------------------------------------------------------------------------------------------------------------ aggregation of a masked grid
+// gcge_mg_aggregate_masked on the device: row r is box point box[r] (strictly ascending) of the box nx x ny x nz, its cell the
+// 2 x 2 x 2 cell of that point.  Integer atomics count the rows of every cell (a count does not depend on the order of its
+// increments); two sums over the cells number the occupied ones and place their members; the members themselves are FOUND, not
+// collected: a cell's points in ascending box index are its rows in ascending order, and box is sorted, so each is a binary search.
+__device__ inline int mg_cell_of(int b, int nx, int ny, int cx, int cy) {
+  const int x = b % nx, y = (b / nx) % ny, z = b / (nx * ny);
+  return cx * ((y / 2) + cy * (z / 2)) + x / 2;
+}
+// cnt[1 + cell] = rows in the cell
+__global__ void k_mg_masked_count(int nf, const int* __restrict__ box, int nx, int ny, int cx, int cy, int* __restrict__ cnt) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < nf) atomicAdd(&cnt[1 + mg_cell_of(box[r], nx, ny, cx, cy)], 1);
+}
+__global__ void k_mg_masked_flag(int ncell, const int* __restrict__ cnt, int* __restrict__ occ) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < ncell) occ[1 + c] = cnt[1 + c] > 0;
+}
+// after the sums: occ[c] = occupied cells before c (the number of cell c when it is one), cnt[c] = rows in the cells before c
+__global__ void k_mg_masked_agg(int nf, const int* __restrict__ box, int nx, int ny, int cx, int cy, const int* __restrict__ occ, int* __restrict__ agg) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < nf) agg[r] = occ[mg_cell_of(box[r], nx, ny, cx, cy)];
+}
+__global__ void k_mg_masked_cells(int nf, const int* __restrict__ box, int nx, int ny, int nz, int cx, int cy, int ncell, int nc,
+                                  const int* __restrict__ occ, const int* __restrict__ cnt, int* __restrict__ ptr, int* __restrict__ mem,
+                                  int* __restrict__ cbox) {
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c == 0) ptr[nc] = nf;
+  if (c >= ncell || cnt[c + 1] == cnt[c]) return;
+  const int I = occ[c], ix = c % cx, iy = (c / cx) % cy, iz = c / (cx * cy);
+  int q = cnt[c];
+  const int q1 = cnt[c + 1];
+  ptr[I] = q; cbox[I] = c;
+  for (int dz = 0; dz < 2; ++dz)
+    for (int dy = 0; dy < 2; ++dy)
+      for (int dx = 0; dx < 2; ++dx) {
+        const int x = 2 * ix + dx, y = 2 * iy + dy, z = 2 * iz + dz;
+        if (x >= nx || y >= ny || z >= nz || q >= q1) continue;
+        const int b = x + nx * (y + ny * z);
+        int lo = 0, hi = nf;                          // first row with box[row] >= b
+        while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (box[mid] < b) lo = mid + 1; else hi = mid; }
+        if (lo < nf && box[lo] == b) mem[q++] = lo;
+      }
 }
 
 // ------------------------------------------------------------------------------------------------------------ Galerkin product
@@ -270,6 +316,66 @@ extern "C" void gcge_hip_mg_agg_grid_device(const int dims[3], int* d_agg, int* 
   mg_inclusive_sum(d_ptr + 1, nc);
   hipLaunchKernelGGL(k_mg_members_grid, dim3(mg_blocks(nc, 256)), dim3(256), 0, mg_stream(), nx, ny, nz, cx, cy, nc, 1, d_ptr, d_mem);
   GCGE_HIP_CHECK(hipGetLastError());
+}
+
+// the cells of a masked grid from its device-resident box array (nf strictly ascending box indices of the box dims, checked by
+// whoever put the geometry on the handle): d_agg / d_mem (nf ints, the caller's) are filled, *d_ptr_out (nc + 1 ints) and *d_cbox_out
+// (nc ints: the coarse level's box array) are allocated here (hipFree).  Returns the number of aggregates; one int comes back.
+extern "C" int gcge_hip_mg_agg_masked_device(const int dims[3], const int* d_box, int nf, int* d_agg, int* d_mem, int** d_ptr_out,
+                                             int** d_cbox_out, int cdims[3], long* d2h) {
+  const int nx = dims[0], ny = dims[1], nz = dims[2];
+  const int cx = (nx + 1) / 2, cy = (ny + 1) / 2, cz = (nz + 1) / 2;
+  const long ncell_l = (long)cx * cy * cz;
+  GCGE_REQUIRE(nf > 0 && (long)nx * ny * nz <= 2147483647L && nf <= (long)nx * ny * nz, "gcge_hip_mg_agg_masked_device: the rows are points of the box");
+  const int ncell = (int)ncell_l;
+  cdims[0] = cx; cdims[1] = cy; cdims[2] = cz;
+  int *d_cnt = nullptr, *d_occ = nullptr;
+  GCGE_HIP_CHECK(hipMalloc(&d_cnt, ((size_t)ncell + 1) * sizeof(int)));
+  GCGE_HIP_CHECK(hipMalloc(&d_occ, ((size_t)ncell + 1) * sizeof(int)));
+  GCGE_HIP_CHECK(hipMemsetAsync(d_cnt, 0, ((size_t)ncell + 1) * sizeof(int), mg_stream()));
+  GCGE_HIP_CHECK(hipMemsetAsync(d_occ, 0, sizeof(int), mg_stream()));
+  hipLaunchKernelGGL(k_mg_masked_count, dim3(mg_blocks(nf, 256)), dim3(256), 0, mg_stream(), nf, d_box, nx, ny, cx, cy, d_cnt);
+  hipLaunchKernelGGL(k_mg_masked_flag, dim3(mg_blocks(ncell, 256)), dim3(256), 0, mg_stream(), ncell, (const int*)d_cnt, d_occ);
+  GCGE_HIP_CHECK(hipGetLastError());
+  mg_inclusive_sum(d_cnt + 1, ncell);
+  mg_inclusive_sum(d_occ + 1, ncell);
+  int nc = 0;
+  GCGE_HIP_CHECK(hipMemcpy(&nc, d_occ + ncell, sizeof nc, hipMemcpyDeviceToHost));
+  if (d2h) *d2h += (long)sizeof nc;
+  GCGE_REQUIRE(nc >= 1 && nc <= nf, "gcge_hip_mg_agg_masked_device: every row lies in a cell");
+  int *d_ptr = nullptr, *d_cbox = nullptr;
+  GCGE_HIP_CHECK(hipMalloc(&d_ptr, ((size_t)nc + 1) * sizeof(int)));
+  GCGE_HIP_CHECK(hipMalloc(&d_cbox, (size_t)nc * sizeof(int)));
+  hipLaunchKernelGGL(k_mg_masked_agg, dim3(mg_blocks(nf, 256)), dim3(256), 0, mg_stream(), nf, d_box, nx, ny, cx, cy, (const int*)d_occ, d_agg);
+  hipLaunchKernelGGL(k_mg_masked_cells, dim3(mg_blocks(ncell, 256)), dim3(256), 0, mg_stream(), nf, d_box, nx, ny, nz, cx, cy, ncell, nc,
+                     (const int*)d_occ, (const int*)d_cnt, d_ptr, d_mem, d_cbox);
+  GCGE_HIP_CHECK(hipGetLastError());
+  GCGE_HIP_CHECK(hipStreamSynchronize(mg_stream()));
+  hipFree(d_cnt); hipFree(d_occ);
+  *d_ptr_out = d_ptr; *d_cbox_out = d_cbox;
+  return nc;
+}
+
+// the same for a host box array, everything copied back: agg, mem (nrows ints), ptr (nrows + 1 ints: nc + 1 used), cbox (nrows ints:
+// nc used) — tests and tools.  Returns the number of aggregates, -2 for a geometry gcge_mg_aggregate_masked refuses.
+extern "C" int gcge_hip_mg_aggregate_masked(const int dims[3], const int* box_of_row, int nrows, int* agg, int* ptr, int* mem, int* cbox, int cdims[3]) {
+  if (gcge_hip_init(-1) != 0 || nrows < 1) return -1;
+  const long nbox = (long)dims[0] * dims[1] * dims[2];
+  if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || nbox > 2147483647L) return -2;
+  for (int r = 0; r < nrows; ++r) if (box_of_row[r] < 0 || box_of_row[r] >= nbox || (r > 0 && box_of_row[r] <= box_of_row[r - 1])) return -2;
+  int *d_box = nullptr, *d_agg = nullptr, *d_mem = nullptr, *d_ptr = nullptr, *d_cbox = nullptr;
+  GCGE_HIP_CHECK(hipMalloc(&d_box, (size_t)nrows * sizeof(int)));
+  GCGE_HIP_CHECK(hipMalloc(&d_agg, (size_t)nrows * sizeof(int)));
+  GCGE_HIP_CHECK(hipMalloc(&d_mem, (size_t)nrows * sizeof(int)));
+  GCGE_HIP_CHECK(hipStreamSynchronize(mg_stream()));
+  GCGE_HIP_CHECK(hipMemcpy(d_box, box_of_row, (size_t)nrows * sizeof(int), hipMemcpyHostToDevice));
+  const int nc = gcge_hip_mg_agg_masked_device(dims, d_box, nrows, d_agg, d_mem, &d_ptr, &d_cbox, cdims, nullptr);
+  GCGE_HIP_CHECK(hipMemcpy(agg, d_agg, (size_t)nrows * sizeof(int), hipMemcpyDeviceToHost));
+  GCGE_HIP_CHECK(hipMemcpy(mem, d_mem, (size_t)nrows * sizeof(int), hipMemcpyDeviceToHost));
+  GCGE_HIP_CHECK(hipMemcpy(ptr, d_ptr, ((size_t)nc + 1) * sizeof(int), hipMemcpyDeviceToHost));
+  GCGE_HIP_CHECK(hipMemcpy(cbox, d_cbox, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+  hipFree(d_box); hipFree(d_agg); hipFree(d_mem); hipFree(d_ptr); hipFree(d_cbox);
+  return nc;
 }
 
 // Ac = scale P^T A P on the device: A (nf rows) as device CSR, agg / ptr / mem device arrays of nc aggregates.  Fills the device

@@ -8,6 +8,7 @@
 // real-space Hamiltonian its blocks, exactly like a matrix the caller uploads.  The prolongations are rectangular matrices
 // (GCGE_HIP_MAT_::rect_ncols): CSR of P for MatDotMultiVec, CSR of P^T for MatTransDotMultiVec, both through the generic CSR
 // kernel (spmm.hip) — one non-zero per fine row, every fine row of the block read or written exactly once.
+// A matrix on a masked grid (the handle carries its geometry) is coarsened by the cells of its bounding box: "masked grids" below.
 // Row slabs (one rank per GPU): a slab of whole planes coarsens by itself (every rank pairs its own planes) — local prolongations, coarse slabs
 // through the slab constructor (gcge_hip_mat_create_slab over RCCL, or a registered factory: the tests' torch.distributed transport).
 #include <hip/hip_runtime.h>
@@ -276,6 +277,161 @@ static bool multigrid_create_device(void*** A_array, void*** B_array, void*** P_
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------------------ masked grids
+// A handle that carries the geometry of a masked grid (gcge_hip_mat_geometry: the grid points inside a sphere in scan order, the
+// PARSEC matrices) is coarsened by the 2 x 2 x 2 cells of its bounding box at every level (gcge_mg_build_masked): the occupied cells
+// in scan order of the coarse box are a masked grid again.  device: the cells from the device-resident box array (mg_device.hip:
+// counts, two sums, members by binary search), Galerkin products and P / P^T as in the device path above — only the coarse levels
+// and their box arrays come back; host: gcge_mg_build_masked on the downloaded CSR.  Either way a coarse level goes up through
+// gcge_hip_mat_create_grid with ITS geometry: the rows stay as given (P / P^T match by construction) and the level carries its
+// geometry like a matrix the caller named one for.  Returns false with nothing left behind when a level is out of the kernels' reach.
+static int g_mg_masked_cells = 1;
+extern "C" void gcge_hip_multigrid_masked_cells(int on) { g_mg_masked_cells = on != 0; }
+extern "C" int gcge_hip_multigrid_get_masked_cells(void) { return g_mg_masked_cells; }
+static bool mg_is_masked_grid(const GCGE_HIP_MAT_* m) {
+  return g_mg_masked_cells && m->geom_kind != 0 && m->d_box != nullptr && (long)m->geom_dims[0] * m->geom_dims[1] * m->geom_dims[2] != (long)m->nrows;
+}
+static void mg_install_masked(void*** A_array, void*** B_array, void*** P_array, int* num_levels, void* A, void* B, bool withB,
+                              std::vector<GCGE_HIP_MAT*>& As, std::vector<GCGE_HIP_MAT*>& Bs, std::vector<GCGE_HIP_MAT*>& Ps, const char* how) {
+  const int L = (int)As.size() + 1;
+  MgHold h;
+  *A_array = (void**)calloc(L, sizeof(void*));
+  *P_array = (void**)calloc(L > 1 ? L - 1 : 1, sizeof(void*));
+  if (B_array != nullptr) *B_array = (void**)calloc(L, sizeof(void*));
+  (*A_array)[0] = A;
+  if (B_array != nullptr) (*B_array)[0] = B;
+  for (int l = 1; l < L; ++l) {
+    (*A_array)[l] = As[l - 1]; h.owned.push_back(As[l - 1]);
+    if (B_array != nullptr && withB) { (*B_array)[l] = Bs[l - 1]; h.owned.push_back(Bs[l - 1]); }
+  }
+  for (int l = 0; l + 1 < L; ++l) { (*P_array)[l] = Ps[l]; h.owned.push_back(Ps[l]); }
+  if (getenv("GCGE_MG_TRACE") != nullptr)
+    for (int l = 0; l < L; ++l) {
+      const GCGE_HIP_MAT* m = (const GCGE_HIP_MAT*)(*A_array)[l];
+      fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, masked grid in the box %d x %d x %d (%.1f%% of it), K1 form %s (%s build)\n", l, m->nrows,
+              m->nnz, m->geom_dims[0], m->geom_dims[1], m->geom_dims[2], 100.0 * m->nrows / ((double)m->geom_dims[0] * m->geom_dims[1] * m->geom_dims[2]),
+              gcge_hip_mat_spmm_form(m), how);
+    }
+  h.A_array = *A_array;
+  g_mg.push_back(h);
+  *num_levels = L;
+}
+
+static bool multigrid_create_masked_device(void*** A_array, void*** B_array, void*** P_array, int* num_levels, const GCGE_HIP_MAT_* mA,
+                                           const GCGE_HIP_MAT_* mB, void* A, void* B) {
+  double scale = 0.5, theta = 0.25; int min_rows = 64;
+  gcge_mg_get_defaults(&scale, &min_rows, &theta);
+  const int max_levels = *num_levels;
+  GCGE_HIP_CHECK(hipStreamSynchronize((hipStream_t)gcge_hip_stream()));
+  std::vector<GCGE_HIP_MAT*> As, Bs, Ps;
+  DevCsr fa{mA->nrows, mA->nnz, mA->d_rowptr, mA->d_colidx, mA->d_val, false};
+  DevCsr fb{0, 0, nullptr, nullptr, nullptr, false};
+  if (mB != nullptr) fb = DevCsr{mB->nrows, mB->nnz, mB->d_rowptr, mB->d_colidx, mB->d_val, false};
+  int dims[3] = {mA->geom_dims[0], mA->geom_dims[1], mA->geom_dims[2]};
+  int* d_box = mA->d_box; bool own_box = false;          // the current level's box array (level 0: the handle's)
+  bool ok = true;
+  double t;
+  for (int l = 0; l + 1 < max_levels; ++l) {
+    const int nf = fa.n;
+    if (nf <= min_rows) break;
+    t = mg_now();
+    int cdims[3] = {0, 0, 0};
+    int *d_agg = nullptr, *d_ptr = nullptr, *d_mem = nullptr, *d_cbox = nullptr;
+    GCGE_HIP_CHECK(hipMalloc(&d_agg, (size_t)nf * sizeof(int)));
+    GCGE_HIP_CHECK(hipMalloc(&d_mem, (size_t)nf * sizeof(int)));
+    const int nc = gcge_hip_mg_agg_masked_device(dims, d_box, nf, d_agg, d_mem, &d_ptr, &d_cbox, cdims, &g_mg_d2h);
+    g_mg_phase[MG_AGGREGATE] += mg_now() - t;
+    if (nc < 1 || (long)nc * 3 > (long)nf * 2) { hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); hipFree(d_cbox); break; }     // coarsening stalled
+    t = mg_now();
+    DevCsr ca{nc, 0, nullptr, nullptr, nullptr, true}, cb{0, 0, nullptr, nullptr, nullptr, false};
+    int rc = gcge_hip_mg_galerkin_device(nf, fa.rp, fa.ci, fa.va, d_agg, nc, d_ptr, d_mem, scale, &ca.rp, &ca.ci, &ca.va, &ca.nnz, &g_mg_d2h);
+    if (rc == 0 && mB != nullptr) {
+      cb = DevCsr{nc, 0, nullptr, nullptr, nullptr, true};
+      rc = gcge_hip_mg_galerkin_device(nf, fb.rp, fb.ci, fb.va, d_agg, nc, d_ptr, d_mem, 1.0, &cb.rp, &cb.ci, &cb.va, &cb.nnz, &g_mg_d2h);
+      if (rc != 0) cb.owned = false;
+    }
+    if (rc != 0) ca.owned = ca.rp != nullptr;
+    g_mg_phase[MG_GALERKIN] += mg_now() - t;
+    if (rc != 0) { devcsr_free(ca); devcsr_free(cb); hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); hipFree(d_cbox); ok = false; break; }
+    t = mg_now();
+    GCGE_HIP_MAT* p = gcge_hip_mat_create_rect_device(nf, nc, d_agg, d_ptr, d_mem);
+    GCGE_REQUIRE(p != nullptr, "MultiGridCreate: a prolongation from device arrays");
+    Ps.push_back(p);
+    hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem);
+    g_mg_phase[MG_OTHER] += mg_now() - t; t = mg_now();
+    GCGE_CSR hc, hb; memset(&hb, 0, sizeof hb);
+    std::vector<int> cbox((size_t)nc);
+    if (gcge_hip_mg_download_csr(nc, nc, ca.nnz, ca.rp, ca.ci, ca.va, &hc, &g_mg_d2h) != 0 ||
+        (mB != nullptr && gcge_hip_mg_download_csr(nc, nc, cb.nnz, cb.rp, cb.ci, cb.va, &hb, &g_mg_d2h) != 0)) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
+    GCGE_HIP_CHECK(hipMemcpy(cbox.data(), d_cbox, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+    g_mg_d2h += (long)((size_t)nc * sizeof(int));
+    g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
+    GCGE_HIP_MAT* a = gcge_hip_mat_create_grid(nc, hc.rowptr, hc.colidx, hc.val, cdims[0], cdims[1], cdims[2], cbox.data());
+    GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
+    As.push_back(a);
+    if (B_array != nullptr && mB != nullptr) {
+      GCGE_HIP_MAT* b = gcge_hip_mat_create_grid(nc, hb.rowptr, hb.colidx, hb.val, cdims[0], cdims[1], cdims[2], cbox.data());
+      GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
+      Bs.push_back(b);
+    }
+    g_mg_phase[MG_COARSE] += mg_now() - t;
+    gcge_csr_free(&hb); gcge_csr_free(&hc);
+    devcsr_free(fa); fa = ca;
+    devcsr_free(fb); fb = cb;
+    if (own_box) hipFree(d_box);
+    d_box = d_cbox; own_box = true;
+    dims[0] = cdims[0]; dims[1] = cdims[1]; dims[2] = cdims[2];
+  }
+  t = mg_now();
+  devcsr_free(fa); devcsr_free(fb);
+  if (own_box) hipFree(d_box);
+  if (!ok) {
+    for (GCGE_HIP_MAT* m : As) gcge_hip_mat_destroy(m);
+    for (GCGE_HIP_MAT* m : Bs) gcge_hip_mat_destroy(m);
+    for (GCGE_HIP_MAT* m : Ps) gcge_hip_mat_destroy(m);
+    if (getenv("GCGE_MG_TRACE") != nullptr) fprintf(stderr, "MultiGridCreate: a level is out of the device path's reach; built on the host\n");
+    return false;
+  }
+  mg_install_masked(A_array, B_array, P_array, num_levels, A, B, mB != nullptr, As, Bs, Ps, "device");
+  g_mg_phase[MG_OTHER] += mg_now() - t;
+  return true;
+}
+
+static void multigrid_create_masked_host(void*** A_array, void*** B_array, void*** P_array, int* num_levels, const GCGE_HIP_MAT_* mA,
+                                         const GCGE_HIP_MAT_* mB, void* A, void* B) {
+  double t = mg_now();
+  GCGE_CSR cA, cB; std::vector<int> rpA, ciA, rpB, ciB; std::vector<double> vaA, vaB;
+  download_csr(mA, &cA, rpA, ciA, vaA);
+  if (mB != nullptr) download_csr(mB, &cB, rpB, ciB, vaB);
+  g_mg_d2h += csr_bytes(mA->nrows, mA->nnz) + (mB != nullptr ? csr_bytes(mB->nrows, mB->nnz) : 0);
+  g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
+  GCGE_MG mg;
+  const int rc = gcge_mg_build_masked(&cA, mB != nullptr ? &cB : nullptr, mA->geom_dims, mA->h_box, *num_levels, 0, 0.0, &mg);
+  if (rc != 0) { fprintf(stderr, "MultiGridCreate: gcge_mg_build_masked failed (%d)\n", rc); abort(); }
+  g_mg_phase[MG_AGGREGATE] += mg_now() - t; t = mg_now();
+  std::vector<GCGE_HIP_MAT*> As, Bs, Ps;
+  for (int l = 1; l < mg.num_levels; ++l) {
+    const int* d = mg.dims[l]; const int* box = gcge_mg_level_box(&mg, l);
+    GCGE_HIP_MAT* a = gcge_hip_mat_create_grid(mg.A[l].nrows, mg.A[l].rowptr, mg.A[l].colidx, mg.A[l].val, d[0], d[1], d[2], box);
+    GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
+    As.push_back(a);
+    if (B_array != nullptr && mB != nullptr) {
+      GCGE_HIP_MAT* b = gcge_hip_mat_create_grid(mg.B[l].nrows, mg.B[l].rowptr, mg.B[l].colidx, mg.B[l].val, d[0], d[1], d[2], box);
+      GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
+      Bs.push_back(b);
+    }
+  }
+  for (int l = 0; l + 1 < mg.num_levels; ++l) {
+    GCGE_HIP_MAT* p = gcge_hip_mat_create_rect(mg.P[l].nrows, mg.P[l].ncols, mg.P[l].rowptr, mg.P[l].colidx, mg.P[l].val,
+                                               mg.PT[l].rowptr, mg.PT[l].colidx, mg.PT[l].val);
+    GCGE_REQUIRE(p != nullptr, "MultiGridCreate: upload of a prolongation");
+    Ps.push_back(p);
+  }
+  g_mg_phase[MG_COARSE] += mg_now() - t;
+  gcge_mg_free(&mg);
+  mg_install_masked(A_array, B_array, P_array, num_levels, A, B, mB != nullptr, As, Bs, Ps, "host");
+}
+
 static void mg_report(double t0) {
   if (getenv("GCGE_MG_TRACE") == nullptr) return;
   fprintf(stderr, "MultiGridCreate (%s path): %.3f s = detect %.3f + aggregate %.3f + Galerkin %.3f + transfers %.3f + coarse upload %.3f + other %.3f; "
@@ -292,6 +448,13 @@ extern "C" void gcge_hip_multigrid_create(void*** A_array, void*** B_array, void
   if (mA->nghost > 0 || mA->part_world > 1) {
     multigrid_create_slab(A_array, B_array, P_array, num_levels, mA, A, B);
     g_mg_seconds = mg_now() - t0;
+    return;
+  }
+  if (mg_is_masked_grid(mA)) {         // a masked grid: the cells of its box at every level, on the device or on the host
+    if (g_mg_mode != 0 || !multigrid_create_masked_device(A_array, B_array, P_array, num_levels, mA, mB, A, B))
+      multigrid_create_masked_host(A_array, B_array, P_array, num_levels, mA, mB, A, B);
+    g_mg_seconds = mg_now() - t0;
+    mg_report(t0);
     return;
   }
   if (g_mg_mode == 0 && multigrid_create_device(A_array, B_array, P_array, num_levels, mA, mB, A, B)) {

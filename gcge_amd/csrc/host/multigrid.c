@@ -116,6 +116,31 @@ int gcge_mg_aggregate_grid(const int dims[3], int *agg, int cdims[3])
 	return cx * cy * cz;
 }
 
+int gcge_mg_aggregate_masked(const int dims[3], const int *box_of_row, int nrows, int *agg, int cdims[3], int *cbox_out)
+{
+	const int nx = dims[0], ny = dims[1], nz = dims[2];
+	const int cx = (nx + 1) / 2, cy = (ny + 1) / 2, cz = (nz + 1) / 2;
+	const long nbox = (long)nx * ny * nz, ncell = (long)cx * cy * cz;
+	int *num, r, nc = 0; long c;
+	if (nx < 1 || ny < 1 || nz < 1 || nbox > 2147483647L || nrows < 0) return -2;
+	for (r = 0; r < nrows; ++r)
+		if (box_of_row[r] < 0 || box_of_row[r] >= nbox || (r > 0 && box_of_row[r] <= box_of_row[r - 1])) return -2;
+	cdims[0] = cx; cdims[1] = cy; cdims[2] = cz;
+	num = (int*)calloc((size_t)ncell, sizeof(int));
+	if (num == NULL) return -3;
+	/* the cell of every row, then the occupied cells numbered in ascending coarse box index */
+	for (r = 0; r < nrows; ++r) {
+		const int b = box_of_row[r], x = b % nx, y = (b / nx) % ny, z = b / (nx * ny);
+		agg[r] = cx * ((y / 2) + cy * (z / 2)) + x / 2;
+		num[agg[r]] = 1;
+	}
+	for (c = 0; c < ncell; ++c)
+		if (num[c]) { cbox_out[nc] = (int)c; num[c] = nc++; }
+	for (r = 0; r < nrows; ++r) agg[r] = num[agg[r]];
+	free(num);
+	return nc;
+}
+
 int gcge_mg_aggregate_graph(const GCGE_CSR *A, double theta, int *agg)
 {
 	const int n = A->nrows;
@@ -304,8 +329,19 @@ void gcge_mg_free(GCGE_MG *mg)
 		if (mg->P) gcge_csr_free(&mg->P[l]);
 		if (mg->PT) gcge_csr_free(&mg->PT[l]);
 	}
-	free(mg->A); free(mg->B); free(mg->P); free(mg->PT); free(mg->dims);
+	free(mg->A); free(mg->B); free(mg->P); free(mg->PT);
+	if (mg->box_levels > 0 && mg->dims != NULL) {     /* gcge_mg_build_masked: the box arrays, their pointers in front of dims */
+		int **box = (int**)((char*)mg->dims - (size_t)mg->box_levels * sizeof(int*));
+		for (l = 0; l < mg->box_levels; ++l) free(box[l]);
+		free(box);
+	} else free(mg->dims);
 	memset(mg, 0, sizeof *mg);
+}
+
+const int *gcge_mg_level_box(const GCGE_MG *mg, int level)
+{
+	if (mg == NULL || mg->dims == NULL || level < 0 || level >= mg->box_levels || level >= mg->num_levels) return NULL;
+	return ((int**)((char*)mg->dims - (size_t)mg->box_levels * sizeof(int*)))[level];
 }
 
 int gcge_mg_build(const GCGE_CSR *A, const GCGE_CSR *B, int max_levels, int min_rows, double scale, GCGE_MG *mg)
@@ -348,6 +384,54 @@ int gcge_mg_build(const GCGE_CSR *A, const GCGE_CSR *B, int max_levels, int min_
 		if (have_grid) { dims[0] = cdims[0]; dims[1] = cdims[1]; dims[2] = cdims[2]; }
 	}
 	if (have_grid) { l = mg->num_levels - 1; mg->dims[l][0] = dims[0]; mg->dims[l][1] = dims[1]; mg->dims[l][2] = dims[2]; }
+	return 0;
+}
+
+/* a masked grid (the grid points inside a sphere, rows in scan order): gcge_mg_build with the 2 x 2 x 2 cells of the bounding box
+ * at every level — a level's occupied cells, in scan order of the coarse box, are the next level's rows */
+int gcge_mg_build_masked(const GCGE_CSR *A, const GCGE_CSR *B, const int dims[3], const int *box_of_row, int max_levels, int min_rows,
+		double scale, GCGE_MG *mg)
+{
+	int l, d[3] = {dims[0], dims[1], dims[2]}, **box;
+	char *blk;
+	memset(mg, 0, sizeof *mg);
+	if (max_levels < 1) max_levels = 1;
+	if (min_rows <= 0) min_rows = g_min_rows;
+	if (scale <= 0.0) scale = g_scale;
+	mg->A = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
+	mg->P = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
+	mg->PT = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
+	blk = (char*)calloc(max_levels, sizeof(int*) + sizeof(int[3]));       /* [box pointers][dims] */
+	if (B != NULL) mg->B = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
+	if (!mg->A || !mg->P || !mg->PT || !blk || (B != NULL && !mg->B)) { free(blk); gcge_mg_free(mg); return -3; }
+	box = (int**)blk; mg->dims = (int (*)[3])(blk + (size_t)max_levels * sizeof(int*)); mg->box_levels = max_levels;
+	mg->A[0] = *A;
+	if (B != NULL) mg->B[0] = *B;
+	mg->num_levels = 1;
+	box[0] = (int*)malloc((size_t)(A->nrows > 0 ? A->nrows : 1) * sizeof(int));
+	if (box[0] == NULL) { gcge_mg_free(mg); return -3; }
+	memcpy(box[0], box_of_row, (size_t)A->nrows * sizeof(int));
+	mg->dims[0][0] = d[0]; mg->dims[0][1] = d[1]; mg->dims[0][2] = d[2];
+	for (l = 0; l + 1 < max_levels; ++l) {
+		const GCGE_CSR *Af = &mg->A[l];
+		const int nf = Af->nrows;
+		int nc, cdims[3] = {0, 0, 0}, *agg, *cbox, rc;
+		if (nf <= min_rows && l > 0) break;
+		agg = (int*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(int)); cbox = (int*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(int));
+		if (agg == NULL || cbox == NULL) { free(agg); free(cbox); gcge_mg_free(mg); return -3; }
+		nc = gcge_mg_aggregate_masked(d, box[l], nf, agg, cdims, cbox);
+		if (nc < 0) { free(agg); free(cbox); gcge_mg_free(mg); return nc; }             /* (level 0 only: the caller's geometry) */
+		if (nf <= min_rows || nc < 1 || (long)nc * 3 > (long)nf * 2) { free(agg); free(cbox); break; }     /* small enough / coarsening stalled */
+		rc = gcge_mg_galerkin(Af, agg, nc, scale, &mg->A[l + 1]);
+		if (rc == 0 && B != NULL) rc = gcge_mg_galerkin(&mg->B[l], agg, nc, 1.0, &mg->B[l + 1]);
+		if (rc == 0) rc = gcge_mg_prolongation(agg, nf, nc, &mg->P[l], &mg->PT[l]);
+		free(agg);
+		mg->num_levels = l + 2;
+		if (rc != 0) { free(cbox); gcge_mg_free(mg); return rc; }
+		box[l + 1] = cbox;                                                 /* (nf ints allocated, nc used) */
+		d[0] = cdims[0]; d[1] = cdims[1]; d[2] = cdims[2];
+		mg->dims[l + 1][0] = d[0]; mg->dims[l + 1][1] = d[1]; mg->dims[l + 1][2] = d[2];
+	}
 	return 0;
 }
 

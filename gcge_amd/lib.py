@@ -111,6 +111,54 @@ def multigrid_stats():
     return dict(zip(("detect", "aggregate", "galerkin", "transfers", "coarse_upload", "other"), list(s))), b.value
 
 
+def multigrid_masked_cells(on=None):
+    """Whether MultiGridCreate of the HIP back-end coarsens a matrix on a masked grid (a handle with a geometry, mat_geometry) by the
+    2 x 2 x 2 cells of its box (1, the default) or as a matrix without a grid (0); returns the setting in force."""
+    h = hip_lib()
+    if on is not None:
+        h.gcge_hip_multigrid_masked_cells(int(on))
+    return h.gcge_hip_multigrid_get_masked_cells()
+
+
+def mat_geometry(mat):
+    """The geometry a HIP matrix handle carries: (kind, dims, box_of_row) with kind 0 none (dims, box None), 1 named by the caller
+    (HipBackend.matrix_grid), 2 recovered at upload; box_of_row[r] = x + nx (y + ny z) as a numpy int32 array."""
+    import numpy as np
+    h = hip_lib()
+    h.gcge_hip_mat_geometry.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    h.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
+    dims = (C.c_int * 3)()
+    kind = h.gcge_hip_mat_geometry(mat, dims, None)
+    if kind == 0:
+        return 0, None, None
+    box = np.zeros(h.gcge_hip_mat_nrows(mat), dtype=np.int32)
+    h.gcge_hip_mat_geometry(mat, dims, box.ctypes.data_as(C.POINTER(C.c_int)))
+    return kind, tuple(dims), box
+
+
+def mg_aggregate_masked(dims, box_of_row, device=False):
+    """The 2 x 2 x 2 cells of a masked grid (gcge_mg_aggregate_masked, include/gcge_multigrid.h): (nc, agg, cdims, cbox) from the
+    host routine, or with device=True (nc, agg, cdims, cbox, ptr, mem) from the kernels of the HIP back-end (ptr / mem: the members
+    of every cell in ascending row order).  nc < 0: the geometry was refused (the arrays are then None)."""
+    import numpy as np
+    box = np.ascontiguousarray(box_of_row, dtype=np.int32)
+    n = len(box)
+    ip = C.POINTER(C.c_int)
+    agg, cbox, cd = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32), (C.c_int * 3)()
+    d = (C.c_int * 3)(*[int(v) for v in dims])
+    if not device:
+        f = host_lib().gcge_mg_aggregate_masked
+        f.argtypes = [C.POINTER(C.c_int * 3), ip, C.c_int, ip, C.POINTER(C.c_int * 3), ip]
+        nc = f(C.byref(d), box.ctypes.data_as(ip), n, agg.ctypes.data_as(ip), C.byref(cd), cbox.ctypes.data_as(ip))
+        return (nc, agg[:n], tuple(cd), cbox[:nc].copy()) if nc >= 0 else (nc, None, None, None)
+    ptr, mem = np.zeros(n + 1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+    f = hip_lib().gcge_hip_mg_aggregate_masked
+    f.argtypes = [C.POINTER(C.c_int * 3), ip, C.c_int, ip, ip, ip, ip, C.POINTER(C.c_int * 3)]
+    nc = f(C.byref(d), box.ctypes.data_as(ip), n, agg.ctypes.data_as(ip), ptr.ctypes.data_as(ip), mem.ctypes.data_as(ip),
+           cbox.ctypes.data_as(ip), C.byref(cd))
+    return (nc, agg[:n], tuple(cd), cbox[:nc].copy(), ptr[:nc + 1].copy(), mem[:n]) if nc >= 0 else (nc, None, None, None, None, None)
+
+
 def mg_galerkin_device(mat, agg, nc, scale):
     """scale P^T A P on the device for a HIP matrix handle and an aggregate map (numpy int32): (rowptr, colidx, val)."""
     import numpy as np

@@ -55,6 +55,10 @@ GCGE_HIP_MAT *gcge_hip_mat_create_grid (int nrows, const int *rowptr, const int 
  * lines / planes from the votes of the star rows' + y / + z neighbours.  A wrong guess costs speed, never the result (the
  * remainder takes every difference); on = 0 switches the recovery off (measurements).                                         */
 void gcge_hip_spmm_star_infer (int on);
+/* The geometry a one-rank handle carries, whatever K1 form its matrix took: 0 none, 1 named by the caller
+ * (gcge_hip_mat_create_grid), 2 recovered at upload (and the grid form built on it).  dims[3] and box_of_row[nrows] (may be
+ * NULL) are filled when there is one.  MultiGridCreate coarsens such a matrix by the 2 x 2 x 2 cells of its box (below).     */
+int  gcge_hip_mat_geometry (const GCGE_HIP_MAT *A, int *dims, int *box_of_row);
 /* Row-partitioned use (one process per GPU): localize the slab with gcge_dist_localize
  * (include/gcge_problems.h), create it with ncols_local = nrows + nghost, then install the halo
  * plan.  exchange(sendbuf, recvbuf, ncols, ctx) must deliver, for every peer, rows
@@ -94,6 +98,19 @@ double gcge_hip_multigrid_seconds (void);    /* host + upload time of the last M
  *     (gcge_mg_build on the downloaded CSR), which mode 0 also falls back to when a level is out of the kernels' reach.         */
 void gcge_hip_multigrid_mode (int mode);
 int  gcge_hip_multigrid_get_mode (void);
+/*     Masked grids (a handle with a geometry whose box holds more points than the matrix has rows: gcge_hip_mat_geometry): every
+ *     level is coarsened by the 2 x 2 x 2 cells of its bounding box (gcge_mg_aggregate_masked / gcge_mg_build_masked,
+ *     include/gcge_multigrid.h); the occupied cells in scan order are the next level, uploaded through gcge_hip_mat_create_grid
+ *     with its own geometry, so its rows stay as given.  Mode 0 counts, numbers and lists the cells on the device from the
+ *     device-resident box array (no part of the fine level comes back), mode 1 runs the host routine; identical hierarchies.
+ *     on = 0: such a matrix is treated as one without a grid (greedy aggregates: the graph branch).  Default 1.
+ *     Row slabs of a masked grid are not coarsened this way.                                                                   */
+void gcge_hip_multigrid_masked_cells (int on);
+int  gcge_hip_multigrid_get_masked_cells (void);
+/*     the device aggregation of a masked grid for a host box array (tests, tools): agg, mem [nrows], ptr [nrows + 1], cbox [nrows]
+ *     as gcge_mg_aggregate_masked and the members of every cell in ascending row order; returns the number of aggregates, < 0 for
+ *     a geometry the host routine refuses                                                                                     */
+int  gcge_hip_mg_aggregate_masked (const int dims[3], const int *box_of_row, int nrows, int *agg, int *ptr, int *mem, int *cbox, int cdims[3]);
 /*     the last MultiGridCreate: seconds of its phases (detect, aggregate, Galerkin, transfers, coarse upload / analysis, other)
  *     and the bytes copied device to host; GCGE_MG_TRACE prints them                                                           */
 void gcge_hip_multigrid_stats (double *seconds6, long *d2h_bytes);

@@ -33,6 +33,14 @@ int gcge_mg_detect_grid (const GCGE_CSR *A, int dims[3], int *arm);     /* also:
  * agg[r] = coarse index of row r, cdims = coarse grid.  Returns the number of aggregates.                          */
 int gcge_mg_aggregate_grid (const int dims[3], int *agg, int cdims[3]);
 
+/* the same cells on a MASKED grid: row r is box point box_of_row[r] = x + nx (y + ny z) of the box `dims` (strictly ascending: the
+ * points inside a sphere in scan order, the PARSEC matrices), its cell is (x / 2, y / 2, z / 2) of the box cdims = ceil(dims / 2).
+ * A cell is a coarse row when it holds at least one fine row (1 to 8 of them); the occupied cells are numbered in ascending coarse
+ * box index, so the coarse rows are a masked grid in scan order again: agg[r] = that number, cbox_out[I] (room for nrows ints) =
+ * the coarse box index of coarse row I.  Returns the number of aggregates — gcge_mg_aggregate_grid's result, bit for bit, when every
+ * box point is a row; -2: box_of_row is not strictly ascending or leaves the box, -3: out of memory.                          */
+int gcge_mg_aggregate_masked (const int dims[3], const int *box_of_row, int nrows, int *agg, int cdims[3], int *cbox_out);
+
 /* greedy aggregation over the strong couplings |a_ij| >= theta * max_k |a_ik| (k != i): pass 1 forms an aggregate from
  * every node whose strong neighbours are all still free, pass 2 attaches the rest to the neighbouring aggregate they are
  * coupled to most strongly, pass 3 turns what is left (isolated rows) into aggregates of their own.
@@ -49,6 +57,7 @@ int gcge_mg_prolongation (const int *agg, int nf, int nc, GCGE_CSR *P, GCGE_CSR 
 /* the whole hierarchy: level 0 is A itself (not copied: A[0] aliases the caller's arrays and is never freed here)   */
 typedef struct GCGE_MG_ {
 	int      num_levels;
+	int      box_levels;  /* > 0: a hierarchy of gcge_mg_build_masked, gcge_mg_level_box names the rows of its levels   */
 	GCGE_CSR *A;          /* [num_levels]      A[0] = the caller's matrix                                  */
 	GCGE_CSR *B;          /* [num_levels] or NULL (B == NULL): Galerkin P^T B P, never rescaled            */
 	GCGE_CSR *P;          /* [num_levels - 1]  P[l]: rows(A[l]) x rows(A[l+1])                              */
@@ -59,6 +68,15 @@ typedef struct GCGE_MG_ {
  * (fewer than 1.5 x fewer rows).  Returns 0 and fills mg (mg->num_levels >= 1), -3 out of memory.                  */
 int  gcge_mg_build (const GCGE_CSR *A, const GCGE_CSR *B, int max_levels, int min_rows, double scale, GCGE_MG *mg);
 void gcge_mg_free (GCGE_MG *mg);
+
+/* gcge_mg_build on a masked grid: the cells of gcge_mg_aggregate_masked at EVERY level (same stopping rules, same scale), level
+ * l on the box mg->dims[l] with its rows named by gcge_mg_level_box (mg, l) (mg->A[l].nrows ascending box indices, owned by mg;
+ * level 0: a copy of box_of_row).  Returns 0, -2: the geometry does not fit A (see gcge_mg_aggregate_masked), -3: out of memory.
+ * The box arrays hang off the block mg->dims points into and box_levels (which sits where the structure had padding) finds them:
+ * GCGE_MG keeps its size and the offsets of its members, callers built against the earlier header still match.              */
+int  gcge_mg_build_masked (const GCGE_CSR *A, const GCGE_CSR *B, const int dims[3], const int *box_of_row, int max_levels, int min_rows,
+		double scale, GCGE_MG *mg);
+const int *gcge_mg_level_box (const GCGE_MG *mg, int level);     /* NULL: the level has none (any other hierarchy)            */
 
 /* The hierarchy of ONE row slab (one rank per GPU): A holds rows [part[rank], part[rank + 1]) with GLOBAL columns of a matrix on the
  * lexicographic grid `dims`; every slab is whole planes.  Every rank pairs ITS OWN planes from its first one (an odd count ends in a
