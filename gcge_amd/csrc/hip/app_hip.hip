@@ -423,6 +423,47 @@ static void HIP_MultiVecAxpby(double alpha, void** x, double beta, void** y, int
                  vy->ld, m, g_stream);
 }
 
+// GCGE_BACKEND.block_moves (include/gcge_ops.h): X, the W start vectors and b of an outer iteration in one sweep over the rows of
+// ritz[:, x0..x1) (vec_kernels.hip: block_moves_kernel).  0 with nothing touched for what the kernel does not take: rows wider than
+// 512 columns, blocks in different row orders, V as source or as b, runs outside [x0, x1) or targets outside their blocks.
+static int HIP_BlockMoves(void** ritz, void** V, int x0, int x1, const int* runs, int w0, void** b, int b0, const double* scale, struct OPS_* ops) {
+  (void)ops;
+  GcgeHipMV *vr = (GcgeHipMV*)ritz, *vv = (GcgeHipMV*)V, *vb = (GcgeHipMV*)b;
+  if (vr == nullptr || vv == nullptr || vr == vv || vb == vv || runs == nullptr || x0 < 0 || x1 <= x0) return 0;
+  if (x1 > vr->ncols || x1 > vv->ncols || vr->nrows != vv->nrows || vr->nrows <= 0 || real_perm(vr->perm) != real_perm(vv->perm)) return 0;
+  if ((vr->ld & 1) || (vv->ld & 1) || ((uintptr_t)vr->d & 15) || ((uintptr_t)vv->d & 15)) return 0;
+  if (vb != nullptr && (scale == nullptr || vb->nrows != vr->nrows || (vb->ld & 1) || ((uintptr_t)vb->d & 15) || real_perm(vb->perm) != real_perm(vr->perm))) return 0;
+  const int c0 = x0 & ~1, c1 = (x1 + 1) & ~1, npairs = (c1 - c0) / 2;
+  if (npairs > 256 || c1 > vr->ld) return 0;
+  int total = 0, prev = x0;
+  for (int i = 0; i < runs[0]; ++i) {
+    const int lo = runs[2 * i + 1], hi = runs[2 * i + 2];
+    if (lo < prev || hi <= lo || hi > x1) return 0;
+    total += hi - lo; prev = hi;
+  }
+  if (w0 < x1 || w0 + total > vv->ncols) return 0;
+  if (vb != nullptr && (b0 < 0 || b0 + total > vb->ncols)) return 0;
+  enter();
+  SlotTimer tm_("block moves (X, W start, b)", x1 - x0);
+  // staging: [0, total) the factors, behind them the 2 npairs positions in the packed runs as ints
+  const size_t nd = (size_t)total + (size_t)npairs;
+  double* dd = gcge_hip_stage_d(nd);
+  double* hs = gcge_hip_stage_h(nd);
+  GCGE_HIP_CHECK(hipStreamSynchronize(g_stream));   // the staging buffers are reused
+  int* hmap = (int*)(hs + total);
+  for (int k = 0; k < 2 * npairs; ++k) hmap[k] = -1;
+  for (int i = 0, blk = 0; i < runs[0]; ++i)
+    for (int col = runs[2 * i + 1]; col < runs[2 * i + 2]; ++col) hmap[col - c0] = blk++;
+  for (int k = 0; k < total; ++k) hs[k] = vb != nullptr ? scale[k] : 0.0;
+  GCGE_HIP_CHECK(hipMemcpyAsync(dd, hs, nd * sizeof(double), hipMemcpyHostToDevice, g_stream));
+  GCGE_REQUIRE(gcge_hip_block_moves(vr->nrows, vr->d + c0, vr->ld, vv->d, vv->ld, vb != nullptr ? vb->d : nullptr, vb != nullptr ? vb->ld : 0, c0, npairs,
+                                    x0, x1, (const int*)(dd + total), dd, w0, b0, g_stream) == 0, "block moves: kernel launch");
+  return 1;
+}
+extern "C" int gcge_hip_block_moves_mv(void** ritz, void** V, int x0, int x1, const int* runs, int w0, void** b, int b0, const double* scale) {
+  return HIP_BlockMoves(ritz, V, x0, x1, runs, w0, b, b0, scale, nullptr);
+}
+
 // app_lapack.c:463-534
 static void HIP_MultiVecLinearComb(void** x, void** y, int is_vec, int* start, int* end, double* coef, int ldc,
                                    double* beta, int incb, struct OPS_* ops) {
@@ -666,6 +707,7 @@ extern "C" void OPS_HIP_Set(struct OPS_* ops) {
   gcge_hip_product_slots(ops, &be);           // MatDotMultiVec / MatTransDotMultiVec, the residual hook, the V-cycle's fused sweeps
   gcge_hip_bpcg_backend(&be);                 // the fused device CG: BlockAMG's smoother, and the solver of unformed b = x diag(scale)
   be.pas_border = gcge_hip_pas_border;        // PAS: y += QX t and g = QX^T q in one pass over QX
+  be.block_moves = HIP_BlockMoves;            // GCG's X / W start / b moves of an outer iteration in one sweep
   be.mat_identity = HIP_MatIdentity; be.mat_free = HIP_MatFree; be.mat_rows_as_given = HIP_MatRowsAsGiven;
   GCGE_SetBackend(ops, &be);
 }

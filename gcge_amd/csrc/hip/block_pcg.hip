@@ -457,6 +457,7 @@ struct HipBpcg {
   long dev_scalar_iters = 0;
   long implicit_r_iters = 0;       // iterations that rebuilt r from two directions (no stored residual)
   long stored_dev_iters = 0;       // iterations of the device-scalar loop with the product stored (matrices without a pattern form)
+  long legacy_start_sums = 0;      // one-sweep starts whose |r|^2 was summed again by the column-dot kernel (right-hand sides moved off an odd column)
   long fused_starts = 0;           // solves started by product + one sweep (cg_start_scaled_stored)
   long surplus_iters = 0;          // iterations enqueued after the last column had retired (no-ops on the data, but they stream)
   long trimmed_iters = 0;          // last iterations of the device-scalar loop whose second pass ran over fewer columns or not at all
@@ -774,7 +775,15 @@ static bool cg_start(CgCall& c, bool without_r) {
   cg_stopping_scales(c);
   if (p0_done) return true;   // started from the scale factors above
   if (pattern && gcge_hip_cg_start_mv(c.mat, c.mv_x, c.xc0, c.mv_b, c.bc0, start_r, k.mv_ws[1], 0, nrhs, c.rho2.data()) == 0) {
-    reduce_over_ranks(c.rho2.data(), nrhs);
+    // right-hand sides the driver moved off an odd column (GCGE_SetRealignedRhs): from there the sweep was declined and |r|^2 came
+    // from the column-dot kernel below, in another order of the row sums.  r is the same bit for bit either way; take those sums
+    // (one more read of r), so that the solve does not depend on where b lies
+    int rb0 = 0;
+    if (GCGE_GetRealignedRhs(&rb0) == c.mv_b && rb0 == c.bc0) {
+      int st2[2] = {0, 0}, en2[2] = {nrhs, nrhs};
+      ops->MultiVecInnerProd('D', start_r, start_r, 0, st2, en2, c.rho2.data(), 1, ops);
+      ++s->legacy_start_sums;
+    } else reduce_over_ranks(c.rho2.data(), nrhs);
     return true;
   }
   // product, axpby, column dots (and the copy p0 = r, which is the caller's)
@@ -1182,6 +1191,7 @@ extern "C" void gcge_hip_bpcg_column_stats(long* col_iters, long* active_col_ite
 }
 extern "C" long gcge_hip_bpcg_surplus_iters(void) { return g_bpcg.surplus_iters; }
 extern "C" long gcge_hip_bpcg_trimmed_iters(void) { return g_bpcg.trimmed_iters; }
+extern "C" long gcge_hip_bpcg_legacy_start_sums(void) { return g_bpcg.legacy_start_sums; }
 extern "C" double gcge_hip_bpcg_last_residual(void) { return g_bpcg.residual; }   // what the last call reported (column 0)
 // the fused CG as the smoother of BlockAMG for the HIP table: same stopping rules as MultiLinearSolverSetup_BlockPCG, its own
 // blocks per level (parked sets above)

@@ -161,6 +161,8 @@ void gcge_hip_reduce_partials16(const double* d_partial, int nblocks, long slab_
 void gcge_hip_reduce_partials_slabs(const double* d_partial, int nblocks, long slab_stride, int cpp, int ncols, double* d_out, void* stream);
 int gcge_hip_resid_sq(int nrows, const double* d_w, long ldw, const double* d_x, long ldx, int m, const double* d_lambda, double* d_out, void* stream);
 int gcge_hip_colscale(int nrows, double* d_y, long ldy, int m, const double* d_s, void* stream);
+int gcge_hip_block_moves(int nrows, const double* d_src, long lds, double* d_v, long ldv, double* d_b, long ldb, int c0, int npairs, int x0, int x1,
+                         const int* d_map, const double* d_scale, int w0, int b0, void* stream);
 int gcge_hip_panel_dot1(int nrows, const double* d_x, long ldx, int k, const double* d_y, long ldy, double* d_out, void* stream);
 int gcge_hip_rank1_update(int nrows, const double* d_x, long ldx, const double* d_c, const double* d_beta, double* d_y, long ldy, int m, void* stream);
 int gcge_hip_colscale1(int nrows, double* d_y, long ldy, double s, void* stream);

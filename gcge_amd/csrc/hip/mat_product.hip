@@ -559,6 +559,14 @@ static int start_sweep_takes(const GCGE_HIP_MAT_* A, const GcgeHipMV* vx, int xc
   if (vr == vx || vn == vx || (A->nghost > 0 && m > A->buf_cols)) return 0;
   return 1;
 }
+// taken / declined for the odd first column of b alone (everything else qualifies, x and r included): gcge_hip_sweep_stats
+static long g_sweep_stats[4] = {0, 0, 0, 0};
+extern "C" void gcge_hip_sweep_stats(long out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_sweep_stats[i]; }
+static int start_sweep_odd_b_only(const GCGE_HIP_MAT_* A, const GcgeHipMV* vx, int xc0, const GcgeHipMV* vb, int bc0, const GcgeHipMV* vr,
+                                  const GcgeHipMV* vn, int rc0, int m) {
+  if (vb == nullptr || !(bc0 & 1)) return 0;
+  return start_sweep_takes(A, vx, xc0, vb, bc0 & ~1, vr, vn, rc0, m);
+}
 static int start_sweep(GCGE_HIP_MAT_* A, GcgeHipMV* vx, int xc0, GcgeHipMV* vb, int bc0, const double* d_scale, GcgeHipMV* vr, GcgeHipMV* vn,
                        int rc0, int m, double* dd) {
   const CgPass cg = {vb != nullptr ? 5 : 6, vr->d + rc0, vr->ld, vn->d + rc0, vn->ld, d_scale, nullptr, nullptr,
@@ -573,7 +581,9 @@ extern "C" int gcge_hip_cg_start_mv(void* mat, void** x, int xc0, void** b, int 
   gcge_hip_enter();
   GCGE_HIP_MAT_* A = (GCGE_HIP_MAT_*)mat;
   GcgeHipMV *vx = (GcgeHipMV*)x, *vb = (GcgeHipMV*)b, *vr = (GcgeHipMV*)r, *vp = (GcgeHipMV*)p0;
-  if (getenv("GCGE_CG_NO_RECOMPUTE") != nullptr || !start_sweep_takes(A, vx, xc0, vb, bc0, vr, vp, rc0, m)) return -1;
+  if (getenv("GCGE_CG_NO_RECOMPUTE") != nullptr) return -1;
+  if (!start_sweep_takes(A, vx, xc0, vb, bc0, vr, vp, rc0, m)) { g_sweep_stats[1] += start_sweep_odd_b_only(A, vx, xc0, vb, bc0, vr, vp, rc0, m); return -1; }
+  ++g_sweep_stats[0];
   GCGE_REQUIRE(xc0 >= 0 && xc0 + m <= vx->ncols && bc0 >= 0 && bc0 + m <= vb->ncols && rc0 >= 0 && rc0 + m <= vr->ncols &&
                rc0 + m <= vp->ncols, "cg_start: column ranges");
   GCGE_REQUIRE(A->nrows == vx->nrows && A->nrows == vb->nrows && A->nrows == vr->nrows && A->nrows == vp->nrows &&
@@ -614,11 +624,13 @@ static int HIP_AmgResidual(void* mat, void** b, int bc0, void** x, int xc0, void
   (void)ops;
   GCGE_HIP_MAT_* A = (GCGE_HIP_MAT_*)mat;
   GcgeHipMV *vx = (GcgeHipMV*)x, *vb = (GcgeHipMV*)b, *vr = (GcgeHipMV*)r;
+  if (m > 0 && A != nullptr && A->rect_ncols == 0 && vr != vb) g_sweep_stats[3] += start_sweep_odd_b_only(A, vx, xc0, vb, bc0, vr, vr, rc0, m);
   if (m <= 0 || !start_sweep_takes(A, vx, xc0, vb, bc0, vr, vr, rc0, m) || A->rect_ncols > 0 || vr == vb) return 0;
   if (xc0 < 0 || xc0 + m > vx->ncols || bc0 < 0 || bc0 + m > vb->ncols || rc0 < 0 || rc0 + m > vr->ncols) return 0;
   if (A->nrows != vx->nrows || A->nrows != vb->nrows || A->nrows != vr->nrows || A->nrows + A->nghost > vx->nrows_alloc) return 0;
   if (real_perm(vx->perm) != real_perm(A->perm) || real_perm(vb->perm) != real_perm(A->perm) || real_perm(vr->perm) != real_perm(A->perm)) return 0;
   gcge_hip_enter();
+  ++g_sweep_stats[2];
   SlotTimer tm_("AMG residual (fused)", m);
   double* dd = gcge_hip_stage_d(6 * (size_t)m);                         // the sweep's column sums |r_j|^2: not used here
   const int rc = start_sweep(A, vx, xc0, vb, bc0, nullptr, vr, vr, rc0, m, dd);

@@ -1,6 +1,7 @@
 // K4 / K6 and helpers — streaming kernels on row-major blocks of vectors.
 //
 //   gcge_hip_axpby        Y[:,0:m) = alpha X[:,0:m) + beta Y      reference: app/app_lapack.c:334-395
+//   gcge_hip_block_moves  V[:,x) = R[:,x), V[:,w) = R[:,runs), b = R[:,runs) diag(s) in one sweep (GCG's ComputeX + head of ComputeW)
 //   gcge_hip_colscale     Y[:,j)  *= s[j]                          (x == NULL branch of :463-534)
 //   gcge_hip_coldots      d[j] = sum_r X[r,j] Y[r,j]               ('D' branch of DenseMatQtAP :70-118)
 //   gcge_hip_fill_uniform counter-based U[0,1) fill (mode 1 of MultiVecSetRandomValue)
@@ -98,6 +99,139 @@ __global__ __launch_bounds__(256) void axpby2_rows_kernel(long nrows, double alp
     if (MODE != 2) a = *reinterpret_cast<const v2d_ax*>(x + row * ldx + j);
     if (MODE != 1) b = *reinterpret_cast<const v2d_ax*>(y + row * ldy + j);
     one(row, a, b);
+  }
+}
+
+// Column ranges the 16-byte form above does not take, in the same row-slab form and with the same operation per element: a lane
+// owns two columns at a 16-byte boundary of BOTH blocks, the lane at an odd first column (`head`) and the one at an odd last column
+// own one (wide: x and y start at the same parity); where the two origins differ in parity every lane owns one column (8-byte
+// lanes).  nl lanes walk a row, nl <= tpr <= 256.  One launch for any parity of the range's ends.
+template <int MODE>
+__global__ __launch_bounds__(256) void axpby_edge_rows_kernel(long nrows, double alpha, const double* __restrict__ x, long ldx,
+    double beta, double* y, long ldy, int m, int head, int wide, int nl, int tpr) {
+  const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
+  if (tx >= nl) return;
+  int j, w;
+  if (!wide) { j = tx; w = 1; }
+  else if (tx < head) { j = 0; w = 1; }
+  else { j = head + 2 * (tx - head); w = min(2, m - j); }
+  const long slab = (((nrows + gridDim.x - 1) / gridDim.x) + rpb - 1) / rpb * rpb;
+  const long rend = min(nrows, ((long)blockIdx.x + 1) * slab);
+  long row = (long)blockIdx.x * slab + ty;
+  if (w == 2) {
+    auto one = [&](long r, v2d_ax a, v2d_ax b) {
+      v2d_ax v;
+      if (MODE == 0) { v.x = alpha * a.x + beta * b.x; v.y = alpha * a.y + beta * b.y; }
+      else if (MODE == 1) { v.x = alpha * a.x; v.y = alpha * a.y; }
+      else { v.x = beta * b.x; v.y = beta * b.y; }
+      __builtin_nontemporal_store(v, reinterpret_cast<v2d_ax*>(y + r * ldy + j));
+    };
+    for (; row + 3L * rpb < rend; row += 4L * rpb) {
+      v2d_ax a[4], b[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long r = row + (long)u * rpb;
+        if (MODE != 2) a[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d_ax*>(x + r * ldx + j)); else a[u] = v2d_ax{0.0, 0.0};
+        if (MODE != 1) b[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d_ax*>(y + r * ldy + j)); else b[u] = v2d_ax{0.0, 0.0};
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(row + (long)u * rpb, a[u], b[u]);
+    }
+    for (; row < rend; row += rpb) {
+      v2d_ax a = v2d_ax{0.0, 0.0}, b = v2d_ax{0.0, 0.0};
+      if (MODE != 2) a = *reinterpret_cast<const v2d_ax*>(x + row * ldx + j);
+      if (MODE != 1) b = *reinterpret_cast<const v2d_ax*>(y + row * ldy + j);
+      one(row, a, b);
+    }
+  } else {
+    auto one = [&](long r, double a, double b) {
+      double v;
+      if (MODE == 0) v = alpha * a + beta * b;
+      else if (MODE == 1) v = alpha * a;
+      else v = beta * b;
+      __builtin_nontemporal_store(v, y + r * ldy + j);
+    };
+    for (; row + 3L * rpb < rend; row += 4L * rpb) {
+      double a[4], b[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const long r = row + (long)u * rpb;
+        if (MODE != 2) a[u] = __builtin_nontemporal_load(x + r * ldx + j); else a[u] = 0.0;
+        if (MODE != 1) b[u] = __builtin_nontemporal_load(y + r * ldy + j); else b[u] = 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) one(row + (long)u * rpb, a[u], b[u]);
+    }
+    for (; row < rend; row += rpb) {
+      double a = 0.0, b = 0.0;
+      if (MODE != 2) a = x[row * ldx + j];
+      if (MODE != 1) b = y[row * ldy + j];
+      one(row, a, b);
+    }
+  }
+}
+
+// The block moves of an outer iteration of GCG in one sweep (GCGE_BACKEND.block_moves, include/gcge_ops.h): a lane loads the column
+// pair (c0 + 2 tx, + 1) of a row of `src` = ritz[:, c0..) with one 16-byte load, c0 even, and stores it up to three times:
+//   V[:, col]                      for the columns in [x0, x1)                                   (X)
+//   V[:, w0 + map[col - c0]]       for the columns of a run (map: position in the packed runs, -1: in none)   (W start vectors)
+//   b[:, b0 + map[col - c0]]       the same times scale[map[..]], when b != NULL                 (right-hand sides)
+// with a 16-byte store where the two targets are neighbours at an even column and 8-byte stores otherwise.  b may lie over src:
+// every store of a row consumes that row's loads.  Rows of <= 64 lanes sit inside one wave, whose loads are one instruction
+// that has returned for every lane before the first store issues (all four rows in flight are waited for in front of the
+// stores); wider rows (SYNC) meet at a barrier between that wait and the first store.  src and b carry no
+// __restrict__: the loads stay in front of the stores.  Where the wait stands is the compiler's doing (the empty asm below pins
+// it); the overlap cases of tests/test_block_moves.py (b from lo - 1, lo, lo + 1 and the 300-column rows) are the guard against a
+// compiler that moves it.
+template <bool SYNC>
+__global__ __launch_bounds__(256) void block_moves_kernel(long nrows, const double* src, long lds, double* V, long ldv, double* b, long ldb,
+    int c0, int npairs, int x0, int x1, const int* __restrict__ map, const double* __restrict__ scale, int w0, int b0, int tpr) {
+  const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
+  const bool live = tx < npairs;
+  const int ca = c0 + 2 * tx;
+  const bool xa = live && ca >= x0 && ca < x1, xb = live && ca + 1 >= x0 && ca + 1 < x1;
+  const int pa = live ? map[2 * tx] : -1, pb = live ? map[2 * tx + 1] : -1;
+  const bool nb = pa >= 0 && pb == pa + 1;                        // neighbours in the packed runs
+  const bool w2 = nb && ((w0 + pa) & 1) == 0, b2 = nb && ((b0 + pa) & 1) == 0;
+  const double sa = (b != nullptr && pa >= 0) ? scale[pa] : 0.0, sb = (b != nullptr && pb >= 0) ? scale[pb] : 0.0;
+  const long slab = (((nrows + gridDim.x - 1) / gridDim.x) + rpb - 1) / rpb * rpb;
+  const long rend = min(nrows, ((long)blockIdx.x + 1) * slab);
+  const int txl = live ? tx : npairs - 1;                 // (idle lanes and rows past the slab repeat a load and store nothing)
+  for (long base = (long)blockIdx.x * slab; base < rend; base += 4L * rpb) {       // (uniform over the block: the barrier)
+    v2d_ax a[4], q[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long r = min(base + (long)u * rpb + ty, rend - 1);
+      a[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d_ax*>(src + r * lds + 2 * txl));
+    }
+    // an (empty) use of the four rows in straight-line code: the wait for every load stands here, in front of the barrier and of
+    // all the conditional stores, which then issue back to back
+    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]));
+    if (SYNC) __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) q[u] = v2d_ax{a[u].x * sa, a[u].y * sb};
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long r = base + (long)u * rpb + ty;
+      if (!live || r >= rend) continue;
+      double* vr = V + r * ldv;
+      if (xa && xb) __builtin_nontemporal_store(a[u], reinterpret_cast<v2d_ax*>(vr + ca));
+      else if (xa) __builtin_nontemporal_store(a[u].x, vr + ca);
+      else if (xb) __builtin_nontemporal_store(a[u].y, vr + ca + 1);
+      if (w2) __builtin_nontemporal_store(a[u], reinterpret_cast<v2d_ax*>(vr + w0 + pa));
+      else {
+        if (pa >= 0) __builtin_nontemporal_store(a[u].x, vr + w0 + pa);
+        if (pb >= 0) __builtin_nontemporal_store(a[u].y, vr + w0 + pb);
+      }
+      if (b != nullptr) {
+        double* br = b + r * ldb + b0;
+        if (b2) __builtin_nontemporal_store(q[u], reinterpret_cast<v2d_ax*>(br + pa));
+        else {
+          if (pa >= 0) __builtin_nontemporal_store(q[u].x, br + pa);
+          if (pb >= 0) __builtin_nontemporal_store(q[u].y, br + pb);
+        }
+      }
+    }
   }
 }
 
@@ -287,20 +421,22 @@ extern "C" int gcge_hip_axpby(int nrows, double alpha, const double* d_x, long l
   }
   const bool vec2 = (m % 2 == 0) && (ldy % 2 == 0) && (((uintptr_t)d_y & 15) == 0) &&
                     (mode >= 2 || ((ldx % 2 == 0) && (((uintptr_t)d_x & 15) == 0)));
-  // A wide range that starts on an odd column of both blocks (the solver's X / P / W ranges move with the number of locked pairs) or
-  // has an odd width: the odd columns at its ends go through the element-wise kernel, the even-aligned middle through the 16-byte
-  // lanes (the element-wise kernel moves a 128-column copy at 3.6 TB/s).  Same operation per element.
-  if (!vec2 && mode <= 2 && m >= 8 && ldy % 2 == 0 && (mode == 2 || ldx % 2 == 0) && (long)nrows >= 1024 &&
-      (mode == 2 || (((uintptr_t)d_x & 15) == ((uintptr_t)d_y & 15)))) {
-    const int head = (((uintptr_t)d_y & 15) == 8) ? 1 : 0;         // one column up to the next 16-byte boundary
-    const int tail = (m - head) % 2;
-    const int mid = m - head - tail;
-    if (mid >= 2 && (head || tail)) {
-      const double* xm = d_x ? d_x + head : nullptr;
-      if (head) hipLaunchKernelGGL(axpby_kernel, dim3(grid_for((long)nrows)), dim3(256), 0, st, (long)nrows, alpha, d_x, ldx, beta, d_y, ldy, 1, mode);
-      if (tail) hipLaunchKernelGGL(axpby_kernel, dim3(grid_for((long)nrows)), dim3(256), 0, st, (long)nrows, alpha, d_x ? d_x + head + mid : nullptr, ldx, beta,
-                                   d_y + head + mid, ldy, 1, mode);
-      return gcge_hip_axpby(nrows, alpha, xm, ldx, beta, d_y + head, ldy, mid, stream);
+  // A range that starts on an odd column of one or both blocks (the solver's X / P / W ranges move with the number of locked pairs) or
+  // has an odd width: one launch of the row-slab kernel with edge lanes — 16-byte lanes between an odd first and last column where
+  // the two origins share their parity, 8-byte lanes where they differ (the element-wise kernel moves a 128-column copy at 3.6 TB/s,
+  // and a single column of a wide block at a tenth of that).  Same operation per element.
+  if (!vec2 && mode <= 2 && m >= 8 && ldy % 2 == 0 && (mode == 2 || ldx % 2 == 0) && (long)nrows >= 1024) {
+    const int py = (((uintptr_t)d_y & 15) == 8) ? 1 : 0, px = mode == 2 ? py : ((((uintptr_t)d_x & 15) == 8) ? 1 : 0);
+    const int wide = px == py, head = wide ? py : 0;
+    const int nl = wide ? head + (m - head + 1) / 2 : m;
+    if (nl <= 256) {
+      int tpr = 1; while (tpr < nl) tpr *= 2;
+      const int rpb = 256 / tpr;
+      long g = ((long)nrows + (long)rpb * 8 - 1) / ((long)rpb * 8); if (g > 8192) g = 8192; if (g < 1) g = 1;
+      if (mode == 0) hipLaunchKernelGGL(axpby_edge_rows_kernel<0>, dim3((unsigned)g), dim3(256), 0, st, (long)nrows, alpha, d_x, ldx, beta, d_y, ldy, m, head, wide, nl, tpr);
+      else if (mode == 1) hipLaunchKernelGGL(axpby_edge_rows_kernel<1>, dim3((unsigned)g), dim3(256), 0, st, (long)nrows, alpha, d_x, ldx, beta, d_y, ldy, m, head, wide, nl, tpr);
+      else hipLaunchKernelGGL(axpby_edge_rows_kernel<2>, dim3((unsigned)g), dim3(256), 0, st, (long)nrows, alpha, d_x, ldx, beta, d_y, ldy, m, head, wide, nl, tpr);
+      return (int)hipGetLastError();
     }
   }
   // x == y with different column ranges (column copies inside one block) is fine for the row form as well: a thread reads
@@ -319,6 +455,21 @@ extern "C" int gcge_hip_axpby(int nrows, double alpha, const double* d_x, long l
   else
     hipLaunchKernelGGL(axpby_kernel, dim3(grid_for((long)nrows * m)), dim3(256), 0, st, (long)nrows, alpha,
                        d_x, ldx, beta, d_y, ldy, m, mode);
+  return (int)hipGetLastError();
+}
+
+// src = ritz + c0 (c0 even, 16-byte aligned rows: lds even), npairs <= 256 column pairs from there; d_map: 2 npairs ints, d_scale: the
+// packed runs' factors (b != NULL); every leading dimension even, V and b 16-byte aligned.  The caller has checked all ranges.
+extern "C" int gcge_hip_block_moves(int nrows, const double* d_src, long lds, double* d_v, long ldv, double* d_b, long ldb, int c0, int npairs,
+                                    int x0, int x1, const int* d_map, const double* d_scale, int w0, int b0, void* stream) {
+  if (nrows <= 0 || npairs <= 0) return 0;
+  int tpr = 1; while (tpr < npairs) tpr *= 2;
+  const int rpb = 256 / tpr;
+  long g = ((long)nrows + (long)rpb * 8 - 1) / ((long)rpb * 8); if (g > 8192) g = 8192; if (g < 1) g = 1;
+  if (tpr > 64) hipLaunchKernelGGL(block_moves_kernel<true>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (long)nrows, d_src, lds, d_v, ldv,
+                                   d_b, ldb, c0, npairs, x0, x1, d_map, d_scale, w0, b0, tpr);
+  else hipLaunchKernelGGL(block_moves_kernel<false>, dim3((unsigned)g), dim3(256), 0, (hipStream_t)stream, (long)nrows, d_src, lds, d_v, ldv,
+                          d_b, ldb, c0, npairs, x0, x1, d_map, d_scale, w0, b0, tpr);
   return (int)hipGetLastError();
 }
 

@@ -41,6 +41,35 @@ typedef struct {
 
 static int imin(int a, int b) { return a < b ? a : b; }
 
+/* Where the W systems' right-hand sides go.  Columns [startN, endX) of the eigenvector block are scratch between ComputeX and the
+ * next ComputeRitzVec, and the reference packs b from the first unconverged column `first` on (ops_eig_sol_gcg.c:560-577).  A
+ * back-end that walks 16-byte column pairs wants an even origin, so an odd `first` moves one column up where the `total` columns
+ * still end inside endX, else one column down where that is still inside startN, else stays (the back-end's slower paths).  The
+ * values of b are the same wherever it lies. */
+static long g_odd_origins = 0, g_realigned = 0, g_fused_moves = 0;
+int GCGE_GcgRhsOrigin(int first, int total, int startN, int endX)
+{
+	if (!(first & 1)) return first;
+	if (first + 1 + total <= endX) return first + 1;
+	if (first - 1 >= startN) return first - 1;
+	return first;
+}
+/* since the library was loaded: outer iterations whose first unconverged column was odd, those of them whose b moved to an even
+ * column, and outer iterations whose X / W / b moves were one sweep of the back-end (GCGE_BACKEND.block_moves) */
+void GCGE_GcgBlockMoveStats(long *odd_origins, long *realigned, long *fused_moves)
+{
+	if (odd_origins != NULL) *odd_origins = g_odd_origins;
+	if (realigned != NULL) *realigned = g_realigned;
+	if (fused_moves != NULL) *fused_moves = g_fused_moves;
+}
+static int rhs_origin(const Ctx *c, const int *offset, int total)
+{
+	/* GCGE_RHS_FIRST_COLUMN=1: b stays at the first unconverged column, as the reference packs it (tests compare the two) */
+	const int b0 = getenv("GCGE_RHS_FIRST_COLUMN") != NULL ? offset[1] : GCGE_GcgRhsOrigin(offset[1], total, c->startN, c->endX);
+	if (offset[1] & 1) { ++g_odd_origins; if (!(b0 & 1)) ++g_realigned; }
+	return b0;
+}
+
 static void rebase(Ctx *c)
 {
 	int N = c->sizeV - c->sizeC;
@@ -218,11 +247,13 @@ static void ComputeX(Ctx *c)
 	g_timing.compX += ops->GetWtime() - t0;
 }
 
-static void ComputeW(Ctx *c, int *offset)
+/* x_pending: ComputeX was left to this call, which moves X, the start vectors and (for BlockAMG over a back-end that forms
+ * b = x diag(scale) itself) b in one sweep of the back-end where its record offers one (GCGE_BACKEND.block_moves) */
+static void ComputeW(Ctx *c, int *offset, int x_pending)
 {
 	struct OPS_ *ops = c->ops; GCGSolver *p = c->p; void **b = c->ritz;
-	int s[2], e[2], idx, blk = 0, i;
-	double sigma = 0.0, *scales = c->scratch, t0 = ops->GetWtime(), t1;
+	int s[2], e[2], idx, blk = 0, i, b0, total = 0, moved = 0, form_b = 0;
+	double sigma = 0.0, *scales = c->scratch, t0 = ops->GetWtime(), t1, tx = 0.0;
 	void (*saved_solver)(void*, void**, void**, int*, int*, struct OPS_*) = ops->MultiLinearSolver;
 	void *saved_ws = ops->multi_linear_solver_workspace;
 	void **cg_ws[3];
@@ -240,14 +271,29 @@ static void ComputeW(Ctx *c, int *offset)
 	GCGE_LINSOL_ARGS args = {0};
 	c->startW = c->endP;
 	for (idx = 0; idx < offset[0]; ++idx) {
+		int lo = offset[idx * 2 + 1], hi = offset[idx * 2 + 2];
+		for (i = 0; i < hi - lo; ++i) scales[total + i] = c->ss_eval[lo + i] + sigma;
+		total += hi - lo;
+	}
+	b0 = rhs_origin(c, offset, total);
+	if (x_pending) {      /* timed as compX (the sweep's W start vectors and b included), not as compW */
+		double ta = ops->GetWtime();
+		form_b = scaled_rhs && GCGE_SolverFormsScaledRhs(ops);
+		moved = GCGE_BackendOf(ops).block_moves(c->ritz, c->V, c->startN, c->endX, offset, c->startW,
+				form_b ? b : NULL, b0, scales, ops);
+		if (moved) { ++g_fused_moves; g_timing.compX += ops->GetWtime() - ta; }
+		else ComputeX(c);
+		tx = ops->GetWtime() - ta;
+	}
+	for (idx = 0; idx < offset[0]; ++idx) {
 		int lo = offset[idx * 2 + 1], hi = offset[idx * 2 + 2], len = hi - lo;
-		/* initial guess: the current Ritz vectors */
+		/* initial guess: the current Ritz vectors, from V (the same bits since ComputeX): a b packed earlier in this loop
+		 * may lie over the eigenvector block's copy */
 		s[0] = lo; e[0] = hi; s[1] = c->startW + blk; e[1] = s[1] + len;
-		ops->MultiVecAxpby(1.0, c->ritz, 0.0, c->V, s, e, ops);
-		/* right-hand side (lambda + sigma) B x, packed from column offset[1] of ritz_vec */
-		for (i = 0; i < len; ++i) scales[blk + i] = c->ss_eval[lo + i] + sigma;
+		if (!moved) ops->MultiVecAxpby(1.0, c->V, 0.0, c->V, s, e, ops);
+		/* right-hand side (lambda + sigma) B x, packed from column b0 of ritz_vec */
 		if (!scaled_rhs) {
-			s[0] = lo; e[0] = hi; s[1] = offset[1] + blk; e[1] = s[1] + len;
+			s[0] = lo; e[0] = hi; s[1] = b0 + blk; e[1] = s[1] + len;
 			ops->MatDotMultiVec(c->B, c->V, b, s, e, ops);
 			ops->MultiVecLinearComb(NULL, b, 0, s, e, NULL, 0, scales + blk, 1, ops);
 		}
@@ -255,7 +301,7 @@ static void ComputeW(Ctx *c, int *offset)
 	}
 	c->endW = c->startW + blk;
 
-	s[0] = offset[1]; e[0] = s[0] + blk; s[1] = c->startW; e[1] = c->endW;
+	s[0] = b0; e[0] = s[0] + blk; s[1] = c->startW; e[1] = c->endW;
 	t1 = ops->GetWtime();
 	if (p->user_defined_multi_linear_solver == 2)
 		ops->MultiLinearSolver(c->A, b, c->V, s, e, ops);
@@ -281,9 +327,11 @@ static void ComputeW(Ctx *c, int *offset)
 		args.sigma = sigma; args.matB = c->B; args.user_scale = scales; args.n_user_scale = blk;
 		args.idle_blocks = cg_ws; args.n_idle = 3;
 	}
-	if (scaled_rhs) args.rhs_scale = scales;
+	if (scaled_rhs && !(moved && form_b)) args.rhs_scale = scales;      /* (b formed by the sweep: an ordinary right-hand side) */
 	GCGE_SetLinearSolverArgs(&args);
+	if ((offset[1] & 1) && !(b0 & 1)) GCGE_SetRealignedRhs(b, b0);
 	ops->MultiLinearSolver(c->A, b, c->V, s, e, ops);
+	GCGE_SetRealignedRhs(NULL, 0);
 	GCGE_SetLinearSolverArgs(NULL);
 	if (sigma != 0.0 && c->B != NULL && ops->MatAxpby != NULL
 			&& p->user_defined_multi_linear_solver != 1)
@@ -297,7 +345,7 @@ static void ComputeW(Ctx *c, int *offset)
 			p->compW_orth_zero_tol, c->ws0, ops);
 	ops->MultiVecOrth(c->V, c->startW, &c->endW, c->B, ops);
 	c->sizeW = c->endW - c->startW;
-	g_timing.compW += ops->GetWtime() - t0;
+	g_timing.compW += ops->GetWtime() - t0 - tx;
 }
 
 /* Second-order variant (-gcge_compW_cg_order 2; reference ComputeW12, ops_eig_sol_gcg.c:697-923): only the first
@@ -307,7 +355,7 @@ static void ComputeW(Ctx *c, int *offset)
 static void ComputeW12(Ctx *c, int *offset)
 {
 	struct OPS_ *ops = c->ops; GCGSolver *p = c->p; void **b = c->ritz;
-	int s[2], e[2], idx, blk = 0, i, total = 0, half, pass;
+	int s[2], e[2], idx, blk = 0, i, total = 0, half, pass, b0;
 	double sigma = 0.0, *scales = c->scratch, t0 = ops->GetWtime(), t1;
 	void (*saved_solver)(void*, void**, void**, int*, int*, struct OPS_*) = ops->MultiLinearSolver;
 	void *saved_ws = ops->multi_linear_solver_workspace;
@@ -322,6 +370,7 @@ static void ComputeW12(Ctx *c, int *offset)
 
 	for (idx = 0; idx < offset[0]; ++idx) total += offset[idx * 2 + 2] - offset[idx * 2 + 1];
 	half = total / 2;
+	b0 = rhs_origin(c, offset, half);                    /* as in ComputeW */
 	if (p->user_defined_multi_linear_solver == 1) {      /* as in ComputeW, without idle blocks */
 		args.sigma = sigma; args.matB = c->B; args.user_scale = scales; args.n_user_scale = half;
 	}
@@ -336,9 +385,9 @@ static void ComputeW12(Ctx *c, int *offset)
 			if (blk + len > half) len = half - blk;
 			if (pass == 0) {
 				s[0] = lo; e[0] = lo + len; s[1] = c->startW + blk; e[1] = s[1] + len;
-				ops->MultiVecAxpby(1.0, c->ritz, 0.0, c->V, s, e, ops);
+				ops->MultiVecAxpby(1.0, c->V, 0.0, c->V, s, e, ops);
 			}
-			s[0] = lo; e[0] = lo + len; s[1] = offset[1] + blk; e[1] = s[1] + len;
+			s[0] = lo; e[0] = lo + len; s[1] = b0 + blk; e[1] = s[1] + len;
 			ops->MatDotMultiVec(c->B, c->V, b, s, e, ops);
 			for (i = 0; i < len; ++i) scales[blk + i] = c->ss_eval[lo + i] + sigma;
 			ops->MultiVecLinearComb(NULL, b, 0, s, e, NULL, 0, scales + blk, 1, ops);
@@ -355,7 +404,8 @@ static void ComputeW12(Ctx *c, int *offset)
 						(sigma != 0.0 && !use_axpby) ? MatDotMultiVecShift : NULL, ops);
 			}
 			GCGE_SetLinearSolverArgs(&args);
-			s[0] = offset[1]; e[0] = s[0] + half; s[1] = c->startW; e[1] = s[1] + half;
+			if ((offset[1] & 1) && !(b0 & 1)) GCGE_SetRealignedRhs(b, b0);
+			s[0] = b0; e[0] = s[0] + half; s[1] = c->startW; e[1] = s[1] + half;
 			ops->MultiLinearSolver(c->A, b, c->V, s, e, ops);
 			g_timing.linsol += ops->GetWtime() - t1;
 			c->endW = c->startW + half;
@@ -365,9 +415,10 @@ static void ComputeW12(Ctx *c, int *offset)
 		}
 	}
 	t1 = ops->GetWtime();
-	s[0] = offset[1]; e[0] = s[0] + half; s[1] = c->endW; e[1] = s[1] + half;
+	s[0] = b0; e[0] = s[0] + half; s[1] = c->endW; e[1] = s[1] + half;
 	ops->MultiLinearSolver(c->A, b, c->V, s, e, ops);
 	g_timing.linsol += ops->GetWtime() - t1;
+	GCGE_SetRealignedRhs(NULL, 0);
 	GCGE_SetLinearSolverArgs(NULL);
 	c->endW += half;
 	assert(c->endW - c->startW <= total);
@@ -512,9 +563,12 @@ static void GCG(void *A, void *B, double *eval, void **evec, int nevGiven, int *
 		}
 		if (numIter == 0) { c->sizeP = 0; c->startP = c->endX; c->endP = c->startP; }
 		else ComputeP(c, c->offsetP);
-		ComputeX(c);
-		if (p->compW_cg_order != 1) ComputeW12(c, c->offsetW);
-		else ComputeW(c, c->offsetW);
+		{   /* X, the W start vectors and b in one sweep where the back-end offers it: ComputeW makes the move */
+			const int fuse = p->compW_cg_order == 1 && GCGE_BackendOf(ops).block_moves != NULL;
+			if (!fuse) ComputeX(c);
+			if (p->compW_cg_order != 1) ComputeW12(c, c->offsetW);
+			else ComputeW(c, c->offsetW, fuse);
+		}
 		tmp = c->offsetP; c->offsetP = c->offsetW; c->offsetW = tmp;
 		ComputeRayleighRitz(c, *nevConv);
 		for (idx = c->sizeV; idx < T; ++idx) c->ss_eval[idx] = c->ss_eval[c->sizeV - 1];

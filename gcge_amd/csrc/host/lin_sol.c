@@ -251,6 +251,11 @@ int GCGE_SolverTakesScaledRhs(struct OPS_ *ops)
 			(ops->MultiLinearSolver == be.scaled_rhs_solver || (ops->MultiLinearSolver == BlockAMG && be.amg_form_rhs != NULL));
 }
 
+int GCGE_SolverFormsScaledRhs(struct OPS_ *ops)
+{
+	return ops->MultiLinearSolver == BlockAMG && GCGE_BackendOf(ops).amg_form_rhs != NULL;
+}
+
 void MultiLinearSolverSetup_BlockAMG(int *max_iter, double *rate, double *tol, const char *tol_type,
 		void **A_array, void **P_array, int num_levels, void ***mv_array_ws[5], double *dbl_ws, int *int_ws,
 		void *pc, struct OPS_ *ops)

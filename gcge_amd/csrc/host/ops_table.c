@@ -50,6 +50,10 @@ void GCGE_SetLinearSolverArgs(const GCGE_LINSOL_ARGS *args)
 }
 const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs(void) { return &g_linsol_args; }
 
+static void **g_realigned_b = NULL; static int g_realigned_b0 = 0;
+void GCGE_SetRealignedRhs(void **b, int b0) { g_realigned_b = b; g_realigned_b0 = b0; }
+void **GCGE_GetRealignedRhs(int *b0) { if (b0 != NULL) *b0 = g_realigned_b0; return g_realigned_b; }
+
 /* The back-end record and the two slots that identify its table.  The lookup applies the opt-out switches, read at every
  * call (the tests flip them inside a running process); each turns off what it names:
  *   GCGE_NO_RESIDUAL_HOOK    residual_sq                                    (CheckConvergence through the slots)
@@ -59,7 +63,8 @@ const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs(void) { return &g_linsol_args; 
  *   GCGE_AMG_NO_FUSIONS      amg_residual, amg_prolong_add, amg_form_rhs,   (the V-cycle's slot calls;
  *                            amg_final_cols                                  every smoothing call runs its last pass whole)
  *   GCGE_AMG_FULL_LAST_PASS  amg_final_cols                                 (the same, alone)
- *   GCGE_NO_RHS_SCALE        scaled_rhs_solver, amg_form_rhs                (the GCG driver forms b = (lambda + sigma) x) */
+ *   GCGE_NO_RHS_SCALE        scaled_rhs_solver, amg_form_rhs                (the GCG driver forms b = (lambda + sigma) x)
+ *   GCGE_NO_BLOCK_MOVES      block_moves                                    (X, the W start vectors and b moved one by one) */
 static GCGE_BACKEND g_backend; static void *g_backend_matvec = NULL, *g_backend_lincomb = NULL;
 void GCGE_SetBackend(struct OPS_ *ops, const GCGE_BACKEND *backend)
 {
@@ -80,6 +85,7 @@ GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
 	if (getenv("GCGE_AMG_NO_FUSIONS") != NULL) { b.amg_residual = NULL; b.amg_prolong_add = NULL; b.amg_form_rhs = NULL; b.amg_final_cols = 0; }
 	if (getenv("GCGE_AMG_FULL_LAST_PASS") != NULL) b.amg_final_cols = 0;
 	if (getenv("GCGE_NO_RHS_SCALE") != NULL) { b.scaled_rhs_solver = NULL; b.amg_form_rhs = NULL; }
+	if (getenv("GCGE_NO_BLOCK_MOVES") != NULL) b.block_moves = NULL;
 	return b;
 }
 

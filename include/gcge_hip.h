@@ -408,6 +408,13 @@ void gcge_hip_lincomb_tune (int row_fragments);   /* 0 automatic (2 for m > 64 o
 /* K4  Y[:,0:m) = alpha X[:,0:m) + beta Y   (d_x NULL: scale only; beta == 0: no read of Y) */
 int gcge_hip_axpby (int nrows, double alpha, const double *d_x, long ldx, double beta,
 		double *d_y, long ldy, int m, void *stream);
+/*     GCGE_BACKEND.block_moves of OPS_HIP_Set (include/gcge_ops.h) on blocks of this back-end, for tests: V[:, x0..x1) = ritz[:, x0..x1),
+ *     V[:, w0 + ..) = the runs of ritz packed, b[:, b0 + ..) = the same times scale (b NULL: none) in one sweep; 0: declined        */
+int gcge_hip_block_moves_mv (void **ritz, void **V, int x0, int x1, const int *runs, int w0, void **b, int b0, const double *scale);
+/*     counters since the library was loaded: out[0] one-sweep starts of the fused block CG taken, out[1] declined ONLY because b starts
+ *     on an odd column (matrix in pattern form, even width, x and r on even columns), out[2] / out[3] the same for the V-cycle's
+ *     fused residual                                                                                                              */
+void gcge_hip_sweep_stats (long out[4]);
 
 #ifdef __cplusplus
 }

@@ -178,6 +178,13 @@ typedef struct GCGE_LINSOL_ARGS_ {
 void       GCGE_SetLinearSolverArgs (const GCGE_LINSOL_ARGS *args);   /* copied; NULL clears */
 const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs (void);              /* never NULL; all zero when nothing is published */
 
+/* Published by the GCG driver around a W solve whose right-hand sides it moved off an odd column (gcg.c: GCGE_GcgRhsOrigin):
+ * the block and the column they now start at; NULL otherwise.  What a solver computes must not depend on where b lies.  A
+ * back-end with two routes for one step that round differently, chosen by b's column (the fused CG's start: |r|^2 summed inside
+ * the product sweep or by the column-dot kernel), takes for these right-hand sides the sums of the route an odd column led to. */
+void       GCGE_SetRealignedRhs (void **b, int b0);                   /* b == NULL clears */
+void     **GCGE_GetRealignedRhs (int *b0);
+
 /* What a back-end offers beyond the slots of struct OPS_ (NULL / 0: not offered).  Registered once by the back-end
  * (GCGE_SetBackend; OPS_HIP_Set does it), it applies to every table whose MatDotMultiVec AND MultiVecLinearComb are the ones
  * `ops` held then; GCGE_BackendOf returns a copy — all zero for other tables — minus what the opt-out switches of the
@@ -201,7 +208,13 @@ const GCGE_LINSOL_ARGS *GCGE_GetLinearSolverArgs (void);              /* never N
  *                 release: PAS's hierarchy of a standard problem takes its coarse masses P^T P from it (NULL: not offered).
  *   mat_rows_as_given   1 when the device rows of a matrix are in the order the caller gave them (0: the back-end re-ordered).
  *   amg_final_cols   1 when the smoother of amg_smoother_setup honours GCGE_LINSOL_ARGS.final_residual_cols: BlockAMG then tells each
- *                 smoothing call that no residual is read (-1), except the cycle's last one, whose column 0 it reads (1). */
+ *                 smoothing call that no residual is read (-1), except the cycle's last one, whose column 0 it reads (1).
+ *   block_moves   the three block moves of an outer iteration of GCG in one sweep over the rows (reference ComputeX + the head of
+ *                 ComputeW, src/ops_eig_sol_gcg.c:458-471,:536-577):  V[:, x0..x1) = ritz[:, x0..x1);  for the runs (lo_i, hi_i) of
+ *                 runs[] = {count; lo_0, hi_0, ...} (all inside [x0, x1)), packed:  V[:, w0 + blk..) = ritz[:, lo_i..hi_i);  and
+ *                 with b != NULL  b[:, b0 + blk..) = ritz[:, lo_i..hi_i) diag(scale[blk..]), every product rounded once.  b may be
+ *                 the block ritz itself with target columns over source columns: every row is read whole before any of it is
+ *                 written.  0 declines with nothing touched. */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -210,6 +223,8 @@ typedef int    (*GCGE_AMG_RESIDUAL_FN) (void *A, void **b, int b0, void **x, int
 typedef int    (*GCGE_AMG_PROLONG_ADD_FN) (void *P, void **xc, int c0, void **xf, int f0, int ncols, struct OPS_ *ops);
 typedef int    (*GCGE_AMG_FORM_RHS_FN) (void **b, int b0, void **x, int x0, const double *scale, int ncols, struct OPS_ *ops);
 typedef void   (*GCGE_LINSOL_FN) (void *mat, void **b, void **x, int *start, int *end, struct OPS_ *ops);
+typedef int    (*GCGE_BLOCK_MOVES_FN) (void **ritz, void **V, int x0, int x1, const int *runs, int w0, void **b, int b0,
+		const double *scale, struct OPS_ *ops);
 typedef struct GCGE_BACKEND_ {
 	GCGE_RESIDUAL_FN residual_sq;
 	int inplace_lincomb_cols;
@@ -222,6 +237,7 @@ typedef struct GCGE_BACKEND_ {
 	void *(*mat_identity) (void *like); void (*mat_free) (void *mat);
 	int  (*mat_rows_as_given) (void *mat);
 	int amg_final_cols;
+	GCGE_BLOCK_MOVES_FN block_moves;
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

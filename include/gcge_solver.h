@@ -86,6 +86,10 @@ void MultiLinearSolverSetup_BlockAMG (int *max_iter, double *rate, double *tol, 
  *     back-end's scaled_rhs_solver, or BlockAMG over a back-end with amg_form_rhs (GCGE_BACKEND).  BlockAMG smooths with the
  *     back-end's amg_smoother_* and takes its amg_residual / amg_prolong_add where the back-end offers them.              */
 int GCGE_SolverTakesScaledRhs (struct OPS_ *ops);
+/*     1: ... and forms b from the scales itself before it starts (BlockAMG over amg_form_rhs; the back-end's scaled_rhs_solver
+ *     never reads b).  The GCG driver then has b written by the sweep that moves X and the start vectors
+ *     (GCGE_BACKEND.block_moves) and publishes an ordinary right-hand side.                                                  */
+int GCGE_SolverFormsScaledRhs (struct OPS_ *ops);
 /*     BlockAMG as the solver of GCG's W systems, the way the reference's SiO2 driver sets it up under OPS_USE_AMG
  *     (test/test_eig_sol_SiO2_MAT.c:96-128,160-170): hierarchy from ops->MultiGridCreate (at most max_levels), work blocks of
  *     block_size columns per level, max_iter = {cycles, smooth0, smooth0, smooth, smooth, ...} (reference: {1, 5, 5, 4, 4, ...}),
@@ -143,6 +147,12 @@ typedef struct GCGE_Timing_ {
 	double initX, checkconv, compP, compRR, rr_matW, dsyevx, compRV, compW, linsol, compX, total;
 } GCGE_Timing;
 const GCGE_Timing *GCGE_LastTiming (void);
+/* column at which ComputeW packs the `total` right-hand sides inside the scratch columns [startN, endX) of the eigenvector block
+ * when the first unconverged column is `first`: even whenever first, first + 1 or first - 1 fits, else `first` */
+int GCGE_GcgRhsOrigin (int first, int total, int startN, int endX);
+/* counters since the library was loaded: outer iterations whose first unconverged column was odd, those of them whose b moved to
+ * an even column, outer iterations whose X / W / b moves were one sweep (GCGE_BACKEND.block_moves).  NULL: not wanted. */
+void GCGE_GcgBlockMoveStats (long *odd_origins, long *realigned, long *fused_moves);
 
 /* ---- harness ---------------------------------------------------------------- */
 /* flag: 0 BlockPCG inside GCG, 1 the back-end's own ops->MultiLinearSolver, 2 both */
