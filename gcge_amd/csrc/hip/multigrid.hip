@@ -2,13 +2,14 @@
 //
 // The reference's BlockAMG (src/ops_lin_sol.c:466-715; ours: csrc/host/lin_sol.c) takes A_0 = A, A_{l+1}, P_l from the back-end:
 // app/app_slepc.c:648-728 extracts them from PETSc GAMG, app/app_hypre.c from BoomerAMG, app/app_lapack.c:863-929 builds a 1-D toy.
-// Here: the CSR arrays of A come back from the device (every upload keeps them), the aggregation hierarchy of
-// include/gcge_multigrid.h (2 x 2 x 2 cells of a detected grid, greedy aggregates otherwise; A_{l+1} = scale P^T A_l P) is built on
-// the host, and every level goes up again through gcge_hip_mat_create — so a coarse Laplacian gets the pattern kernels, a coarse
-// real-space Hamiltonian its blocks, exactly like a matrix the caller uploads.  The prolongations are rectangular matrices
+// Here: the aggregation hierarchy of include/gcge_multigrid.h (2 x 2 x 2 cells of a detected grid or of a masked grid's box, greedy
+// aggregates otherwise; A_{l+1} = scale P^T A_l P), built from the device-resident CSR of A one level after the other
+// (multigrid_create_device: aggregates, Galerkin products and P / P^T on the device, mg_device.hip) or, in mode 1 and when a level
+// is out of the kernels' reach, by the host builders on the downloaded CSR (multigrid_create_host).  Either way every coarse level
+// goes up through gcge_hip_mat_create (gcge_hip_mat_create_grid on a masked grid) — so a coarse Laplacian gets the pattern kernels,
+// a coarse real-space Hamiltonian its blocks, exactly like a matrix the caller uploads.  The prolongations are rectangular matrices
 // (GCGE_HIP_MAT_::rect_ncols): CSR of P for MatDotMultiVec, CSR of P^T for MatTransDotMultiVec, both through the generic CSR
 // kernel (spmm.hip) — one non-zero per fine row, every fine row of the block read or written exactly once.
-// A matrix on a masked grid (the handle carries its geometry) is coarsened by the cells of its bounding box: "masked grids" below.
 // Row slabs (one rank per GPU): a slab of whole planes coarsens by itself (every rank pairs its own planes) — local prolongations, coarse slabs
 // through the slab constructor (gcge_hip_mat_create_slab over RCCL, or a registered factory: the tests' torch.distributed transport).
 #include <hip/hip_runtime.h>
@@ -58,6 +59,7 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_rect_csr(const GCGE_CSR* P) {
   return gcge_hip_mat_create_rect(nr, nc, P->rowptr, P->colidx, P->val, tp.data(), tc.data(), tv.data());
 }
 
+
 // one hierarchy per MultiGridCreate call; found again through the A_array pointer MultiGridDestroy hands back
 struct MgHold { void** A_array; std::vector<GCGE_HIP_MAT*> owned; };
 static std::vector<MgHold> g_mg;
@@ -90,9 +92,74 @@ static long csr_bytes(long nrows, long nnz) { return (nrows + 1) * (long)sizeof(
 static gcge_hip_slab_factory_fn g_slab_factory = nullptr; static void* g_slab_factory_ctx = nullptr;
 extern "C" void gcge_hip_set_slab_factory(gcge_hip_slab_factory_fn fn, void* ctx) { g_slab_factory = fn; g_slab_factory_ctx = ctx; }
 
+// ------------------------------------------------------------------------------------------------------------ what every build ends in
+// the arguments of the MultiGridCreate slot, and what a build hands over: the coarse handles in hierarchy order (As / Bs: levels 1 ..,
+// Bs empty without a B to coarsen), the grid or box of every level (zeros: aggregated over the graph) and what the trace says of it
+struct MgSlot { void*** A_array; void*** B_array; void*** P_array; int* num_levels; void* A; void* B; };
+struct MgBuilt {
+  std::vector<GCGE_HIP_MAT*> As, Bs, Ps;
+  std::vector<std::array<int, 3>> dims;
+  bool masked = false; const char* how = "";       // how: " (device build)", " (host build)" or nothing
+  int rank = 0, world = 0; std::vector<long> global_rows;       // a row slab: the rows of all ranks, level by level
+};
+
+static void mg_install(const MgSlot& s, const MgBuilt& b) {
+  const int L = (int)b.As.size() + 1;
+  MgHold h;
+  *s.A_array = (void**)calloc(L, sizeof(void*));
+  *s.P_array = (void**)calloc(L > 1 ? L - 1 : 1, sizeof(void*));
+  if (s.B_array != nullptr) *s.B_array = (void**)calloc(L, sizeof(void*));
+  (*s.A_array)[0] = s.A;
+  if (s.B_array != nullptr) (*s.B_array)[0] = s.B;
+  for (int l = 1; l < L; ++l) {
+    (*s.A_array)[l] = b.As[l - 1]; h.owned.push_back(b.As[l - 1]);
+    if (!b.Bs.empty()) { (*s.B_array)[l] = b.Bs[l - 1]; h.owned.push_back(b.Bs[l - 1]); }
+  }
+  for (int l = 0; l + 1 < L; ++l) { (*s.P_array)[l] = b.Ps[l]; h.owned.push_back(b.Ps[l]); }
+  if (getenv("GCGE_MG_TRACE") != nullptr)
+    for (int l = 0; l < L; ++l) {
+      const GCGE_HIP_MAT* m = (const GCGE_HIP_MAT*)(*s.A_array)[l];
+      const int* d = b.dims[l].data();
+      if (b.world > 0)
+        fprintf(stderr, "MultiGridCreate: rank %d of %d, level %d: %d of %ld rows, %ld non-zeros, grid %d x %d x %d, K1 form %s\n", b.rank, b.world, l, m->nrows,
+                b.global_rows[l], m->nnz, d[0], d[1], d[2], gcge_hip_mat_spmm_form(m));
+      else if (b.masked)
+        fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, masked grid in the box %d x %d x %d (%.1f%% of it), K1 form %s%s\n", l, m->nrows,
+                m->nnz, d[0], d[1], d[2], 100.0 * m->nrows / ((double)d[0] * d[1] * d[2]), gcge_hip_mat_spmm_form(m), b.how);
+      else
+        fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, grid %d x %d x %d, K1 form %s%s\n", l, m->nrows, m->nnz, d[0], d[1], d[2],
+                gcge_hip_mat_spmm_form(m), b.how);
+    }
+  h.A_array = *s.A_array;
+  g_mg.push_back(h);
+  *s.num_levels = L;
+}
+
+// a finished host hierarchy as handles: all A_l / B_l level by level through make(l, csr), then all P_l
+template <class Make> static void mg_load_host(const GCGE_MG& mg, bool withB, MgBuilt& out, Make make) {
+  for (int l = 1; l < mg.num_levels; ++l) {
+    GCGE_HIP_MAT* a = make(l, mg.A[l]);
+    GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
+    out.As.push_back(a);
+    if (withB) {
+      GCGE_HIP_MAT* b = make(l, mg.B[l]);
+      GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
+      out.Bs.push_back(b);
+    }
+  }
+  for (int l = 0; l + 1 < mg.num_levels; ++l) {
+    GCGE_HIP_MAT* p = gcge_hip_mat_create_rect(mg.P[l].nrows, mg.P[l].ncols, mg.P[l].rowptr, mg.P[l].colidx, mg.P[l].val,
+                                               mg.PT[l].rowptr, mg.PT[l].colidx, mg.PT[l].val);
+    GCGE_REQUIRE(p != nullptr, "MultiGridCreate: upload of a prolongation");
+    out.Ps.push_back(p);
+  }
+  for (int l = 0; l < mg.num_levels; ++l) out.dims.push_back({mg.dims[l][0], mg.dims[l][1], mg.dims[l][2]});
+}
+
+// ------------------------------------------------------------------------------------------------------------ row slabs
 // a row slab (one rank per GPU): whole planes of a detected grid, cut on any plane boundary — every rank coarsens its own slab
-// (gcge_mg_build_slab), the coarse slabs go through the slab constructor (ghost list, halo plan: collective)
-static void multigrid_create_slab(void*** A_array, void*** B_array, void*** P_array, int* num_levels, const GCGE_HIP_MAT_* mA, void* A, void* B) {
+// (gcge_mg_build_slab), the coarse slabs go through the slab constructor (ghost list, halo plan: collective); no B below level 0
+static void multigrid_create_slab(const MgSlot& s, const GCGE_HIP_MAT_* mA) {
   GCGE_REQUIRE(mA->h_part != nullptr && mA->part_world >= 1, "MultiGridCreate on a row slab: the partition of all ranks (gcge_hip_mat_create_slab / gcge_hip_mat_set_partition)");
   GCGE_REQUIRE(mA->nghost == 0 || mA->h_ghost_global != nullptr, "MultiGridCreate on a row slab: the global rows behind the halo columns (gcge_hip_mat_create_local_ghosts)");
   const int world = mA->part_world;
@@ -109,79 +176,114 @@ static void multigrid_create_slab(void*** A_array, void*** B_array, void*** P_ar
     abort();
   }
   GCGE_MG mg; long* parts = nullptr;
-  const int rc = gcge_mg_build_slab(&cA, dims, mA->h_part, rank, world, *num_levels, 0.0, &mg, &parts);
+  const int rc = gcge_mg_build_slab(&cA, dims, mA->h_part, rank, world, *s.num_levels, 0.0, &mg, &parts);
   if (rc != 0) { fprintf(stderr, "MultiGridCreate (HIP back-end): gcge_mg_build_slab failed (%d) — slabs must be whole planes of the %d x %d x %d grid\n", rc, dims[0], dims[1], dims[2]); abort(); }
-  const int L = mg.num_levels;
-  MgHold h;
-  *A_array = (void**)calloc(L, sizeof(void*));
-  *P_array = (void**)calloc(L > 1 ? L - 1 : 1, sizeof(void*));
-  if (B_array != nullptr) *B_array = (void**)calloc(L, sizeof(void*));
-  (*A_array)[0] = A;
-  if (B_array != nullptr) (*B_array)[0] = B;
+  MgBuilt built;
+  built.rank = rank; built.world = world;
+  for (int l = 0; l < mg.num_levels; ++l) built.global_rows.push_back(parts[(size_t)l * (world + 1) + world]);
   const int buf_cols = mA->buf_cols > 0 ? mA->buf_cols : 128;
-  for (int l = 1; l < L; ++l) {
+  mg_load_host(mg, false, built, [&](int l, const GCGE_CSR& c) {
     const long* pl = parts + (size_t)l * (world + 1);
-    GCGE_HIP_MAT* a = g_slab_factory != nullptr
-        ? g_slab_factory(pl, world, rank, mg.A[l].rowptr, mg.A[l].colidx, mg.A[l].val, buf_cols, g_slab_factory_ctx)
-        : gcge_hip_mat_create_slab(pl, mg.A[l].rowptr, mg.A[l].colidx, mg.A[l].val, buf_cols);
+    GCGE_HIP_MAT* a = g_slab_factory != nullptr ? g_slab_factory(pl, world, rank, c.rowptr, c.colidx, c.val, buf_cols, g_slab_factory_ctx)
+                                                : gcge_hip_mat_create_slab(pl, c.rowptr, c.colidx, c.val, buf_cols);
     GCGE_REQUIRE(a != nullptr, "MultiGridCreate: construction of a coarse slab");
     if (a->h_part == nullptr) gcge_hip_mat_set_partition(a, pl, world);
-    (*A_array)[l] = a; h.owned.push_back(a);
-  }
-  for (int l = 0; l + 1 < L; ++l) {
-    GCGE_HIP_MAT* p = gcge_hip_mat_create_rect(mg.P[l].nrows, mg.P[l].ncols, mg.P[l].rowptr, mg.P[l].colidx, mg.P[l].val,
-                                               mg.PT[l].rowptr, mg.PT[l].colidx, mg.PT[l].val);
-    GCGE_REQUIRE(p != nullptr, "MultiGridCreate: upload of a prolongation");
-    (*P_array)[l] = p; h.owned.push_back(p);
-  }
-  if (getenv("GCGE_MG_TRACE") != nullptr)
-    for (int l = 0; l < L; ++l)
-      fprintf(stderr, "MultiGridCreate: rank %d of %d, level %d: %d of %ld rows, %ld non-zeros, grid %d x %d x %d, K1 form %s\n", rank, world, l, mg.A[l].nrows,
-              parts[(size_t)l * (world + 1) + world], (long)mg.A[l].nnz, mg.dims[l][0], mg.dims[l][1], mg.dims[l][2], gcge_hip_mat_spmm_form((const GCGE_HIP_MAT*)(*A_array)[l]));
+    return a;
+  });
   gcge_mg_free(&mg);
   free(parts);
-  h.A_array = *A_array;
-  g_mg.push_back(h);
-  *num_levels = L;
+  mg_install(s, built);
 }
 
-// ------------------------------------------------------------------------------------------------------------ the device path
-// gcge_mg_build's hierarchy (same stopping rules, same defaults) from the device-resident CSR of A (and B), one level after the other:
-// grid detection from the sampled rows only, grid aggregates and their members on the device (graph levels: the unchanged host
-// aggregation on that level's CSR, which is then downloaded), the Galerkin products on the device (mg_device.hip), P / P^T built on
-// the device.  Every coarse level is downloaded (8 x smaller than its parent on a grid) for gcge_hip_mat_create, which analyses it
-// exactly as in the host path; the next level is coarsened from the Galerkin output, in hierarchy order — never from the coarse
-// handle, whose rows gcge_hip_mat_create may re-order.  Returns false with nothing left behind when a level is out of the kernels'
-// reach (a coarse row of more than 512 distinct columns, 2^31 entries): the caller then builds on the host.
+// ------------------------------------------------------------------------------------------------------------ the host builds
+// mode 1, and whatever the device build gives up on: gcge_mg_build on the downloaded CSR of A (and B) — gcge_mg_build_masked with the
+// handle's geometry on a masked grid, whose levels go up through gcge_hip_mat_create_grid with THEIR geometry (see below)
+static void multigrid_create_host(const MgSlot& s, const GCGE_HIP_MAT_* mA, const GCGE_HIP_MAT_* mB, bool masked) {
+  double t = mg_now();
+  GCGE_CSR cA, cB; std::vector<int> rpA, ciA, rpB, ciB; std::vector<double> vaA, vaB;
+  download_csr(mA, &cA, rpA, ciA, vaA);
+  if (mB != nullptr) download_csr(mB, &cB, rpB, ciB, vaB);
+  g_mg_d2h += csr_bytes(mA->nrows, mA->nnz) + (mB != nullptr ? csr_bytes(mB->nrows, mB->nnz) : 0);
+  g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
+  GCGE_MG mg;
+  MgBuilt built;
+  built.masked = masked;
+  if (masked) {
+    const int rc = gcge_mg_build_masked(&cA, mB != nullptr ? &cB : nullptr, mA->geom_dims, mA->h_box, *s.num_levels, 0, 0.0, &mg);
+    if (rc != 0) { fprintf(stderr, "MultiGridCreate: gcge_mg_build_masked failed (%d)\n", rc); abort(); }
+    built.how = " (host build)";
+  } else if (gcge_mg_build(&cA, mB != nullptr ? &cB : nullptr, *s.num_levels, 0, 0.0, &mg) != 0) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
+  g_mg_phase[masked ? MG_AGGREGATE : MG_OTHER] += mg_now() - t; t = mg_now();       // (all of the host builder, whatever it did)
+  mg_load_host(mg, s.B_array != nullptr && mB != nullptr, built, [&](int l, const GCGE_CSR& c) {
+    const int* d = mg.dims[l];
+    return masked ? gcge_hip_mat_create_grid(c.nrows, c.rowptr, c.colidx, c.val, d[0], d[1], d[2], gcge_mg_level_box(&mg, l))
+                  : gcge_hip_mat_create(c.nrows, c.nrows, 0, c.rowptr, c.colidx, c.val);
+  });
+  g_mg_phase[MG_COARSE] += mg_now() - t;
+  gcge_mg_free(&mg);
+  mg_install(s, built);
+}
+
+// ------------------------------------------------------------------------------------------------------------ the device build
+// The host builders' hierarchy (same stopping rules, same defaults) from the device-resident CSR of A (and B), one level after the
+// other: aggregate, Galerkin products (mg_device.hip), P / P^T from the device arrays, then the coarse level is downloaded (8 x smaller
+// than its parent on a grid) and uploaded again through the constructor that analyses it exactly as in the host build; the next level
+// is coarsened from the Galerkin output, in hierarchy order — never from the coarse handle, whose rows gcge_hip_mat_create may
+// re-order.  Only the aggregation differs between the three kinds of coarsening:
+//   grid    2 x 2 x 2 cells of the grid detected from the sampled rows, and their members, in closed form on the device;
+//   graph   the unchanged host aggregation on that level's CSR (downloaded once, then the coarse download of the level before);
+//   masked  a handle that carries the geometry of a masked grid (gcge_hip_mat_geometry: the grid points inside a sphere in scan order,
+//           the PARSEC matrices): the occupied 2 x 2 x 2 cells of its bounding box, in scan order of the coarse box a masked grid
+//           again, from the device-resident box array (counts, two sums, members by binary search); the coarse box array comes back
+//           with the level, which goes up through gcge_hip_mat_create_grid with ITS geometry: the rows stay as given (P / P^T match
+//           by construction) and the level carries its geometry like a matrix the caller named one for.
+// Returns false with nothing left behind when a level is out of the kernels' reach (a coarse row of more than 512 distinct columns,
+// 2^31 entries): the caller then builds on the host.
+static int g_mg_masked_cells = 1;
+extern "C" void gcge_hip_multigrid_masked_cells(int on) { g_mg_masked_cells = on != 0; }
+extern "C" int gcge_hip_multigrid_get_masked_cells(void) { return g_mg_masked_cells; }
+static bool mg_is_masked_grid(const GCGE_HIP_MAT_* m) {
+  return g_mg_masked_cells && m->geom_kind != 0 && m->d_box != nullptr && (long)m->geom_dims[0] * m->geom_dims[1] * m->geom_dims[2] != (long)m->nrows;
+}
+
 struct DevCsr { int n; long nnz; int* rp; int* ci; double* va; bool owned; };
 static void devcsr_free(DevCsr& c) { if (c.owned) { hipFree(c.rp); hipFree(c.ci); hipFree(c.va); } c = DevCsr{0, 0, nullptr, nullptr, nullptr, false}; }
+enum MgKind { MG_GRID, MG_GRAPH, MG_MASKED };
 
-static bool multigrid_create_device(void*** A_array, void*** B_array, void*** P_array, int* num_levels, const GCGE_HIP_MAT_* mA,
-                                    const GCGE_HIP_MAT_* mB, void* A, void* B) {
+static bool multigrid_create_device(const MgSlot& s, const GCGE_HIP_MAT_* mA, const GCGE_HIP_MAT_* mB, bool masked) {
   double scale = 0.5, theta = 0.25; int min_rows = 64;
   gcge_mg_get_defaults(&scale, &min_rows, &theta);
-  const int max_levels = *num_levels;
+  const int max_levels = *s.num_levels;
   GCGE_HIP_CHECK(hipStreamSynchronize((hipStream_t)gcge_hip_stream()));
   double t = mg_now();
   int dims[3] = {0, 0, 0};
-  const int have_grid = gcge_hip_mg_detect_grid_device(mA->nrows, mA->d_rowptr, mA->d_colidx, dims, &g_mg_d2h);
-  g_mg_phase[MG_DETECT] += mg_now() - t;
-  std::vector<GCGE_HIP_MAT*> As, Bs, Ps;
-  std::vector<std::array<int, 3>> ldims;
+  MgKind kind = MG_MASKED;
+  if (masked) memcpy(dims, mA->geom_dims, sizeof dims);
+  else {
+    kind = gcge_hip_mg_detect_grid_device(mA->nrows, mA->d_rowptr, mA->d_colidx, dims, &g_mg_d2h) ? MG_GRID : MG_GRAPH;
+    if (kind == MG_GRAPH) dims[0] = dims[1] = dims[2] = 0;
+    g_mg_phase[MG_DETECT] += mg_now() - t;
+  }
+  MgBuilt built;
+  built.masked = masked; built.how = " (device build)";
   DevCsr fa{mA->nrows, mA->nnz, mA->d_rowptr, mA->d_colidx, mA->d_val, false};
   DevCsr fb{0, 0, nullptr, nullptr, nullptr, false};
   if (mB != nullptr) fb = DevCsr{mB->nrows, mB->nnz, mB->d_rowptr, mB->d_colidx, mB->d_val, false};
-  GCGE_CSR hostA; memset(&hostA, 0, sizeof hostA);       // the current level's CSR on the host (graph aggregation), once downloaded
+  GCGE_CSR hostA; memset(&hostA, 0, sizeof hostA);       // the level's CSR on the host once it is there (what a graph level aggregates)
+  int* d_box = mA->d_box; bool own_box = false;          // masked: the level's box array (level 0: the handle's)
   bool ok = true;
   for (int l = 0; l + 1 < max_levels; ++l) {
     const int nf = fa.n;
     if (nf <= min_rows) break;
     t = mg_now();
     int nc = 0, cdims[3] = {0, 0, 0};
-    int *d_agg = nullptr, *d_ptr = nullptr, *d_mem = nullptr;
+    int *d_agg = nullptr, *d_ptr = nullptr, *d_mem = nullptr, *d_cbox = nullptr;
     GCGE_HIP_CHECK(hipMalloc(&d_agg, (size_t)nf * sizeof(int)));
     GCGE_HIP_CHECK(hipMalloc(&d_mem, (size_t)nf * sizeof(int)));
-    if (have_grid) {
+    if (kind == MG_MASKED) {
+      nc = gcge_hip_mg_agg_masked_device(dims, d_box, nf, d_agg, d_mem, &d_ptr, &d_cbox, cdims, &g_mg_d2h);
+      g_mg_phase[MG_AGGREGATE] += mg_now() - t;
+    } else if (kind == MG_GRID) {
       nc = ((dims[0] + 1) / 2) * ((dims[1] + 1) / 2) * ((dims[2] + 1) / 2);
       GCGE_HIP_CHECK(hipMalloc(&d_ptr, ((size_t)nc + 1) * sizeof(int)));
       gcge_hip_mg_agg_grid_device(dims, d_agg, d_ptr, d_mem, cdims);
@@ -203,7 +305,8 @@ static bool multigrid_create_device(void*** A_array, void*** B_array, void*** P_
       }
       g_mg_phase[MG_TRANSFER] += mg_now() - t;
     }
-    if (nc < 1 || (long)nc * 3 > (long)nf * 2) { hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); break; }     // coarsening stalled
+    auto free_agg = [&] { hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); };
+    if (nc < 1 || (long)nc * 3 > (long)nf * 2) { free_agg(); hipFree(d_cbox); break; }     // coarsening stalled
     t = mg_now();
     DevCsr ca{nc, 0, nullptr, nullptr, nullptr, true}, cb{0, 0, nullptr, nullptr, nullptr, false};
     int rc = gcge_hip_mg_galerkin_device(nf, fa.rp, fa.ci, fa.va, d_agg, nc, d_ptr, d_mem, scale, &ca.rp, &ca.ci, &ca.va, &ca.nnz, &g_mg_d2h);
@@ -214,222 +317,59 @@ static bool multigrid_create_device(void*** A_array, void*** B_array, void*** P_
     }
     if (rc != 0) ca.owned = ca.rp != nullptr;
     g_mg_phase[MG_GALERKIN] += mg_now() - t;
-    if (rc != 0) { devcsr_free(ca); devcsr_free(cb); hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); ok = false; break; }
+    if (rc != 0) { devcsr_free(ca); devcsr_free(cb); free_agg(); hipFree(d_cbox); ok = false; break; }
     t = mg_now();
     GCGE_HIP_MAT* p = gcge_hip_mat_create_rect_device(nf, nc, d_agg, d_ptr, d_mem);
     GCGE_REQUIRE(p != nullptr, "MultiGridCreate: a prolongation from device arrays");
-    Ps.push_back(p);
-    hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem);
+    built.Ps.push_back(p);
+    free_agg();
     g_mg_phase[MG_OTHER] += mg_now() - t; t = mg_now();
     GCGE_CSR hc, hb; memset(&hb, 0, sizeof hb);
+    std::vector<int> cbox(masked ? (size_t)nc : 0);
     if (gcge_hip_mg_download_csr(nc, nc, ca.nnz, ca.rp, ca.ci, ca.va, &hc, &g_mg_d2h) != 0 ||
         (mB != nullptr && gcge_hip_mg_download_csr(nc, nc, cb.nnz, cb.rp, cb.ci, cb.va, &hb, &g_mg_d2h) != 0)) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
+    if (masked) {
+      GCGE_HIP_CHECK(hipMemcpy(cbox.data(), d_cbox, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+      g_mg_d2h += (long)((size_t)nc * sizeof(int));
+    }
     g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
-    GCGE_HIP_MAT* a = gcge_hip_mat_create(nc, nc, 0, hc.rowptr, hc.colidx, hc.val);
+    auto upload = [&](const GCGE_CSR& c) {
+      return masked ? gcge_hip_mat_create_grid(nc, c.rowptr, c.colidx, c.val, cdims[0], cdims[1], cdims[2], cbox.data())
+                    : gcge_hip_mat_create(nc, nc, 0, c.rowptr, c.colidx, c.val);
+    };
+    GCGE_HIP_MAT* a = upload(hc);
     GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
-    As.push_back(a);
-    if (B_array != nullptr && mB != nullptr) {
-      GCGE_HIP_MAT* b = gcge_hip_mat_create(nc, nc, 0, hb.rowptr, hb.colidx, hb.val);
+    built.As.push_back(a);
+    if (s.B_array != nullptr && mB != nullptr) {
+      GCGE_HIP_MAT* b = upload(hb);
       GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
-      Bs.push_back(b);
+      built.Bs.push_back(b);
     }
     g_mg_phase[MG_COARSE] += mg_now() - t;
     gcge_csr_free(&hb);
     gcge_csr_free(&hostA); hostA = hc;
     devcsr_free(fa); fa = ca;
     devcsr_free(fb); fb = cb;
-    ldims.push_back({dims[0], dims[1], dims[2]});
-    if (have_grid) { dims[0] = cdims[0]; dims[1] = cdims[1]; dims[2] = cdims[2]; }
+    if (own_box) hipFree(d_box);
+    d_box = d_cbox; own_box = masked;
+    built.dims.push_back({dims[0], dims[1], dims[2]});
+    if (kind != MG_GRAPH) { dims[0] = cdims[0]; dims[1] = cdims[1]; dims[2] = cdims[2]; }
   }
   t = mg_now();
   devcsr_free(fa); devcsr_free(fb);
   gcge_csr_free(&hostA);
-  if (!ok) {
-    for (GCGE_HIP_MAT* m : As) gcge_hip_mat_destroy(m);
-    for (GCGE_HIP_MAT* m : Bs) gcge_hip_mat_destroy(m);
-    for (GCGE_HIP_MAT* m : Ps) gcge_hip_mat_destroy(m);
-    if (getenv("GCGE_MG_TRACE") != nullptr) fprintf(stderr, "MultiGridCreate: a level is out of the device path's reach; built on the host\n");
-    return false;
-  }
-  const int L = (int)As.size() + 1;
-  ldims.push_back({dims[0], dims[1], dims[2]});
-  MgHold h;
-  *A_array = (void**)calloc(L, sizeof(void*));
-  *P_array = (void**)calloc(L > 1 ? L - 1 : 1, sizeof(void*));
-  if (B_array != nullptr) *B_array = (void**)calloc(L, sizeof(void*));
-  (*A_array)[0] = A;
-  if (B_array != nullptr) (*B_array)[0] = B;
-  for (int l = 1; l < L; ++l) {
-    (*A_array)[l] = As[l - 1]; h.owned.push_back(As[l - 1]);
-    if (B_array != nullptr && mB != nullptr) { (*B_array)[l] = Bs[l - 1]; h.owned.push_back(Bs[l - 1]); }
-  }
-  for (int l = 0; l + 1 < L; ++l) { (*P_array)[l] = Ps[l]; h.owned.push_back(Ps[l]); }
-  if (getenv("GCGE_MG_TRACE") != nullptr)
-    for (int l = 0; l < L; ++l) {
-      const GCGE_HIP_MAT* m = (const GCGE_HIP_MAT*)(*A_array)[l];
-      fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, grid %d x %d x %d, K1 form %s (device build)\n", l, m->nrows, m->nnz,
-              have_grid ? ldims[l][0] : 0, have_grid ? ldims[l][1] : 0, have_grid ? ldims[l][2] : 0, gcge_hip_mat_spmm_form(m));
-    }
-  h.A_array = *A_array;
-  g_mg.push_back(h);
-  *num_levels = L;
-  g_mg_phase[MG_OTHER] += mg_now() - t;
-  return true;
-}
-
-// ------------------------------------------------------------------------------------------------------------ masked grids
-// A handle that carries the geometry of a masked grid (gcge_hip_mat_geometry: the grid points inside a sphere in scan order, the
-// PARSEC matrices) is coarsened by the 2 x 2 x 2 cells of its bounding box at every level (gcge_mg_build_masked): the occupied cells
-// in scan order of the coarse box are a masked grid again.  device: the cells from the device-resident box array (mg_device.hip:
-// counts, two sums, members by binary search), Galerkin products and P / P^T as in the device path above — only the coarse levels
-// and their box arrays come back; host: gcge_mg_build_masked on the downloaded CSR.  Either way a coarse level goes up through
-// gcge_hip_mat_create_grid with ITS geometry: the rows stay as given (P / P^T match by construction) and the level carries its
-// geometry like a matrix the caller named one for.  Returns false with nothing left behind when a level is out of the kernels' reach.
-static int g_mg_masked_cells = 1;
-extern "C" void gcge_hip_multigrid_masked_cells(int on) { g_mg_masked_cells = on != 0; }
-extern "C" int gcge_hip_multigrid_get_masked_cells(void) { return g_mg_masked_cells; }
-static bool mg_is_masked_grid(const GCGE_HIP_MAT_* m) {
-  return g_mg_masked_cells && m->geom_kind != 0 && m->d_box != nullptr && (long)m->geom_dims[0] * m->geom_dims[1] * m->geom_dims[2] != (long)m->nrows;
-}
-static void mg_install_masked(void*** A_array, void*** B_array, void*** P_array, int* num_levels, void* A, void* B, bool withB,
-                              std::vector<GCGE_HIP_MAT*>& As, std::vector<GCGE_HIP_MAT*>& Bs, std::vector<GCGE_HIP_MAT*>& Ps, const char* how) {
-  const int L = (int)As.size() + 1;
-  MgHold h;
-  *A_array = (void**)calloc(L, sizeof(void*));
-  *P_array = (void**)calloc(L > 1 ? L - 1 : 1, sizeof(void*));
-  if (B_array != nullptr) *B_array = (void**)calloc(L, sizeof(void*));
-  (*A_array)[0] = A;
-  if (B_array != nullptr) (*B_array)[0] = B;
-  for (int l = 1; l < L; ++l) {
-    (*A_array)[l] = As[l - 1]; h.owned.push_back(As[l - 1]);
-    if (B_array != nullptr && withB) { (*B_array)[l] = Bs[l - 1]; h.owned.push_back(Bs[l - 1]); }
-  }
-  for (int l = 0; l + 1 < L; ++l) { (*P_array)[l] = Ps[l]; h.owned.push_back(Ps[l]); }
-  if (getenv("GCGE_MG_TRACE") != nullptr)
-    for (int l = 0; l < L; ++l) {
-      const GCGE_HIP_MAT* m = (const GCGE_HIP_MAT*)(*A_array)[l];
-      fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, masked grid in the box %d x %d x %d (%.1f%% of it), K1 form %s (%s build)\n", l, m->nrows,
-              m->nnz, m->geom_dims[0], m->geom_dims[1], m->geom_dims[2], 100.0 * m->nrows / ((double)m->geom_dims[0] * m->geom_dims[1] * m->geom_dims[2]),
-              gcge_hip_mat_spmm_form(m), how);
-    }
-  h.A_array = *A_array;
-  g_mg.push_back(h);
-  *num_levels = L;
-}
-
-static bool multigrid_create_masked_device(void*** A_array, void*** B_array, void*** P_array, int* num_levels, const GCGE_HIP_MAT_* mA,
-                                           const GCGE_HIP_MAT_* mB, void* A, void* B) {
-  double scale = 0.5, theta = 0.25; int min_rows = 64;
-  gcge_mg_get_defaults(&scale, &min_rows, &theta);
-  const int max_levels = *num_levels;
-  GCGE_HIP_CHECK(hipStreamSynchronize((hipStream_t)gcge_hip_stream()));
-  std::vector<GCGE_HIP_MAT*> As, Bs, Ps;
-  DevCsr fa{mA->nrows, mA->nnz, mA->d_rowptr, mA->d_colidx, mA->d_val, false};
-  DevCsr fb{0, 0, nullptr, nullptr, nullptr, false};
-  if (mB != nullptr) fb = DevCsr{mB->nrows, mB->nnz, mB->d_rowptr, mB->d_colidx, mB->d_val, false};
-  int dims[3] = {mA->geom_dims[0], mA->geom_dims[1], mA->geom_dims[2]};
-  int* d_box = mA->d_box; bool own_box = false;          // the current level's box array (level 0: the handle's)
-  bool ok = true;
-  double t;
-  for (int l = 0; l + 1 < max_levels; ++l) {
-    const int nf = fa.n;
-    if (nf <= min_rows) break;
-    t = mg_now();
-    int cdims[3] = {0, 0, 0};
-    int *d_agg = nullptr, *d_ptr = nullptr, *d_mem = nullptr, *d_cbox = nullptr;
-    GCGE_HIP_CHECK(hipMalloc(&d_agg, (size_t)nf * sizeof(int)));
-    GCGE_HIP_CHECK(hipMalloc(&d_mem, (size_t)nf * sizeof(int)));
-    const int nc = gcge_hip_mg_agg_masked_device(dims, d_box, nf, d_agg, d_mem, &d_ptr, &d_cbox, cdims, &g_mg_d2h);
-    g_mg_phase[MG_AGGREGATE] += mg_now() - t;
-    if (nc < 1 || (long)nc * 3 > (long)nf * 2) { hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); hipFree(d_cbox); break; }     // coarsening stalled
-    t = mg_now();
-    DevCsr ca{nc, 0, nullptr, nullptr, nullptr, true}, cb{0, 0, nullptr, nullptr, nullptr, false};
-    int rc = gcge_hip_mg_galerkin_device(nf, fa.rp, fa.ci, fa.va, d_agg, nc, d_ptr, d_mem, scale, &ca.rp, &ca.ci, &ca.va, &ca.nnz, &g_mg_d2h);
-    if (rc == 0 && mB != nullptr) {
-      cb = DevCsr{nc, 0, nullptr, nullptr, nullptr, true};
-      rc = gcge_hip_mg_galerkin_device(nf, fb.rp, fb.ci, fb.va, d_agg, nc, d_ptr, d_mem, 1.0, &cb.rp, &cb.ci, &cb.va, &cb.nnz, &g_mg_d2h);
-      if (rc != 0) cb.owned = false;
-    }
-    if (rc != 0) ca.owned = ca.rp != nullptr;
-    g_mg_phase[MG_GALERKIN] += mg_now() - t;
-    if (rc != 0) { devcsr_free(ca); devcsr_free(cb); hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); hipFree(d_cbox); ok = false; break; }
-    t = mg_now();
-    GCGE_HIP_MAT* p = gcge_hip_mat_create_rect_device(nf, nc, d_agg, d_ptr, d_mem);
-    GCGE_REQUIRE(p != nullptr, "MultiGridCreate: a prolongation from device arrays");
-    Ps.push_back(p);
-    hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem);
-    g_mg_phase[MG_OTHER] += mg_now() - t; t = mg_now();
-    GCGE_CSR hc, hb; memset(&hb, 0, sizeof hb);
-    std::vector<int> cbox((size_t)nc);
-    if (gcge_hip_mg_download_csr(nc, nc, ca.nnz, ca.rp, ca.ci, ca.va, &hc, &g_mg_d2h) != 0 ||
-        (mB != nullptr && gcge_hip_mg_download_csr(nc, nc, cb.nnz, cb.rp, cb.ci, cb.va, &hb, &g_mg_d2h) != 0)) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
-    GCGE_HIP_CHECK(hipMemcpy(cbox.data(), d_cbox, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
-    g_mg_d2h += (long)((size_t)nc * sizeof(int));
-    g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
-    GCGE_HIP_MAT* a = gcge_hip_mat_create_grid(nc, hc.rowptr, hc.colidx, hc.val, cdims[0], cdims[1], cdims[2], cbox.data());
-    GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
-    As.push_back(a);
-    if (B_array != nullptr && mB != nullptr) {
-      GCGE_HIP_MAT* b = gcge_hip_mat_create_grid(nc, hb.rowptr, hb.colidx, hb.val, cdims[0], cdims[1], cdims[2], cbox.data());
-      GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
-      Bs.push_back(b);
-    }
-    g_mg_phase[MG_COARSE] += mg_now() - t;
-    gcge_csr_free(&hb); gcge_csr_free(&hc);
-    devcsr_free(fa); fa = ca;
-    devcsr_free(fb); fb = cb;
-    if (own_box) hipFree(d_box);
-    d_box = d_cbox; own_box = true;
-    dims[0] = cdims[0]; dims[1] = cdims[1]; dims[2] = cdims[2];
-  }
-  t = mg_now();
-  devcsr_free(fa); devcsr_free(fb);
   if (own_box) hipFree(d_box);
   if (!ok) {
-    for (GCGE_HIP_MAT* m : As) gcge_hip_mat_destroy(m);
-    for (GCGE_HIP_MAT* m : Bs) gcge_hip_mat_destroy(m);
-    for (GCGE_HIP_MAT* m : Ps) gcge_hip_mat_destroy(m);
+    for (GCGE_HIP_MAT* m : built.As) gcge_hip_mat_destroy(m);
+    for (GCGE_HIP_MAT* m : built.Bs) gcge_hip_mat_destroy(m);
+    for (GCGE_HIP_MAT* m : built.Ps) gcge_hip_mat_destroy(m);
     if (getenv("GCGE_MG_TRACE") != nullptr) fprintf(stderr, "MultiGridCreate: a level is out of the device path's reach; built on the host\n");
     return false;
   }
-  mg_install_masked(A_array, B_array, P_array, num_levels, A, B, mB != nullptr, As, Bs, Ps, "device");
+  built.dims.push_back({dims[0], dims[1], dims[2]});
+  mg_install(s, built);
   g_mg_phase[MG_OTHER] += mg_now() - t;
   return true;
-}
-
-static void multigrid_create_masked_host(void*** A_array, void*** B_array, void*** P_array, int* num_levels, const GCGE_HIP_MAT_* mA,
-                                         const GCGE_HIP_MAT_* mB, void* A, void* B) {
-  double t = mg_now();
-  GCGE_CSR cA, cB; std::vector<int> rpA, ciA, rpB, ciB; std::vector<double> vaA, vaB;
-  download_csr(mA, &cA, rpA, ciA, vaA);
-  if (mB != nullptr) download_csr(mB, &cB, rpB, ciB, vaB);
-  g_mg_d2h += csr_bytes(mA->nrows, mA->nnz) + (mB != nullptr ? csr_bytes(mB->nrows, mB->nnz) : 0);
-  g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
-  GCGE_MG mg;
-  const int rc = gcge_mg_build_masked(&cA, mB != nullptr ? &cB : nullptr, mA->geom_dims, mA->h_box, *num_levels, 0, 0.0, &mg);
-  if (rc != 0) { fprintf(stderr, "MultiGridCreate: gcge_mg_build_masked failed (%d)\n", rc); abort(); }
-  g_mg_phase[MG_AGGREGATE] += mg_now() - t; t = mg_now();
-  std::vector<GCGE_HIP_MAT*> As, Bs, Ps;
-  for (int l = 1; l < mg.num_levels; ++l) {
-    const int* d = mg.dims[l]; const int* box = gcge_mg_level_box(&mg, l);
-    GCGE_HIP_MAT* a = gcge_hip_mat_create_grid(mg.A[l].nrows, mg.A[l].rowptr, mg.A[l].colidx, mg.A[l].val, d[0], d[1], d[2], box);
-    GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
-    As.push_back(a);
-    if (B_array != nullptr && mB != nullptr) {
-      GCGE_HIP_MAT* b = gcge_hip_mat_create_grid(mg.B[l].nrows, mg.B[l].rowptr, mg.B[l].colidx, mg.B[l].val, d[0], d[1], d[2], box);
-      GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
-      Bs.push_back(b);
-    }
-  }
-  for (int l = 0; l + 1 < mg.num_levels; ++l) {
-    GCGE_HIP_MAT* p = gcge_hip_mat_create_rect(mg.P[l].nrows, mg.P[l].ncols, mg.P[l].rowptr, mg.P[l].colidx, mg.P[l].val,
-                                               mg.PT[l].rowptr, mg.PT[l].colidx, mg.PT[l].val);
-    GCGE_REQUIRE(p != nullptr, "MultiGridCreate: upload of a prolongation");
-    Ps.push_back(p);
-  }
-  g_mg_phase[MG_COARSE] += mg_now() - t;
-  gcge_mg_free(&mg);
-  mg_install_masked(A_array, B_array, P_array, num_levels, A, B, mB != nullptr, As, Bs, Ps, "host");
 }
 
 static void mg_report(double t0) {
@@ -445,67 +385,15 @@ extern "C" void gcge_hip_multigrid_create(void*** A_array, void*** B_array, void
   GCGE_REQUIRE(mA != nullptr && mA->rect_ncols == 0 && num_levels != nullptr && *num_levels >= 1, "MultiGridCreate: a square matrix and a level count");
   for (int i = 0; i < MG_NPHASE; ++i) g_mg_phase[i] = 0.0;
   g_mg_d2h = 0;
-  if (mA->nghost > 0 || mA->part_world > 1) {
-    multigrid_create_slab(A_array, B_array, P_array, num_levels, mA, A, B);
-    g_mg_seconds = mg_now() - t0;
-    return;
+  const MgSlot s{A_array, B_array, P_array, num_levels, A, B};
+  const bool slab = mA->nghost > 0 || mA->part_world > 1;
+  if (slab) multigrid_create_slab(s, mA);
+  else {
+    const bool masked = mg_is_masked_grid(mA);         // a masked grid: the cells of its box at every level, on the device or on the host
+    if (g_mg_mode != 0 || !multigrid_create_device(s, mA, mB, masked)) multigrid_create_host(s, mA, mB, masked);
   }
-  if (mg_is_masked_grid(mA)) {         // a masked grid: the cells of its box at every level, on the device or on the host
-    if (g_mg_mode != 0 || !multigrid_create_masked_device(A_array, B_array, P_array, num_levels, mA, mB, A, B))
-      multigrid_create_masked_host(A_array, B_array, P_array, num_levels, mA, mB, A, B);
-    g_mg_seconds = mg_now() - t0;
-    mg_report(t0);
-    return;
-  }
-  if (g_mg_mode == 0 && multigrid_create_device(A_array, B_array, P_array, num_levels, mA, mB, A, B)) {
-    g_mg_seconds = mg_now() - t0;
-    mg_report(t0);
-    return;
-  }
-  double t = mg_now();
-  GCGE_CSR cA, cB; std::vector<int> rpA, ciA, rpB, ciB; std::vector<double> vaA, vaB;
-  download_csr(mA, &cA, rpA, ciA, vaA);
-  if (mB != nullptr) download_csr(mB, &cB, rpB, ciB, vaB);
-  g_mg_d2h += csr_bytes(mA->nrows, mA->nnz) + (mB != nullptr ? csr_bytes(mB->nrows, mB->nnz) : 0);
-  g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
-  GCGE_MG mg;
-  if (gcge_mg_build(&cA, mB != nullptr ? &cB : nullptr, *num_levels, 0, 0.0, &mg) != 0) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
-  g_mg_phase[MG_OTHER] += mg_now() - t; t = mg_now();
-  const int L = mg.num_levels;
-  MgHold h;
-  *A_array = (void**)calloc(L, sizeof(void*));
-  *P_array = (void**)calloc(L > 1 ? L - 1 : 1, sizeof(void*));
-  if (B_array != nullptr) *B_array = (void**)calloc(L, sizeof(void*));
-  (*A_array)[0] = A;
-  if (B_array != nullptr) (*B_array)[0] = B;
-  for (int l = 1; l < L; ++l) {
-    GCGE_HIP_MAT* a = gcge_hip_mat_create(mg.A[l].nrows, mg.A[l].nrows, 0, mg.A[l].rowptr, mg.A[l].colidx, mg.A[l].val);
-    GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
-    (*A_array)[l] = a; h.owned.push_back(a);
-    if (B_array != nullptr && mB != nullptr) {
-      GCGE_HIP_MAT* b = gcge_hip_mat_create(mg.B[l].nrows, mg.B[l].nrows, 0, mg.B[l].rowptr, mg.B[l].colidx, mg.B[l].val);
-      GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
-      (*B_array)[l] = b; h.owned.push_back(b);
-    }
-  }
-  for (int l = 0; l + 1 < L; ++l) {
-    GCGE_HIP_MAT* p = gcge_hip_mat_create_rect(mg.P[l].nrows, mg.P[l].ncols, mg.P[l].rowptr, mg.P[l].colidx, mg.P[l].val,
-                                               mg.PT[l].rowptr, mg.PT[l].colidx, mg.PT[l].val);
-    GCGE_REQUIRE(p != nullptr, "MultiGridCreate: upload of a prolongation");
-    (*P_array)[l] = p; h.owned.push_back(p);
-  }
-  g_mg_phase[MG_COARSE] += mg_now() - t;
-  if (getenv("GCGE_MG_TRACE") != nullptr) {
-    for (int l = 0; l < L; ++l)
-      fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, grid %d x %d x %d, K1 form %s\n", l, mg.A[l].nrows, (long)mg.A[l].nnz,
-              mg.dims[l][0], mg.dims[l][1], mg.dims[l][2], gcge_hip_mat_spmm_form((const GCGE_HIP_MAT*)(*A_array)[l]));
-  }
-  gcge_mg_free(&mg);
-  h.A_array = *A_array;
-  g_mg.push_back(h);
-  *num_levels = L;
   g_mg_seconds = mg_now() - t0;
-  mg_report(t0);
+  if (!slab) mg_report(t0);
 }
 
 extern "C" void gcge_hip_multigrid_destroy(void*** A_array, void*** B_array, void*** P_array, int* num_levels, struct OPS_* ops) {

@@ -344,83 +344,57 @@ const int *gcge_mg_level_box(const GCGE_MG *mg, int level)
 	return ((int**)((char*)mg->dims - (size_t)mg->box_levels * sizeof(int*)))[level];
 }
 
-int gcge_mg_build(const GCGE_CSR *A, const GCGE_CSR *B, int max_levels, int min_rows, double scale, GCGE_MG *mg)
+/* the arrays of a hierarchy of at most max_levels levels around level 0 = the caller's A (and B, NULL: none); with_box: room for the
+ * box array of every level, their pointers in front of dims ([box pointers][dims], found again through box_levels) */
+static int mg_alloc(GCGE_MG *mg, const GCGE_CSR *A, const GCGE_CSR *B, int max_levels, int with_box)
 {
-	int l, have_grid, dims[3] = {0, 0, 0};
+	char *blk;
 	memset(mg, 0, sizeof *mg);
-	if (max_levels < 1) max_levels = 1;
-	if (min_rows <= 0) min_rows = g_min_rows;
-	if (scale <= 0.0) scale = g_scale;
 	mg->A = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
 	mg->P = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
 	mg->PT = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	mg->dims = (int (*)[3])calloc(max_levels, sizeof(int[3]));
+	blk = (char*)calloc(max_levels, (with_box ? sizeof(int*) : 0) + sizeof(int[3]));
 	if (B != NULL) mg->B = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	if (!mg->A || !mg->P || !mg->PT || !mg->dims || (B != NULL && !mg->B)) { gcge_mg_free(mg); return -3; }
+	if (!mg->A || !mg->P || !mg->PT || !blk || (B != NULL && !mg->B)) { free(blk); gcge_mg_free(mg); return -3; }
+	mg->dims = (int (*)[3])(blk + (with_box ? (size_t)max_levels * sizeof(int*) : 0));
+	if (with_box) mg->box_levels = max_levels;
 	mg->A[0] = *A;
 	if (B != NULL) mg->B[0] = *B;
 	mg->num_levels = 1;
-	have_grid = gcge_mg_detect_grid(A, dims, NULL);
-	for (l = 0; l + 1 < max_levels; ++l) {
-		const GCGE_CSR *Af = &mg->A[l];
-		const int nf = Af->nrows;
-		int nc, cdims[3] = {0, 0, 0}, *agg, rc;
-		if (nf <= min_rows) break;
-		agg = (int*)malloc((size_t)nf * sizeof(int));
-		if (agg == NULL) { gcge_mg_free(mg); return -3; }
-		if (have_grid) {
-			mg->dims[l][0] = dims[0]; mg->dims[l][1] = dims[1]; mg->dims[l][2] = dims[2];
-			nc = gcge_mg_aggregate_grid(dims, agg, cdims);
-		} else {
-			nc = gcge_mg_aggregate_graph(Af, g_theta, agg);
-		}
-		if (nc < 1 || (long)nc * 3 > (long)nf * 2) { free(agg); break; }     /* coarsening stalled */
-		rc = gcge_mg_galerkin(Af, agg, nc, scale, &mg->A[l + 1]);
-		if (rc == 0 && B != NULL) rc = gcge_mg_galerkin(&mg->B[l], agg, nc, 1.0, &mg->B[l + 1]);
-		if (rc == 0) rc = gcge_mg_prolongation(agg, nf, nc, &mg->P[l], &mg->PT[l]);
-		free(agg);
-		if (rc != 0) { mg->num_levels = l + 2; gcge_mg_free(mg); return rc; }
-		mg->num_levels = l + 2;
-		if (have_grid) { dims[0] = cdims[0]; dims[1] = cdims[1]; dims[2] = cdims[2]; }
-	}
-	if (have_grid) { l = mg->num_levels - 1; mg->dims[l][0] = dims[0]; mg->dims[l][1] = dims[1]; mg->dims[l][2] = dims[2]; }
 	return 0;
 }
 
-/* a masked grid (the grid points inside a sphere, rows in scan order): gcge_mg_build with the 2 x 2 x 2 cells of the bounding box
- * at every level — a level's occupied cells, in scan order of the coarse box, are the next level's rows */
-int gcge_mg_build_masked(const GCGE_CSR *A, const GCGE_CSR *B, const int dims[3], const int *box_of_row, int max_levels, int min_rows,
+/* gcge_mg_build (box_of_row == NULL: a detected grid, or the graph with theta = g_theta; dims recorded on a grid only) and
+ * gcge_mg_build_masked (the cells of the box `dims` at every level, every level's dims and box array recorded) */
+static int mg_build_levels(const GCGE_CSR *A, const GCGE_CSR *B, const int *dims, const int *box_of_row, int max_levels, int min_rows,
 		double scale, GCGE_MG *mg)
 {
-	int l, d[3] = {dims[0], dims[1], dims[2]}, **box;
-	char *blk;
-	memset(mg, 0, sizeof *mg);
+	const int masked = box_of_row != NULL;
+	int l, have_grid = masked, d[3] = {0, 0, 0}, **box = NULL, rc;
 	if (max_levels < 1) max_levels = 1;
 	if (min_rows <= 0) min_rows = g_min_rows;
 	if (scale <= 0.0) scale = g_scale;
-	mg->A = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	mg->P = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	mg->PT = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	blk = (char*)calloc(max_levels, sizeof(int*) + sizeof(int[3]));       /* [box pointers][dims] */
-	if (B != NULL) mg->B = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	if (!mg->A || !mg->P || !mg->PT || !blk || (B != NULL && !mg->B)) { free(blk); gcge_mg_free(mg); return -3; }
-	box = (int**)blk; mg->dims = (int (*)[3])(blk + (size_t)max_levels * sizeof(int*)); mg->box_levels = max_levels;
-	mg->A[0] = *A;
-	if (B != NULL) mg->B[0] = *B;
-	mg->num_levels = 1;
-	box[0] = (int*)malloc((size_t)(A->nrows > 0 ? A->nrows : 1) * sizeof(int));
-	if (box[0] == NULL) { gcge_mg_free(mg); return -3; }
-	memcpy(box[0], box_of_row, (size_t)A->nrows * sizeof(int));
-	mg->dims[0][0] = d[0]; mg->dims[0][1] = d[1]; mg->dims[0][2] = d[2];
+	if ((rc = mg_alloc(mg, A, B, max_levels, masked)) != 0) return rc;
+	if (masked) {
+		box = (int**)((char*)mg->dims - (size_t)max_levels * sizeof(int*));
+		box[0] = (int*)malloc((size_t)(A->nrows > 0 ? A->nrows : 1) * sizeof(int));
+		if (box[0] == NULL) { gcge_mg_free(mg); return -3; }
+		memcpy(box[0], box_of_row, (size_t)A->nrows * sizeof(int));
+		memcpy(d, dims, sizeof d);
+	} else have_grid = gcge_mg_detect_grid(A, d, NULL);
 	for (l = 0; l + 1 < max_levels; ++l) {
 		const GCGE_CSR *Af = &mg->A[l];
 		const int nf = Af->nrows;
-		int nc, cdims[3] = {0, 0, 0}, *agg, *cbox, rc;
-		if (nf <= min_rows && l > 0) break;
-		agg = (int*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(int)); cbox = (int*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(int));
-		if (agg == NULL || cbox == NULL) { free(agg); free(cbox); gcge_mg_free(mg); return -3; }
-		nc = gcge_mg_aggregate_masked(d, box[l], nf, agg, cdims, cbox);
-		if (nc < 0) { free(agg); free(cbox); gcge_mg_free(mg); return nc; }             /* (level 0 only: the caller's geometry) */
+		int nc, cdims[3] = {0, 0, 0}, *agg, *cbox = NULL;
+		if (have_grid) memcpy(mg->dims[l], d, sizeof d);
+		if (nf <= min_rows && !(masked && l == 0)) break;          /* (a masked level 0 is aggregated whatever its size: the caller's geometry) */
+		agg = (int*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(int));
+		if (masked) cbox = (int*)malloc((size_t)(nf > 0 ? nf : 1) * sizeof(int));
+		if (agg == NULL || (masked && cbox == NULL)) { free(agg); free(cbox); gcge_mg_free(mg); return -3; }
+		if (masked) nc = gcge_mg_aggregate_masked(d, box[l], nf, agg, cdims, cbox);
+		else if (have_grid) nc = gcge_mg_aggregate_grid(d, agg, cdims);
+		else nc = gcge_mg_aggregate_graph(Af, g_theta, agg);
+		if (masked && nc < 0) { free(agg); free(cbox); gcge_mg_free(mg); return nc; }             /* (level 0 only: -2 / -3) */
 		if (nf <= min_rows || nc < 1 || (long)nc * 3 > (long)nf * 2) { free(agg); free(cbox); break; }     /* small enough / coarsening stalled */
 		rc = gcge_mg_galerkin(Af, agg, nc, scale, &mg->A[l + 1]);
 		if (rc == 0 && B != NULL) rc = gcge_mg_galerkin(&mg->B[l], agg, nc, 1.0, &mg->B[l + 1]);
@@ -428,11 +402,24 @@ int gcge_mg_build_masked(const GCGE_CSR *A, const GCGE_CSR *B, const int dims[3]
 		free(agg);
 		mg->num_levels = l + 2;
 		if (rc != 0) { free(cbox); gcge_mg_free(mg); return rc; }
-		box[l + 1] = cbox;                                                 /* (nf ints allocated, nc used) */
-		d[0] = cdims[0]; d[1] = cdims[1]; d[2] = cdims[2];
-		mg->dims[l + 1][0] = d[0]; mg->dims[l + 1][1] = d[1]; mg->dims[l + 1][2] = d[2];
+		if (masked) box[l + 1] = cbox;                                     /* (nf ints allocated, nc used) */
+		if (have_grid) memcpy(d, cdims, sizeof d);
 	}
+	if (have_grid) memcpy(mg->dims[mg->num_levels - 1], d, sizeof d);
 	return 0;
+}
+
+int gcge_mg_build(const GCGE_CSR *A, const GCGE_CSR *B, int max_levels, int min_rows, double scale, GCGE_MG *mg)
+{
+	return mg_build_levels(A, B, NULL, NULL, max_levels, min_rows, scale, mg);
+}
+
+/* a masked grid (the grid points inside a sphere, rows in scan order): gcge_mg_build with the 2 x 2 x 2 cells of the bounding box
+ * at every level — a level's occupied cells, in scan order of the coarse box, are the next level's rows */
+int gcge_mg_build_masked(const GCGE_CSR *A, const GCGE_CSR *B, const int dims[3], const int *box_of_row, int max_levels, int min_rows,
+		double scale, GCGE_MG *mg)
+{
+	return mg_build_levels(A, B, dims, box_of_row, max_levels, min_rows, scale, mg);
 }
 
 /* ---------------------------------------------------------------- row slabs (one rank per GPU)
@@ -483,14 +470,10 @@ int gcge_mg_build_slab(const GCGE_CSR *A, const int dims[3], const long *part, i
 	if (max_levels < 1) max_levels = 1;
 	if (scale <= 0.0) scale = g_scale;
 	if (A->row_begin != part[rank] || A->nrows != (int)(part[rank + 1] - part[rank]) || (long)d[0] * d[1] * d[2] != part[world]) return -2;
-	mg->A = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	mg->P = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	mg->PT = (GCGE_CSR*)calloc(max_levels, sizeof(GCGE_CSR));
-	mg->dims = (int (*)[3])calloc(max_levels, sizeof(int[3]));
+	if (mg_alloc(mg, A, NULL, max_levels, 0) != 0) return -3;
 	parts = (long*)calloc((size_t)max_levels * (world + 1), sizeof(long));
 	zf = (long*)calloc(2 * ((size_t)world + 1), sizeof(long)); zc = zf ? zf + world + 1 : NULL;
-	if (!mg->A || !mg->P || !mg->PT || !mg->dims || !parts || !zf) { gcge_mg_free(mg); free(parts); free(zf); return -3; }
-	mg->A[0] = *A; mg->num_levels = 1;
+	if (!parts || !zf) { gcge_mg_free(mg); free(parts); free(zf); return -3; }
 	memcpy(parts, part, (size_t)(world + 1) * sizeof(long));
 	mg->dims[0][0] = d[0]; mg->dims[0][1] = d[1]; mg->dims[0][2] = d[2];
 	for (l = 0; l + 1 < max_levels; ++l) {

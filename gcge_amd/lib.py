@@ -19,6 +19,12 @@ class CSR(C.Structure):
                 ("colidx", C.POINTER(C.c_int)), ("val", C.POINTER(C.c_double))]
 
 
+class MG(C.Structure):
+    """GCGE_MG (include/gcge_multigrid.h)."""
+    _fields_ = [("num_levels", C.c_int), ("box_levels", C.c_int), ("A", C.POINTER(CSR)), ("B", C.POINTER(CSR)),
+                ("P", C.POINTER(CSR)), ("PT", C.POINTER(CSR)), ("dims", C.POINTER(C.c_int * 3))]
+
+
 class Timing(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("initX", "checkconv", "compP", "compRR", "rr_matW",
                                           "dsyevx", "compRV", "compW", "linsol", "compX", "total")]
@@ -88,6 +94,13 @@ def csr_arrays(A):
     return (np.ctypeslib.as_array(A.rowptr, (n + 1,)).copy(),
             np.ctypeslib.as_array(A.colidx, (max(nnz, 1),))[:nnz].copy(),
             np.ctypeslib.as_array(A.val, (max(nnz, 1),))[:nnz].copy())
+
+
+def csr_to_scipy(A):
+    """A host CSR struct as a scipy matrix (copies)."""
+    import scipy.sparse as sp
+    rp, ci, va = csr_arrays(A)
+    return sp.csr_matrix((va, ci, rp), shape=(A.nrows, A.ncols))
 
 
 def _take_csr(out):

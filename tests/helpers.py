@@ -7,7 +7,7 @@ import os
 import numpy as np
 
 import pyoracle as po
-from gcge_amd.lib import host_lib, make_problem, run_gcg
+from gcge_amd.lib import CSR, MG, csr_to_scipy, host_lib, make_problem, run_gcg
 from gcge_amd.ops_struct import OpsTable
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -29,19 +29,8 @@ def test_matrix(kind, size, **kw):
     return make_problem(kind, size, **kw)
 
 
-def csr_to_scipy(A):
-    import scipy.sparse as sp
-    n = A.nrows
-    rp = np.ctypeslib.as_array(A.rowptr, shape=(n + 1,)).copy()
-    ci = np.ctypeslib.as_array(A.colidx, shape=(int(A.nnz),)).copy()
-    va = np.ctypeslib.as_array(A.val, shape=(int(A.nnz),)).copy()
-    return sp.csr_matrix((va, ci, rp), shape=(n, A.ncols))
-
-
 def csr_from_scipy(S):
     """scipy sparse matrix -> (CSR struct, keepalive arrays) with ascending column indices inside every row."""
-    import ctypes as C
-    from gcge_amd.lib import CSR
     S = S.tocsr()
     S.sort_indices()
     rp = np.ascontiguousarray(S.indptr, dtype=np.int32)
@@ -231,27 +220,15 @@ def block_amg_solve(backend, A_handles, P_handles, b, x0, max_iter, rate, tol, t
 def mg_hierarchy(A, max_levels, scale=0.0, min_rows=0, B=None):
     """The aggregation hierarchy of include/gcge_multigrid.h (csrc/host/multigrid.c) of a CSR struct as scipy matrices:
     {"A": [...], "P": [...], "PT": [...], "dims": [...], "B": [...] or None}."""
-    import scipy.sparse as sp
-    from gcge_amd.lib import CSR
     h = host_lib()
-
-    class MG(C.Structure):
-        _fields_ = [("num_levels", C.c_int), ("A", C.POINTER(CSR)), ("B", C.POINTER(CSR)), ("P", C.POINTER(CSR)),
-                    ("PT", C.POINTER(CSR)), ("dims", C.POINTER(C.c_int * 3))]
     mg = MG()
     h.gcge_mg_build.argtypes = [C.POINTER(CSR), C.POINTER(CSR), C.c_int, C.c_int, C.c_double, C.POINTER(MG)]
     rc = h.gcge_mg_build(C.byref(A), C.byref(B) if B is not None else None, max_levels, min_rows, scale, C.byref(mg))
     assert rc == 0, rc
-
-    def to_sp(c):
-        rp = np.ctypeslib.as_array(c.rowptr, shape=(c.nrows + 1,)).copy()
-        ci = np.ctypeslib.as_array(c.colidx, shape=(max(1, int(c.nnz)),))[:int(c.nnz)].copy()
-        va = np.ctypeslib.as_array(c.val, shape=(max(1, int(c.nnz)),))[:int(c.nnz)].copy()
-        return sp.csr_matrix((va, ci, rp), shape=(c.nrows, c.ncols))
     L = mg.num_levels
-    out = {"A": [to_sp(mg.A[lev]) for lev in range(L)], "P": [to_sp(mg.P[lev]) for lev in range(L - 1)],
-           "PT": [to_sp(mg.PT[lev]) for lev in range(L - 1)], "dims": [tuple(mg.dims[lev]) for lev in range(L)],
-           "B": [to_sp(mg.B[lev]) for lev in range(L)] if B is not None else None}
+    out = {"A": [csr_to_scipy(mg.A[lev]) for lev in range(L)], "P": [csr_to_scipy(mg.P[lev]) for lev in range(L - 1)],
+           "PT": [csr_to_scipy(mg.PT[lev]) for lev in range(L - 1)], "dims": [tuple(mg.dims[lev]) for lev in range(L)],
+           "B": [csr_to_scipy(mg.B[lev]) for lev in range(L)] if B is not None else None}
     h.gcge_mg_free.argtypes = [C.POINTER(MG)]
     h.gcge_mg_free(C.byref(mg))
     return out
@@ -260,13 +237,7 @@ def mg_hierarchy(A, max_levels, scale=0.0, min_rows=0, B=None):
 def mg_hierarchy_slab(A_slab, dims, part, rank, max_levels, scale=0.0):
     """gcge_mg_build_slab (csrc/host/multigrid.c) of one row slab with GLOBAL columns: {"A": [scipy slabs with global columns],
     "P": [...local...], "part": [[...] per level], "dims": [...]}."""
-    import scipy.sparse as sp
-    from gcge_amd.lib import CSR
     h = host_lib()
-
-    class MG(C.Structure):
-        _fields_ = [("num_levels", C.c_int), ("A", C.POINTER(CSR)), ("B", C.POINTER(CSR)), ("P", C.POINTER(CSR)),
-                    ("PT", C.POINTER(CSR)), ("dims", C.POINTER(C.c_int * 3))]
     mg = MG()
     world = len(part) - 1
     parr = (C.c_long * (world + 1))(*[int(v) for v in part])
@@ -276,14 +247,8 @@ def mg_hierarchy_slab(A_slab, dims, part, rank, max_levels, scale=0.0):
                                      C.POINTER(MG), C.POINTER(C.POINTER(C.c_long))]
     rc = h.gcge_mg_build_slab(C.byref(A_slab), C.byref(d), parr, rank, world, max_levels, scale, C.byref(mg), C.byref(pl))
     assert rc == 0, rc
-
-    def to_sp(c):
-        rp = np.ctypeslib.as_array(c.rowptr, shape=(c.nrows + 1,)).copy()
-        ci = np.ctypeslib.as_array(c.colidx, shape=(max(1, int(c.nnz)),))[:int(c.nnz)].copy()
-        va = np.ctypeslib.as_array(c.val, shape=(max(1, int(c.nnz)),))[:int(c.nnz)].copy()
-        return sp.csr_matrix((va, ci, rp), shape=(c.nrows, c.ncols))
     L = mg.num_levels
-    out = {"A": [to_sp(mg.A[lev]) for lev in range(L)], "P": [to_sp(mg.P[lev]) for lev in range(L - 1)],
+    out = {"A": [csr_to_scipy(mg.A[lev]) for lev in range(L)], "P": [csr_to_scipy(mg.P[lev]) for lev in range(L - 1)],
            "part": [[pl[lev * (world + 1) + r] for r in range(world + 1)] for lev in range(L)],
            "dims": [tuple(mg.dims[lev]) for lev in range(L)]}
     h.gcge_mg_free.argtypes = [C.POINTER(MG)]

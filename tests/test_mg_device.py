@@ -248,3 +248,50 @@ def test_device_build_does_not_download_the_fine_matrix(hip):
     assert got[1][1] >= fine
     assert got[0][2]["galerkin"] > 0.0 and got[0][2]["detect"] > 0.0
     hip.free_matrix(mA)
+
+
+# ---------------------------------------------------------------------------------------------- 5. a level out of the device build's reach
+def chain_with_hubs(case, n=2400):
+    """tridiag(-1, 2, -1) plus symmetric -1e-3 couplings of hub rows to far columns"""
+    import scipy.sparse as sp
+    hubs = {0: range(2, n, 2)} if case == "first" else {0: range(8, n, 8), 2: range(12, n, 8)}
+    r = np.concatenate([np.full(len(c), h) for h, c in hubs.items()])
+    c = np.concatenate([np.asarray(c) for c in hubs.values()])
+    far = sp.coo_matrix((np.full(len(r), -1e-3), (r, c)), shape=(n, n))
+    return csr_from_scipy(sp.diags([-1.0, 2.0, -1.0], [-1, 0, 1], shape=(n, n)) + far + far.T)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case,longest", [("first", (1201, 1200, 600)), ("second", (302, 302, 600))])
+def test_device_build_falls_back_to_the_host_and_leaves_nothing_behind(hip, case, longest):
+    """A coarse row of more than 512 distinct columns is out of the Galerkin kernel's reach (its overflow flag: a designed return):
+    "first" fails at the first coarse level with nothing built, "second" at the second with one level to free.  Either way
+    MultiGridCreate gives the host build's hierarchy, and again on a second call."""
+    from helpers import mg_hierarchy
+    A, keep = chain_with_hubs(case)
+    ref = mg_hierarchy(A, 4)
+    assert ref["dims"][0] == (2400, 1, 1) and [m.shape[0] for m in ref["A"]] == [2400, 1200, 600, 300]
+    assert tuple(int(np.diff(m.indptr).max()) for m in ref["A"][:3]) == longest
+    fine = (A.nrows + 1) * 4 + int(A.nnz) * 12
+    mA = hip.matrix(A)
+    snaps = {}
+    try:
+        for mode in (0, 1):
+            multigrid_mode(mode)
+            snaps[mode] = hierarchy_snapshot(hip, mA, None, 4)
+            if mode == 0:
+                assert multigrid_stats()[1] >= fine                   # the host build ran
+                assert hip_lib().gcge_hip_multigrid_get_mode() == 0
+                snaps["again"] = hierarchy_snapshot(hip, mA, None, 4)
+    finally:
+        multigrid_mode(0)
+    d = snaps[0]
+    assert d["L"] == 4
+    for other in (snaps[1], snaps["again"]):
+        assert d["L"] == other["L"]
+        assert d["form"] == other["form"] and d["order"] == other["order"]
+        for key in ("A", "B", "P", "PT"):
+            assert len(d[key]) == len(other[key])
+            for x, y in zip(d[key], other[key]):
+                same_csr(x, y)
+    hip.free_matrix(mA)

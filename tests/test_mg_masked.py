@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from gcge_amd.lib import CSR, ball_geometry, host_lib, make_problem
+from gcge_amd.lib import CSR, MG, ball_geometry, host_lib, make_problem
 from helpers import csr_from_scipy, csr_to_scipy, load_golden, mg_hierarchy, uniform
 
 BALL16 = dict(K=6, R0=1.5, R1=2.0, seed=12345)          # the golden case sio2ball_16_nev10
@@ -78,15 +78,8 @@ def np_members(agg, nc):
     return ptr, mem
 
 
-class MG(C.Structure):
-    """GCGE_MG (include/gcge_multigrid.h)"""
-    _fields_ = [("num_levels", C.c_int), ("box_levels", C.c_int), ("A", C.POINTER(CSR)), ("B", C.POINTER(CSR)), ("P", C.POINTER(CSR)),
-                ("PT", C.POINTER(CSR)), ("dims", C.POINTER(C.c_int * 3))]
-
-
 def host_hierarchy(A, B, dims, box, max_levels):
     """gcge_mg_build_masked as scipy matrices and numpy box arrays"""
-    import scipy.sparse as sp
     h = host_lib()
     ip = C.POINTER(C.c_int)
     h.gcge_mg_build_masked.argtypes = [C.POINTER(CSR), C.POINTER(CSR), C.POINTER(C.c_int * 3), ip, C.c_int, C.c_int, C.c_double, C.POINTER(MG)]
@@ -100,13 +93,9 @@ def host_hierarchy(A, B, dims, box, max_levels):
     if rc != 0:
         return rc
 
-    def to_sp(c):
-        nnz = int(c.nnz)
-        return sp.csr_matrix((np.ctypeslib.as_array(c.val, (max(1, nnz),))[:nnz].copy(), np.ctypeslib.as_array(c.colidx, (max(1, nnz),))[:nnz].copy(),
-                              np.ctypeslib.as_array(c.rowptr, (c.nrows + 1,)).copy()), shape=(c.nrows, c.ncols))
     L = mg.num_levels
-    out = {"A": [to_sp(mg.A[l]) for l in range(L)], "B": [to_sp(mg.B[l]) for l in range(L)] if B is not None else [],
-           "P": [to_sp(mg.P[l]) for l in range(L - 1)], "PT": [to_sp(mg.PT[l]) for l in range(L - 1)],
+    out = {"A": [csr_to_scipy(mg.A[l]) for l in range(L)], "B": [csr_to_scipy(mg.B[l]) for l in range(L)] if B is not None else [],
+           "P": [csr_to_scipy(mg.P[l]) for l in range(L - 1)], "PT": [csr_to_scipy(mg.PT[l]) for l in range(L - 1)],
            "dims": [tuple(mg.dims[l]) for l in range(L)],
            "box": [np.ctypeslib.as_array(h.gcge_mg_level_box(C.byref(mg), l), (mg.A[l].nrows,)).copy() for l in range(L)]}
     assert not h.gcge_mg_level_box(C.byref(mg), L)

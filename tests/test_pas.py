@@ -10,7 +10,7 @@ import pytest
 import scipy.sparse as sp
 
 import pyoracle as po
-from gcge_amd.lib import CSR, host_lib, make_problem, run_gcg, run_pas
+from gcge_amd.lib import CSR, MG, host_lib, make_problem, run_gcg, run_pas
 from gcge_amd.ops_struct import OPS, OpsTable
 from helpers import OracleBackend, csr_from_scipy, lap3d_exact, uniform
 
@@ -124,9 +124,6 @@ class Setup:
 
     def apply_dense_rows(self):
         """rows of level H, from the host builder the back-ends' MultiGridCreate runs (gcge_mg_build, same defaults)"""
-        class MG(C.Structure):
-            _fields_ = [("num_levels", C.c_int), ("A", C.POINTER(CSR)), ("B", C.POINTER(CSR)), ("P", C.POINTER(CSR)),
-                        ("PT", C.POINTER(CSR)), ("dims", C.c_void_p)]
         h = host_lib()
         # own prototypes: other test modules bind these symbols with their own argtypes
         build = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p)(

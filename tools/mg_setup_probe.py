@@ -5,12 +5,11 @@ total set-up time, for one problem of the existing generators.
   python tools/mg_setup_probe.py ball <G> <K> [levels] [solve]
 
 ball: the masked grid of BASELINE config 5 (the ball in the G^3 box, K atoms, R0 = 2.0, R1 = 5.0 as in bench.py --config c5), its
-geometry named; each mode is run with the cells of the box and with the graph branch (gcge_hip_multigrid_masked_cells), and the rows
-and K1 form of every level are listed.  With `solve`: one GCG solve (nev 10, block 64 columns of W) with BlockAMG over each of the
+geometry named; each mode is run with the cells of the box and with the graph branch (gcge_hip_multigrid_masked_cells).  With `solve`: one GCG solve (nev 10, block 64 columns of W) with BlockAMG over each of the
 two hierarchies, 8 / 24 smoothing steps: outer iterations and seconds.
 
 Mode 0 builds the hierarchy on the device (csrc/hip/mg_device.hip), mode 1 on the host (csrc/host/multigrid.c); both give the same
-hierarchy.  Each mode is timed on a fresh MultiGridCreate after one warm-up call."""
+hierarchy.  Each mode is timed on a fresh MultiGridCreate after one warm-up call; the rows, K1 form and row order of its levels are listed."""
 import ctypes as C
 import os
 import sys
@@ -35,6 +34,8 @@ def main():
     g.gcge_hip_mat_spmm_form.restype = C.c_char_p
     g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
     g.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
+    g.gcge_hip_mat_row_order.restype = C.c_char_p
+    g.gcge_hip_mat_row_order.argtypes = [C.c_void_p]
     if ball:
         A, B = make_problem("sio2ball", size, K=int(sys.argv[3]), R0=2.0, R1=5.0, seed=12345)
         t = time.perf_counter()
@@ -62,9 +63,10 @@ def main():
                 create(C.byref(A_arr), bref, C.byref(P_arr), C.byref(nl), mA, mB, hip.ops_handle)
                 total = time.perf_counter() - t
                 secs, d2h = multigrid_stats()
-                if ball and rep == 1 and mode == 0:
+                if rep == 1:
                     for lev, a in enumerate(C.cast(A_arr, C.POINTER(C.c_void_p * nl.value)).contents):
-                        print("  level %d: %d rows, K1 form %s" % (lev, g.gcge_hip_mat_nrows(a), g.gcge_hip_mat_spmm_form(a).decode()))
+                        print("  level %d: %d rows, K1 form %s, row order %s" % (lev, g.gcge_hip_mat_nrows(a), g.gcge_hip_mat_spmm_form(a).decode(),
+                                                                                g.gcge_hip_mat_row_order(a).decode()))
                 destroy(C.byref(A_arr), bref, C.byref(P_arr), C.byref(nl), hip.ops_handle)
             print("mode %d (%s): %d levels, %.3f s  [%s]  device->host %.1f MB (%.1f%% of the fine CSR)" % (
                 mode, "device" if mode == 0 else "host", nl.value, total, "  ".join("%s %.3f" % kv for kv in secs.items()), d2h / 1e6, 100.0 * d2h / fine))
