@@ -159,6 +159,8 @@ extern "C" int gcge_hip_dense_profile_report(char* buf, int len) {
 // Anything else flushes the held-back scaling first.  The speculative Gram column is served only to the IMMEDIATELY following data call (epoch
 // check) on the same block and column range; every entry point that touches block data goes through enter().
 static unsigned long g_epoch = 0;
+// the squared column norms of the panel the last MultiVecLinearComb wrote, where it summed them (GCGE_BACKEND.panel_norms_sq)
+static double* g_norms_d = nullptr; static GcgeHipMV* g_norms_owner = nullptr; static int g_norms_c0 = 0, g_norms_c1 = 0; static unsigned long g_norms_epoch = 0;
 static GcgeHipMV* g_pend_owner = nullptr;   // the one block with a held-back scaling (its pend_col >= 0), or NULL
 static int g_mgs_fuse = 1;
 extern "C" void gcge_hip_set_mgs_fusion(int on) { g_mgs_fuse = on; }
@@ -290,6 +292,7 @@ static void HIP_MultiVecCreateByMultiVec(void*** mv, int num_vec, void** src, st
 static void HIP_MultiVecDestroy(void*** mv, int num_vec, struct OPS_* ops) {
   GcgeHipMV* v = *(GcgeHipMV**)mv;
   enter();
+  if (v != nullptr && v == g_norms_owner) g_norms_owner = nullptr;
   if (v) { delete v->spec_dots; gcge_hip_pool_free(v->d, v->bytes); gcge_hip_perm_release(v->perm); free(v); }
   *mv = nullptr;
 }
@@ -425,26 +428,32 @@ static void HIP_MultiVecAxpby(double alpha, void** x, double beta, void** y, int
 
 // GCGE_BACKEND.block_moves (include/gcge_ops.h): X, the W start vectors and b of an outer iteration in one sweep over the rows of
 // ritz[:, x0..x1) (vec_kernels.hip: block_moves_kernel).  0 with nothing touched for what the kernel does not take: rows wider than
-// 512 columns, blocks in different row orders, V as source or as b, runs outside [x0, x1) or targets outside their blocks.
+// 512 columns, blocks in different row orders, V as b, V as source with an X move asked for, runs outside [x0, x1) or targets outside
+// their blocks.  V as the source of the runs alone (ritz == V, x0 == x1: the Ritz vectors already live in V): the sweep walks the
+// column pairs from the first run to the last and writes the W start vectors and b only.
 static int HIP_BlockMoves(void** ritz, void** V, int x0, int x1, const int* runs, int w0, void** b, int b0, const double* scale, struct OPS_* ops) {
   (void)ops;
   GcgeHipMV *vr = (GcgeHipMV*)ritz, *vv = (GcgeHipMV*)V, *vb = (GcgeHipMV*)b;
-  if (vr == nullptr || vv == nullptr || vr == vv || vb == vv || runs == nullptr || x0 < 0 || x1 <= x0) return 0;
-  if (x1 > vr->ncols || x1 > vv->ncols || vr->nrows != vv->nrows || vr->nrows <= 0 || real_perm(vr->perm) != real_perm(vv->perm)) return 0;
+  if (vr == nullptr || vv == nullptr || vb == vv || runs == nullptr || x0 < 0) return 0;
+  const bool from_v = vr == vv;
+  if (from_v ? (x1 != x0 || runs[0] < 1) : (x1 <= x0)) return 0;
+  const int s0 = from_v ? runs[1] : x0, s1 = from_v ? runs[2 * runs[0]] : x1;      // the source columns the sweep walks
+  if (s0 < 0 || s1 <= s0) return 0;
+  if (s1 > vr->ncols || s1 > vv->ncols || vr->nrows != vv->nrows || vr->nrows <= 0 || real_perm(vr->perm) != real_perm(vv->perm)) return 0;
   if ((vr->ld & 1) || (vv->ld & 1) || ((uintptr_t)vr->d & 15) || ((uintptr_t)vv->d & 15)) return 0;
   if (vb != nullptr && (scale == nullptr || vb->nrows != vr->nrows || (vb->ld & 1) || ((uintptr_t)vb->d & 15) || real_perm(vb->perm) != real_perm(vr->perm))) return 0;
-  const int c0 = x0 & ~1, c1 = (x1 + 1) & ~1, npairs = (c1 - c0) / 2;
+  const int c0 = s0 & ~1, c1 = (s1 + 1) & ~1, npairs = (c1 - c0) / 2;
   if (npairs > 256 || c1 > vr->ld) return 0;
-  int total = 0, prev = x0;
+  int total = 0, prev = s0;
   for (int i = 0; i < runs[0]; ++i) {
     const int lo = runs[2 * i + 1], hi = runs[2 * i + 2];
-    if (lo < prev || hi <= lo || hi > x1) return 0;
+    if (lo < prev || hi <= lo || hi > s1) return 0;
     total += hi - lo; prev = hi;
   }
-  if (w0 < x1 || w0 + total > vv->ncols) return 0;
+  if (w0 < s1 || w0 + total > vv->ncols) return 0;
   if (vb != nullptr && (b0 < 0 || b0 + total > vb->ncols)) return 0;
   enter();
-  SlotTimer tm_("block moves (X, W start, b)", x1 - x0);
+  SlotTimer tm_(from_v ? "block moves (W start, b)" : "block moves (X, W start, b)", s1 - s0);
   // staging: [0, total) the factors, behind them the 2 npairs positions in the packed runs as ints
   const size_t nd = (size_t)total + (size_t)npairs;
   double* dd = gcge_hip_stage_d(nd);
@@ -457,7 +466,7 @@ static int HIP_BlockMoves(void** ritz, void** V, int x0, int x1, const int* runs
   for (int k = 0; k < total; ++k) hs[k] = vb != nullptr ? scale[k] : 0.0;
   GCGE_HIP_CHECK(hipMemcpyAsync(dd, hs, nd * sizeof(double), hipMemcpyHostToDevice, g_stream));
   GCGE_REQUIRE(gcge_hip_block_moves(vr->nrows, vr->d + c0, vr->ld, vv->d, vv->ld, vb != nullptr ? vb->d : nullptr, vb != nullptr ? vb->ld : 0, c0, npairs,
-                                    x0, x1, (const int*)(dd + total), dd, w0, b0, g_stream) == 0, "block moves: kernel launch");
+                                    from_v ? 0 : x0, from_v ? 0 : x1, (const int*)(dd + total), dd, w0, b0, g_stream) == 0, "block moves: kernel launch");
   return 1;
 }
 extern "C" int gcge_hip_block_moves_mv(void** ritz, void** V, int x0, int x1, const int* runs, int w0, void** b, int b0, const double* scale) {
@@ -541,10 +550,65 @@ static void HIP_MultiVecLinearComb(void** x, void** y, int is_vec, int* start, i
     // (y == x with the output columns inside the input range: the rows of X just read hold it)
     const bool inplace_ = vx == vy && start[1] + j0 >= start[0] && start[1] + j0 + mp <= end[0];
     DenseProfScope prof_(1, vy->nrows, k, mp, 8.0 * (double)vy->nrows * (k + mp + ((beta != nullptr && !inplace_) ? mp : 0)));
-    int rc = gcge_hip_lincomb(vy->nrows, vx->d + start[0], vx->ld, k, dc, mp, beta ? dc + (size_t)k * mp : nullptr,
-                              vy->d + start[1] + j0, vy->ld, g_stream);
+    // an update y = x c + y diag(beta) of one panel of <= 64 columns also sums the squares of what it stores where the register
+    // form takes it (GCGE_BACKEND.panel_norms_sq: the "twice is enough" test of the orthonormalisation asks for them next)
+    int rc = 1;
+    if (beta != nullptr && m <= 64 && getenv("GCGE_NO_PANEL_NORMS") == nullptr) {
+      if (g_norms_d == nullptr) GCGE_HIP_CHECK(hipMalloc(&g_norms_d, 64 * sizeof(double)));
+      rc = gcge_hip_lincomb_norms(vy->nrows, vx->d + start[0], vx->ld, k, dc, mp, dc + (size_t)k * mp, vy->d + start[1], vy->ld, g_norms_d, g_stream);
+      if (rc == 0) { g_norms_owner = vy; g_norms_c0 = start[1]; g_norms_c1 = end[1]; g_norms_epoch = g_epoch; }
+    }
+    if (rc == 1) rc = gcge_hip_lincomb(vy->nrows, vx->d + start[0], vx->ld, k, dc, mp, beta ? dc + (size_t)k * mp : nullptr,
+                                       vy->d + start[1] + j0, vy->ld, g_stream);
     GCGE_REQUIRE(rc == 0, "MultiVecLinearComb: kernel launch");
   }
+}
+
+// GCGE_BACKEND.panel_norms_sq (include/gcge_ops.h): the squared column norms the last MultiVecLinearComb summed on its way
+static int HIP_PanelNormsSq(void** y, int start, int end, double* out, struct OPS_* ops) {
+  (void)ops;
+  const bool fresh = (GcgeHipMV*)y == g_norms_owner && g_norms_owner != nullptr && start == g_norms_c0 && end == g_norms_c1 && g_norms_epoch == g_epoch;
+  enter();
+  if (!fresh || out == nullptr) return 0;
+  const int m = end - start;
+  double* hd = gcge_hip_stage_h(m);
+  GCGE_HIP_CHECK(hipMemcpyAsync(hd, g_norms_d, m * sizeof(double), hipMemcpyDeviceToHost, g_stream));
+  GCGE_HIP_CHECK(hipStreamSynchronize(g_stream));
+  for (int j = 0; j < m; ++j) out[j] = hd[j];
+  return 1;
+}
+extern "C" int gcge_hip_panel_norms_sq_mv(void** y, int start, int end, double* out) { return HIP_PanelNormsSq(y, start, end, out, nullptr); }
+
+// GCGE_BACKEND.ritz_in_place (include/gcge_ops.h): V[:, n0..x1) = V[:, n0..w1) C in place and V[:, p0..p0 + np) = S[:, 0..np) behind
+// it, one launch of the panel update's register form with the row copy in its epilogue (lincomb_mfma.hip).
+static int HIP_RitzInPlace(void** V, int n0, int x1, int w1, const double* coef, int ldc, void** S, int p0, int np, struct OPS_* ops) {
+  (void)ops;
+  GcgeHipMV *vv = (GcgeHipMV*)V, *vs = (GcgeHipMV*)S;
+  const int k = w1 - n0, m = x1 - n0;
+  if (vv == nullptr || coef == nullptr || n0 < 0 || m < 1 || m > 128 || k < m || w1 > vv->ncols || ldc < k || np < 0) return 0;
+  if ((vv->ld & 1) || ((uintptr_t)vv->d & 15)) return 0;
+  if (np > 0) {
+    if (vs == nullptr || vs == vv || np > vs->ncols || p0 < 0 || p0 + np > vv->ncols || (p0 < x1 && p0 + np > n0)) return 0;
+    if (vs->nrows != vv->nrows || real_perm(vs->perm) != real_perm(vv->perm)) return 0;
+  }
+  if (vv->nrows <= 0) return 1;
+  enter();
+  SlotTimer tm_("Ritz vectors in place + P", m);
+  const size_t len = (size_t)k * m;
+  GCGE_HIP_CHECK(hipStreamSynchronize(g_stream));   // staging buffers are reused
+  double* hc = gcge_hip_stage_h(len);
+  for (int i = 0; i < k; ++i)
+    for (int j = 0; j < m; ++j) hc[(size_t)i * m + j] = coef[(size_t)j * ldc + i];
+  double* dc = gcge_hip_stage_d(len);
+  GCGE_HIP_CHECK(hipMemcpyAsync(dc, hc, len * sizeof(double), hipMemcpyHostToDevice, g_stream));
+  DenseProfScope prof_(1, vv->nrows, k, m, 8.0 * (double)vv->nrows * (k + m + 2 * np));
+  const int rc = gcge_hip_lincomb_copy(vv->nrows, vv->d + n0, vv->ld, k, dc, m, nullptr, vv->d + n0, vv->ld, np > 0 ? vs->d : nullptr,
+                                       np > 0 ? vs->ld : 0, vv->d + p0, vv->ld, np, g_stream);
+  GCGE_REQUIRE(rc == 0 || rc == 1, "ritz in place: kernel launch");
+  return rc == 0;
+}
+extern "C" int gcge_hip_ritz_in_place_mv(void** V, int n0, int x1, int w1, const double* coef, int ldc, void** S, int p0, int np) {
+  return HIP_RitzInPlace(V, n0, x1, w1, coef, ldc, S, p0, np, nullptr);
 }
 
 // app_lapack.c:299-313 -> DenseMatQtAP(matA == NULL) :64-183.  Result to HOST, column-major ldIP.
@@ -708,6 +772,8 @@ extern "C" void OPS_HIP_Set(struct OPS_* ops) {
   gcge_hip_bpcg_backend(&be);                 // the fused device CG: BlockAMG's smoother, and the solver of unformed b = x diag(scale)
   be.pas_border = gcge_hip_pas_border;        // PAS: y += QX t and g = QX^T q in one pass over QX
   be.block_moves = HIP_BlockMoves;            // GCG's X / W start / b moves of an outer iteration in one sweep
+  be.ritz_in_place = HIP_RitzInPlace;         // GCG's Ritz vectors written over X, P moved in behind them: no ComputeX
+  be.panel_norms_sq = HIP_PanelNormsSq;       // column norms summed by the panel update that wrote the columns
   be.mat_identity = HIP_MatIdentity; be.mat_free = HIP_MatFree; be.mat_rows_as_given = HIP_MatRowsAsGiven;
   GCGE_SetBackend(ops, &be);
 }

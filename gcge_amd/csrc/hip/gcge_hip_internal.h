@@ -154,6 +154,11 @@ int gcge_hip_cg_start_scaled_mv(void* mat, void** x, int xc0, const double* host
 int gcge_hip_pas_border(void** QX, int s, void** q, int q0, void** y, int y0, int m, double beta, const double* t, int ldt, double* g, int ldg);
 
 // ---- kernel files: what other translation units launch or build through them and gcge_hip.h does not name --------------------------
+// lincomb_mfma.hip: the panel update by its register form with a row copy / the column norms in its epilogue (1: not taken)
+int gcge_hip_lincomb_copy(int nrows, const double* d_x, long ldx, int k, const double* d_c, int m, const double* d_beta, double* d_y, long ldy,
+                          const double* d_src, long lds, double* d_dst, long ldd, int ncopy, void* stream);
+int gcge_hip_lincomb_norms(int nrows, const double* d_x, long ldx, int k, const double* d_c, int m, const double* d_beta, double* d_y, long ldy,
+                           double* d_norms, void* stream);
 // vec_kernels.hip
 double* gcge_hip_partial_ws(size_t len);
 void gcge_hip_reduce_partials(const double* d_partial, int nblocks, int len, double* d_out, void* stream);

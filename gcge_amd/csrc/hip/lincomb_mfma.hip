@@ -39,12 +39,50 @@ typedef double v4d __attribute__((ext_vector_type(4)));
 constexpr int LC_KT = 32;          // k-tile
 constexpr int LC_XS = LC_KT + 2;   // LDS row stride of the X tile (doubles)
 
+typedef double v2d_lc __attribute__((ext_vector_type(2)));
+// what the optional epilogues of the kernels below take (EPI, described in front of lincomb_direct_kernel)
+struct LcEpilogue {
+  const double* cp_src; long cp_lds; double* cp_dst; long cp_ldd; int cp_n;   // EPI = 1
+  double* norm_part;                                                          // EPI = 2: [4 gridDim.x][16 NT]
+};
+
+// rows [rw, rw + nr) of a wave: dst[row][c0 + U col) = src[row][c0 + U col) for col < w, U doubles per lane (T = U doubles).  Eight
+// loads per lane in flight; the empty asm is a use of all eight in straight-line code, so the one wait for them stands in front of
+// the guarded stores, which then issue back to back (as in block_moves_kernel, vec_kernels.hip).
+template <typename T, int U>
+__device__ __forceinline__ void lc_copy_rows(const double* src, long lds, double* dst, long ldd, int c0, int w, long rw, int nr,
+                                             long nrows, int lane) {
+  const int tot = nr * w;
+  for (int base = 0; base < tot; base += 512) {
+    T v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int e = min(base + 64 * u + lane, tot - 1), row = e / w, col = e - row * w;
+      v[u] = *reinterpret_cast<const T*>(src + min(rw + row, nrows - 1) * lds + c0 + U * col);
+    }
+    asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]));
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int e = base + 64 * u + lane, row = e / w, col = e - row * w;
+      if (e < tot && rw + row < nrows) *reinterpret_cast<T*>(dst + (rw + row) * ldd + c0 + U * col) = v[u];
+    }
+  }
+}
+
+__device__ __forceinline__ void lc_copy_epilogue(const LcEpilogue& ep, long rw, int nr, long nrows, int lane) {
+  if (ep.cp_n <= 0) return;
+  const bool wide = ((((uintptr_t)ep.cp_src | (uintptr_t)ep.cp_dst) & 15) == 0) && (((ep.cp_lds | ep.cp_ldd) & 1) == 0);
+  const int npair = wide ? ep.cp_n / 2 : 0;
+  if (npair > 0) lc_copy_rows<v2d_lc, 2>(ep.cp_src, ep.cp_lds, ep.cp_dst, ep.cp_ldd, 0, npair, rw, nr, nrows, lane);
+  if (2 * npair < ep.cp_n) lc_copy_rows<double, 1>(ep.cp_src, ep.cp_lds, ep.cp_dst, ep.cp_ldd, 2 * npair, ep.cp_n - 2 * npair, rw, nr, nrows, lane);
+}
+
 // NT 16-column output fragments per wave: m <= 16 NT.  RF 16-row fragments per wave: a block owns 64 RF rows and every
 // coefficient fragment read from LDS feeds RF MFMAs (RF = 2: 8 MFMAs per 6 LDS reads at m = 64 instead of 4 per 5; PMC
 // showed the RF = 1 form issuing MFMAs at 52-62 % of the pipe rate, profiles/r01_dense/10).
-template <int NT, int RF>
+template <int NT, int RF, int EPI = 0>
 __global__ __launch_bounds__(256, (RF == 2 && NT <= 4) ? 2 : 1) void lincomb_kernel(long nrows, const double* x, long ldx, int k,
-    const double* __restrict__ cpad, int m, const double* __restrict__ beta, double* y, long ldy, int cs) {
+    const double* __restrict__ cpad, int m, const double* __restrict__ beta, double* y, long ldy, int cs, LcEpilogue ep) {
   extern __shared__ __align__(16) double lds[];
   constexpr int BR = 64 * RF;       // rows per block
   double* xs = lds;                 // [BR][LC_XS]
@@ -135,6 +173,8 @@ __global__ __launch_bounds__(256, (RF == 2 && NT <= 4) ? 2 : 1) void lincomb_ker
       }
     }
   }
+  // EPI = 1: the wave's rows of the staging block (every read of the block's rows lies in front of the last barrier)
+  if constexpr (EPI == 1) lc_copy_epilogue(ep, r0 + 16 * RF * wave, 16 * RF, nrows, lane);
 }
 
 
@@ -150,12 +190,22 @@ __global__ __launch_bounds__(256, (RF == 2 && NT <= 4) ? 2 : 1) void lincomb_ker
 // NT column fragments; the 2 NT accumulator tiles live in a[0 : 16 NT) by name (agpr_tiles.inc), so no v_accvgpr
 // shuttling.  k odd: the pair (k-1, k) would read one column past the operand; the last k-tile therefore blends the
 // second half of its loads with 0 by an integer mask (after the loads have been issued: no predicate near them).
+//
+// Two optional epilogues (EPI; the row copy also in lincomb_kernel above), each an instantiation of its own so that the plain
+// kernels keep their registers:
+//   EPI = 1  row copy: after its stores a wave copies the rows it owns of a staging block, dst[:, 0..n) = src[:, 0..n).  The target
+//            may lie INSIDE the input range of an in-place update (the Ritz vectors written over X while P, formed beforehand in a
+//            work block, lands behind them: GCGE_BACKEND.ritz_in_place): the rows are the wave's own, whose last read fed the MFMAs
+//            that its stores have already consumed.  16-byte lanes where both origins are even, 8-byte lanes otherwise (and for the
+//            last column of an odd n); loads unconditional at clamped addresses, eight in flight, only the stores guarded.
+//   EPI = 2  column norms: the squares of the values a lane stores (valid rows and columns only) are summed per lane over its 8
+//            rows, then over the four kk lane groups as (g0 + g1) + (g2 + g3), and lane group 0 writes the wave's 16 NT sums as one
+//            row of a partial-sum slab; lc_norms_chunks and reduce_partials (vec_kernels.hip) add the rows in a fixed order — no
+//            atomics, the same sums on every run.
 #include "agpr_tiles.inc"
-typedef double v2d_lc __attribute__((ext_vector_type(2)));
-
-template <int NT, int RF, int MINB, int KTD, bool ASM = true>
+template <int NT, int RF, int MINB, int KTD, bool ASM = true, int EPI = 0>
 __global__ __launch_bounds__(256, MINB) void lincomb_direct_kernel(long nrows, const double* x, long ldx, int k,
-    const double* __restrict__ cpad, int m, const double* __restrict__ beta, double* y, long ldy, int cs) {
+    const double* __restrict__ cpad, int m, const double* __restrict__ beta, double* y, long ldy, int cs, LcEpilogue ep) {
   extern __shared__ __align__(16) double lds[];       // [2][KTD][cs]
   constexpr int NJ = KTD / 8;                          // 16-byte loads per row fragment and k-tile
   constexpr int CE = (KTD * 16 * NT + 255) / 256;      // coefficient elements per thread and tile (NT odd at k-tiles of 8: the last round is half
@@ -276,6 +326,11 @@ __global__ __launch_bounds__(256, MINB) void lincomb_direct_kernel(long nrows, c
   }
   // the MFMAs are inline asm, invisible to the hazard recogniser: let the last ones retire before the tiles are read
   if constexpr (PIN) asm volatile("s_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15\n\ts_nop 15" ::: "memory");
+  double nsq[EPI == 2 ? NT : 1];
+  if constexpr (EPI == 2) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) nsq[t] = 0.0;
+  }
 #pragma unroll
   for (int f = 0; f < RF; ++f) {
     const long rw = r0 + 16 * f;
@@ -308,9 +363,36 @@ __global__ __launch_bounds__(256, MINB) void lincomb_direct_kernel(long nrows, c
       for (int u = 0; u < 4; ++u) {
         const long row = rw + 4 * u + kk;
         if (col < m && row < nrows) y[row * ldy + col] = acc[t][u];
+        if constexpr (EPI == 2) { const double v = (col < m && row < nrows) ? acc[t][u] : 0.0; nsq[t] = fma(v, v, nsq[t]); }
       }
     }
   }
+  if constexpr (EPI == 1) lc_copy_epilogue(ep, r0, 16 * RF, nrows, lane);
+  if constexpr (EPI == 2) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const double a = nsq[t] + __shfl_xor(nsq[t], 16);      // kk 0 + 1 | 2 + 3 (either lane of a pair adds the same two numbers)
+      const double s = a + __shfl_xor(a, 32);                // (0 + 1) + (2 + 3)
+      if (kk == 0) ep.norm_part[((long)blockIdx.x * 4 + wave) * (16 * NT) + 16 * t + li] = s;
+    }
+  }
+}
+
+// stage 1 of the norms' reduction: block c adds the slab's rows [c chunk, (c + 1) chunk) — 16 row groups x 64 columns, fixed tree
+__global__ __launch_bounds__(1024) void lc_norms_chunks(const double* __restrict__ partial, long nrows_part, int chunk,
+                                                        double* __restrict__ out) {
+  __shared__ double red[16][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const long b0 = (long)blockIdx.x * chunk, b1 = min(nrows_part, b0 + chunk);
+  double s = 0.0;
+  for (long b = b0 + ty; b < b1; b += 16) s += partial[b * 64 + tx];
+  red[ty][tx] = s;
+  __syncthreads();
+  for (int h = 8; h > 0; h >>= 1) {
+    if (ty < h) red[ty][tx] += red[ty + h][tx];
+    __syncthreads();
+  }
+  if (ty == 0) out[(long)blockIdx.x * 64 + tx] = red[0][tx];
 }
 
 }  // namespace gcge
@@ -334,15 +416,21 @@ static int g_lc_wide_only = 0;   // 1: panels of 65 .. 96 columns take the 128-c
 extern "C" void gcge_hip_lincomb_wide_only(int on) { g_lc_wide_only = on != 0; }
 extern "C" void gcge_hip_lincomb_tune(int row_fragments) { if (row_fragments >= 0 && row_fragments <= 14) g_lc_rf = row_fragments; }
 
+// epi: 0 plain; 1: the row copy of `ep` in the epilogue of whichever form the plain call would take (1 with nothing launched under
+// a tuning code's variant of the direct form); 2: the column norms, direct form only — 1 with nothing launched where the direct
+// form in its automatic variant would not be chosen
 template <int NT>
 static int lc_launch(int nrows, const double* x, long ldx, int k, const double* c, int m,
-                     const double* beta, double* y, long ldy, hipStream_t st) {
+                     const double* beta, double* y, long ldy, hipStream_t st, int epi = 0, LcEpilogue ep = LcEpilogue()) {
   // An operand that starts on an odd column of a 16-byte aligned block (the solver's X / P / W ranges move with the
   // number of converged pairs) is widened by the column in front of it, which meets a zero coefficient row: the direct
   // form's 16-byte loads stay aligned (the staged kernel it fell back to: 25.0 against 19.5 ms at k = 192, m = 128).
   // That column belongs to the same block of vectors (blocks are zero-filled at creation: finite).
   int shift = 0;
   if ((((uintptr_t)x & 15) == 8) && (ldx % 2 == 0) && ((g_lc_rf == 0 && NT >= 4) || g_lc_rf >= 3)) { shift = 1; x -= 1; k += 1; }
+  const bool direct = ((g_lc_rf == 0 && NT >= 4) || g_lc_rf >= 3) && (((uintptr_t)x & 15) == 0) && (ldx % 2 == 0) && k >= 2;
+  if (epi == 1 && direct && !(g_lc_rf == 0 || g_lc_rf == 3)) return 1;     // (the tuning codes' variants carry no epilogue)
+  if (epi == 2 && !(direct && (g_lc_rf == 0 || g_lc_rf == 3) && NT == 4)) return 1;
   const int kp = (k + LC_KT - 1) / LC_KT * LC_KT, mp = 16 * NT;
   if ((size_t)(kp + LC_KT) * mp > g_cpad_len) {   // grows rarely; freeing synchronises with kernels still reading the old one (one k-tile of slack: see CE_RAGGED)
     if (g_cpad) GCGE_HIP_CHECK(hipFree(g_cpad));
@@ -362,10 +450,23 @@ static int lc_launch(int nrows, const double* x, long ldx, int k, const double* 
   // returned wrong panels (caught by test_lincomb_row_fragment_variants_vs_oracle at k = 192, m = 64).  Those widths take
   // the builtin MFMA (the compiler owns the accumulators); m = 128 at two waves per SIMD keeps the named tiles and is
   // covered by the same test with all 16 tiles live.
-  if (((g_lc_rf == 0 && NT >= 4) || g_lc_rf >= 3) && (((uintptr_t)x & 15) == 0) && (ldx % 2 == 0) && k >= 2) {
+  if (direct) {
     const int csd = 16 * NT + 8;   // coefficient rows 2 apart land on the other half of the 64 LDS banks
-#define GCGE_LCD(RFV, MB, KTV, ASMV) hipLaunchKernelGGL((lincomb_direct_kernel<NT, RFV, MB, KTV, ASMV>), dim3((unsigned)(((long)nrows + 64 * RFV - 1) / (64 * RFV))), dim3(256), \
-                                             (size_t)2 * KTV * csd * sizeof(double), st, (long)nrows, x, ldx, k, g_cpad, m, beta, y, ldy, csd)
+#define GCGE_LCD_E(RFV, MB, KTV, ASMV, EPIV) hipLaunchKernelGGL((lincomb_direct_kernel<NT, RFV, MB, KTV, ASMV, EPIV>), dim3((unsigned)(((long)nrows + 64 * RFV - 1) / (64 * RFV))), dim3(256), \
+                                             (size_t)2 * KTV * csd * sizeof(double), st, (long)nrows, x, ldx, k, g_cpad, m, beta, y, ldy, csd, ep)
+#define GCGE_LCD(RFV, MB, KTV, ASMV) GCGE_LCD_E(RFV, MB, KTV, ASMV, 0)
+    // the epilogue variants of the automatic choice below (same template arguments otherwise: the same k-order, the same bits)
+    if (epi == 1) {
+      if constexpr (NT == 8) GCGE_LCD_E(2, 2, 8, true, 1);
+      else if constexpr (NT == 4) GCGE_LCD_E(2, 3, 8, false, 1);
+      else if constexpr (NT >= 5) GCGE_LCD_E(2, 2, 8, false, 1);
+      else GCGE_LCD_E(2, 2, 16, false, 1);
+      return 0;
+    }
+    if (epi == 2) {
+      if constexpr (NT == 4) GCGE_LCD_E(2, 3, 8, false, 2);
+      return 0;
+    }
     // tuning codes (gcge_hip_lincomb_tune / GCGE_LINCOMB_RF): 3 the automatic direct form also for narrow panels;
     // 7: k-tiles of 32 (named tiles); 10: k-tiles of 16 at two waves per SIMD (named tiles); 13 / 14: builtin, k-tiles of 8 / 16
     if constexpr (NT == 8) {
@@ -384,6 +485,7 @@ static int lc_launch(int nrows, const double* x, long ldx, int k, const double* 
       GCGE_LCD(2, 2, 16, false);
     }
 #undef GCGE_LCD
+#undef GCGE_LCD_E
     return 0;
   }
   const int cs = (16 * NT + 31) / 32 * 32 + 16;  // row stride of the C tile: 16 mod 32 doubles
@@ -393,13 +495,28 @@ static int lc_launch(int nrows, const double* x, long ldx, int k, const double* 
   const int rf = (g_lc_rf == 0 || g_lc_rf >= 3) ? (((NT == 8 || (NT == 4 && k >= 128)) && (long)nrows >= 128L * 256 * 8) ? 2 : 1) : g_lc_rf;
   const size_t shmem = (size_t)(64 * rf * LC_XS + LC_KT * cs) * sizeof(double);
   const unsigned grid = (unsigned)(((long)nrows + 64 * rf - 1) / (64 * rf));
+  if (epi == 1) {
+    if (rf == 2) hipLaunchKernelGGL((lincomb_kernel<NT, 2, 1>), dim3(grid), dim3(256), shmem, st, (long)nrows, x, ldx, k, g_cpad, m, beta, y, ldy, cs, ep);
+    else hipLaunchKernelGGL((lincomb_kernel<NT, 1, 1>), dim3(grid), dim3(256), shmem, st, (long)nrows, x, ldx, k, g_cpad, m, beta, y, ldy, cs, ep);
+    return 0;
+  }
   if (rf == 2)
     hipLaunchKernelGGL((lincomb_kernel<NT, 2>), dim3(grid), dim3(256), shmem, st, (long)nrows, x, ldx, k, g_cpad, m, beta,
-                       y, ldy, cs);
+                       y, ldy, cs, ep);
   else
     hipLaunchKernelGGL((lincomb_kernel<NT, 1>), dim3(grid), dim3(256), shmem, st, (long)nrows, x, ldx, k, g_cpad, m, beta,
-                       y, ldy, cs);
+                       y, ldy, cs, ep);
   return 0;
+}
+
+static int lc_dispatch(int nrows, const double* d_x, long ldx, int k, const double* d_c, int m, const double* d_beta, double* d_y,
+                       long ldy, hipStream_t st, int epi, const LcEpilogue& ep) {
+  if (m <= 16) return lc_launch<1>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st, epi, ep);
+  if (m <= 32) return lc_launch<2>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st, epi, ep);
+  if (m <= 64) return lc_launch<4>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st, epi, ep);
+  if (m <= 80 && g_lc_wide_only == 0) return lc_launch<5>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st, epi, ep);
+  if (m <= 96 && g_lc_wide_only == 0) return lc_launch<6>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st, epi, ep);
+  return lc_launch<8>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st, epi, ep);
 }
 
 // d_c: row-major k x m coefficient block on the device; d_beta: m scale factors or NULL
@@ -408,12 +525,41 @@ extern "C" int gcge_hip_lincomb(int nrows, const double* d_x, long ldx, int k, c
   gcge_hip_apply_pending();
   if (nrows <= 0 || m <= 0 || k <= 0) return 0;
   if (m > 128) return -2;  // callers split wider panels
-  hipStream_t st = (hipStream_t)stream;
-  if (m <= 16) lc_launch<1>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st);
-  else if (m <= 32) lc_launch<2>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st);
-  else if (m <= 64) lc_launch<4>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st);
-  else if (m <= 80 && g_lc_wide_only == 0) lc_launch<5>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st);
-  else if (m <= 96 && g_lc_wide_only == 0) lc_launch<6>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st);
-  else lc_launch<8>(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st);
+  lc_dispatch(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, (hipStream_t)stream, 0, LcEpilogue());
   return (int)hipGetLastError();
+}
+
+// The same update by the direct form, followed in the same launch by the row copy  dst[:, 0..ncopy) = src[:, 0..ncopy)  (blocks of
+// nrows rows, 8-byte aligned; dst may lie inside x's column range, see EPI = 1 above), by the kernel gcge_hip_lincomb would launch
+// for this shape.  Returns 1 with nothing launched under a tuning code's variant of the direct form, 0 once launched.
+extern "C" int gcge_hip_lincomb_copy(int nrows, const double* d_x, long ldx, int k, const double* d_c, int m, const double* d_beta,
+                                     double* d_y, long ldy, const double* d_src, long lds, double* d_dst, long ldd, int ncopy, void* stream) {
+  gcge_hip_apply_pending();
+  if (nrows <= 0 || m <= 0 || k <= 0 || m > 128) return 1;
+  LcEpilogue ep = LcEpilogue();
+  ep.cp_src = d_src; ep.cp_lds = lds; ep.cp_dst = d_dst; ep.cp_ldd = ldd; ep.cp_n = ncopy > 0 ? ncopy : 0;
+  const int rc = lc_dispatch(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, (hipStream_t)stream, 1, ep);
+  if (rc != 0) return rc;
+  return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// The same update of a panel of 33 .. 64 columns by the direct form, which also sums the squares of what it stores: d_norms[0..m)
+// = the columns' squared norms over the nrows rows, in a fixed order (EPI = 2 above).  Returns 1 with nothing launched where the
+// direct form would not be chosen.
+extern "C" int gcge_hip_lincomb_norms(int nrows, const double* d_x, long ldx, int k, const double* d_c, int m, const double* d_beta,
+                                      double* d_y, long ldy, double* d_norms, void* stream) {
+  gcge_hip_apply_pending();
+  if (nrows <= 0 || k <= 0 || m <= 32 || m > 64) return 1;
+  hipStream_t st = (hipStream_t)stream;
+  const long nwaves = (((long)nrows + 127) / 128) * 4;                 // rows of the partial-sum slab, 64 sums each
+  int chunk = (int)((nwaves + 1023) / 1024); if (chunk < 16) chunk = 16;
+  const int nchunks = (int)((nwaves + chunk - 1) / chunk);
+  double* part = gcge_hip_partial_ws((size_t)(nwaves + nchunks) * 64);
+  LcEpilogue ep = LcEpilogue();
+  ep.norm_part = part;
+  const int rc = lc_dispatch(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st, 2, ep);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(lc_norms_chunks, dim3(nchunks), dim3(1024), 0, st, part, nwaves, chunk, part + nwaves * 64);
+  gcge_hip_reduce_partials(part + nwaves * 64, nchunks, 64, d_norms, st);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -30,6 +30,8 @@ typedef struct {
 	struct OPS_ *ops; GCGSolver *p;
 	void *A, *B;
 	void **V, **ritz, **ws0, **ws1, **ws2;
+	void **cur;                       /* the block that holds the current Ritz vectors in its columns [startN, endX): ritz, or V (in_place) */
+	int in_place;                     /* the Ritz vectors are written over X, P is formed before them, no ComputeX (RitzVecInPlace)  */
 	/* column bookkeeping of V = [ C | N.. X | P | W ] */
 	int sizeC, sizeN, startN, endN, sizeX, endX;
 	int sizeP, startP, endP, sizeW, startW, endW, sizeV;
@@ -46,7 +48,8 @@ static int imin(int a, int b) { return a < b ? a : b; }
  * back-end that walks 16-byte column pairs wants an even origin, so an odd `first` moves one column up where the `total` columns
  * still end inside endX, else one column down where that is still inside startN, else stays (the back-end's slower paths).  The
  * values of b are the same wherever it lies. */
-static long g_odd_origins = 0, g_realigned = 0, g_fused_moves = 0;
+static long g_odd_origins = 0, g_realigned = 0, g_fused_moves = 0, g_ritz_in_place = 0;
+void GCGE_GcgRitzInPlaceStats(long *fused_launches) { if (fused_launches != NULL) *fused_launches = g_ritz_in_place; }
 int GCGE_GcgRhsOrigin(int first, int total, int startN, int endX)
 {
 	if (!(first & 1)) return first;
@@ -138,14 +141,14 @@ static int CheckConvergence(Ctx *c, int numCheck, int *offset)
 	double *res = c->scratch, *tol = p->tol, *ev = c->ss_eval + c->startN;
 	int s[2], e[2], idx, state, nun, nevConv; double t0 = ops->GetWtime();
 	GCGE_RESIDUAL_FN hook = GCGE_BackendOf(ops).residual_sq;
-	if (numCheck > 0 && hook != NULL && hook(c->A, c->B, c->ritz, c->startN, c->startN + numCheck, ev, res)) {
+	if (numCheck > 0 && hook != NULL && hook(c->A, c->B, c->cur, c->startN, c->startN + numCheck, ev, res)) {
 		GCGE_COMM *comm = GCGE_GetComm();          /* the back-end summed over its own rows */
 		if (comm != NULL) comm->allreduce_sum(res, numCheck, comm->ctx);
 		for (idx = 0; idx < numCheck; ++idx) res[idx] = sqrt(res[idx]);
 	} else if (numCheck > 0) {
 		s[0] = c->startN; e[0] = c->startN + numCheck; s[1] = 0; e[1] = numCheck;
-		ops->MatDotMultiVec(c->A, c->ritz, c->ws0, s, e, ops);
-		ops->MatDotMultiVec(c->B, c->ritz, c->ws1, s, e, ops);
+		ops->MatDotMultiVec(c->A, c->cur, c->ws0, s, e, ops);
+		ops->MatDotMultiVec(c->B, c->cur, c->ws1, s, e, ops);
 		ops->MultiVecLinearComb(NULL, c->ws1, 0, s, e, NULL, 0, ev, 1, ops);   /* lambda B x */
 		s[0] = 0; e[0] = numCheck; s[1] = 0; e[1] = numCheck;
 		ops->MultiVecAxpby(-1.0, c->ws1, 1.0, c->ws0, s, e, ops);             /* A x - lambda B x */
@@ -187,11 +190,15 @@ static int CheckConvergence(Ctx *c, int numCheck, int *offset)
 	return nevConv;
 }
 
-static void ComputeP(Ctx *c, int *offset)
+/* the host half of ComputeP: the coefficient columns of P behind X's in ss_evec (gathered, zeroed, orthonormalised); sets startP,
+ * endP, sizeP and returns the columns.  It reads offset[] (the previous iteration's runs), ss_evec's first sizeX - sizeC columns
+ * and sizeC / sizeX / sizeV as ComputeRayleighRitz left them — none of which the convergence check in front of ComputeP changes,
+ * so it may run right after the Rayleigh-Ritz step as well. */
+static double *ComputeP_coef(Ctx *c, int *offset)
 {
 	struct OPS_ *ops = c->ops; GCGSolver *p = c->p;
-	int N = c->sizeV - c->sizeC, idx, col, blk = 0, s[2], e[2], sP, eP;
-	double *evec = c->ss_evec, *coef; double t0 = ops->GetWtime();
+	int N = c->sizeV - c->sizeC, idx, col, blk = 0, sP, eP;
+	double *evec = c->ss_evec;
 	/* gather the RR eigenvector columns of the (previously) unconverged pairs behind X */
 	for (idx = 0; idx < offset[0]; ++idx) {
 		int lo = offset[idx * 2 + 1], hi = offset[idx * 2 + 2];
@@ -223,8 +230,14 @@ static void ComputeP(Ctx *c, int *offset)
 		dense->MultiVecOrth((void**)&blockP, sP, &eP, NULL, dense);
 	}
 	c->startP = sP + c->sizeC; c->endP = eP + c->sizeC; c->sizeP = c->endP - c->startP;
+	return evec + (size_t)N * (c->sizeX - c->sizeC);
+}
+
+static void ComputeP(Ctx *c, int *offset)
+{
+	struct OPS_ *ops = c->ops; int N = c->sizeV - c->sizeC, s[2], e[2];
+	double t0 = ops->GetWtime(), *coef = ComputeP_coef(c, offset);
 	/* P = V[:, N..W) * coef, staged through a work block */
-	coef = evec + (size_t)N * (c->sizeX - c->sizeC);
 	if (c->sizeP <= GCGE_BackendOf(ops).inplace_lincomb_cols &&
 			c->startP >= c->startN && c->endP <= c->endW) {
 		/* the P columns lie inside [N, W): a back-end that works row by row writes them in place */
@@ -245,6 +258,37 @@ static void ComputeX(Ctx *c)
 	s[0] = c->startN; e[0] = c->endX; s[1] = c->startN; e[1] = c->endX;
 	ops->MultiVecAxpby(1.0, c->ritz, 0.0, c->V, s, e, ops);
 	g_timing.compX += ops->GetWtime() - t0;
+}
+
+/* ComputeRitzVec for a back-end that writes the Ritz vectors over X (GCGE_BACKEND.ritz_in_place).  The copy ritz[N..X) -> V[N..X)
+ * of ComputeX exists only because ComputeP needs the old V[N..X) after the Ritz vectors are formed; here P comes first, into the
+ * idle work block ws0 (with_p: not before the first iteration, where there is no P), and one launch then forms
+ * V[:, N..X) = V[:, N..W) evec in place and moves ws0 into V[:, P).  Same kernels, same coefficients: X and P hold the same bits
+ * as after ComputeRitzVec / ComputeP / ComputeX.  The last iteration forms a P that nobody uses. */
+static void RitzVecInPlace(Ctx *c, int with_p)
+{
+	struct OPS_ *ops = c->ops; int N = c->sizeV - c->sizeC, s[2], e[2]; double t0 = ops->GetWtime(), t1;
+	if (with_p) {
+		double *coef = ComputeP_coef(c, c->offsetP);
+		s[0] = c->startN; e[0] = c->endW; s[1] = 0; e[1] = c->sizeP;
+		ops->MultiVecLinearComb(c->V, c->ws0, 0, s, e, coef, N, NULL, 0, ops);
+	}
+	t1 = ops->GetWtime();
+	g_timing.compP += t1 - t0;
+	if (GCGE_BackendOf(ops).ritz_in_place(c->V, c->startN, c->endX, c->endW, c->ss_evec, N, c->ws0, c->startP, c->sizeP, ops)) {
+		++g_ritz_in_place;
+		g_timing.compRV += ops->GetWtime() - t1;
+		return;
+	}
+	/* declined for this shape: the three steps, to the same state */
+	ComputeRitzVec(c);
+	if (c->sizeP > 0) {
+		t1 = ops->GetWtime();
+		s[0] = 0; e[0] = c->sizeP; s[1] = c->startP; e[1] = c->endP;
+		ops->MultiVecAxpby(1.0, c->ws0, 0.0, c->V, s, e, ops);
+		g_timing.compP += ops->GetWtime() - t1;
+	}
+	ComputeX(c);
 }
 
 /* x_pending: ComputeX was left to this call, which moves X, the start vectors and (for BlockAMG over a back-end that forms
@@ -279,10 +323,14 @@ static void ComputeW(Ctx *c, int *offset, int x_pending)
 	if (x_pending) {      /* timed as compX (the sweep's W start vectors and b included), not as compW */
 		double ta = ops->GetWtime();
 		form_b = scaled_rhs && GCGE_SolverFormsScaledRhs(ops);
-		moved = GCGE_BackendOf(ops).block_moves(c->ritz, c->V, c->startN, c->endX, offset, c->startW,
-				form_b ? b : NULL, b0, scales, ops);
+		if (c->in_place)      /* X is in place already: V is the source of the runs, no X move (an empty range) */
+			moved = GCGE_BackendOf(ops).block_moves(c->V, c->V, c->endX, c->endX, offset, c->startW,
+					form_b ? b : NULL, b0, scales, ops);
+		else
+			moved = GCGE_BackendOf(ops).block_moves(c->ritz, c->V, c->startN, c->endX, offset, c->startW,
+					form_b ? b : NULL, b0, scales, ops);
 		if (moved) { ++g_fused_moves; g_timing.compX += ops->GetWtime() - ta; }
-		else ComputeX(c);
+		else if (!c->in_place) ComputeX(c);
 		tx = ops->GetWtime() - ta;
 	}
 	for (idx = 0; idx < offset[0]; ++idx) {
@@ -514,7 +562,7 @@ static void GCG(void *A, void *B, double *eval, void **evec, int nevGiven, int *
 	c->sizeC = 0; c->sizeN = b; c->sizeX = nevInit; c->sizeP = 0; c->sizeW = 0;
 	c->sizeV = c->sizeX; c->startN = 0; c->endN = c->sizeN; c->endX = c->sizeX;
 	c->startP = c->endX; c->endP = c->startP; c->startW = c->endP; c->endW = c->startW;
-	c->V = p->mv_ws[0]; c->ritz = evec;
+	c->V = p->mv_ws[0]; c->ritz = evec; c->cur = evec;
 	c->ws0 = p->mv_ws[1]; c->ws1 = p->mv_ws[2]; c->ws2 = p->mv_ws[3];
 	c->ss_eval = p->dbl_ws;
 	for (idx = 0; idx < T; ++idx) c->ss_eval[idx] = 1.0;
@@ -528,10 +576,17 @@ static void GCG(void *A, void *B, double *eval, void **evec, int nevGiven, int *
 	c->offsetP[0] = 0; c->offsetW[0] = 0;
 	t_start = ops->GetWtime();
 
+	/* Ritz vectors in place where the back-end offers it, nothing reads V or ss_evec behind X between the Ritz vectors and
+	 * ComputeP (nevInit == nevMax: the absorb branch below never runs), ComputeW takes its start vectors from V, and the
+	 * widest panel [startN, endX), the first one, is one the back-end updates in place */
+	c->in_place = GCGE_BackendOf(ops).ritz_in_place != NULL && nevInit == nevMax && p->compW_cg_order == 1 &&
+			c->endX - c->startN <= GCGE_BackendOf(ops).inplace_lincomb_cols;
+	if (c->in_place) c->cur = c->V;
+
 	InitializeX(c, nevGiven);
 	ComputeRayleighRitz(c, 0);
 	for (idx = c->sizeV; idx < T; ++idx) c->ss_eval[idx] = c->ss_eval[c->sizeV - 1];
-	ComputeRitzVec(c);
+	if (c->in_place) RitzVecInPlace(c, 0); else ComputeRitzVec(c);
 
 	*nevConv = imin(*nevConv, nevMax);
 	nev0 = *nevConv; *nevConv = 0;
@@ -562,19 +617,25 @@ static void GCG(void *A, void *B, double *eval, void **evec, int nevGiven, int *
 			}
 		}
 		if (numIter == 0) { c->sizeP = 0; c->startP = c->endX; c->endP = c->startP; }
-		else ComputeP(c, c->offsetP);
+		else if (!c->in_place) ComputeP(c, c->offsetP);     /* (in place: P came with the Ritz vectors) */
 		{   /* X, the W start vectors and b in one sweep where the back-end offers it: ComputeW makes the move */
 			const int fuse = p->compW_cg_order == 1 && GCGE_BackendOf(ops).block_moves != NULL;
-			if (!fuse) ComputeX(c);
+			if (!fuse && !c->in_place) ComputeX(c);
 			if (p->compW_cg_order != 1) ComputeW12(c, c->offsetW);
 			else ComputeW(c, c->offsetW, fuse);
 		}
 		tmp = c->offsetP; c->offsetP = c->offsetW; c->offsetW = tmp;
 		ComputeRayleighRitz(c, *nevConv);
 		for (idx = c->sizeV; idx < T; ++idx) c->ss_eval[idx] = c->ss_eval[c->sizeV - 1];
-		ComputeRitzVec(c);
+		if (c->in_place) RitzVecInPlace(c, 1); else ComputeRitzVec(c);
 		++numIter;
 	} while (numIter < numIterMax);
+	if (c->in_place) {   /* the caller's eigenvector block: once per solve */
+		int s[2], e[2]; double t0 = ops->GetWtime();
+		s[0] = 0; e[0] = c->sizeX; s[1] = 0; e[1] = c->sizeX;
+		ops->MultiVecAxpby(1.0, c->V, 0.0, c->ritz, s, e, ops);
+		g_timing.compX += ops->GetWtime() - t0;
+	}
 
 	p->numIter = numIter + (p->numIterMax - numIterMax);
 	p->sizeV = c->sizeV;

@@ -64,7 +64,9 @@ void **GCGE_GetRealignedRhs(int *b0) { if (b0 != NULL) *b0 = g_realigned_b0; ret
  *                            amg_final_cols                                  every smoothing call runs its last pass whole)
  *   GCGE_AMG_FULL_LAST_PASS  amg_final_cols                                 (the same, alone)
  *   GCGE_NO_RHS_SCALE        scaled_rhs_solver, amg_form_rhs                (the GCG driver forms b = (lambda + sigma) x)
- *   GCGE_NO_BLOCK_MOVES      block_moves                                    (X, the W start vectors and b moved one by one) */
+ *   GCGE_NO_BLOCK_MOVES      block_moves                                    (X, the W start vectors and b moved one by one)
+ *   GCGE_NO_RITZ_IN_PLACE    ritz_in_place                                  (Ritz vectors into the eigenvector block, then ComputeX)
+ *   GCGE_NO_PANEL_NORMS      panel_norms_sq                                 (column norms by a sweep of their own) */
 static GCGE_BACKEND g_backend; static void *g_backend_matvec = NULL, *g_backend_lincomb = NULL;
 void GCGE_SetBackend(struct OPS_ *ops, const GCGE_BACKEND *backend)
 {
@@ -86,6 +88,8 @@ GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
 	if (getenv("GCGE_AMG_FULL_LAST_PASS") != NULL) b.amg_final_cols = 0;
 	if (getenv("GCGE_NO_RHS_SCALE") != NULL) { b.scaled_rhs_solver = NULL; b.amg_form_rhs = NULL; }
 	if (getenv("GCGE_NO_BLOCK_MOVES") != NULL) b.block_moves = NULL;
+	if (getenv("GCGE_NO_RITZ_IN_PLACE") != NULL) b.ritz_in_place = NULL;
+	if (getenv("GCGE_NO_PANEL_NORMS") != NULL) b.panel_norms_sq = NULL;
 	return b;
 }
 

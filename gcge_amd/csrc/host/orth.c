@@ -44,6 +44,13 @@ static void negate(double *v, int n) { int i; for (i = 0; i < n; ++i) v[i] = -v[
  * orthogonal to the basis to rounding — a further pass would remove O(eps ||w_j||).  The reference's absolute test
  * (|c| < 50 eps) asks for a third Gram product + panel update whenever the second pass's coefficients exceed 1e-14 in
  * absolute terms, which they do for columns of norm ~1.  Costs one column-norm sweep after the first pass. */
+static long g_kahan_tests = 0, g_kahan_more = 0, g_kahan_norms_from_update = 0;
+void GCGE_OrthKahanStats(long *tests, long *another_pass, long *norms_from_update)
+{
+	if (tests != NULL) *tests = g_kahan_tests;
+	if (another_pass != NULL) *another_pass = g_kahan_more;
+	if (norms_from_update != NULL) *norms_from_update = g_kahan_norms_from_update;
+}
 static void project_out(void **x, int s0, int e0, int s1, int e1, void *B,
 		int max_reorth, double reorth_tol, int lazy, void **mv_ws, double *coef, struct OPS_ *ops)
 {
@@ -67,11 +74,24 @@ static void project_out(void **x, int s0, int e0, int s1, int e1, void *B,
 					for (i = 0; i < k; ++i) c2 += coef[(size_t)k * j + i] * coef[(size_t)k * j + i];
 					if (!(c2 <= 0.01 * wn[j])) small = 0;     /* also catches wn = 0 and NaN */
 				}
+				++g_kahan_tests;
 				if (small) break;
+				++g_kahan_more;
 			}
-			/* the columns as the next pass will see them */
-			start[0] = s1; end[0] = e1; start[1] = s1; end[1] = e1;
-			ops->MultiVecInnerProd('D', x, x, 0, start, end, wn, 1, ops);
+			/* the columns as the next pass will see them: from the update that has just written them where the back-end summed
+			 * their squares on its way (the local rows' sums; rounded in another order than the sweep's, and wn feeds only the
+			 * comparison above), else by a sweep of their own */
+			{
+				GCGE_PANEL_NORMS_FN from_update = GCGE_BackendOf(ops).panel_norms_sq;
+				if (from_update != NULL && from_update(x, s1, e1, wn, ops)) {
+					GCGE_COMM *comm = GCGE_GetComm();
+					if (comm != NULL) comm->allreduce_sum(wn, m, comm->ctx);
+					++g_kahan_norms_from_update;
+				} else {
+					start[0] = s1; end[0] = e1; start[1] = s1; end[1] = e1;
+					ops->MultiVecInnerProd('D', x, x, 0, start, end, wn, 1, ops);
+				}
+			}
 		}
 	}
 	free(wn);

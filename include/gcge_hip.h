@@ -411,6 +411,9 @@ int gcge_hip_axpby (int nrows, double alpha, const double *d_x, long ldx, double
 /*     GCGE_BACKEND.block_moves of OPS_HIP_Set (include/gcge_ops.h) on blocks of this back-end, for tests: V[:, x0..x1) = ritz[:, x0..x1),
  *     V[:, w0 + ..) = the runs of ritz packed, b[:, b0 + ..) = the same times scale (b NULL: none) in one sweep; 0: declined        */
 int gcge_hip_block_moves_mv (void **ritz, void **V, int x0, int x1, const int *runs, int w0, void **b, int b0, const double *scale);
+/*     GCGE_BACKEND.ritz_in_place and .panel_norms_sq of OPS_HIP_Set (include/gcge_ops.h) on blocks of this back-end, for tests             */
+int gcge_hip_ritz_in_place_mv (void **V, int n0, int x1, int w1, const double *coef, int ldc, void **S, int p0, int np);
+int gcge_hip_panel_norms_sq_mv (void **y, int start, int end, double *out);
 /*     counters since the library was loaded: out[0] one-sweep starts of the fused block CG taken, out[1] declined ONLY because b starts
  *     on an odd column (matrix in pattern form, even width, x and r on even columns), out[2] / out[3] the same for the V-cycle's
  *     fused residual                                                                                                              */

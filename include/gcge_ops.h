@@ -214,7 +214,20 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *                 runs[] = {count; lo_0, hi_0, ...} (all inside [x0, x1)), packed:  V[:, w0 + blk..) = ritz[:, lo_i..hi_i);  and
  *                 with b != NULL  b[:, b0 + blk..) = ritz[:, lo_i..hi_i) diag(scale[blk..]), every product rounded once.  b may be
  *                 the block ritz itself with target columns over source columns: every row is read whole before any of it is
- *                 written.  0 declines with nothing touched. */
+ *                 written.  0 declines with nothing touched.  With ritz == V and an empty range x0 == x1 no X move is asked for
+ *                 and V itself is the source (the Ritz vectors already live there: ritz_in_place): the runs, ascending and ending
+ *                 at or before w0, are read and the W start vectors and b (a block other than V) written, nothing else.
+ *   ritz_in_place   the Ritz vectors written over X and P moved in behind them, in one launch:  V[:, n0..x1) = V[:, n0..w1) C  in
+ *                 place (C column-major, (w1 - n0) x (x1 - n0), leading dimension ldc), and after it  V[:, p0..p0 + np) =
+ *                 S[:, 0..np)  for a staging block S (np == 0: none; the target lies outside [n0, x1), inside [n0, w1) or not).
+ *                 Every output row is written after the last read of that row.  Same arithmetic as MultiVecLinearComb + MultiVecAxpby:
+ *                 the same bits.  0 declines with nothing touched: more than 128 output columns, blocks in different row orders,
+ *                 unaligned leading dimensions, shapes whose MultiVecLinearComb does not work row by row from registers.  GCG then
+ *                 forms P before the Ritz vectors and drops the reference's ComputeX (src/ops_eig_sol_gcg.c:458-471).
+ *   panel_norms_sq   out[j] = sum over the LOCAL rows of y[r, start + j]^2, j < end - start, for the panel y[:, start..end) that the
+ *                 LAST call of MultiVecLinearComb wrote, summed by that call from the values it stored (no second pass over the
+ *                 panel; a fixed order: the same sums on every run, rounded otherwise than MultiVecInnerProd('D')'s).  0 when that
+ *                 call did not collect them, or wrote another panel, or any other call came in between. */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -225,6 +238,9 @@ typedef int    (*GCGE_AMG_FORM_RHS_FN) (void **b, int b0, void **x, int x0, cons
 typedef void   (*GCGE_LINSOL_FN) (void *mat, void **b, void **x, int *start, int *end, struct OPS_ *ops);
 typedef int    (*GCGE_BLOCK_MOVES_FN) (void **ritz, void **V, int x0, int x1, const int *runs, int w0, void **b, int b0,
 		const double *scale, struct OPS_ *ops);
+typedef int    (*GCGE_RITZ_IN_PLACE_FN) (void **V, int n0, int x1, int w1, const double *coef, int ldc, void **S, int p0, int np,
+		struct OPS_ *ops);
+typedef int    (*GCGE_PANEL_NORMS_FN) (void **y, int start, int end, double *out, struct OPS_ *ops);
 typedef struct GCGE_BACKEND_ {
 	GCGE_RESIDUAL_FN residual_sq;
 	int inplace_lincomb_cols;
@@ -238,6 +254,8 @@ typedef struct GCGE_BACKEND_ {
 	int  (*mat_rows_as_given) (void *mat);
 	int amg_final_cols;
 	GCGE_BLOCK_MOVES_FN block_moves;
+	GCGE_RITZ_IN_PLACE_FN ritz_in_place;
+	GCGE_PANEL_NORMS_FN panel_norms_sq;
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

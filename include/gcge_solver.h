@@ -153,6 +153,13 @@ int GCGE_GcgRhsOrigin (int first, int total, int startN, int endX);
 /* counters since the library was loaded: outer iterations whose first unconverged column was odd, those of them whose b moved to
  * an even column, outer iterations whose X / W / b moves were one sweep (GCGE_BACKEND.block_moves).  NULL: not wanted. */
 void GCGE_GcgBlockMoveStats (long *odd_origins, long *realigned, long *fused_moves);
+/* counters since the library was loaded: launches that wrote the Ritz vectors over X and moved P in behind them
+ * (GCGE_BACKEND.ritz_in_place; 0 over a table that does not offer it: the driver then keeps ComputeRitzVec / ComputeP / ComputeX) */
+void GCGE_GcgRitzInPlaceStats (long *fused_launches);
+/* counters since the library was loaded, of the "twice is enough" test of the Cholesky-QR scheme's projection (orth.c: project_out):
+ * times it was made, times it asked for another pass, times the column norms came from the panel update that wrote the columns
+ * (GCGE_BACKEND.panel_norms_sq) */
+void GCGE_OrthKahanStats (long *tests, long *another_pass, long *norms_from_update);
 
 /* ---- harness ---------------------------------------------------------------- */
 /* flag: 0 BlockPCG inside GCG, 1 the back-end's own ops->MultiLinearSolver, 2 both */
