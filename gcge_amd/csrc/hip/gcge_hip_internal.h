@@ -104,6 +104,10 @@ extern "C" int gcge_hip_mg_galerkin_device(int nf, const int* d_rowptr, const in
                                            long* nnz_out, long* d2h);
 extern "C" int gcge_hip_mg_agg_masked_device(const int dims[3], const int* d_box, int nf, int* d_agg, int* d_mem, int** d_ptr_out, int** d_cbox_out,
                                              int cdims[3], long* d2h);
+// mg_aggregate.hip: MIS-2 aggregation (gcge_mg_aggregate_mis2) of an n-row device CSR; agg / mem: the caller's, *d_ptr_out allocated
+// there; returns the number of aggregates, -1: the rounds reached their cap, nothing allocated (the caller aggregates on the host)
+extern "C" int gcge_hip_mg_agg_graph_device(int n, const int* d_rowptr, const int* d_colidx, const double* d_val, double theta, int* d_agg,
+                                            int* d_mem, int** d_ptr_out, long* d2h);
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_rect_device(int nf, int nc, const int* d_agg, const int* d_ptr, const int* d_mem);
 extern "C" int gcge_hip_mg_download_csr(int nrows, int ncols, long nnz, const int* d_rp, const int* d_ci, const double* d_va, GCGE_CSR* out, long* d2h);
 void gcge_hip_mg_members_host(const int* agg, int nf, int nc, std::vector<int>& ptr, std::vector<int>& mem);

@@ -451,6 +451,18 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_grid(int nrows, const int* rowptr, 
   if (A != nullptr && box_of_row != nullptr && nx > 0 && ny > 0 && nz > 0) mat_set_geometry(A, 1, nx, ny, nz, box_of_row);
   return A;
 }
+// A whole matrix whose rows stay as given whatever the row order search would do and whatever order another matrix of its size lives
+// in: the coarse levels of a hierarchy whose prolongations are numbered like its rows (multigrid.hip).  It shares the identity order of
+// its size when there is one (or none yet); beside a re-ordered matrix of the same size it carries no order record, which means the
+// caller's order to every block created for it.
+extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_as_given(int nrows, const int* rowptr, const int* colidx, const double* val) {
+  GCGE_HIP_MAT* A = gcge_hip_mat_create_local(nrows, nrows, nrows, 0, rowptr, colidx, val);
+  if (A == nullptr) return nullptr;
+  GcgePerm* P = perm_find(nrows);
+  if (P == nullptr) P = perm_register(nrows, nullptr);
+  if (P->identity) A->perm = gcge_hip_perm_acquire(P);
+  return A;
+}
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_csr(const GCGE_CSR* A) {
   if (A->row_begin == 0 && A->nrows == A->ncols) return gcge_hip_mat_create(A->nrows, A->ncols, 0, A->rowptr, A->colidx, A->val);
   // a localized slab: ncols = nrows + nghost (gcge_dist_localize)

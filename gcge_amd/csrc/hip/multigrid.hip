@@ -7,7 +7,9 @@
 // (multigrid_create_device: aggregates, Galerkin products and P / P^T on the device, mg_device.hip) or, in mode 1 and when a level
 // is out of the kernels' reach, by the host builders on the downloaded CSR (multigrid_create_host).  Either way every coarse level
 // goes up through gcge_hip_mat_create (gcge_hip_mat_create_grid on a masked grid) — so a coarse Laplacian gets the pattern kernels,
-// a coarse real-space Hamiltonian its blocks, exactly like a matrix the caller uploads.  The prolongations are rectangular matrices
+// a coarse real-space Hamiltonian its blocks, exactly like a matrix the caller uploads.  A matrix without a grid under
+// gcge_mg_set_graph_method (1) is aggregated by MIS-2 on the device (mg_aggregate.hip) and its coarse levels go up through
+// gcge_hip_mat_create_as_given: their rows keep the hierarchy's numbering whatever the row order search would do.  The prolongations are rectangular matrices
 // (GCGE_HIP_MAT_::rect_ncols): CSR of P for MatDotMultiVec, CSR of P^T for MatTransDotMultiVec, both through the generic CSR
 // kernel (spmm.hip) — one non-zero per fine row, every fine row of the block read or written exactly once.
 // Row slabs (one rank per GPU): a slab of whole planes coarsens by itself (every rank pairs its own planes) — local prolongations, coarse slabs
@@ -214,10 +216,12 @@ static void multigrid_create_host(const MgSlot& s, const GCGE_HIP_MAT_* mA, cons
     built.how = " (host build)";
   } else if (gcge_mg_build(&cA, mB != nullptr ? &cB : nullptr, *s.num_levels, 0, 0.0, &mg) != 0) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
   g_mg_phase[masked ? MG_AGGREGATE : MG_OTHER] += mg_now() - t; t = mg_now();       // (all of the host builder, whatever it did)
+  const bool as_given = !masked && gcge_mg_get_graph_method() == 1;       // (MIS-2 levels: rows as given; a level on a grid has dims)
   mg_load_host(mg, s.B_array != nullptr && mB != nullptr, built, [&](int l, const GCGE_CSR& c) {
     const int* d = mg.dims[l];
-    return masked ? gcge_hip_mat_create_grid(c.nrows, c.rowptr, c.colidx, c.val, d[0], d[1], d[2], gcge_mg_level_box(&mg, l))
-                  : gcge_hip_mat_create(c.nrows, c.nrows, 0, c.rowptr, c.colidx, c.val);
+    if (masked) return gcge_hip_mat_create_grid(c.nrows, c.rowptr, c.colidx, c.val, d[0], d[1], d[2], gcge_mg_level_box(&mg, l));
+    if (as_given && d[0] == 0) return gcge_hip_mat_create_as_given(c.nrows, c.rowptr, c.colidx, c.val);
+    return gcge_hip_mat_create(c.nrows, c.nrows, 0, c.rowptr, c.colidx, c.val);
   });
   g_mg_phase[MG_COARSE] += mg_now() - t;
   gcge_mg_free(&mg);
@@ -231,7 +235,13 @@ static void multigrid_create_host(const MgSlot& s, const GCGE_HIP_MAT_* mA, cons
 // is coarsened from the Galerkin output, in hierarchy order — never from the coarse handle, whose rows gcge_hip_mat_create may
 // re-order.  Only the aggregation differs between the three kinds of coarsening:
 //   grid    2 x 2 x 2 cells of the grid detected from the sampled rows, and their members, in closed form on the device;
-//   graph   the unchanged host aggregation on that level's CSR (downloaded once, then the coarse download of the level before);
+//   graph   method 0: the unchanged greedy host aggregation on that level's CSR (downloaded once, then the coarse download of the
+//           level before), coarse levels through gcge_hip_mat_create — whose row order search may re-order a level of 65 536 rows or
+//           more inside its handle while P / P^T keep the hierarchy's numbering: open for this method;
+//           method 1 (gcge_mg_set_graph_method): MIS-2 aggregation on the level's device CSR (mg_aggregate.hip; host-driven rounds, one
+//           int per round comes back, the level itself does not), coarse levels through gcge_hip_mat_create_as_given: rows as given,
+//           so P / P^T, the blocks of MultiVecCreateByMat and the smoother's parked blocks agree by construction.  Rounds that reach
+//           their cap hand the level to the host routine on a downloaded CSR;
 //   masked  a handle that carries the geometry of a masked grid (gcge_hip_mat_geometry: the grid points inside a sphere in scan order,
 //           the PARSEC matrices): the occupied 2 x 2 x 2 cells of its bounding box, in scan order of the coarse box a masked grid
 //           again, from the device-resident box array (counts, two sums, members by binary search); the coarse box array comes back
@@ -272,6 +282,7 @@ static bool multigrid_create_device(const MgSlot& s, const GCGE_HIP_MAT_* mA, co
   GCGE_CSR hostA; memset(&hostA, 0, sizeof hostA);       // the level's CSR on the host once it is there (what a graph level aggregates)
   int* d_box = mA->d_box; bool own_box = false;          // masked: the level's box array (level 0: the handle's)
   bool ok = true;
+  const bool mis2 = kind == MG_GRAPH && gcge_mg_get_graph_method() == 1, trace = getenv("GCGE_MG_TRACE") != nullptr;
   for (int l = 0; l + 1 < max_levels; ++l) {
     const int nf = fa.n;
     if (nf <= min_rows) break;
@@ -288,13 +299,20 @@ static bool multigrid_create_device(const MgSlot& s, const GCGE_HIP_MAT_* mA, co
       GCGE_HIP_CHECK(hipMalloc(&d_ptr, ((size_t)nc + 1) * sizeof(int)));
       gcge_hip_mg_agg_grid_device(dims, d_agg, d_ptr, d_mem, cdims);
       g_mg_phase[MG_AGGREGATE] += mg_now() - t;
+    } else if (mis2 && (nc = gcge_hip_mg_agg_graph_device(nf, fa.rp, fa.ci, fa.va, theta, d_agg, d_mem, &d_ptr, &g_mg_d2h)) >= 0) {
+      g_mg_phase[MG_AGGREGATE] += mg_now() - t;
+      if (trace) fprintf(stderr, "MultiGridCreate: level %d: %d rows aggregated on the device in %d rounds: %d aggregates\n", l, nf, gcge_hip_mg_graph_rounds(), nc);
     } else {
+      if (mis2) {
+        g_mg_phase[MG_AGGREGATE] += mg_now() - t; t = mg_now();
+        if (trace) fprintf(stderr, "MultiGridCreate: level %d: the device aggregation gave up after %d rounds; aggregated on the host\n", l, gcge_hip_mg_graph_rounds());
+      }
       if (hostA.rowptr == nullptr) {
         if (gcge_hip_mg_download_csr(nf, nf, fa.nnz, fa.rp, fa.ci, fa.va, &hostA, &g_mg_d2h) != 0) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
         g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
       }
       std::vector<int> agg((size_t)nf), ptr, mem;
-      nc = gcge_mg_aggregate_graph(&hostA, theta, agg.data());
+      nc = mis2 ? gcge_mg_aggregate_mis2(&hostA, theta, agg.data()) : gcge_mg_aggregate_graph(&hostA, theta, agg.data());
       if (nc >= 1) gcge_hip_mg_members_host(agg.data(), nf, nc, ptr, mem);
       g_mg_phase[MG_AGGREGATE] += mg_now() - t; t = mg_now();
       if (nc >= 1) {
@@ -334,8 +352,9 @@ static bool multigrid_create_device(const MgSlot& s, const GCGE_HIP_MAT_* mA, co
     }
     g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
     auto upload = [&](const GCGE_CSR& c) {
-      return masked ? gcge_hip_mat_create_grid(nc, c.rowptr, c.colidx, c.val, cdims[0], cdims[1], cdims[2], cbox.data())
-                    : gcge_hip_mat_create(nc, nc, 0, c.rowptr, c.colidx, c.val);
+      if (masked) return gcge_hip_mat_create_grid(nc, c.rowptr, c.colidx, c.val, cdims[0], cdims[1], cdims[2], cbox.data());
+      if (mis2) return gcge_hip_mat_create_as_given(nc, c.rowptr, c.colidx, c.val);
+      return gcge_hip_mat_create(nc, nc, 0, c.rowptr, c.colidx, c.val);
     };
     GCGE_HIP_MAT* a = upload(hc);
     GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");

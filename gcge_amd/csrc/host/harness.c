@@ -10,6 +10,7 @@
 
 #include "gcge_solver.h"
 #include "gcge_pas.h"
+#include "gcge_multigrid.h"
 
 /* ---- BlockAMG as the solver of the W systems: what the reference's SiO2 driver does under OPS_USE_AMG
  * (test/test_eig_sol_SiO2_MAT.c:96-128,160-170): hierarchy from ops->MultiGridCreate, per-level work blocks, parameter arrays
@@ -97,7 +98,12 @@ static int run_gcg(void *A, void *B, int flag, int argc, char *argv[], struct OP
 	ops->GetOptionFromCommandLine("-gcge_amg_smooth", 'i', &amg_smooth, argc, argv, ops);
 	ops->GetOptionFromCommandLine("-gcge_amg_rate", 'f', &amg_rate, argc, argv, ops);
 	if (amg_levels >= 2) {
+		/* -gcge_amg_graph <0|1>: how a matrix without a grid is aggregated (gcge_mg_set_graph_method), for this hierarchy only */
+		const int graph_before = gcge_mg_get_graph_method(); int amg_graph = graph_before;
+		ops->GetOptionFromCommandLine("-gcge_amg_graph", 'i', &amg_graph, argc, argv, ops);
+		gcge_mg_set_graph_method(amg_graph);
 		amg = GCGE_AMGCreate(A, B, amg_levels, block_size, amg_cycles, amg_smooth0, amg_smooth, amg_rate, ops);
+		gcge_mg_set_graph_method(graph_before);
 		if (amg == NULL) { ops->Printf("-gcge_amg_levels: the back-end has no MultiGridCreate\n"); return -7; }
 		GCGE_AMGInstall(amg, ops);
 		flag = 1;
@@ -189,7 +195,7 @@ int GCGE_RunPAS(void *A, void *B, int flag, int argc, char *argv[], struct OPS_ 
 {
 	int nevConv = 30, multiMax = 1, block_size, nevMax, nevInit, L, l, i, rc = 0, pas_conv;
 	double gapMin = 1e-5, tol_pas[2] = {1e-1, 1e-8}, tol_rr[2] = {1e-1, 1e-8}, t0;
-	int pas_levels = 3, pas_max_iter = 50, pas_rr_max_iter = 100, pas_only = 0, sizeV;
+	int pas_levels = 3, pas_max_iter = 50, pas_rr_max_iter = 100, pas_only = 0, sizeV, graph_before, amg_graph;
 	void **A_array = NULL, **B_array = NULL, **P_array = NULL, ***mv_ws[7], **evec, *I0 = NULL;
 	GCGE_MAT_FREE_FN mat_free = NULL;
 	double *eval, *dbl_ws; int *int_ws; long ldbl, lint;
@@ -221,7 +227,11 @@ int GCGE_RunPAS(void *A, void *B, int flag, int argc, char *argv[], struct OPS_ 
 		}
 	}
 	L = pas_levels;
+	graph_before = amg_graph = gcge_mg_get_graph_method();       /* -gcge_amg_graph: as in GCGE_RunGCG */
+	ops->GetOptionFromCommandLine("-gcge_amg_graph", 'i', &amg_graph, argc, argv, ops);
+	gcge_mg_set_graph_method(amg_graph);
 	ops->MultiGridCreate(&A_array, &B_array, &P_array, &L, A, B != NULL ? B : I0, ops);
+	gcge_mg_set_graph_method(graph_before);
 	if (L < 2) {
 		ops->Printf("PAS: the hierarchy has %d level(s); PAS needs 2 or more\n", L);
 		ops->MultiGridDestroy(&A_array, &B_array, &P_array, &L, ops);

@@ -199,6 +199,92 @@ int gcge_mg_aggregate_graph(const GCGE_CSR *A, double theta, int *agg)
 	return nc;
 }
 
+/* ---------------------------------------------------------------- MIS-2 aggregation (the definition: include/gcge_multigrid.h) */
+static int g_graph_method = 0;
+void gcge_mg_set_graph_method(int method) { if (method == 0 || method == 1) g_graph_method = method; }
+int gcge_mg_get_graph_method(void) { return g_graph_method; }
+
+typedef struct { uint64_t key; int row; } Mis2Pri;
+static int cmp_pri_desc(const void *a, const void *b)
+{
+	const Mis2Pri *x = (const Mis2Pri*)a, *y = (const Mis2Pri*)b;
+	if (x->key != y->key) return x->key > y->key ? -1 : 1;
+	return (x->row < y->row) - (x->row > y->row);
+}
+/* entry k of row r is a strong edge to column c */
+static inline int mis2_strong(const GCGE_CSR *A, const double *thr, int n, int r, int k)
+{
+	const int c = A->colidx[k]; const double a = A->val[k];
+	if (c == r || c < 0 || c >= n || a == 0.0) return 0;
+	return fabs(a) >= (thr[r] < thr[c] ? thr[r] : thr[c]);
+}
+
+int gcge_mg_aggregate_mis2(const GCGE_CSR *A, double theta, int *agg)
+{
+	enum { UNDECIDED = 0, ROOT = 1, COVERED = 2 };
+	const int n = A->nrows;
+	const size_t na = n > 0 ? (size_t)n : 1;
+	double *thr = (double*)malloc(na * sizeof(double));
+	Mis2Pri *ord = (Mis2Pri*)malloc(na * sizeof(Mis2Pri));
+	int *num = (int*)malloc(na * sizeof(int)), *second = (int*)malloc(na * sizeof(int)), nc = 0, r, k, k2, i, left;
+	char *state = (char*)calloc(na, 1);
+	if (!thr || !ord || !num || !second || !state) { free(thr); free(ord); free(num); free(second); free(state); return -3; }
+	for (r = 0; r < n; ++r) {
+		double mx = 0.0;
+		for (k = A->rowptr[r]; k < A->rowptr[r + 1]; ++k)
+			if (A->colidx[k] != r && A->colidx[k] >= 0 && A->colidx[k] < n && fabs(A->val[k]) > mx) mx = fabs(A->val[k]);
+		thr[r] = theta * mx;
+		ord[r].key = gcge_mg_mis2_key(r); ord[r].row = r;
+	}
+	/* roots: in descending priority, a row nobody has covered yet is a root and covers everything within two strong edges */
+	qsort(ord, (size_t)n, sizeof(Mis2Pri), cmp_pri_desc);
+	for (i = 0; i < n; ++i) {
+		r = ord[i].row;
+		if (state[r] != UNDECIDED) continue;
+		state[r] = ROOT;
+		for (k = A->rowptr[r]; k < A->rowptr[r + 1]; ++k) {
+			int c;
+			if (!mis2_strong(A, thr, n, r, k)) continue;
+			c = A->colidx[k];
+			if (state[c] == UNDECIDED) state[c] = COVERED;
+			for (k2 = A->rowptr[c]; k2 < A->rowptr[c + 1]; ++k2)
+				if (mis2_strong(A, thr, n, c, k2) && state[A->colidx[k2]] == UNDECIDED) state[A->colidx[k2]] = COVERED;
+		}
+	}
+	do {
+		/* numbering: the roots in ascending row order */
+		for (r = 0, nc = 0; r < n; ++r) { num[r] = nc; nc += state[r] == ROOT; }
+		/* join 1: to the root among the strong neighbours with the largest coupling, ties to the smaller root row */
+		for (r = 0; r < n; ++r) {
+			double best = -1.0; int to = -1;
+			if (state[r] == ROOT) { agg[r] = num[r]; continue; }
+			for (k = A->rowptr[r]; k < A->rowptr[r + 1]; ++k) {
+				const int c = A->colidx[k]; const double w = fabs(A->val[k]);
+				if (!mis2_strong(A, thr, n, r, k) || state[c] != ROOT) continue;
+				if (w > best || (w == best && c < to)) { best = w; to = c; }
+			}
+			agg[r] = to >= 0 ? num[to] : -1;
+		}
+		/* join 2: to the aggregate of the strong neighbour placed so far with the largest coupling, ties to the smaller aggregate;
+		 * kept apart until every row has chosen, so that a row placed here attracts nobody */
+		for (r = 0, left = 0; r < n; ++r) {
+			double best = -1.0; int to = -1;
+			second[r] = -1;
+			if (agg[r] >= 0) continue;
+			for (k = A->rowptr[r]; k < A->rowptr[r + 1]; ++k) {
+				const int c = A->colidx[k]; const double w = fabs(A->val[k]);
+				if (!mis2_strong(A, thr, n, r, k) || agg[c] < 0) continue;
+				if (w > best || (w == best && agg[c] < to)) { best = w; to = agg[c]; }
+			}
+			second[r] = to;
+			if (to < 0) { state[r] = ROOT; ++left; }       /* (an unsymmetric matrix only) */
+		}
+	} while (left > 0);
+	for (r = 0; r < n; ++r) if (agg[r] < 0) agg[r] = second[r];
+	free(thr); free(ord); free(num); free(second); free(state);
+	return nc;
+}
+
 /* ---------------------------------------------------------------- transfers and coarse operators */
 /* members of every aggregate in ascending fine-row order: ptr[nc + 1], mem[nf] */
 static int aggregate_members(const int *agg, int nf, int nc, int **ptr_out, int **mem_out)
@@ -364,7 +450,7 @@ static int mg_alloc(GCGE_MG *mg, const GCGE_CSR *A, const GCGE_CSR *B, int max_l
 	return 0;
 }
 
-/* gcge_mg_build (box_of_row == NULL: a detected grid, or the graph with theta = g_theta; dims recorded on a grid only) and
+/* gcge_mg_build (box_of_row == NULL: a detected grid, or the graph by the selected method with theta = g_theta; dims recorded on a grid only) and
  * gcge_mg_build_masked (the cells of the box `dims` at every level, every level's dims and box array recorded) */
 static int mg_build_levels(const GCGE_CSR *A, const GCGE_CSR *B, const int *dims, const int *box_of_row, int max_levels, int min_rows,
 		double scale, GCGE_MG *mg)
@@ -393,7 +479,7 @@ static int mg_build_levels(const GCGE_CSR *A, const GCGE_CSR *B, const int *dims
 		if (agg == NULL || (masked && cbox == NULL)) { free(agg); free(cbox); gcge_mg_free(mg); return -3; }
 		if (masked) nc = gcge_mg_aggregate_masked(d, box[l], nf, agg, cdims, cbox);
 		else if (have_grid) nc = gcge_mg_aggregate_grid(d, agg, cdims);
-		else nc = gcge_mg_aggregate_graph(Af, g_theta, agg);
+		else nc = g_graph_method == 1 ? gcge_mg_aggregate_mis2(Af, g_theta, agg) : gcge_mg_aggregate_graph(Af, g_theta, agg);
 		if (masked && nc < 0) { free(agg); free(cbox); gcge_mg_free(mg); return nc; }             /* (level 0 only: -2 / -3) */
 		if (nf <= min_rows || nc < 1 || (long)nc * 3 > (long)nf * 2) { free(agg); free(cbox); break; }     /* small enough / coarsening stalled */
 		rc = gcge_mg_galerkin(Af, agg, nc, scale, &mg->A[l + 1]);

@@ -172,6 +172,53 @@ def mg_aggregate_masked(dims, box_of_row, device=False):
     return (nc, agg[:n], tuple(cd), cbox[:nc].copy(), ptr[:nc + 1].copy(), mem[:n]) if nc >= 0 else (nc, None, None, None, None, None)
 
 
+def multigrid_graph_method(method=None):
+    """How a matrix without a grid is aggregated (gcge_mg_set_graph_method, include/gcge_multigrid.h), process-wide, by the host
+    builders and by MultiGridCreate of every back-end: 0 the greedy routine (default), 1 MIS-2; returns the method in force."""
+    h = host_lib()
+    if method is not None:
+        h.gcge_mg_set_graph_method(C.c_int(int(method)))
+    return h.gcge_mg_get_graph_method()
+
+
+def mg_aggregate_graph(arrays_or_mat, theta=0.25, device=False):
+    """MIS-2 aggregation (gcge_mg_aggregate_mis2, include/gcge_multigrid.h) of a symmetric matrix: (nc, agg) from the host routine
+    for (rowptr, colidx, val) arrays, or with device=True (nc, agg, ptr, mem) from the kernels of the HIP back-end for such arrays
+    or a HIP matrix handle (its device CSR; ptr / mem: the members of every aggregate in ascending row order).  nc < 0: the routine
+    failed (the arrays are then None)."""
+    import numpy as np
+    ip, dp = C.POINTER(C.c_int), C.POINTER(C.c_double)
+    if isinstance(arrays_or_mat, (tuple, list)):
+        rp, ci, va = (np.ascontiguousarray(arrays_or_mat[0], dtype=np.int32), np.ascontiguousarray(arrays_or_mat[1], dtype=np.int32),
+                      np.ascontiguousarray(arrays_or_mat[2], dtype=np.float64))
+        n, mat = len(rp) - 1, None
+    else:
+        if not device:
+            raise ValueError("the host routine takes (rowptr, colidx, val) arrays")
+        h = hip_lib()
+        h.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
+        n, mat = h.gcge_hip_mat_nrows(arrays_or_mat), arrays_or_mat
+    agg = np.zeros(max(n, 1), dtype=np.int32)
+    if not device:
+        A = CSR(n, n, 0, len(ci), rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), va.ctypes.data_as(dp))
+        f = host_lib().gcge_mg_aggregate_mis2
+        f.argtypes = [C.POINTER(CSR), C.c_double, ip]
+        nc = f(C.byref(A), float(theta), agg.ctypes.data_as(ip))
+        return (nc, agg[:n]) if nc >= 0 else (nc, None)
+    ptr, mem = np.zeros(n + 1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
+    h = hip_lib()
+    if mat is None:
+        f = h.gcge_hip_mg_aggregate_graph_csr
+        f.argtypes = [C.c_int, ip, ip, dp, C.c_double, ip, ip, ip]
+        nc = f(n, rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), va.ctypes.data_as(dp), float(theta), agg.ctypes.data_as(ip),
+               ptr.ctypes.data_as(ip), mem.ctypes.data_as(ip))
+    else:
+        f = h.gcge_hip_mg_aggregate_graph
+        f.argtypes = [C.c_void_p, C.c_double, ip, ip, ip]
+        nc = f(mat, float(theta), agg.ctypes.data_as(ip), ptr.ctypes.data_as(ip), mem.ctypes.data_as(ip))
+    return (nc, agg[:n], ptr[:nc + 1].copy(), mem[:n]) if nc >= 0 else (nc, None, None, None)
+
+
 def mg_galerkin_device(mat, agg, nc, scale):
     """scale P^T A P on the device for a HIP matrix handle and an aggregate map (numpy int32): (rowptr, colidx, val)."""
     import numpy as np

@@ -50,6 +50,10 @@ GCGE_HIP_MAT *gcge_hip_mat_create_csr (const GCGE_CSR *A);
  * map); results are those of gcge_hip_mat_create on the same arrays.                                                          */
 GCGE_HIP_MAT *gcge_hip_mat_create_grid (int nrows, const int *rowptr, const int *colidx, const double *val,
 		int nx, int ny, int nz, const int *box_of_row);
+/* a whole matrix (one rank) whose rows stay as given: the row order search of gcge_hip_mat_create is not run and the order of another
+ * live matrix of the same size is not adopted; gcge_hip_mat_row_order reports "as given".  What MultiGridCreate uploads the coarse
+ * levels of a MIS-2 hierarchy with (below).                                                                                     */
+GCGE_HIP_MAT *gcge_hip_mat_create_as_given (int nrows, const int *rowptr, const int *colidx, const double *val);
 /* A matrix of that kind that names NO geometry (read from a file: gcge_load_matrix_market, gcge_load_petsc_binary) gets it
  * recovered at upload by gcge_hip_mat_create itself: x lines from the (r, r + 1) couplings, planes and the shifts between
  * lines / planes from the votes of the star rows' + y / + z neighbours.  A wrong guess costs speed, never the result (the
@@ -94,7 +98,7 @@ double gcge_hip_multigrid_seconds (void);    /* host + upload time of the last M
 /*     Where the hierarchy is built (whole matrices, one rank; row slabs always coarsen as below).  mode 0 (default): on the device
  *     (csrc/hip/mg_device.hip) from the handle's device CSR — grid detection from the sampled rows only, grid aggregates, members and
  *     the Galerkin products A_{l+1} = scale P^T A_l P on the device, P / P^T built there; graph levels download their CSR for the
- *     host aggregation; every coarse level is downloaded for gcge_hip_mat_create.  Bit-identical to mode 1, the host build
+ *     host aggregation (graph method 0, below); every coarse level is downloaded for gcge_hip_mat_create.  Bit-identical to mode 1, the host build
  *     (gcge_mg_build on the downloaded CSR), which mode 0 also falls back to when a level is out of the kernels' reach.         */
 void gcge_hip_multigrid_mode (int mode);
 int  gcge_hip_multigrid_get_mode (void);
@@ -111,6 +115,23 @@ int  gcge_hip_multigrid_get_masked_cells (void);
  *     as gcge_mg_aggregate_masked and the members of every cell in ascending row order; returns the number of aggregates, < 0 for
  *     a geometry the host routine refuses                                                                                     */
 int  gcge_hip_mg_aggregate_masked (const int dims[3], const int *box_of_row, int nrows, int *agg, int *ptr, int *mem, int *cbox, int cdims[3]);
+/*     Matrices without a grid (FE matrices on tetrahedra, a matrix in an order the upload cannot undo, a masked grid with
+ *     gcge_hip_multigrid_masked_cells (0)): gcge_mg_set_graph_method (include/gcge_multigrid.h) selects how they are aggregated.
+ *     0 (default): the greedy host routine on the level's downloaded CSR, coarse levels through gcge_hip_mat_create.
+ *     1: MIS-2 aggregation (gcge_mg_aggregate_mis2) by the kernels of csrc/hip/mg_aggregate.hip on the level's device CSR, inside the
+ *     same level loop — the fine level never comes back, one int per round does; at most 64 rounds, after which the level is
+ *     aggregated by the host routine on a downloaded CSR (GCGE_MG_TRACE says so).  Every coarse A_l and B_l of such a hierarchy, in
+ *     mode 0 and in mode 1, goes up through gcge_hip_mat_create_as_given: P / P^T, the blocks of MultiVecCreateByMat (A_l) and the
+ *     level's rows agree whatever gcge_hip_spmm_reorder_mode says; level 0 keeps the order of its handle.  Host routine, kernels and
+ *     gcge_mg_build give the same hierarchy byte for byte.  The harness option is -gcge_amg_graph <0|1>.
+ *     gcge_hip_mg_aggregate_graph runs the device routine on a handle's device CSR (tests, tools): agg, mem [nrows], ptr [nrows + 1]
+ *     (the members of every aggregate in ascending row order); returns the number of aggregates, -1 when the rounds reached their
+ *     cap, -2 bad arguments.  _csr: the same for host arrays.  gcge_hip_mg_graph_rounds: the rounds of the last device aggregation;
+ *     gcge_hip_mg_graph_round_cap: the cap, 1 .. 64 (tests of the fall-back).                                                    */
+int  gcge_hip_mg_aggregate_graph (const GCGE_HIP_MAT *A, double theta, int *agg, int *ptr, int *mem);
+int  gcge_hip_mg_aggregate_graph_csr (int n, const int *rowptr, const int *colidx, const double *val, double theta, int *agg, int *ptr, int *mem);
+int  gcge_hip_mg_graph_rounds (void);
+void gcge_hip_mg_graph_round_cap (int cap);
 /*     the last MultiGridCreate: seconds of its phases (detect, aggregate, Galerkin, transfers, coarse upload / analysis, other)
  *     and the bytes copied device to host; GCGE_MG_TRACE prints them                                                           */
 void gcge_hip_multigrid_stats (double *seconds6, long *d2h_bytes);

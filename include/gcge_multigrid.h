@@ -6,7 +6,8 @@
  * app/app_hypre.c BoomerAMG, app/app_lapack.c:863-929 builds a fixed 1-D toy).  This header is what OUR back-ends build
  * it from: plain aggregation on the host CSR arrays —
  *   - a lexicographic nx x ny x nz grid read off the rows' column offsets is coarsened 2 x 2 x 2 (cell-centred);
- *   - any other symmetric matrix by greedy aggregation over its strong couplings (Vanek / Mandel / Brezina);
+ *   - any other symmetric matrix by greedy aggregation over its strong couplings (Vanek / Mandel / Brezina), or, when
+ *     gcge_mg_set_graph_method (1) asks for it, by MIS-2 aggregation (roots two strong edges apart; Bell / Dalton / Olson 2012);
  *   - P is the piecewise-constant prolongation of the aggregates (one 1.0 per row), A_{l+1} = scale * P^T A_l P.
  * scale = 1 is the Galerkin operator.  Piecewise-constant P over-estimates the energy of a smooth coarse function by 2
  * for second-order operators whatever the dimension (only the jumps across aggregate faces count), so the correction a
@@ -46,6 +47,40 @@ int gcge_mg_aggregate_masked (const int dims[3], const int *box_of_row, int nrow
  * coupled to most strongly, pass 3 turns what is left (isolated rows) into aggregates of their own.
  * Returns the number of aggregates.                                                                                */
 int gcge_mg_aggregate_graph (const GCGE_CSR *A, double theta, int *agg);
+
+/* MIS-2 aggregation over the strong couplings, defined so that this sequential routine and the kernels of the HIP back-end
+ * (csrc/hip/mg_aggregate.hip) give the same aggregates byte for byte on a symmetric matrix with ascending columns:
+ *   strength   thr[r] = theta * max |a_rc| over c != r, c < n (0 without such an entry); entry (r, c) is a strong edge when c != r,
+ *              c < n, a_rc != 0 and |a_rc| >= min (thr[r], thr[c]) - read from row r and thr alone, symmetric whenever A is;
+ *   priority   rows are compared by (gcge_mg_mis2_key (r), r), the larger wins; the mixer is a bijection, so no two keys tie;
+ *   roots      the maximal independent set of the distance-2 graph of the strong edges taken greedily in descending priority: a
+ *              row is a root exactly when no root of higher priority lies within two strong edges of it (a row without a strong
+ *              edge is a root); the roots in ascending ROW order are aggregates 0 .. nc - 1, so coarse rows follow the fine order;
+ *   join 1     every other row with a root among its strong neighbours joins the one it is coupled to by the largest |a_rc|
+ *              (ties: the smaller root row);
+ *   join 2     every row still free has a strong neighbour placed in join 1 and joins the aggregate of the one with the largest
+ *              |a_rc| (ties: the smaller aggregate); rows placed here attract nobody.
+ * On a structurally unsymmetric matrix a row the two joins leave free becomes a root itself (renumbered, joins repeated): the
+ * result is a partition whatever the input.  Returns the number of aggregates, -3: out of memory.                          */
+#define GCGE_MG_MIS2_SEED 0x4D49533247434745ULL
+#if defined(__HIPCC__)
+#define GCGE_MG_HD __host__ __device__
+#else
+#define GCGE_MG_HD
+#endif
+/* the 64-bit mixer of gcge_uniform (csrc/host/problems.c) applied to GCGE_MG_MIS2_SEED + r; never 0 for a row index */
+GCGE_MG_HD static inline uint64_t gcge_mg_mis2_key (int r)
+{
+	uint64_t z = GCGE_MG_MIS2_SEED + (uint64_t)r;
+	z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+	z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+	return z ^ (z >> 31);
+}
+int gcge_mg_aggregate_mis2 (const GCGE_CSR *A, double theta, int *agg);
+/* which of the two a matrix without a grid is aggregated by, process-wide like gcge_mg_set_defaults: 0 the greedy routine (default),
+ * 1 MIS-2.  gcge_mg_build and the back-ends' MultiGridCreate slots read it; any other value is ignored.                       */
+void gcge_mg_set_graph_method (int method);
+int  gcge_mg_get_graph_method (void);
 
 /* Ac = scale * P^T A P for the piecewise-constant P of `agg` (nc aggregates): nc x nc CSR, ascending columns.
  * Rows of the sum are accumulated in ascending fine-row order, entries of a row in storage order (deterministic).   */

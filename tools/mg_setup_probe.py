@@ -3,10 +3,17 @@ total set-up time, for one problem of the existing generators.
 
   python tools/mg_setup_probe.py <lap3d|fe3d|sio2> <size> [levels]
   python tools/mg_setup_probe.py ball <G> <K> [levels] [solve]
+  python tools/mg_setup_probe.py perm <size> [levels] [solve]
+  python tools/mg_setup_probe.py delaunay <points> [levels] [solve]
 
 ball: the masked grid of BASELINE config 5 (the ball in the G^3 box, K atoms, R0 = 2.0, R1 = 5.0 as in bench.py --config c5), its
 geometry named; each mode is run with the cells of the box and with the graph branch (gcge_hip_multigrid_masked_cells).  With `solve`: one GCG solve (nev 10, block 64 columns of W) with BlockAMG over each of the
 two hierarchies, 8 / 24 smoothing steps: outer iterations and seconds.
+
+perm: lap3d <size> under a random symmetric permutation; delaunay: the P1 stiffness matrix on the Delaunay tetrahedra of random points in
+a cube (hull nodes eliminated), the matrix of tools/generic_probe.py.  Neither shows a grid in the order it arrives in: both graph
+methods are run (gcge_mg_set_graph_method: 0 greedy on the host, 1 MIS-2 on the device), with GCGE_MG_TRACE on in the measured call (the
+rounds of every level); with `solve` one GCG solve (nev 10) with BlockAMG over each method's hierarchy.
 
 Mode 0 builds the hierarchy on the device (csrc/hip/mg_device.hip), mode 1 on the host (csrc/host/multigrid.c); both give the same
 hierarchy.  Each mode is timed on a fresh MultiGridCreate after one warm-up call; the rows, K1 form and row order of its levels are listed."""
@@ -21,10 +28,11 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     import torch  # noqa: F401  (one libamdhip64, shared with torch)
     from gcge_amd import HipBackend
-    from gcge_amd.lib import ball_geometry, hip_lib, make_problem, multigrid_masked_cells, multigrid_mode, multigrid_stats, run_gcg
+    from gcge_amd.lib import (CSR, ball_geometry, csr_to_scipy, hip_lib, make_problem, multigrid_graph_method, multigrid_masked_cells,
+                              multigrid_mode, multigrid_stats, run_gcg)
     from gcge_amd.ops_struct import OPS
     kind, size = sys.argv[1], int(sys.argv[2])
-    ball = kind == "ball"
+    ball, graph = kind == "ball", kind in ("perm", "delaunay")
     rest = sys.argv[4:] if ball else sys.argv[3:]
     solve = "solve" in rest
     rest = [v for v in rest if v != "solve"]
@@ -41,6 +49,15 @@ def main():
         t = time.perf_counter()
         mA = hip.matrix_grid(A, (size, size, size), ball_geometry(size))
         print("upload with the geometry named: %.2f s" % (time.perf_counter() - t))
+    elif graph:
+        import numpy as np
+        S = permuted_lap3d(make_problem, csr_to_scipy, size) if kind == "perm" else delaunay_stiffness(size)
+        keep = (np.ascontiguousarray(S.indptr, dtype=np.int32), np.ascontiguousarray(S.indices, dtype=np.int32), np.ascontiguousarray(S.data))
+        A, B = CSR(S.shape[0], S.shape[0], 0, int(S.nnz), keep[0].ctypes.data_as(C.POINTER(C.c_int)), keep[1].ctypes.data_as(C.POINTER(C.c_int)),
+                   keep[2].ctypes.data_as(C.POINTER(C.c_double))), None
+        t = time.perf_counter()
+        mA = hip.matrix(A)
+        print("upload: %.2f s, K1 form %s, row order %s" % (time.perf_counter() - t, g.gcge_hip_mat_spmm_form(mA).decode(), g.gcge_hip_mat_row_order(mA).decode()))
     else:
         A, B = make_problem(kind, size)
         mA = hip.matrix(A)
@@ -50,8 +67,11 @@ def main():
     destroy = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p)(st.MultiGridDestroy)
     fine = (A.nrows + 1) * 4 + int(A.nnz) * 12
     print("%s %d: %d rows, %d non-zeros, fine CSR %.1f MB%s" % (kind, size, A.nrows, A.nnz, fine / 1e6, ", with B" if mB else ""))
-    for cells in ((1, 0) if ball else (1,)):
+    for method, cells in [(m, 1) for m in (0, 1)] if graph else [(None, c) for c in ((1, 0) if ball else (1,))]:
         multigrid_masked_cells(cells)
+        if graph:
+            multigrid_graph_method(method)
+            print("graph method %d (%s)" % (method, "greedy aggregation on the host" if method == 0 else "MIS-2 aggregation on the device"))
         if ball:
             print("masked cells %s" % ("on: 2 x 2 x 2 cells of the box" if cells else "off: the graph branch"))
         for mode in (0, 1):
@@ -59,9 +79,12 @@ def main():
             for rep in range(2):
                 A_arr, B_arr, P_arr, nl = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int(levels)
                 bref = C.byref(B_arr) if mB is not None else None
+                if graph and rep == 1:
+                    os.environ["GCGE_MG_TRACE"] = "1"
                 t = time.perf_counter()
                 create(C.byref(A_arr), bref, C.byref(P_arr), C.byref(nl), mA, mB, hip.ops_handle)
                 total = time.perf_counter() - t
+                os.environ.pop("GCGE_MG_TRACE", None)
                 secs, d2h = multigrid_stats()
                 if rep == 1:
                     for lev, a in enumerate(C.cast(A_arr, C.POINTER(C.c_void_p * nl.value)).contents):
@@ -79,7 +102,48 @@ def main():
                                                          "-gcge_initX_orth_method", "chol", "-gcge_compW_orth_method", "chol"])
             print("  GCG + BlockAMG (8 / 24 smoothing steps): nevConv %d, %d outer iterations, %.2f s (set-up included), lambda_1 %.12g" % (
                 res.nevConv, res.numIter, time.perf_counter() - t, ev[0]))
+        if graph and solve:
+            hip.set_random_mode(0)
+            C.CDLL(None).srand(0)
+            t = time.perf_counter()
+            ev, res = run_gcg(hip.ops_handle, mA, None, ["-nevConv", 10, "-gcge_amg_levels", levels, "-gcge_amg_graph", method,
+                                                         "-gcge_initX_orth_method", "chol", "-gcge_compW_orth_method", "chol"])
+            print("  GCG + BlockAMG over the method-%d hierarchy: nevConv %d, %d outer iterations, %.2f s (set-up included), lambda_1 %.12g" % (
+                method, res.nevConv, res.numIter, time.perf_counter() - t, ev[0]))
     multigrid_masked_cells(1)
+    multigrid_graph_method(0)
+
+
+def permuted_lap3d(make_problem, csr_to_scipy, size, seed=7):
+    import numpy as np
+    S = csr_to_scipy(make_problem("lap3d", size)[0])
+    p = np.random.default_rng(seed).permutation(S.shape[0])
+    S = S[p][:, p].tocsr()
+    S.sort_indices()
+    return S
+
+
+def delaunay_stiffness(npts, seed=1):
+    """P1 stiffness matrix on the Delaunay tetrahedra of npts random points in the unit cube, the hull nodes eliminated (Dirichlet)"""
+    import numpy as np
+    import scipy.sparse as sp
+    from scipy.spatial import Delaunay
+    pts = np.random.default_rng(seed).random((npts, 3))
+    tri = Delaunay(pts)
+    T = tri.simplices
+    M = np.concatenate([np.ones((T.shape[0], 4, 1)), pts[T]], axis=2)
+    vol = np.abs(np.linalg.det(M)) / 6.0
+    ok = vol > 1e-14
+    T, M, vol = T[ok], M[ok], vol[ok]
+    Gm = np.linalg.inv(M)[:, 1:, :]                  # gradients of the barycentric coordinates
+    Ke = np.einsum("tdi,tdj->tij", Gm, Gm) * vol[:, None, None]
+    I, J = np.repeat(T[:, :, None], 4, axis=2).ravel(), np.repeat(T[:, None, :], 4, axis=1).ravel()
+    K = sp.coo_matrix((Ke.ravel(), (I, J)), shape=(npts, npts)).tocsr()
+    inner = np.setdiff1d(np.arange(npts), np.unique(tri.convex_hull.ravel()))
+    K = K[inner][:, inner].tocsr()
+    K = ((K + K.T) * 0.5).tocsr()                    # (the assembly sums in an order of its own: symmetric to the last bit)
+    K.sort_indices()
+    return K
 
 
 if __name__ == "__main__":
