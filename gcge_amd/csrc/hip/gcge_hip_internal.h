@@ -166,6 +166,7 @@ int gcge_hip_lincomb_norms(int nrows, const double* d_x, long ldx, int k, const 
 // vec_kernels.hip
 double* gcge_hip_partial_ws(size_t len);
 void gcge_hip_reduce_partials(const double* d_partial, int nblocks, int len, double* d_out, void* stream);
+void gcge_hip_reduce_partials_head(const double* d_partial, int nblocks, int len, int nout, double* d_out, void* stream);
 void gcge_hip_reduce_partials16(const double* d_partial, int nblocks, long slab_stride, int ncols, double* d_out, void* stream);
 void gcge_hip_reduce_partials_slabs(const double* d_partial, int nblocks, long slab_stride, int cpp, int ncols, double* d_out, void* stream);
 int gcge_hip_resid_sq(int nrows, const double* d_w, long ldw, const double* d_x, long ldx, int m, const double* d_lambda, double* d_out, void* stream);

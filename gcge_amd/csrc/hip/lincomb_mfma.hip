@@ -560,6 +560,6 @@ extern "C" int gcge_hip_lincomb_norms(int nrows, const double* d_x, long ldx, in
   const int rc = lc_dispatch(nrows, d_x, ldx, k, d_c, m, d_beta, d_y, ldy, st, 2, ep);
   if (rc != 0) return rc;
   hipLaunchKernelGGL(lc_norms_chunks, dim3(nchunks), dim3(1024), 0, st, part, nwaves, chunk, part + nwaves * 64);
-  gcge_hip_reduce_partials(part + nwaves * 64, nchunks, 64, d_norms, st);
+  gcge_hip_reduce_partials_head(part + nwaves * 64, nchunks, 64, m, d_norms, st);   // d_norms holds m sums, the slab rows 64
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -330,8 +330,9 @@ __global__ __launch_bounds__(256) void resid_sq_partial(long nrows, const double
 }
 // out[j] = sum_b partial[b*len + j]; 16 row groups x 64 columns per block, fixed summation
 // tree => bitwise reproducible, and no thread walks more than nblocks/16 entries
+// (rows of len sums each; the first nout <= len of them are written)
 __global__ __launch_bounds__(1024) void reduce_partials(const double* __restrict__ partial, int nblocks, int len,
-    double* __restrict__ out) {
+    double* __restrict__ out, int nout) {
   __shared__ double red[16][64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int j = blockIdx.x * 64 + tx;
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(1024) void reduce_partials(const double* __restrict
     if (ty < h) red[ty][tx] += red[ty + h][tx];
     __syncthreads();
   }
-  if (ty == 0 && j < len) out[j] = red[0][tx];
+  if (ty == 0 && j < nout) out[j] = red[0][tx];
 }
 
 __device__ __forceinline__ double u01(unsigned long long seed, unsigned long long index) {
@@ -638,7 +639,7 @@ extern "C" int gcge_hip_panel_dot1(int nrows, const double* d_x, long ldx, int k
   panel_geometry(nrows, rpi, &nb, &rpb);
   double* part = gcge_hip_partial_ws((size_t)nb * k);
   hipLaunchKernelGGL(panel_dot1_partial<4>, dim3((unsigned)nb), dim3(256), 0, st, (long)nrows, d_x, ldx, d_y, ldy, k, part, rpb, tpc);
-  hipLaunchKernelGGL(reduce_partials, dim3((k + 63) / 64), dim3(1024), 0, st, part, (int)nb, k, d_out);
+  hipLaunchKernelGGL(reduce_partials, dim3((k + 63) / 64), dim3(1024), 0, st, part, (int)nb, k, d_out, k);
   return (int)hipGetLastError();
 }
 // Y[:, 0:m) = x c^T + Y diag(beta): d_c, d_beta device arrays of m (d_beta NULL: beta = 1)
@@ -664,7 +665,7 @@ extern "C" int gcge_hip_mgs_step(int nrows, double* d_xk, long ld, double s, con
   panel_geometry(nrows, rpi, &nb, &rpb);      // the SAME slabs as gcge_hip_panel_dot1 would take for these w columns
   double* part = gcge_hip_partial_ws((size_t)nb * w);
   hipLaunchKernelGGL(mgs_step_kernel<4>, dim3((unsigned)nb), dim3(256), 0, st, (long)nrows, d_xk, ld, s, d_c, w, part, rpb, tpc);
-  hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(1024), 0, st, part, (int)nb, w, d_dots);
+  hipLaunchKernelGGL(reduce_partials, dim3(1), dim3(1024), 0, st, part, (int)nb, w, d_dots, w);
   return (int)hipGetLastError();
 }
 extern "C" int gcge_hip_colscale1(int nrows, double* d_y, long ldy, double s, void* stream) {
@@ -688,7 +689,7 @@ extern "C" int gcge_hip_coldots(int nrows, const double* d_x, long ldx, const do
   double* part = gcge_hip_partial_ws((size_t)nb * m);
   hipLaunchKernelGGL(coldots_partial, dim3((unsigned)nb), dim3(256), 0, st, (long)nrows, d_x, ldx, d_y, ldy, m,
                      part, rpb);
-  hipLaunchKernelGGL(reduce_partials, dim3((m + 63) / 64), dim3(1024), 0, st, part, (int)nb, m, d_out);
+  hipLaunchKernelGGL(reduce_partials, dim3((m + 63) / 64), dim3(1024), 0, st, part, (int)nb, m, d_out, m);
   return (int)hipGetLastError();
 }
 
@@ -705,7 +706,7 @@ extern "C" int gcge_hip_coldots2(int nrows, const double* d_x, long ldx, const d
   nb = ((long)nrows + rpb - 1) / rpb;
   double* part = gcge_hip_partial_ws((size_t)nb * 2 * m);
   hipLaunchKernelGGL(coldots2_partial, dim3((unsigned)nb), dim3(256), 0, st, (long)nrows, d_x, ldx, d_y, ldy, m, part, rpb);
-  hipLaunchKernelGGL(reduce_partials, dim3((2 * m + 63) / 64), dim3(1024), 0, st, part, (int)nb, 2 * m, d_out);
+  hipLaunchKernelGGL(reduce_partials, dim3((2 * m + 63) / 64), dim3(1024), 0, st, part, (int)nb, 2 * m, d_out, 2 * m);
   return (int)hipGetLastError();
 }
 
@@ -713,14 +714,15 @@ extern "C" int gcge_hip_coldots2(int nrows, const double* d_x, long ldx, const d
 extern "C" int gcge_hip_resid_sq(int nrows, const double* d_w, long ldw, const double* d_x, long ldx, int m, const double* d_lambda,
                                  double* d_out, void* stream) {
   gcge_hip_apply_pending();
-  if (nrows <= 0 || m <= 0) return 0;
+  if (m <= 0) return 0;
   hipStream_t st = (hipStream_t)stream;
+  if (nrows <= 0) return (int)hipMemsetAsync(d_out, 0, m * sizeof(double), st);   // an empty slab adds zeros to the sum across ranks
   long nb = ((long)nrows + 255) / 256; if (nb > 2048) nb = 2048;
   const long rpb = (((long)nrows + nb - 1) / nb + 3) / 4 * 4;
   nb = ((long)nrows + rpb - 1) / rpb;
   double* part = gcge_hip_partial_ws((size_t)nb * m);
   hipLaunchKernelGGL(resid_sq_partial, dim3((unsigned)nb), dim3(256), 0, st, (long)nrows, d_w, ldw, d_x, ldx, m, d_lambda, part, rpb);
-  hipLaunchKernelGGL(reduce_partials, dim3((m + 63) / 64), dim3(1024), 0, st, part, (int)nb, m, d_out);
+  hipLaunchKernelGGL(reduce_partials, dim3((m + 63) / 64), dim3(1024), 0, st, part, (int)nb, m, d_out, m);
   return (int)hipGetLastError();
 }
 
@@ -777,7 +779,12 @@ extern "C" void gcge_hip_reduce_partials16(const double* d_partial, int nblocks,
 // exported so other translation units reuse the same fixed-order reduction
 extern "C" void gcge_hip_reduce_partials(const double* d_partial, int nblocks, int len, double* d_out, void* stream) {
   hipLaunchKernelGGL(reduce_partials, dim3((len + 63) / 64), dim3(1024), 0, (hipStream_t)stream, d_partial, nblocks,
-                     len, d_out);
+                     len, d_out, len);
+}
+// the same sums from rows of len, of which only the first nout are written (a slab whose rows are padded to a fixed width)
+extern "C" void gcge_hip_reduce_partials_head(const double* d_partial, int nblocks, int len, int nout, double* d_out, void* stream) {
+  hipLaunchKernelGGL(reduce_partials, dim3((nout + 63) / 64), dim3(1024), 0, (hipStream_t)stream, d_partial, nblocks,
+                     len, d_out, nout);
 }
 
 extern "C" int gcge_hip_fill_uniform(int nrows, long row_begin, long nglobal, double* d_y, long ldy, int c0,
