@@ -186,6 +186,13 @@ int gcge_hip_pad8_spmm_dot(int nrows, const int* d_orp, const int* d_pcol, const
 void gcge_hip_spmm_pad8_auto(double avg_octets_per_row);
 void gcge_hip_spmm_pad8_row_map(const int* d_map);
 void gcge_hip_spmm_pad8_row_map_add(const int* d_map);
+void gcge_hip_spmm_pad8_tune(int rows_per_wave, int batch, int store_policy, int col_pass);   // rows_per_wave 0: back to automatic
+void gcge_hip_spmm_pad8_gridcap(int cap);
+void gcge_hip_spmm_pad8_schedule(const int* d_sched, int len, int rows_per_wave, int grid);
+// spmm.hip: process-wide tuning of the CSR kernels (defaults: 16 rows per wave, XCD group 1, plain stores; the stream kernel, batch 16; no map)
+void gcge_hip_spmm_tune(int rows_per_wave, int xcd_group, int nt_store);
+void gcge_hip_spmm_variant(int variant, int batch);
+void gcge_hip_spmm_set_chunk_map(const int* d_map, unsigned len);
 // spmm_pattern.hip, spmm_ring.hip
 int gcge_hip_pattern_spmm_vals(int nrows, const unsigned short* d_pid, const void* d_tab, int npat, int lt, long span, long span2, const double* d_x,
                                long ldx, double* d_y, long ldy, int ncols, double* d_dots, double* d_dots_yy, void* stream, long near,

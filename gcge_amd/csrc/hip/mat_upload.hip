@@ -251,7 +251,9 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local_ghosts(int nrows, int ncols_l
   GCGE_HIP_CHECK(hipMemcpy(A->d_rowptr, rowptr, ((size_t)nrows + 1) * sizeof(int), hipMemcpyHostToDevice));
   GCGE_HIP_CHECK(hipMemcpy(A->d_colidx, colidx, nnz * sizeof(int), hipMemcpyHostToDevice));
   GCGE_HIP_CHECK(hipMemcpy(A->d_val, val, nnz * sizeof(double), hipMemcpyHostToDevice));
-  // pad-8 copy: every row padded to a multiple of 8 entries with (own column, 0.0)
+  // pad-8 copy: every row padded to a multiple of 8 entries with (own column, 0.0).  The kernel LOADS the X row a pad names (weight
+  // 0), so a pad's column must be a row of X: row r is one because ncols_local >= nrows (required above, nghost >= 0).  Matrices
+  // with more rows than columns (multigrid.hip's prolongations) have no pad-8 copy and take gcge_hip_csr_spmm.
   std::vector<int> orp((size_t)nrows + 1);
   size_t noct = 0;
   for (int r = 0; r < nrows; ++r) { orp[r] = (int)noct; noct += ((size_t)(rowptr[r + 1] - rowptr[r]) + 7) / 8; }

@@ -11,7 +11,10 @@
 //     (pad entries: the row's own column with value 0, so every load is
 //     unconditional — a branch around a load makes hipcc drain vmcnt(0) after
 //     each one), so a step of G <= 8 non-zeros never straddles a row and
-//     64-entry index/value chunks stay aligned;
+//     64-entry index/value chunks stay aligned.  A pad is LOADED like any entry:
+//     its column must name a row of X (the uploads pad row r with column r and
+//     require ncols_local >= nrows; a caller with more rows than X has pads
+//     any valid row), and that row of X must be finite;
 //   * BATCH steps are in flight per wave regardless of row boundaries;
 //   * Y is written once with a cache policy chosen by the caller
 //     (plain / nt / sc1 = write-through without keeping the line in L2).
@@ -221,12 +224,20 @@ extern "C" void gcge_hip_spmm_pad8_auto(double avg_octets_per_row) {
   if (g_p8_user) return;
   g_p8_rpw = avg_octets_per_row >= 4.0 ? 1 : (avg_octets_per_row >= 2.5 ? 2 : (avg_octets_per_row >= 1.5 ? 4 : 8));
 }
+// Tuning by hand (experiments, tests): holds for the process until rows_per_wave == 0 hands the choice back to
+// gcge_hip_spmm_pad8_auto and restores batch 8 / store 1 (nt) / col_pass 0, whatever the other arguments say.  Values out of range
+// leave their knob alone.  col_pass: columns per pass, 0 = the widest that fits (128) — even and at most 128: a pass stores
+// 16-byte pairs (an odd cap would write a column beyond ncols) and one wave covers 128 columns.
 extern "C" void gcge_hip_spmm_pad8_tune(int rows_per_wave, int batch, int store_policy, int col_pass) {
+  if (rows_per_wave == 0) {
+    g_p8_user = 0; g_p8_rpw = 8; g_p8_batch = 8; g_p8_store = 1; g_p8_pass = 0;
+    return;
+  }
   g_p8_user = 1;
   if (rows_per_wave >= 1 && rows_per_wave <= 64) g_p8_rpw = rows_per_wave;
   if (batch == 4 || batch == 8 || batch == 16) g_p8_batch = batch;
   if (store_policy >= 0 && store_policy <= 2) g_p8_store = store_policy;
-  if (col_pass >= 0) g_p8_pass = col_pass;  // 0: widest pass that fits (<=128 columns)
+  if (col_pass >= 0 && col_pass <= 128 && (col_pass & 1) == 0) g_p8_pass = col_pass;
 }
 
 static int g_p8_acc_early = 1;   // adding lists request their Y rows up front (0: at the end of each row, the round-4 form)
@@ -236,6 +247,9 @@ extern "C" void gcge_hip_spmm_pad8_gridcap(int cap) { g_p8_gridcap = cap; }
 // optional per-XCD chunk schedule (device array of 8*len ints) valid for ONE rows-per-wave value
 static const int* g_p8_sched = nullptr; static int g_p8_sched_len = 0, g_p8_sched_rpw = 0, g_p8_sched_grid = 0;
 extern "C" void gcge_hip_spmm_pad8_schedule(const int* d_sched, int len, int rows_per_wave, int grid) {
+  // the kernel deals the lists to gridDim.x / 8 blocks per XCD: a grid that is no positive multiple of 8 would leave slots unwalked
+  // (or, below 8, the walk without an end), so such a schedule is not installed
+  if (len <= 0 || grid < 8 || (grid & 7)) d_sched = nullptr;
   g_p8_sched = d_sched; g_p8_sched_len = len; g_p8_sched_rpw = rows_per_wave; g_p8_sched_grid = grid;
 }
 

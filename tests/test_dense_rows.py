@@ -35,15 +35,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import uniform
-
-GR = 3                                    # guard rows behind nrows
-IN_GUARD = float(2 ** 40)
-OUT_BITS = np.uint64(0xFFF8C0DEC0DEC0DE)  # a NaN no kernel produces
-OUT_GUARD = np.array([OUT_BITS]).view(np.float64)[0]
-# (columns in front of the operand inside ld, parity of ld): origins on even and odd columns, even and odd leading dimensions
-LAYOUTS = [(2, 0), (1, 0), (2, 1), (1, 1)]
-EVEN_LD = [(2, 0), (1, 0)]
+from helpers import (EVEN_LD, IN_GUARD, LAYOUTS, OUT_BITS, OUT_GUARD, Block, bits, check_vec, draw, out_vec, vec)
 
 SMALL = [1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 33, 63, 64, 65, 127, 128, 129, 255, 257, 1023, 1024, 1025]
 GRAM_SHAPES = [(1, 2), (3, 5), (16, 16), (17, 64), (64, 64), (65, 33), (128, 70), (129, 64), (192, 64), (256, 64), (320, 17),
@@ -127,74 +119,6 @@ def slab_rows(kernel, n, cols):
         return cdiv(cdiv(n, max(1, min(cap, nb))), rpi) * rpi, cap, nb
     nb = cdiv(n, 256)                       # coldots, coldots2, resid_sq
     return cdiv(cdiv(n, min(2048, nb)), 4) * 4, 2048, nb
-
-
-# ---- data ---------------------------------------------------------------------------------------------------------------------
-def draw(seed, shape, real):
-    """nonzero integers in [-3, 3] as doubles, or uniform - 0.5"""
-    if real and int(np.prod(shape)) <= 1 << 20:
-        return np.ascontiguousarray(uniform(seed, shape) - 0.5)
-    if real:   # (the splitmix stream in numpy takes seconds at the threshold rows)
-        return np.random.default_rng(seed).random(shape) - 0.5
-    v = np.random.default_rng(seed).integers(0, 6, shape, dtype=np.int8)
-    return (v - 3 + (v >= 3)).astype(np.float64)
-
-
-def bits(a):
-    return a.view(np.uint64)
-
-
-class Block:
-    """A row-major block of rows + GR rows and ld columns filled with `guard`, the operand at [0, rows) x [gl, gl + cols)."""
-
-    def __init__(self, torch, data, layout, guard, gl=None):
-        rows, cols = data.shape
-        self.gl = layout[0] if gl is None else gl
-        gr = 1 if (self.gl + cols + 1) % 2 == layout[1] else 2
-        self.rows, self.cols, self.ld, self.guard = rows, cols, self.gl + cols + gr, guard
-        self.host = np.full((rows + GR, self.ld), guard)
-        self.host[:rows, self.gl:self.gl + cols] = data
-        self.dev = torch.from_numpy(self.host).cuda()
-        self.ptr = self.dev.data_ptr() + 8 * self.gl
-
-    def check(self, ref, what, bound=None):
-        """operand == ref (or within bound of it), everything round it bit for bit what it was"""
-        got = self.dev.cpu().numpy()
-        op = got[:self.rows, self.gl:self.gl + self.cols]
-        if bound is None:
-            assert np.array_equal(op, ref), (what, "operand", np.argwhere(op != ref)[:4].tolist())
-        else:
-            assert np.all(np.abs(op - ref) <= bound), (what, float(np.max(np.abs(op - ref) / bound)))
-        gb = bits(np.array([self.guard]))[0]
-        for name, part in (("rows behind", got[self.rows:]), ("columns in front", got[:self.rows, :self.gl]),
-                           ("columns behind", got[:self.rows, self.gl + self.cols:])):
-            assert np.all(bits(part) == gb), (what, "guard", name)
-
-    def unchanged(self, what):
-        assert np.array_equal(bits(self.dev.cpu().numpy()), bits(self.host)), (what, "an input block was written")
-
-
-def vec(torch, data, guard=IN_GUARD):
-    """a device vector with one guard entry in front and GR behind: (tensor, pointer of element 0)"""
-    data = np.asarray(data, dtype=np.float64).ravel()
-    host = np.concatenate([[guard, guard], data, [guard] * GR])    # two in front: the vector stays 16-byte aligned
-    dev = torch.from_numpy(host).cuda()
-    return dev, dev.data_ptr() + 16, data.size
-
-
-def check_vec(v, ref, what, bound=None):
-    dev, _, n = v
-    got = dev.cpu().numpy()
-    ref = np.asarray(ref).ravel()
-    if bound is None:
-        assert np.array_equal(got[2:2 + n], ref), (what, "result", np.argwhere(got[2:2 + n] != ref)[:4].tolist())
-    else:
-        assert np.all(np.abs(got[2:2 + n] - ref) <= np.asarray(bound).ravel()), (what, float(np.max(np.abs(got[2:2 + n] - ref) / np.asarray(bound).ravel())))
-    assert np.all(bits(got[:2]) == OUT_BITS) and np.all(bits(got[2 + n:]) == OUT_BITS), (what, "guard round the result")
-
-
-def out_vec(torch, n):
-    return vec(torch, np.full(n, OUT_GUARD), OUT_GUARD)
 
 
 # ---- the operations in plain numpy, written so that they take float64, int64, longdouble or absolute values alike ------------
