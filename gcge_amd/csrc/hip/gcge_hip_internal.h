@@ -92,7 +92,17 @@ struct GCGE_HIP_MAT_ {
 struct GcgePerm { int n; int* perm; int* iperm; int identity; long refs; unsigned id; };
 extern "C" struct GcgePerm* gcge_hip_perm_acquire(struct GcgePerm* p);      // ++refs (NULL passes through)
 extern "C" void gcge_hip_perm_release(struct GcgePerm* p);
+extern "C" struct GcgePerm* gcge_hip_perm_live(int n);          // mat_upload.hip: the live order of size n (NULL: none); no reference taken
+extern "C" struct GcgePerm* gcge_hip_perm_identity(int n);      // ... the identity order of size n, registered if none is live (NULL: a re-ordered one is)
 extern "C" void gcge_hip_halo_native_free(struct GCGE_HIP_MAT_* A);
+// mat_device.hip: gcge_hip_mat_create_device whose fall-back is gcge_hip_mat_create_as_given and which runs beside a re-ordered matrix of
+// its size (the coarse levels of a MIS-2 hierarchy, multigrid.hip)
+extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_device_as_given(int nrows, long nnz, const int* d_rowptr, const int* d_colidx, const double* d_val);
+// tests only: a download of d_pid (nrows) / d_tab (npat * pat_lt entries of 16 bytes), returns npat * pat_lt (0: no pattern form; NULL
+// outputs are skipped); and the row hash of the device search cut to its low bits (64: all of it, the default; small values force
+// collisions for the verify pass to find)
+extern "C" long gcge_hip_mat_pattern_table(const GCGE_HIP_MAT* A, unsigned short* pid_out, void* tab_out);
+extern "C" void gcge_hip_mat_device_hash_bits(int bits);
 // multigrid.hip: the MultiGridCreate / MultiGridDestroy slots of OPS_HIP_Set
 extern "C" void gcge_hip_multigrid_create(void*** A_array, void*** B_array, void*** P_array, int* num_levels, void* A, void* B, struct OPS_* ops);
 extern "C" void gcge_hip_multigrid_destroy(void*** A_array, void*** B_array, void*** P_array, int* num_levels, struct OPS_* ops);

@@ -14,6 +14,7 @@
 
 #include "gcge_hip.h"
 #include "gcge_hip_internal.h"
+#include "pattern_table.h"
 
 #define g_spmm_path (gcge_hip_spmm_path_get())
 #define g_offset_patterns (gcge_hip_offset_patterns_get())
@@ -22,7 +23,7 @@
 // Pattern format: rows written as {(column - row, value)} in CSR order; at most 64 KB of table.  Leaves
 // A->d_pid == NULL when the matrix has too many distinct rows (irregular matrices give up after a few
 // hundred rows, so the scan costs nothing there).
-struct PatEntryH { double val; long off; };
+typedef GcgePatEntry PatEntryH;
 // by_offsets: rows are compared by their column offsets only; the table then carries 1.0 for every present entry and the
 // values travel per row (A->d_rowval: 8 doubles per row in table-slot order, tables of at most 8 slots): stencils with
 // variable coefficients keep the pattern kernels at 64 more bytes per row and 16-column pass.
@@ -33,7 +34,7 @@ static void build_patterns(GCGE_HIP_MAT* A, int nrows, int ncols_local, const in
   for (int r = 0; r < nrows; ++r) maxlen = std::max(maxlen, rowptr[r + 1] - rowptr[r]);
   const int lt = gcge_hip_pattern_width(maxlen);
   if (lt == 0 || nrows == 0 || (by_offsets && lt > 8)) return;
-  const int maxpat = std::min(65535, (int)(64 * 1024 / (lt * sizeof(PatEntryH))));
+  const int maxpat = gcge_pat_max_patterns(lt);
   std::vector<PatEntryH> tab;
   std::unordered_map<uint64_t, std::vector<int>> byhash;
   std::vector<unsigned short> pid((size_t)nrows);
@@ -74,100 +75,36 @@ static void build_patterns(GCGE_HIP_MAT* A, int nrows, int ncols_local, const in
     }
     pid[r] = (unsigned short)found; prev = found;
   }
-  A->npat = (int)(tab.size() / lt); A->pat_lt = lt; A->pat_span = 0;
-  // reuse distance that matters for the launch geometry: the longest offset of the MOST FREQUENT pattern
-  // (interior rows); boundary and halo patterns may reach much further
+  // (b) the table side, shared with the device search (pattern_table.h): spans of the most frequent pattern, then the chain layout
+  // from the rows' distinct (pattern, head, tail, mask) keys in order of first occurrence
+  A->npat = (int)(tab.size() / lt); A->pat_lt = lt;
   std::vector<long> freq((size_t)A->npat, 0);
   for (int r = 0; r < nrows; ++r) ++freq[pid[r]];
-  const int common = (int)(std::max_element(freq.begin(), freq.end()) - freq.begin());
-  A->pat_span2 = 0;
-  for (int k = 0; k < lt; ++k) {
-    const long o = tab[(size_t)common * lt + k].off;
-    A->pat_span = std::max(A->pat_span, o < 0 ? -o : o);
-  }
-  for (int k = 0; k < lt; ++k) {
-    const long o = tab[(size_t)common * lt + k].off, ao = o < 0 ? -o : o;
-    if (ao < A->pat_span) A->pat_span2 = std::max(A->pat_span2, ao);
-  }
-  // Chain layout (spmm_pattern_chain_kernel): possible when the interior stencil reaches -S, 0 and +S with S a
-  // multiple of 32 rows and all patterns together use at most lt distinct offsets.  Every pattern is then rewritten
-  // on the same slots [-S, 0, +S, the other offsets ascending]: entries a row does not have get value 0 but keep
-  // their offset as long as the address stays inside the block of vectors (patterns are split by that validity),
-  // so what a lane loads through a slot depends on its position only, never on its pattern.
-  do {
-    const long S = A->pat_span;
-    if (lt < 4 || S <= 0 || S % 32 != 0) break;
-    // canonical slots: the offsets of the interior stencil, chain first
-    std::vector<long> offs;
-    { bool m = false, c = false, q = false;
-      for (int k = 0; k < lt; ++k) {
-        const PatEntryH& e = tab[(size_t)common * lt + k];
-        if (e.val == 0.0 && e.off == 0) continue;
-        offs.push_back(e.off); m |= e.off == -S; c |= e.off == 0; q |= e.off == S;
-      }
-      if (!(m && c && q)) break; }
-    std::vector<long> slot = {-S, 0, S};
-    std::sort(offs.begin(), offs.end());
-    // second longest offset L with both signs present: slots 3,4 (line exchange of spmm_pattern_chain2_kernel)
-    long Lline = 0;
-    for (long o : offs) { const long ao = o < 0 ? -o : o; if (ao < S && ao > Lline && std::binary_search(offs.begin(), offs.end(), -o)) Lline = ao; }
-    if (Lline >= 8 && Lline % 8 == 0 && lt >= 5) { slot.push_back(-Lline); slot.push_back(Lline); } else Lline = 0;
-    for (long o : offs) if (o != -S && o != 0 && o != S && !(Lline && (o == -Lline || o == Lline))) slot.push_back(o);
-    const int nslot_used = (int)slot.size();
-    if (nslot_used > lt) break;
-    while ((int)slot.size() < lt) slot.push_back(0);            // unused slots: own row, value 0
-    // per generic pattern: value on every canonical slot + the entries that fit no slot ("extras": halo columns of
-    // a row slab).  An extra may ride in slot 0 of a row of the first S rows (no predecessor in the chain: slot 0 is
-    // loaded explicitly when a wave starts) or in slot 2 of a row of the last S rows (no successor reads it).
-    const int np = A->npat;
-    std::vector<double> pval((size_t)np * lt, 0.0);
-    std::vector<std::vector<PatEntryH>> extras((size_t)np);
-    bool ok = true;
-    for (int p = 0; p < np && ok; ++p)
-      for (int k = 0; k < lt; ++k) {
-        const PatEntryH& e = tab[(size_t)p * lt + k];
-        if (e.val == 0.0 && e.off == 0) continue;
-        int sidx = -1;
-        for (int q = 0; q < nslot_used; ++q) if (slot[q] == e.off) { sidx = q; break; }
-        if (sidx >= 0) pval[(size_t)p * lt + sidx] += e.val;
-        else { extras[p].push_back(e); if (extras[p].size() > 2) ok = false; }
-      }
-    if (!ok) break;
+  GcgePatPlan plan;
+  gcge_pat_plan(tab, freq, lt, plan);
+  A->pat_span = plan.span; A->pat_span2 = plan.span2;
+  if (plan.chain) {
     std::unordered_map<uint64_t, int> id_of;
-    std::vector<PatEntryH> ctab;
+    std::vector<uint64_t> keys;
     std::vector<unsigned short> cpid((size_t)nrows);
-    for (int r = 0; r < nrows && ok; ++r) {
-      unsigned mask = 0;   // slots whose canonical address leaves the block of vectors
-      for (int q = 0; q < nslot_used; ++q) { const long c = (long)r + slot[q]; if (c < 0 || c >= ncols_local) mask |= 1u << q; }
-      const unsigned head = r < S, tail = (long)r + S >= nrows;
-      const uint64_t key = ((uint64_t)pid[r] << 32) | ((uint64_t)head << 31) | ((uint64_t)tail << 30) | mask;
+    bool ok = true;
+    for (int r = 0; r < nrows; ++r) {
+      const uint64_t key = gcge_pat_row_key(plan, pid[r], r, nrows, ncols_local);
       auto it = id_of.find(key);
       if (it == id_of.end()) {
-        const int id = (int)(ctab.size() / lt);
-        if (id >= maxpat) { ok = false; break; }
-        std::vector<PatEntryH> row((size_t)lt);
-        for (int q = 0; q < lt; ++q) {
-          row[q].val = pval[(size_t)pid[r] * lt + q];
-          row[q].off = (q < nslot_used && !(mask >> q & 1)) ? slot[q] : 0;
-          if (mask >> q & 1) { if (row[q].val != 0.0) ok = false; row[q].val = 0.0; }   // an entry cannot point outside
-        }
-        for (const PatEntryH& e : extras[pid[r]]) {
-          if (head && row[0].val == 0.0) row[0] = e;
-          else if (tail && row[2].val == 0.0) row[2] = e;
-          else ok = false;
-        }
-        for (int q = 0; q < lt; ++q) ctab.push_back(row[q]);
-        it = id_of.emplace(key, id).first;
+        if ((int)keys.size() >= maxpat) { ok = false; break; }
+        it = id_of.emplace(key, (int)keys.size()).first;
+        keys.push_back(key);
       }
       cpid[r] = (unsigned short)it->second;
     }
-    if (!ok) break;
-    tab.swap(ctab); pid.swap(cpid);
-    A->npat = (int)(tab.size() / lt); A->pat_span2 = Lline ? -Lline : -1;
-    A->pat_near = 0;
-    if (Lline && lt == 7 && nslot_used == 7 && slot[5] == -1 && slot[6] == 1)
-      for (const PatEntryH& e : tab) A->pat_near = std::max(A->pat_near, e.off < 0 ? -e.off : e.off);
-  } while (0);
+    std::vector<PatEntryH> ctab;
+    if (ok && gcge_pat_chain_table(plan, keys, ctab)) {
+      tab.swap(ctab); pid.swap(cpid);
+      A->npat = (int)(tab.size() / lt);
+      gcge_pat_chain_spans(plan, tab, &A->pat_span2, &A->pat_near);
+    }
+  }
   if (by_offsets) {
     // the row's values in the slot order of ITS table row: an entry sits in the slot that carries its offset (the
     // diagonal in slot 1 of a chain-layout table, where slots whose address would leave the block also read offset 0)
@@ -355,6 +292,14 @@ static GcgePerm* perm_register(int n, const int* perm /* NULL: identity */) {
   }
   g_perms.push_back(p);
   return p;
+}
+// for mat_device.hip: the live order of size n (NULL: none), and the identity order of size n, registered when no order of that size
+// is live (NULL: a re-ordered one is) — neither takes a reference
+extern "C" GcgePerm* gcge_hip_perm_live(int n) { return perm_find(n); }
+extern "C" GcgePerm* gcge_hip_perm_identity(int n) {
+  GcgePerm* P = perm_find(n);
+  if (P == nullptr) P = perm_register(n, nullptr);
+  return P->identity ? P : nullptr;
 }
 // P A P^T as CSR with ascending columns: new row i = old row perm[i], old column c -> iperm[c]
 static void permute_csr(int n, const int* rowptr, const int* colidx, const double* val, const GcgePerm* P,

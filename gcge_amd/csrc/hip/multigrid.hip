@@ -247,11 +247,20 @@ static void multigrid_create_host(const MgSlot& s, const GCGE_HIP_MAT_* mA, cons
 //           again, from the device-resident box array (counts, two sums, members by binary search); the coarse box array comes back
 //           with the level, which goes up through gcge_hip_mat_create_grid with ITS geometry: the rows stay as given (P / P^T match
 //           by construction) and the level carries its geometry like a matrix the caller named one for.
+// Grid and MIS-2 levels skip that round trip by default (gcge_hip_multigrid_device_levels): the Galerkin output goes to
+// gcge_hip_mat_create_device (MIS-2: its as-given variant), which analyses it on the device with the host constructors' result and
+// downloads a level only to fall back to them; masked levels need gcge_hip_mat_create_grid and greedy-graph levels are wanted on the
+// host by the next aggregation anyway, so both keep the round trip.
 // Returns false with nothing left behind when a level is out of the kernels' reach (a coarse row of more than 512 distinct columns,
 // 2^31 entries): the caller then builds on the host.
 static int g_mg_masked_cells = 1;
 extern "C" void gcge_hip_multigrid_masked_cells(int on) { g_mg_masked_cells = on != 0; }
 extern "C" int gcge_hip_multigrid_get_masked_cells(void) { return g_mg_masked_cells; }
+// grid and MIS-2 hierarchies: the coarse levels go from the Galerkin output into gcge_hip_mat_create_device (1, default) or are
+// downloaded for the host constructors (0); the same hierarchy either way
+static int g_mg_device_levels = 1;
+extern "C" void gcge_hip_multigrid_device_levels(int on) { g_mg_device_levels = on != 0; }
+extern "C" int gcge_hip_multigrid_get_device_levels(void) { return g_mg_device_levels; }
 static bool mg_is_masked_grid(const GCGE_HIP_MAT_* m) {
   return g_mg_masked_cells && m->geom_kind != 0 && m->d_box != nullptr && (long)m->geom_dims[0] * m->geom_dims[1] * m->geom_dims[2] != (long)m->nrows;
 }
@@ -342,31 +351,54 @@ static bool multigrid_create_device(const MgSlot& s, const GCGE_HIP_MAT_* mA, co
     built.Ps.push_back(p);
     free_agg();
     g_mg_phase[MG_OTHER] += mg_now() - t; t = mg_now();
-    GCGE_CSR hc, hb; memset(&hb, 0, sizeof hb);
-    std::vector<int> cbox(masked ? (size_t)nc : 0);
-    if (gcge_hip_mg_download_csr(nc, nc, ca.nnz, ca.rp, ca.ci, ca.va, &hc, &g_mg_d2h) != 0 ||
-        (mB != nullptr && gcge_hip_mg_download_csr(nc, nc, cb.nnz, cb.rp, cb.ci, cb.va, &hb, &g_mg_d2h) != 0)) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
-    if (masked) {
-      GCGE_HIP_CHECK(hipMemcpy(cbox.data(), d_cbox, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
-      g_mg_d2h += (long)((size_t)nc * sizeof(int));
+    GCGE_CSR hc, hb; memset(&hc, 0, sizeof hc); memset(&hb, 0, sizeof hb);
+    if (g_mg_device_levels && (kind == MG_GRID || mis2)) {
+      // the coarse level never leaves the device: the constructor for device arrays analyses the Galerkin output where it is, and
+      // downloads it only to fall back to the host constructor named below (its bytes are booked here)
+      auto ingest = [&](const DevCsr& c) {
+        long s0[4], s1[4];
+        gcge_hip_mat_device_stats(s0);
+        GCGE_HIP_MAT* m = mis2 ? gcge_hip_mat_create_device_as_given(nc, c.nnz, c.rp, c.ci, c.va) : gcge_hip_mat_create_device(nc, c.nnz, c.rp, c.ci, c.va);
+        gcge_hip_mat_device_stats(s1);
+        g_mg_d2h += s1[3] - s0[3];
+        return m;
+      };
+      GCGE_HIP_MAT* a = ingest(ca);
+      GCGE_REQUIRE(a != nullptr, "MultiGridCreate: a coarse matrix from device arrays");
+      built.As.push_back(a);
+      if (s.B_array != nullptr && mB != nullptr) {
+        GCGE_HIP_MAT* b = ingest(cb);
+        GCGE_REQUIRE(b != nullptr, "MultiGridCreate: a coarse B from device arrays");
+        built.Bs.push_back(b);
+      }
+      g_mg_phase[MG_COARSE] += mg_now() - t;
+      gcge_csr_free(&hostA); memset(&hostA, 0, sizeof hostA);       // (a level the host has to aggregate is downloaded when it is needed)
+    } else {
+      std::vector<int> cbox(masked ? (size_t)nc : 0);
+      if (gcge_hip_mg_download_csr(nc, nc, ca.nnz, ca.rp, ca.ci, ca.va, &hc, &g_mg_d2h) != 0 ||
+          (mB != nullptr && gcge_hip_mg_download_csr(nc, nc, cb.nnz, cb.rp, cb.ci, cb.va, &hb, &g_mg_d2h) != 0)) { fprintf(stderr, "MultiGridCreate: out of host memory\n"); abort(); }
+      if (masked) {
+        GCGE_HIP_CHECK(hipMemcpy(cbox.data(), d_cbox, (size_t)nc * sizeof(int), hipMemcpyDeviceToHost));
+        g_mg_d2h += (long)((size_t)nc * sizeof(int));
+      }
+      g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
+      auto upload = [&](const GCGE_CSR& c) {
+        if (masked) return gcge_hip_mat_create_grid(nc, c.rowptr, c.colidx, c.val, cdims[0], cdims[1], cdims[2], cbox.data());
+        if (mis2) return gcge_hip_mat_create_as_given(nc, c.rowptr, c.colidx, c.val);
+        return gcge_hip_mat_create(nc, nc, 0, c.rowptr, c.colidx, c.val);
+      };
+      GCGE_HIP_MAT* a = upload(hc);
+      GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
+      built.As.push_back(a);
+      if (s.B_array != nullptr && mB != nullptr) {
+        GCGE_HIP_MAT* b = upload(hb);
+        GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
+        built.Bs.push_back(b);
+      }
+      g_mg_phase[MG_COARSE] += mg_now() - t;
+      gcge_csr_free(&hb);
+      gcge_csr_free(&hostA); hostA = hc;
     }
-    g_mg_phase[MG_TRANSFER] += mg_now() - t; t = mg_now();
-    auto upload = [&](const GCGE_CSR& c) {
-      if (masked) return gcge_hip_mat_create_grid(nc, c.rowptr, c.colidx, c.val, cdims[0], cdims[1], cdims[2], cbox.data());
-      if (mis2) return gcge_hip_mat_create_as_given(nc, c.rowptr, c.colidx, c.val);
-      return gcge_hip_mat_create(nc, nc, 0, c.rowptr, c.colidx, c.val);
-    };
-    GCGE_HIP_MAT* a = upload(hc);
-    GCGE_REQUIRE(a != nullptr, "MultiGridCreate: upload of a coarse matrix");
-    built.As.push_back(a);
-    if (s.B_array != nullptr && mB != nullptr) {
-      GCGE_HIP_MAT* b = upload(hb);
-      GCGE_REQUIRE(b != nullptr, "MultiGridCreate: upload of a coarse B");
-      built.Bs.push_back(b);
-    }
-    g_mg_phase[MG_COARSE] += mg_now() - t;
-    gcge_csr_free(&hb);
-    gcge_csr_free(&hostA); hostA = hc;
     devcsr_free(fa); fa = ca;
     devcsr_free(fb); fb = cb;
     if (own_box) hipFree(d_box);

@@ -17,6 +17,11 @@ class HipBackendImpl:
         self.g.gcge_hip_mv_to_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_long]
         self.g.gcge_hip_mv_from_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_long]
         self.g.gcge_hip_set_random_mode.argtypes = [C.c_int, C.c_ulonglong]
+        self.g.gcge_hip_mat_create_device.restype = C.c_void_p
+        self.g.gcge_hip_mat_create_device.argtypes = [C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.g.gcge_hip_mv_to_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long]
+        self.g.gcge_hip_mv_nrows.argtypes = [C.c_void_p]
+        self.device = device
         if self.g.gcge_hip_init(device) != 0:
             raise RuntimeError("HIP back-end: no GPU visible (there is no CPU fallback)")
         self.ops_handle = C.c_void_p()
@@ -31,6 +36,58 @@ class HipBackendImpl:
         if not m:
             raise RuntimeError("gcge_hip_mat_create_csr failed")
         return C.c_void_p(m)
+
+    def matrix_from_device(self, crow, col=None, val=None, nrows=None):
+        """A whole square matrix from CSR arrays that live on the GPU (gcge_hip_mat_create_device): a torch sparse_csr tensor alone,
+        three torch device tensors, or three objects with __cuda_array_interface__ (row pointers, ascending columns, values).
+        Indices are converted to int32 and values to float64 on the device where needed; the producer's stream is synchronised
+        before the call (torch's current stream for tensors, the whole device for other objects); the handle owns copies and
+        nothing of the caller's is kept.  ValueError: the arrays are not a matrix (the library says why on stderr)."""
+        import torch
+        if col is None and val is None:
+            if not (isinstance(crow, torch.Tensor) and crow.layout == torch.sparse_csr):
+                raise TypeError("matrix_from_device: one argument must be a torch sparse_csr tensor")
+            if crow.dim() != 2 or crow.shape[0] != crow.shape[1]:
+                raise ValueError("matrix_from_device: a square matrix is required")
+            nrows = crow.shape[0]
+            crow, col, val = crow.crow_indices(), crow.col_indices(), crow.values()
+        elif col is None or val is None:
+            raise TypeError("matrix_from_device: row pointers, columns and values are required")
+        foreign = not all(isinstance(t, torch.Tensor) for t in (crow, col, val))
+        dev = torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
+
+        def on_device(t, dtype):
+            if not isinstance(t, torch.Tensor):
+                if not hasattr(t, "__cuda_array_interface__"):
+                    raise TypeError("matrix_from_device: torch device tensors or objects with __cuda_array_interface__ are required")
+                t = torch.as_tensor(t, device=dev)
+            if not t.is_cuda:
+                raise TypeError("matrix_from_device: the arrays must live on the GPU (HipBackend.matrix takes host arrays)")
+            return t.reshape(-1).to(dtype=dtype).contiguous()
+
+        rp, ci, va = on_device(crow, torch.int32), on_device(col, torch.int32), on_device(val, torch.float64)
+        if nrows is None:
+            nrows = rp.numel() - 1
+        if rp.numel() != nrows + 1 or ci.numel() != va.numel():
+            raise ValueError("matrix_from_device: nrows + 1 row pointers and as many columns as values are required")
+        if foreign:
+            torch.cuda.synchronize(rp.device)
+        else:
+            torch.cuda.current_stream(rp.device).synchronize()
+        m = self.g.gcge_hip_mat_create_device(int(nrows), int(va.numel()), rp.data_ptr(), ci.data_ptr(), va.data_ptr())
+        if not m:
+            raise ValueError("gcge_hip_mat_create_device refused the arrays")
+        return C.c_void_p(m)
+
+    def mv_to_torch(self, mv, c0, c1):
+        """Columns [c0, c1) of a block of vectors as a new (n, c1 - c0) float64 tensor on the GPU, rows in the caller's order
+        (gcge_hip_mv_to_device): nothing passes through the host."""
+        import torch
+        n = self.g.gcge_hip_mv_nrows(mv)
+        out = torch.empty((n, c1 - c0), dtype=torch.float64, device=torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device()))
+        if out.numel():
+            self.g.gcge_hip_mv_to_device(mv, c0, c1, out.data_ptr(), c1 - c0)
+        return out
 
     def matrix_grid(self, csr, dims, box_of_row):
         """A matrix on a masked grid: box_of_row[r] = x + nx (y + ny z) (int32 array, ascending); see gcge_hip_mat_create_grid."""

@@ -133,6 +133,44 @@ def multigrid_masked_cells(on=None):
     return h.gcge_hip_multigrid_get_masked_cells()
 
 
+def multigrid_device_levels(on=None):
+    """Whether the device build of a grid or MIS-2 hierarchy hands its coarse levels to gcge_hip_mat_create_device straight from the
+    Galerkin output (1, the default) or downloads them for the host constructors (0); returns the setting in force."""
+    h = hip_lib()
+    if on is not None:
+        h.gcge_hip_multigrid_device_levels(int(on))
+    return h.gcge_hip_multigrid_get_device_levels()
+
+
+def mat_device_stats():
+    """gcge_hip_mat_device_stats: (matrices analysed on the device, fall-backs to the host path, fall-backs caused by a hash
+    collision, bytes copied device to host) since the library was loaded."""
+    out = (C.c_long * 4)()
+    hip_lib().gcge_hip_mat_device_stats(out)
+    return tuple(out)
+
+
+def mat_device_hash_bits(bits):
+    """Tests: the device pattern search keeps only the low `bits` bits of its row hash (64: all of it, the default)."""
+    hip_lib().gcge_hip_mat_device_hash_bits(int(bits))
+
+
+def mat_pattern_table(mat):
+    """Tests: (pid, table) of a HIP matrix handle's pattern form as numpy arrays — pid uint16 per row, the table as raw bytes (16
+    per entry: value, column offset) — or (None, None) when the matrix has no pattern form."""
+    import numpy as np
+    h = hip_lib()
+    h.gcge_hip_mat_pattern_table.restype = C.c_long
+    h.gcge_hip_mat_pattern_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    h.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
+    nt = h.gcge_hip_mat_pattern_table(mat, None, None)
+    if nt == 0:
+        return None, None
+    pid, tab = np.zeros(h.gcge_hip_mat_nrows(mat), dtype=np.uint16), np.zeros(nt * 16, dtype=np.uint8)
+    h.gcge_hip_mat_pattern_table(mat, pid.ctypes.data_as(C.c_void_p), tab.ctypes.data_as(C.c_void_p))
+    return pid, tab
+
+
 def mat_geometry(mat):
     """The geometry a HIP matrix handle carries: (kind, dims, box_of_row) with kind 0 none (dims, box None), 1 named by the caller
     (HipBackend.matrix_grid), 2 recovered at upload; box_of_row[r] = x + nx (y + ny z) as a numpy int32 array."""

@@ -54,6 +54,26 @@ GCGE_HIP_MAT *gcge_hip_mat_create_grid (int nrows, const int *rowptr, const int 
  * live matrix of the same size is not adopted; gcge_hip_mat_row_order reports "as given".  What MultiGridCreate uploads the coarse
  * levels of a MIS-2 hierarchy with (below).                                                                                     */
 GCGE_HIP_MAT *gcge_hip_mat_create_as_given (int nrows, const int *rowptr, const int *colidx, const double *val);
+/* A whole square matrix (one rank) from DEVICE-resident CSR arrays (csrc/hip/mat_device.hip): nrows + 1, nnz and nnz entries, columns
+ * ascending within a row, complete when the call is made (the caller synchronises its producer).  The call runs on gcge_hip_stream()
+ * and synchronises itself; the handle owns copies, so the arrays may be freed afterwards.  Malformed input returns NULL with one
+ * line on stderr — checked on the device in this order: rowptr[0] == 0, rowptr non-decreasing, rowptr[nrows] == nnz (reads rowptr
+ * only), then every column in [0, nrows) (reads colidx[0 .. nnz) by position); nothing is addressed through an unchecked value.
+ * The CSR and pad-8 copies are made on the device, and so is the search for a pattern table: a 64-bit hash per row, the classes of
+ * equal hashes in a small table (only a row whose hash differs from its predecessor's touches it), every row verified entry by
+ * entry, as bits, against the first row of its class, ids by first occurrence; the table itself is then built by the host code
+ * gcge_hip_mat_create uses (csrc/hip/pattern_table.h) from the class representatives, so pid / table / spans are those of the host
+ * path bit for bit.  The handle is then what gcge_hip_mat_create_as_given returns for the same arrays: rows as given, the identity
+ * order of its size.  The matrix is downloaded once and handed to gcge_hip_mat_create (whose result this then is: by-offset
+ * patterns, star / dense / tile forms, the row order search) when a re-ordered matrix of this size is live or when the device
+ * search gives up: rows longer than 16, more classes than a table holds, a hash collision, tile mode 2.
+ * One difference from the host search: rows are equal here when their lengths and all their entries agree as bits; the host's
+ * comparison with the previous row's pattern also merges an EMPTY row with a preceding row whose only entries are explicitly
+ * stored (offset 0, +-0.0).  Matrices without explicitly stored zeros on the diagonal are not affected.
+ * gcge_hip_mat_device_stats: since load, out[0] matrices analysed on the device, out[1] fall-backs to the host path, out[2] those
+ * caused by a hash collision, out[3] bytes copied device to host by these constructors.                                          */
+GCGE_HIP_MAT *gcge_hip_mat_create_device (int nrows, long nnz, const int *d_rowptr, const int *d_colidx, const double *d_val);
+void gcge_hip_mat_device_stats (long out[4]);
 /* A matrix of that kind that names NO geometry (read from a file: gcge_load_matrix_market, gcge_load_petsc_binary) gets it
  * recovered at upload by gcge_hip_mat_create itself: x lines from the (r, r + 1) couplings, planes and the shifts between
  * lines / planes from the votes of the star rows' + y / + z neighbours.  A wrong guess costs speed, never the result (the
@@ -111,6 +131,12 @@ int  gcge_hip_multigrid_get_mode (void);
  *     Row slabs of a masked grid are not coarsened this way.                                                                   */
 void gcge_hip_multigrid_masked_cells (int on);
 int  gcge_hip_multigrid_get_masked_cells (void);
+/*     Coarse levels without the host (grid and MIS-2 hierarchies of mode 0): on = 1 (default) hands every coarse A_l / B_l to
+ *     gcge_hip_mat_create_device straight from the Galerkin output (MIS-2: its as-given variant); a level comes back only when that
+ *     constructor falls back.  on = 0: every coarse level is downloaded and uploaded through the host constructors.  Identical
+ *     hierarchies either way.  Masked and greedy-graph levels always take the host constructors.                                */
+void gcge_hip_multigrid_device_levels (int on);
+int  gcge_hip_multigrid_get_device_levels (void);
 /*     the device aggregation of a masked grid for a host box array (tests, tools): agg, mem [nrows], ptr [nrows + 1], cbox [nrows]
  *     as gcge_mg_aggregate_masked and the members of every cell in ascending row order; returns the number of aggregates, < 0 for
  *     a geometry the host routine refuses                                                                                     */
@@ -195,6 +221,9 @@ int  gcge_hip_mat_set_halo_rccl (GCGE_HIP_MAT *A, int nglobal, int npeer, const 
 /* columns [c0,c1) <-> host column-major array with leading dimension ldh (>= nrows) */
 void gcge_hip_mv_to_host   (void **mv, int c0, int c1, double *host, long ldh);
 void gcge_hip_mv_from_host (void **mv, int c0, int c1, const double *host, long ldh);
+/* columns [c0,c1) -> DEVICE row-major array: d_out[r * ldo + (j - c0)] (ldo >= c1 - c0), rows in the caller's order whatever order the
+ * block lives in; one gather kernel on gcge_hip_stream(), which the call synchronises                                              */
+void gcge_hip_mv_to_device (void **mv, int c0, int c1, double *d_out, long ldo);
 int  gcge_hip_mv_nrows (void **mv);
 int  gcge_hip_mv_ncols (void **mv);
 double *gcge_hip_mv_device_ptr (void **mv, long *ld);

@@ -1,7 +1,7 @@
 """Multigrid set-up of the HIP back-end in both modes: the phase split of MultiGridCreate, the bytes copied device to host and the
 total set-up time, for one problem of the existing generators.
 
-  python tools/mg_setup_probe.py <lap3d|fe3d|sio2> <size> [levels]
+  python tools/mg_setup_probe.py <lap3d|fe3d|sio2> <size> [levels] [hostlevels]
   python tools/mg_setup_probe.py ball <G> <K> [levels] [solve]
   python tools/mg_setup_probe.py perm <size> [levels] [solve]
   python tools/mg_setup_probe.py delaunay <points> [levels] [solve]
@@ -14,6 +14,9 @@ perm: lap3d <size> under a random symmetric permutation; delaunay: the P1 stiffn
 a cube (hull nodes eliminated), the matrix of tools/generic_probe.py.  Neither shows a grid in the order it arrives in: both graph
 methods are run (gcge_mg_set_graph_method: 0 greedy on the host, 1 MIS-2 on the device), with GCGE_MG_TRACE on in the measured call (the
 rounds of every level); with `solve` one GCG solve (nev 10) with BlockAMG over each method's hierarchy.
+
+hostlevels (any kind): gcge_hip_multigrid_device_levels(0) — the device build downloads every coarse level for the host constructors
+instead of handing it to gcge_hip_mat_create_device.
 
 Mode 0 builds the hierarchy on the device (csrc/hip/mg_device.hip), mode 1 on the host (csrc/host/multigrid.c); both give the same
 hierarchy.  Each mode is timed on a fresh MultiGridCreate after one warm-up call; the rows, K1 form and row order of its levels are listed."""
@@ -35,10 +38,15 @@ def main():
     ball, graph = kind == "ball", kind in ("perm", "delaunay")
     rest = sys.argv[4:] if ball else sys.argv[3:]
     solve = "solve" in rest
-    rest = [v for v in rest if v != "solve"]
+    hostlevels = "hostlevels" in rest
+    rest = [v for v in rest if v not in ("solve", "hostlevels")]
     levels = int(rest[0]) if rest else 6
     hip = HipBackend()
     g = hip_lib()
+    if hostlevels:
+        from gcge_amd.lib import multigrid_device_levels
+        multigrid_device_levels(0)
+        print("coarse levels through the host constructors (device levels off)")
     g.gcge_hip_mat_spmm_form.restype = C.c_char_p
     g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
     g.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
