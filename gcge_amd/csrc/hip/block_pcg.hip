@@ -345,8 +345,10 @@ __global__ __launch_bounds__(256) void cg_start_scaled_stored(long nrows, const 
 }
 
 struct RingPtrs { const double* p[16]; };
-// x[:, j] += sum_{q < cnt} coef[q * m + j] * ring[q][:, j]      (cnt <= 16)
-__global__ __launch_bounds__(256) void cg_accum_x(long nrows, RingPtrs ring, int cnt, long ldp, double* __restrict__ x,
+// x[:, j] = xsrc[:, j] + sum_{q < cnt} coef[q * m + j] * ring[q][:, j]      (cnt <= 16)
+// xsrc: the x the terms are added to — x itself, or, in the first flush of a call whose initial guess lies elsewhere
+// (GCGE_LINSOL_ARGS.x_src), those columns, which are only read (cnt == 0: a plain copy)
+__global__ __launch_bounds__(256) void cg_accum_x(long nrows, RingPtrs ring, int cnt, long ldp, const double* xsrc, long ldxs, double* x,
     long ldx, int m, const double* __restrict__ coef, int tpr) {
   const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
   const int j = 2 * tx;
@@ -354,7 +356,7 @@ __global__ __launch_bounds__(256) void cg_accum_x(long nrows, RingPtrs ring, int
   const long slab = (((nrows + gridDim.x - 1) / gridDim.x) + rpb - 1) / rpb * rpb;
   const long rend = min(nrows, ((long)blockIdx.x + 1) * slab);
   for (long row = (long)blockIdx.x * slab + ty; row < rend; row += rpb) {
-    v2d xv = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(x + row * ldx + j));
+    v2d xv = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(xsrc + row * ldxs + j));
 #pragma unroll 4
     for (int q = 0; q < cnt; ++q) {
       const v2d pv = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(ring.p[q] + row * ldp + j));
@@ -461,6 +463,7 @@ struct HipBpcg {
   long fused_starts = 0;           // solves started by product + one sweep (cg_start_scaled_stored)
   long surplus_iters = 0;          // iterations enqueued after the last column had retired (no-ops on the data, but they stream)
   long trimmed_iters = 0;          // last iterations of the device-scalar loop whose second pass ran over fewer columns or not at all
+  long starts_in_place = 0, starts_materialised = 0;   // calls with the initial guess elsewhere (args.x_src): started from it in one sweep / copied first
 };
 static HipBpcg g_bpcg;
 
@@ -574,6 +577,7 @@ struct CgCall {
   GCGE_LINSOL_ARGS args;                                   // (include/gcge_ops.h); operator: A, or A + sigma B when it published a shift
   CgSwitches env;
   double *dx, *dr, *dp, *dw; long ldx, ldr, ldp, ldw;      // x at its first column; r, p, w
+  const double* dxs; long ldxs;                            // what the next x flush reads: x, or args.x_src until x has been written once
   bool one_pass;                                           // all four can be walked with 16-byte lanes
   CgGrid grid;
   std::vector<double> norm_b, rho1, rho2, pTw, init_res, last_res, coef;
@@ -737,20 +741,65 @@ static void cg_stopping_scales(CgCall& c) {
   }
 }
 
+extern "C" int gcge_hip_block_moves_mv(void** ritz, void** V, int x0, int x1, const int* runs, int w0, void** b, int b0, const double* scale);
+
+// The initial guess lies in columns [x_src_col, x_src_col + nrhs) of the block args.x_src, which this call only reads; the result
+// goes to mv_x, and with rhs_scale b = x_src diag(rhs_scale) is left in mv_b (GCGE_LINSOL_ARGS, include/gcge_ops.h).
+// one_sweep (pattern matrix, no shift, not "rel", a ring: x is only written by the flushes) and operands the sweep takes: kernel
+// MODE 8 reads x where it lies, stores r / p0 and b and sums rho — nothing is copied, the first x flush reads x_src (c.dxs).
+// Returns true then (p0 in place, c.rho2 summed).  Everything else: x and b are made first, by the block-move sweep where it takes
+// them and by the slots otherwise — the same bits — and the call goes on as if it had been handed them (false).
+static bool cg_start_elsewhere(CgCall& c, void** start_r, bool one_sweep) {
+  HipBpcg* s = c.s; BpcgBlocks& k = s->blk; struct OPS_* ops = c.ops;
+  void** src = c.args.x_src; const int sc0 = c.args.x_src_col, nrhs = c.nrhs;
+  const double* scale = c.args.rhs_scale;
+  c.args.x_src = nullptr; c.args.x_src_col = 0;
+  if (gcge_hip_mv_nrows(src) != c.n || gcge_hip_mv_row_order_id(src) != gcge_hip_mv_row_order_id(c.mv_x) || sc0 < 0 || sc0 + nrhs > gcge_hip_mv_ncols(src) ||
+      (src == c.mv_x && sc0 < c.xc0 + nrhs && c.xc0 < sc0 + nrhs)) {
+    fprintf(stderr, "HIP_BlockPCG: the initial guess (GCGE_LINSOL_ARGS.x_src) does not match x in shape or overlaps it\n"); abort();
+  }
+  long lds = 0;
+  const double* ds = gcge_hip_mv_device_ptr(src, &lds);
+  if (one_sweep && scale != nullptr && c.one_pass && !(lds & 1) && !((uintptr_t)(ds + sc0) & 15) &&
+      gcge_hip_cg_start_scaled_b_mv(c.mat, src, sc0, scale, start_r, k.mv_ws[1], 0, nrhs, c.mv_b, c.bc0, c.rho2.data()) == 0) {
+    reduce_over_ranks(c.rho2.data(), nrhs);
+    c.dxs = ds + sc0; c.ldxs = lds;
+    c.args.rhs_scale = nullptr;          // b is formed
+    ++s->starts_in_place;
+    return true;
+  }
+  const int runs[3] = {1, sc0, sc0 + nrhs};
+  if (!(scale != nullptr && src == c.mv_x && gcge_hip_block_moves_mv(src, c.mv_x, sc0 + nrhs, sc0 + nrhs, runs, c.xc0, c.mv_b, c.bc0, scale))) {
+    int st2[2] = {sc0, c.xc0}, en2[2] = {sc0 + nrhs, c.xc0 + nrhs};
+    ops->MultiVecAxpby(1.0, src, 0.0, c.mv_x, st2, en2, ops);
+    if (scale != nullptr) {
+      st2[0] = c.xc0; en2[0] = c.xc0 + nrhs; st2[1] = c.bc0; en2[1] = c.bc0 + nrhs;
+      ops->MultiVecAxpby(1.0, c.mv_x, 0.0, c.mv_b, st2, en2, ops);
+      std::vector<double> sc(scale, scale + nrhs);
+      ops->MultiVecLinearComb(NULL, c.mv_b, 0, st2, en2, NULL, 0, sc.data(), 1, ops);
+    }
+  }
+  c.args.rhs_scale = nullptr;            // b is formed: an ordinary right-hand side from here on
+  ++s->starts_materialised;
+  return false;
+}
+
 // r = b - A x ; c.rho2 = diag(r^T r) summed over the ranks ; c.norm_b.  Returns whether p0 = r is in place as well (the one-sweep
 // routes write both; without_r: they write p0 alone).
 // The caller may have declared b = x diag(scale) without forming it (args.rhs_scale: our GCG driver's systems
 // A w = (lambda + sigma) x, started from w = x).  The one-sweep starts then take the scale factors
 // and neither read nor need b; every other route forms b first, here, on the device.
-static bool cg_start(CgCall& c, bool without_r) {
+static bool cg_start(CgCall& c, bool without_r, bool ring_recompute) {
   HipBpcg* s = c.s; BpcgBlocks& k = s->blk; struct OPS_* ops = c.ops;
   const int nrhs = c.nrhs;
   const bool rel = 0 == strcmp(s->tol_type, "rel");                                     // needs |b|: b is formed
-  const bool pattern = c.args.sigma == 0.0 && gcge_hip_cg_recompute_pays(c.mat);        // r, p0 and rho in one sweep (kernel MODES 5, 6)
+  const bool pattern = c.args.sigma == 0.0 && gcge_hip_cg_recompute_pays(c.mat);        // r, p0 and rho in one sweep (kernel MODES 5, 6, 8)
   void** start_r = without_r ? k.mv_ws[1] : k.mv_ws[0];
-  const double* rhs_scale = c.args.rhs_scale;
   bool p0_done = false;
-  if (rhs_scale != nullptr && !rel && pattern &&
+  if (c.args.x_src != nullptr) p0_done = cg_start_elsewhere(c, start_r, !rel && pattern && ring_recompute);
+  const double* rhs_scale = c.args.rhs_scale;
+  if (p0_done) {
+  } else if (rhs_scale != nullptr && !rel && pattern &&
       gcge_hip_cg_start_scaled_mv(c.mat, c.mv_x, c.xc0, rhs_scale, start_r, k.mv_ws[1], 0, nrhs, c.rho2.data()) == 0) {
     reduce_over_ranks(c.rho2.data(), nrhs);
     p0_done = true;
@@ -798,14 +847,47 @@ static bool cg_start(CgCall& c, bool without_r) {
 // The pending x updates of a call with a ring: p_k lives in slots[cur]; x still lacks the terms of the npend directions from
 // slots[first_slot] on.
 struct CgPending { int npend = 0, first_slot = 0, cur = 0; };
+static void launch_accum_x(long n, const RingPtrs& rp, int cnt, long ldp, const double* xs, long ldxs, double* x, long ldx, int m, const double* d_coef,
+                           hipStream_t st) {
+  const int tpr = cg_tpr(m);
+  long g = (n + (256 / tpr) * 8 - 1) / ((256 / tpr) * 8); if (g > 8192) g = 8192; if (g < 1) g = 1;
+  hipLaunchKernelGGL(cg_accum_x, dim3((unsigned)g), dim3(256), 0, st, n, rp, cnt, ldp, xs, ldxs, x, ldx, m, d_coef, tpr);
+}
+// the flush on operator-table blocks with host coefficients (include/gcge_hip.h; tests)
+extern "C" int gcge_hip_cg_accum_x_mv(void** src, int sc0, void** x, int xc0, int m, void*** ring, int cnt, const double* host_coef) {
+  long lds = 0, ldx = 0, ldp = 0;
+  const double* ds = gcge_hip_mv_device_ptr(src, &lds);
+  double* dx = gcge_hip_mv_device_ptr(x, &ldx);
+  if (ds == nullptr || dx == nullptr || m <= 0 || m > 512 || cnt < 0 || cnt > 16 || (cnt > 0 && (ring == nullptr || host_coef == nullptr))) return -1;
+  const int n = gcge_hip_mv_nrows(x);
+  if (gcge_hip_mv_nrows(src) != n || sc0 < 0 || sc0 + m > gcge_hip_mv_ncols(src) || xc0 < 0 || xc0 + m > gcge_hip_mv_ncols(x)) return -1;
+  if (!cg_vec_ok(m, {ds + sc0, dx + xc0}, {lds, ldx})) return -1;
+  RingPtrs rp;
+  for (int q = 0; q < 16; ++q) {
+    long ldq = 0;
+    void** slot = cnt > 0 ? ring[q < cnt ? q : 0] : src;
+    rp.p[q] = gcge_hip_mv_device_ptr(slot, &ldq);
+    if (cnt > 0 && (rp.p[q] == nullptr || gcge_hip_mv_nrows(slot) != n || gcge_hip_mv_ncols(slot) < m || (q > 0 && ldq != ldp) || !cg_vec_ok(m, {rp.p[q]}, {ldq}))) return -1;
+    if (q == 0) ldp = ldq;
+  }
+  hipStream_t st = (hipStream_t)gcge_hip_stream();
+  double* d_coef = nullptr;
+  if (cnt > 0) {
+    GCGE_HIP_CHECK(hipMalloc(&d_coef, (size_t)cnt * m * sizeof(double)));
+    GCGE_HIP_CHECK(hipMemcpy(d_coef, host_coef, (size_t)cnt * m * sizeof(double), hipMemcpyHostToDevice));
+  }
+  launch_accum_x((long)n, rp, cnt, ldp, ds + sc0, lds, dx + xc0, ldx, m, d_coef, st);
+  GCGE_HIP_CHECK(hipStreamSynchronize(st));
+  if (d_coef != nullptr) GCGE_HIP_CHECK(hipFree(d_coef));
+  return 0;
+}
 // x += sum over the pending directions q of p_q diag(d_coef[q * nrhs ..])  (cg_accum_x); d_coef: device memory
-static void cg_flush_x(const CgCall& c, const CgPlan& p, CgPending& w, const double* d_coef) {
-  if (w.npend == 0) return;
+static void cg_flush_x(CgCall& c, const CgPlan& p, CgPending& w, const double* d_coef) {
+  if (w.npend == 0 && c.dxs == c.dx) return;   // (nothing pending but x never written: a plain copy of the initial guess)
   RingPtrs rp;
   for (int q = 0; q < 16; ++q) { long ldq; rp.p[q] = gcge_hip_mv_device_ptr(p.slots[(w.first_slot + (q < w.npend ? q : 0)) % p.R], &ldq); }
-  const int tpr = cg_tpr(c.nrhs);
-  long g = ((long)c.n + (256 / tpr) * 8 - 1) / ((256 / tpr) * 8); if (g > 8192) g = 8192; if (g < 1) g = 1;
-  hipLaunchKernelGGL(cg_accum_x, dim3((unsigned)g), dim3(256), 0, c.st, (long)c.n, rp, w.npend, c.ldp, c.dx, c.ldx, c.nrhs, d_coef, tpr);
+  launch_accum_x((long)c.n, rp, w.npend, c.ldp, c.dxs, c.ldxs, c.dx, c.ldx, c.nrhs, d_coef, c.st);
+  c.dxs = c.dx; c.ldxs = c.ldx;
   w.first_slot = (w.first_slot + w.npend) % p.R; w.npend = 0;
 }
 
@@ -1100,6 +1182,7 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
   c.dr = gcge_hip_mv_device_ptr(k.mv_ws[0], &c.ldr);
   c.dp = gcge_hip_mv_device_ptr(k.mv_ws[1], &c.ldp);
   c.dw = gcge_hip_mv_device_ptr(k.mv_ws[2], &c.ldw);
+  c.dxs = c.dx; c.ldxs = c.ldx;
   c.one_pass = nrhs <= 512 && cg_vec_ok(nrhs, {c.dw, c.dr, c.dp, c.dx}, {c.ldw, c.ldr, c.ldp, c.ldx});
   c.grid = cg_grid(n);
   for (std::vector<double>* v : {&c.norm_b, &c.rho1, &c.rho2, &c.pTw, &c.init_res, &c.last_res, &c.coef}) v->assign(nrhs, 0.0);
@@ -1111,7 +1194,7 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
   const bool plan_first = c.args.sigma == 0.0 && gcge_hip_cg_recompute_pays(mat);
   CgPlan plan = {};
   if (plan_first) plan = cg_plan(c);
-  const bool p0_done = cg_start(c, plan_first && plan.start_without_r);
+  const bool p0_done = cg_start(c, plan_first && plan.start_without_r, plan_first && plan.recompute);
   if (!plan_first) plan = cg_plan(c);
   s->spmm_calls++; s->spmm_cols += nrhs;
   c.nact = 0;
@@ -1129,6 +1212,7 @@ static void HIP_BlockPCG_run(void* mat, void** mv_b, void** mv_x, int* start_bx,
     res = plan.loop == CG_DEVICE_SCALARS ? cg_loop_device_scalars(c, plan)
         : plan.loop == CG_HOST_SCALARS   ? cg_loop_host_scalars(c, plan) : cg_loop_two_sweeps(c);
   }
+  if (c.dxs != c.dx) { CgPending none; cg_flush_x(c, plan, none, s->d_coef); }   // no iteration ran: x = the initial guess
   s->niter = res.niter;
   s->residual = res.residual;
 }
@@ -1192,6 +1276,7 @@ extern "C" void gcge_hip_bpcg_column_stats(long* col_iters, long* active_col_ite
 extern "C" long gcge_hip_bpcg_surplus_iters(void) { return g_bpcg.surplus_iters; }
 extern "C" long gcge_hip_bpcg_trimmed_iters(void) { return g_bpcg.trimmed_iters; }
 extern "C" long gcge_hip_bpcg_legacy_start_sums(void) { return g_bpcg.legacy_start_sums; }
+extern "C" long gcge_hip_bpcg_start_in_place_stats(long* declined) { if (declined) *declined = g_bpcg.starts_materialised; return g_bpcg.starts_in_place; }
 extern "C" double gcge_hip_bpcg_last_residual(void) { return g_bpcg.residual; }   // what the last call reported (column 0)
 // the fused CG as the smoother of BlockAMG for the HIP table: same stopping rules as MultiLinearSolverSetup_BlockPCG, its own
 // blocks per level (parked sets above)
@@ -1206,6 +1291,7 @@ extern "C" void gcge_hip_bpcg_backend(GCGE_BACKEND* be) {
   be->amg_smoother_residual = amg_smoother_residual;
   be->scaled_rhs_solver = HIP_BlockPCG;
   be->amg_final_cols = 1;
+  be->start_in_place = 1;               // HIP_BlockPCG accepts an initial guess elsewhere (GCGE_LINSOL_ARGS.x_src: cg_start_elsewhere)
 }
 extern "C" void gcge_hip_bpcg_release(struct OPS_* ops) {
   for (int i = 0; i < g_nparked; ++i) bpcg_destroy_set(&g_parked[i], ops);

@@ -164,6 +164,8 @@ void gcge_hip_product_slots(struct OPS_* ops, GCGE_BACKEND* be);
 void gcge_hip_spmm_dot_mv(void* mat, void** x, void** y, int* start, int* end, double* host_dots, struct OPS_* ops);
 void gcge_hip_spmm_dot2_mv(void* mat, void** x, void** y, int* start, int* end, double* host_dots, double* host_yy, struct OPS_* ops);
 int gcge_hip_cg_start_scaled_mv(void* mat, void** x, int xc0, const double* host_scale, void** r, void** p0, int rc0, int m, double* host_rho);
+int gcge_hip_cg_start_scaled_b_mv(void* mat, void** x, int xc0, const double* host_scale, void** r, void** p0, int rc0, int m, void** b, int bc0,
+                                  double* host_rho);
 // pas_border.hip
 int gcge_hip_pas_border(void** QX, int s, void** q, int q0, void** y, int y0, int m, double beta, const double* t, int ldt, double* g, int ldg);
 

@@ -567,9 +567,10 @@ static int start_sweep_odd_b_only(const GCGE_HIP_MAT_* A, const GcgeHipMV* vx, i
   if (vb == nullptr || !(bc0 & 1)) return 0;
   return start_sweep_takes(A, vx, xc0, vb, bc0 & ~1, vr, vn, rc0, m);
 }
+// (d_scale with vb: MODE 8, b is the store target of the right-hand sides the sweep forms)
 static int start_sweep(GCGE_HIP_MAT_* A, GcgeHipMV* vx, int xc0, GcgeHipMV* vb, int bc0, const double* d_scale, GcgeHipMV* vr, GcgeHipMV* vn,
                        int rc0, int m, double* dd) {
-  const CgPass cg = {vb != nullptr ? 5 : 6, vr->d + rc0, vr->ld, vn->d + rc0, vn->ld, d_scale, nullptr, nullptr,
+  const CgPass cg = {vb == nullptr ? 6 : (d_scale != nullptr ? 8 : 5), vr->d + rc0, vr->ld, vn->d + rc0, vn->ld, d_scale, nullptr, nullptr,
                      vb != nullptr ? vb->d + bc0 : nullptr, vb != nullptr ? vb->ld : 0};
   return spmm_halo(A, vx, xc0, nullptr, 0, m, dd, nullptr, &cg);
 }
@@ -597,12 +598,16 @@ extern "C" int gcge_hip_cg_start_mv(void* mat, void** x, int xc0, void** b, int 
 
 // The same start for right-hand sides b_j = scale_j x_j (x = the initial guess): the GCG driver's systems
 // A w = (lambda + sigma) x start from w = x, so b is never formed and never read.  host_scale: m factors.
-extern "C" int gcge_hip_cg_start_scaled_mv(void* mat, void** x, int xc0, const double* host_scale, void** r, void** p0, int rc0,
-                                           int m, double* host_rho) {
+// b != NULL (kernel MODE 8): the right-hand sides the sweep forms, b[:, bc0:bc0+m) = x[:, xc0:xc0+m) diag(scale) rounded once, are
+// stored as well — for a solver that reads b later (BlockAMG) while x is an initial guess that lies in another block and is only
+// read (GCGE_LINSOL_ARGS.x_src).  b must be a block other than x, r and p0; one rank (no halo rows).
+extern "C" int gcge_hip_cg_start_scaled_b_mv(void* mat, void** x, int xc0, const double* host_scale, void** r, void** p0, int rc0,
+                                             int m, void** b, int bc0, double* host_rho) {
   gcge_hip_enter();
   GCGE_HIP_MAT_* A = (GCGE_HIP_MAT_*)mat;
-  GcgeHipMV *vx = (GcgeHipMV*)x, *vr = (GcgeHipMV*)r, *vp = (GcgeHipMV*)p0;
-  if (getenv("GCGE_CG_NO_RECOMPUTE") != nullptr || !start_sweep_takes(A, vx, xc0, nullptr, 0, vr, vp, rc0, m)) return -1;
+  GcgeHipMV *vx = (GcgeHipMV*)x, *vr = (GcgeHipMV*)r, *vp = (GcgeHipMV*)p0, *vb = (GcgeHipMV*)b;
+  if (getenv("GCGE_CG_NO_RECOMPUTE") != nullptr || !start_sweep_takes(A, vx, xc0, vb, bc0, vr, vp, rc0, m)) return -1;
+  if (vb != nullptr && (vb == vx || vb == vr || vb == vp || A->nghost > 0 || bc0 < 0 || bc0 + m > vb->ncols || vb->nrows != A->nrows)) return -1;
   GCGE_REQUIRE(xc0 >= 0 && xc0 + m <= vx->ncols && rc0 >= 0 && rc0 + m <= vr->ncols && rc0 + m <= vp->ncols, "cg_start: column ranges");
   GCGE_REQUIRE(A->nrows == vx->nrows && A->nrows == vr->nrows && A->nrows == vp->nrows &&
                A->nrows + A->nghost <= vx->nrows_alloc, "cg_start: shapes");
@@ -611,9 +616,13 @@ extern "C" int gcge_hip_cg_start_scaled_mv(void* mat, void** x, int xc0, const d
   GCGE_HIP_CHECK(hipStreamSynchronize(g_stream));   // the staging buffers are reused
   memcpy(hs, host_scale, m * sizeof(double));
   GCGE_HIP_CHECK(hipMemcpyAsync(dd + 6 * (size_t)m, hs, m * sizeof(double), hipMemcpyHostToDevice, g_stream));
-  if (start_sweep(A, vx, xc0, nullptr, 0, dd + 6 * (size_t)m, vr, vp, rc0, m, dd) != 0) return -1;
+  if (start_sweep(A, vx, xc0, vb, bc0, dd + 6 * (size_t)m, vr, vp, rc0, m, dd) != 0) return -1;
   memcpy(host_rho, sums_to_host(dd, (size_t)m), m * sizeof(double));   // (behind the upload from the same pinned block in stream order)
   return 0;
+}
+extern "C" int gcge_hip_cg_start_scaled_mv(void* mat, void** x, int xc0, const double* host_scale, void** r, void** p0, int rc0,
+                                           int m, double* host_rho) {
+  return gcge_hip_cg_start_scaled_b_mv(mat, x, xc0, host_scale, r, p0, rc0, m, nullptr, 0, host_rho);
 }
 
 // ---- two steps of a V-cycle in one sweep each (GCGE_BACKEND.amg_residual / amg_prolong_add; csrc/host/lin_sol.c) ----------

@@ -60,6 +60,9 @@ struct PatEntry { double val; long off; };   // 16 bytes: one ds_read_b128
 //      B = cg.b the right-hand sides and X the initial guess: one sweep instead of product, axpby, column dots and copy
 //   6  mode 5 with the right-hand side B = X diag(scale) (scale = cg.alpha) formed on the fly from the row's own X value:
 //      the GCG driver's systems A w = (lambda + sigma) x start from w = x, so neither B nor a second read is needed
+//   8  mode 6 that also STORES the right-hand side it formed: B[r,j] = scale_j X[r,j] (the once-rounded product the residual was
+//      taken from) goes to cg.b / cg.ldb, here a store target.  X may be columns of any block other than R, PNEW and B: the
+//      GCG driver's W systems start from the Ritz vectors where they lie (GCGE_LINSOL_ARGS.x_src) and BlockAMG still gets its b
 //   4  residual norms of Ritz pairs (standard problem): partial: sum_r ((A X)[r,j] - lambda_j X[r,j])^2 with
 //      lambda = cg.alpha; nothing is stored (CheckConvergence of the GCG driver, one read of X instead of 11 streams)
 struct CgArgs { double* r; size_t ldr; double* pnew; size_t ldp; const double* alpha; const double* beta; const int* flag; const double* b; size_t ldb;
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(256) void spmm_pattern_kernel(
   const size_t ldrl = MODE == 5 ? cg.ldb : cg.ldr;
   CgCoef cf = (MODE == 3 || MODE == 7) ? cg_coef(cg, 2 * i, act) : CgCoef{0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0, 0.0};
   if (MODE == 7 && act) { cf.bp0 = cg.b[2 * i]; cf.bp1 = cg.b[2 * i + 1]; }   // beta of the previous iteration
-  if ((RES || MODE == 6) && act) { cf.al0 = cg.alpha[2 * i]; cf.al1 = cg.alpha[2 * i + 1]; }   // lambda / rhs scale of this lane's column pair
+  if ((RES || MODE == 6 || MODE == 8) && act) { cf.al0 = cg.alpha[2 * i]; cf.al1 = cg.alpha[2 * i + 1]; }   // lambda / rhs scale of this lane's column pair
   double d0 = 0.0, d1 = 0.0, e0 = 0.0, e1 = 0.0;   // x.y and y.y column sums (DOT)
 
   // tile t = (group of 4 lines q, slice a inside the line); wave w takes line 4q + w
@@ -152,10 +155,10 @@ __global__ __launch_bounds__(256) void spmm_pattern_kernel(
         d0 = fma(a0 * wgt, buf[LT].x, d0); d1 = fma(a1 * wgt, buf[LT].y, d1);
         e0 = fma(a0 * wgt, a0, e0); e1 = fma(a1 * wgt, a1, e1);
       }
-      if (MODE == 5 || MODE == 6) {
-        // MODE 6: the product is rounded on its own (as the column scaling that used to form B did), then subtracted
+      if (MODE == 5 || MODE == 6 || MODE == 8) {
+        // MODE 6, 8: the product is rounded on its own (as the column scaling that used to form B did), then subtracted
         v2d rv = buf[LT + DOT + UPD - 1];
-        if (MODE == 6) {
+        if (MODE != 5) {
 #pragma clang fp contract(off)   // no fma(scale, x, -Ax): __dmul_rn is a plain product in the HIP headers and would be contracted
           rv = v2d{cf.al0 * buf[LT].x, cf.al1 * buf[LT].y};
         }
@@ -163,6 +166,7 @@ __global__ __launch_bounds__(256) void spmm_pattern_kernel(
         if (ok) {
           __builtin_nontemporal_store(rn, reinterpret_cast<v2d*>(cg.r + (size_t)row * cg.ldr + 2 * i));
           if (cg.pnew != cg.r) __builtin_nontemporal_store(rn, reinterpret_cast<v2d*>(cg.pnew + (size_t)row * cg.ldp + 2 * i));   // (equal: the residual alone, a V-cycle's r = b - A x)
+          if (MODE == 8) __builtin_nontemporal_store(rv, reinterpret_cast<v2d*>(const_cast<double*>(cg.b) + (size_t)row * cg.ldb + 2 * i));
         }
         d0 = fma(wgt * rn.x, rn.x, d0); d1 = fma(wgt * rn.y, rn.y, d1);
       }
@@ -422,7 +426,7 @@ __device__ __forceinline__ void chain2_body(
       d0 = fma(a0 * wgt, b.x, d0); d1 = fma(a1 * wgt, b.y, d1);
       e0 = fma(a0 * wgt, a0, e0); e1 = fma(a1 * wgt, a1, e1);
     }
-    if (MODE == 5 || MODE == 6) {
+    if (MODE == 5 || MODE == 6 || MODE == 8) {
       v2d rv;
       if (MODE == 5) rv = oth[NO + UPD];
       else {   // B = X diag(scale), rounded like the column scaling (no contraction into fma(scale, x, -Ax))
@@ -433,6 +437,7 @@ __device__ __forceinline__ void chain2_body(
       if (ok) {
         __builtin_nontemporal_store(rn, reinterpret_cast<v2d*>(cg.r + (size_t)row * cg.ldr + 2 * i));
         if (cg.pnew != cg.r) __builtin_nontemporal_store(rn, reinterpret_cast<v2d*>(cg.pnew + (size_t)row * cg.ldp + 2 * i));   // (equal: the residual alone)
+        if (MODE == 8) __builtin_nontemporal_store(rv, reinterpret_cast<v2d*>(const_cast<double*>(cg.b) + (size_t)row * cg.ldb + 2 * i));   // b = x diag(scale)
       }
       d0 = fma(wgt * rn.x, rn.x, d0); d1 = fma(wgt * rn.y, rn.y, d1);
     }
@@ -521,7 +526,7 @@ __global__ __launch_bounds__(64 * NW) void spmm_pattern_chain2_kernel(
     s_cf[threadIdx.x] = v2d{c.al0, c.al1}; s_cf[8 + threadIdx.x] = v2d{c.cb0, c.cb1}; s_cf[16 + threadIdx.x] = v2d{c.cr0, c.cr1};
     if (MODE == 7) s_cf[24 + threadIdx.x] = (2 * (int)threadIdx.x < m) ? v2d{cg.b[2 * threadIdx.x], cg.b[2 * threadIdx.x + 1]} : v2d{0.0, 0.0};
   }
-  if ((MODE == 4 || MODE == 6) && threadIdx.x < 8)
+  if ((MODE == 4 || MODE == 6 || MODE == 8) && threadIdx.x < 8)
     s_cf[threadIdx.x] = (2 * (int)threadIdx.x < m) ? v2d{cg.alpha[2 * threadIdx.x], cg.alpha[2 * threadIdx.x + 1]} : v2d{0.0, 0.0};
   __syncthreads();
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -802,6 +807,7 @@ extern "C" int gcge_hip_pattern_spmm_vals(int nrows, const unsigned short* d_pid
 //   mode 3: R -= (A X) diag(alpha); PNEW = R diag(cr) + X diag(cb); d_dots[j] = sum_r cr_j R[r,j]^2  (d_dots_yy unused)
 //   mode 4: d_dots[j] = sum_r ((A X)[r,j] - alpha_j X[r,j])^2  (residuals of Ritz pairs, alpha = the Ritz values)
 //   mode 5: R = B - A X; PNEW = R; d_dots[j] = sum_r R[r,j]^2  (start of the CG; d_b / ldb: the right-hand sides)
+//   mode 6: mode 5 with B = X diag(alpha) formed on the fly; mode 8: ... and stored through d_b / ldb (written, despite the type)
 // Geometry as gcge_hip_pattern_spmm; a chain-layout table without line exchange runs through the plain kernel
 // (its table is a valid generic one).  -1: not applicable (alignment), the caller keeps the unfused recurrence.
 // near > 0: the table's slots are [-S, 0, +S, -L, +L, -1, +1] (7-point stencil) and near is the largest |offset| in it
@@ -825,13 +831,14 @@ extern "C" int gcge_hip_pattern_cg_vals(int mode, int nrows, const unsigned shor
                                         double* d_dots, double* d_dots_yy, void* stream, const double* d_b, long ldb, long near,
                                         const double* d_rowval) {
   if (d_rowval != nullptr && lt > 8) return -1;
-  if (mode != 2 && mode != 3 && mode != 4 && mode != 5 && mode != 6 && mode != 7) return -1;
+  if (mode != 2 && mode != 3 && mode != 4 && mode != 5 && mode != 6 && mode != 7 && mode != 8) return -1;
   if (nrows <= 0 || ncols <= 0) return 0;
   if ((ncols & 1) || (ldx & 1) || ((uintptr_t)d_x & 15) || d_dots == nullptr) return -1;
-  if (mode == 6 && d_alpha == nullptr) return -1;
+  if ((mode == 6 || mode == 8) && d_alpha == nullptr) return -1;
   if (mode == 7 && (d_b == nullptr || (ldr & 1) || (ldp & 1) || ((uintptr_t)d_r & 15) || ((uintptr_t)d_pnew & 15) || d_pnew == d_x || d_pnew == d_r)) return -1;
-  if ((mode == 3 || mode == 5 || mode == 6) && ((ldr & 1) || (ldp & 1) || ((uintptr_t)d_r & 15) || ((uintptr_t)d_pnew & 15) || d_pnew == d_x || d_r == d_x)) return -1;
-  if (mode == 5 && (d_b == nullptr || (ldb & 1) || ((uintptr_t)d_b & 15))) return -1;
+  if ((mode == 3 || mode == 5 || mode == 6 || mode == 8) && ((ldr & 1) || (ldp & 1) || ((uintptr_t)d_r & 15) || ((uintptr_t)d_pnew & 15) || d_pnew == d_x || d_r == d_x)) return -1;
+  if ((mode == 5 || mode == 8) && (d_b == nullptr || (ldb & 1) || ((uintptr_t)d_b & 15))) return -1;
+  if (mode == 8 && (d_b == d_x || d_b == d_r || d_b == d_pnew)) return -1;   // a store target: its own block
   if ((size_t)npat * lt * sizeof(PatEntry) > 64 * 1024) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int npass = (ncols + 15) / 16;
@@ -888,6 +895,9 @@ extern "C" int gcge_hip_pattern_cg_vals(int mode, int nrows, const unsigned shor
     } else if (mode == 6) {
       const CgArgs cg = {d_r + c0, (size_t)ldr, d_pnew + c0, (size_t)ldp, d_alpha + c0, nullptr, nullptr, nullptr, 0, d_rowval};
       rc = pat_dispatch<6>(lt, nrows, d_pid, d_tab, npat, d_x + c0, (size_t)ldx, nullptr, 0, m, pp, yyo, nb, line, st, cline, nw, cg, gy);
+    } else if (mode == 8) {
+      const CgArgs cg = {d_r + c0, (size_t)ldr, d_pnew + c0, (size_t)ldp, d_alpha + c0, nullptr, nullptr, d_b + c0, (size_t)ldb, d_rowval};
+      rc = pat_dispatch<8>(lt, nrows, d_pid, d_tab, npat, d_x + c0, (size_t)ldx, nullptr, 0, m, pp, yyo, nb, line, st, cline, nw, cg, gy);
     } else if (mode == 7) {   // d_r: p_{k-1} (read only), d_b: the previous iteration's beta
       const CgArgs cg = {d_r + c0, (size_t)ldr, d_pnew + c0, (size_t)ldp, d_alpha + c0, d_beta + c0, d_flag + c0, d_b + c0, 0, d_rowval};
       rc = pat_dispatch<7>(lt, nrows, d_pid, d_tab, npat, d_x + c0, (size_t)ldx, nullptr, 0, m, pp, yyo, nb, line, st, cline, nw, cg, gy);

@@ -48,8 +48,29 @@ static int imin(int a, int b) { return a < b ? a : b; }
  * back-end that walks 16-byte column pairs wants an even origin, so an odd `first` moves one column up where the `total` columns
  * still end inside endX, else one column down where that is still inside startN, else stays (the back-end's slower paths).  The
  * values of b are the same wherever it lies. */
-static long g_odd_origins = 0, g_realigned = 0, g_fused_moves = 0, g_ritz_in_place = 0;
+static long g_odd_origins = 0, g_realigned = 0, g_fused_moves = 0, g_ritz_in_place = 0, g_start_in_place = 0, g_start_declined = 0;
 void GCGE_GcgRitzInPlaceStats(long *fused_launches) { if (fused_launches != NULL) *fused_launches = g_ritz_in_place; }
+void GCGE_GcgStartInPlaceStats(long *in_place, long *declined)
+{
+	if (in_place != NULL) *in_place = g_start_in_place;
+	if (declined != NULL) *declined = g_start_declined;
+}
+/* The W systems can start from the Ritz vectors where they lie when the unconverged runs are one contiguous range of V whose first
+ * column and length, and the W origin, are even (the back-end's one-sweep start walks 16-byte column pairs) */
+int GCGE_GcgStartInPlaceRange(const int *offset, int startW, int *lo, int *total)
+{
+	int idx, first, end;
+	if (offset == NULL || offset[0] < 1) return 0;
+	first = end = offset[1];
+	for (idx = 0; idx < offset[0]; ++idx) {
+		if (offset[2 * idx + 1] != end || offset[2 * idx + 2] < end) return 0;      /* a hole between two runs */
+		end = offset[2 * idx + 2];
+	}
+	if (end <= first || ((first | (end - first) | startW) & 1)) return 0;
+	if (lo != NULL) *lo = first;
+	if (total != NULL) *total = end - first;
+	return 1;
+}
 int GCGE_GcgRhsOrigin(int first, int total, int startN, int endX)
 {
 	if (!(first & 1)) return first;
@@ -296,7 +317,7 @@ static void RitzVecInPlace(Ctx *c, int with_p)
 static void ComputeW(Ctx *c, int *offset, int x_pending)
 {
 	struct OPS_ *ops = c->ops; GCGSolver *p = c->p; void **b = c->ritz;
-	int s[2], e[2], idx, blk = 0, i, b0, total = 0, moved = 0, form_b = 0;
+	int s[2], e[2], idx, blk = 0, i, b0, total = 0, moved = 0, form_b = 0, src_lo = 0, src_n = 0, from_x = 0;
 	double sigma = 0.0, *scales = c->scratch, t0 = ops->GetWtime(), t1, tx = 0.0;
 	void (*saved_solver)(void*, void**, void**, int*, int*, struct OPS_*) = ops->MultiLinearSolver;
 	void *saved_ws = ops->multi_linear_solver_workspace;
@@ -323,7 +344,16 @@ static void ComputeW(Ctx *c, int *offset, int x_pending)
 	if (x_pending) {      /* timed as compX (the sweep's W start vectors and b included), not as compW */
 		double ta = ops->GetWtime();
 		form_b = scaled_rhs && GCGE_SolverFormsScaledRhs(ops);
-		if (c->in_place)      /* X is in place already: V is the source of the runs, no X move (an empty range) */
+		/* X in place, b = x diag(scale) formed by the solver, one rank (a rank-local choice of route would reorder collectives),
+		 * one even-aligned source range: nothing is moved, the solver's first sweep reads the start vectors where they lie and
+		 * stores b (GCGE_LINSOL_ARGS.x_src) */
+		if (c->in_place && form_b && GCGE_BackendOf(ops).start_in_place) {
+			from_x = GCGE_GetComm() == NULL && GCGE_GcgStartInPlaceRange(offset, c->startW, &src_lo, &src_n);
+			if (from_x) ++g_start_in_place; else ++g_start_declined;
+		}
+		assert(!from_x || src_n == total);
+		if (from_x) moved = 1;
+		else if (c->in_place)      /* X is in place already: V is the source of the runs, no X move (an empty range) */
 			moved = GCGE_BackendOf(ops).block_moves(c->V, c->V, c->endX, c->endX, offset, c->startW,
 					form_b ? b : NULL, b0, scales, ops);
 		else
@@ -376,6 +406,7 @@ static void ComputeW(Ctx *c, int *offset, int x_pending)
 		args.idle_blocks = cg_ws; args.n_idle = 3;
 	}
 	if (scaled_rhs && !(moved && form_b)) args.rhs_scale = scales;      /* (b formed by the sweep: an ordinary right-hand side) */
+	if (from_x) { args.rhs_scale = scales; args.x_src = c->V; args.x_src_col = src_lo; }
 	GCGE_SetLinearSolverArgs(&args);
 	if ((offset[1] & 1) && !(b0 & 1)) GCGE_SetRealignedRhs(b, b0);
 	ops->MultiLinearSolver(c->A, b, c->V, s, e, ops);

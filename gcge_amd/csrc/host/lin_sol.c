@@ -157,23 +157,29 @@ static struct amg_level amg_level(const BlockAMGSolver *bamg, int l, void **mv_b
 	if (l > 0) { v.b = bamg->mv_array_ws[0][l]; v.x = bamg->mv_array_ws[1][l]; v.start[0] = v.start[1] = 0; v.end[0] = v.end[1] = m; }
 	return v;
 }
+/* first != NULL with first->x_src: the call's initial guess lies there and its b is still to be formed from it (this call of the
+ * smoother is told so, the later ones see an ordinary b and x) */
 static void smooth(const GCGE_BACKEND *be, const BlockAMGSolver *bamg, int l, int max_iter, int last, struct amg_level *v,
-		struct OPS_ *ops)
+		GCGE_LINSOL_ARGS *first, struct OPS_ *ops)
 {
 	void **mv_ws[3] = {bamg->mv_array_ws[2][l], bamg->mv_array_ws[3][l], bamg->mv_array_ws[4][l]};
-	if (be->amg_final_cols) {      /* last: the cycle's residual is column 0 of this call's (see below) */
-		GCGE_LINSOL_ARGS a = *GCGE_GetLinearSolverArgs();
-		a.final_residual_cols = last ? 1 : -1;
+	const GCGE_LINSOL_ARGS published = *GCGE_GetLinearSolverArgs();
+	const int elsewhere = first != NULL && first->x_src != NULL;
+	if (be->amg_final_cols || elsewhere) {      /* last: the cycle's residual is column 0 of this call's (see below) */
+		GCGE_LINSOL_ARGS a = published;
+		if (be->amg_final_cols) a.final_residual_cols = last ? 1 : -1;
+		if (elsewhere) { a.x_src = first->x_src; a.x_src_col = first->x_src_col; a.rhs_scale = first->rhs_scale; first->x_src = NULL; }
 		GCGE_SetLinearSolverArgs(&a);
 	}
 	if (be->amg_smoother_setup != NULL) be->amg_smoother_setup(max_iter, bamg->rate[l], bamg->tol[l], bamg->tol_type, ops);
 	else MultiLinearSolverSetup_BlockPCG(max_iter, bamg->rate[l], bamg->tol[l], bamg->tol_type, mv_ws, bamg->dbl_ws, bamg->int_ws,
 			NULL, NULL, ops);
 	ops->MultiLinearSolver(bamg->A_array[l], v->b, v->x, v->start, v->end, ops);
+	if (elsewhere) GCGE_SetLinearSolverArgs(&published);
 }
 
 static void BlockAlgebraicMultiGrid(const GCGE_BACKEND *be, BlockAMGSolver *bamg, void **mv_b, void **mv_x, int *start_bx,
-		int *end_bx, struct OPS_ *ops)
+		int *end_bx, GCGE_LINSOL_ARGS *first, struct OPS_ *ops)
 {
 	GCGE_LINSOL_FN solver = ops->MultiLinearSolver;
 	void *solver_ws = ops->multi_linear_solver_workspace;
@@ -185,7 +191,7 @@ static void BlockAlgebraicMultiGrid(const GCGE_BACKEND *be, BlockAMGSolver *bamg
 		void *A = bamg->A_array[l], **r = bamg->mv_array_ws[2][l];
 		f = amg_level(bamg, l, mv_b, mv_x, start_bx, end_bx);
 		c = amg_level(bamg, l + 1, mv_b, mv_x, start_bx, end_bx);
-		smooth(be, bamg, l, bamg->max_iter[2 * l + 1], 0, &f, ops);
+		smooth(be, bamg, l, bamg->max_iter[2 * l + 1], 0, &f, first, ops);
 		if (!(be->amg_residual != NULL && be->amg_residual(A, f.b, f.start[0], f.x, f.start[1], r, 0, m, ops))) {
 			int s[2] = {f.start[1], 0}, e[2] = {f.end[1], m};
 			ops->MatDotMultiVec(A, f.x, r, s, e, ops);                 /* r = b - A x */
@@ -196,7 +202,7 @@ static void BlockAlgebraicMultiGrid(const GCGE_BACKEND *be, BlockAMGSolver *bamg
 		ops->MultiVecAxpby(0.0, NULL, 0.0, c.x, cs, ce, ops);
 	}
 	f = amg_level(bamg, L - 1, mv_b, mv_x, start_bx, end_bx);
-	smooth(be, bamg, L - 1, bamg->max_iter[2 * L - 1], L == 1, &f, ops);
+	smooth(be, bamg, L - 1, bamg->max_iter[2 * L - 1], L == 1, &f, first, ops);
 	for (l = L - 2; l >= 0; --l) {
 		void **r = bamg->mv_array_ws[2][l];
 		f = amg_level(bamg, l, mv_b, mv_x, start_bx, end_bx);
@@ -206,7 +212,7 @@ static void BlockAlgebraicMultiGrid(const GCGE_BACKEND *be, BlockAMGSolver *bamg
 			ops->MultiVecFromItoJ(bamg->P_array, l + 1, l, c.x, r, cs, ce, bamg->mv_array_ws[4], ops);
 			ops->MultiVecAxpby(1.0, r, 1.0, f.x, s, e, ops);
 		}
-		smooth(be, bamg, l, bamg->max_iter[2 * l + 2], l == 0, &f, ops);
+		smooth(be, bamg, l, bamg->max_iter[2 * l + 2], l == 0, &f, first, ops);
 	}
 	/* residual of the smoothing call that ran last (src/ops_lin_sol.c:643: read from the solver behind the table) */
 	bamg->residual = be->amg_smoother_setup != NULL ? be->amg_smoother_residual(ops) :
@@ -220,11 +226,27 @@ static void BlockAMG(void *mat, void **mv_b, void **mv_x, int *start_bx, int *en
 	BlockAMGSolver *bamg = (BlockAMGSolver*)ops->multi_linear_solver_workspace;
 	const GCGE_BACKEND be = GCGE_BackendOf(ops);
 	const GCGE_LINSOL_ARGS args = *GCGE_GetLinearSolverArgs();
+	GCGE_LINSOL_ARGS first = args;      /* what the first smoothing call (always level 0's) is told beyond the others */
 	int idx;
 	(void)mat;      /* level 0 of the hierarchy IS the matrix (src/ops_lin_sol.c:477) */
+	/* the initial guess lies elsewhere (args.x_src: the GCG driver over a back-end with start_in_place): the back-end's smoother
+	 * takes it from there in its first call and leaves b = x_src diag(scale) behind; any other smoother gets the copy first */
+	first.x_src = NULL;
+	if (args.x_src != NULL) {
+		if (be.start_in_place && be.amg_smoother_setup != NULL && args.rhs_scale != NULL) first = args;
+		else {
+			int s[2], e[2];
+			s[0] = args.x_src_col; e[0] = s[0] + end_bx[1] - start_bx[1]; s[1] = start_bx[1]; e[1] = end_bx[1];
+			ops->MultiVecAxpby(1.0, args.x_src, 0.0, mv_x, s, e, ops);
+		}
+	}
 	/* systems published as b = x diag(scale) (GCGE_SolverTakesScaledRhs): b is formed here, once, from the initial guess;
 	 * the smoothing calls then see an ordinary right-hand side */
-	if (args.rhs_scale != NULL) {
+	if (first.x_src != NULL) {
+		GCGE_LINSOL_ARGS formed = args;
+		formed.rhs_scale = NULL; formed.x_src = NULL; formed.x_src_col = 0;
+		GCGE_SetLinearSolverArgs(&formed);
+	} else if (args.rhs_scale != NULL) {
 		GCGE_LINSOL_ARGS formed = args;
 		const int ncols = end_bx[1] - start_bx[1];
 		if (!(be.amg_form_rhs != NULL && be.amg_form_rhs(mv_b, start_bx[0], mv_x, start_bx[1], args.rhs_scale, ncols, ops))) {
@@ -233,15 +255,19 @@ static void BlockAMG(void *mat, void **mv_b, void **mv_x, int *start_bx, int *en
 			ops->MultiVecAxpby(1.0, mv_x, 0.0, mv_b, s, e, ops);
 			ops->MultiVecLinearComb(NULL, mv_b, 0, s, e, NULL, 0, (double*)args.rhs_scale, 1, ops);
 		}
-		formed.rhs_scale = NULL;
+		formed.rhs_scale = NULL; formed.x_src = NULL; formed.x_src_col = 0;
+		GCGE_SetLinearSolverArgs(&formed);
+	} else if (args.x_src != NULL) {      /* copied above, b was the caller's */
+		GCGE_LINSOL_ARGS formed = args;
+		formed.x_src = NULL; formed.x_src_col = 0;
 		GCGE_SetLinearSolverArgs(&formed);
 	}
 	for (idx = 0; idx < bamg->max_iter[0]; ++idx) {
-		BlockAlgebraicMultiGrid(&be, bamg, mv_b, mv_x, start_bx, end_bx, ops);
+		BlockAlgebraicMultiGrid(&be, bamg, mv_b, mv_x, start_bx, end_bx, &first, ops);
 		bamg->niter = idx + 1;
 		if (bamg->residual < bamg->tol[0]) break;
 	}
-	if (args.rhs_scale != NULL || be.amg_final_cols) GCGE_SetLinearSolverArgs(&args);   /* (the caller clears it) */
+	if (args.rhs_scale != NULL || args.x_src != NULL || be.amg_final_cols) GCGE_SetLinearSolverArgs(&args);   /* (the caller clears it) */
 }
 
 int GCGE_SolverTakesScaledRhs(struct OPS_ *ops)

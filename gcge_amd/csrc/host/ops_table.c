@@ -66,7 +66,8 @@ void **GCGE_GetRealignedRhs(int *b0) { if (b0 != NULL) *b0 = g_realigned_b0; ret
  *   GCGE_NO_RHS_SCALE        scaled_rhs_solver, amg_form_rhs                (the GCG driver forms b = (lambda + sigma) x)
  *   GCGE_NO_BLOCK_MOVES      block_moves                                    (X, the W start vectors and b moved one by one)
  *   GCGE_NO_RITZ_IN_PLACE    ritz_in_place                                  (Ritz vectors into the eigenvector block, then ComputeX)
- *   GCGE_NO_PANEL_NORMS      panel_norms_sq                                 (column norms by a sweep of their own) */
+ *   GCGE_NO_PANEL_NORMS      panel_norms_sq                                 (column norms by a sweep of their own)
+ *   GCGE_NO_START_IN_PLACE   start_in_place                                 (the W start vectors and b moved before the solve) */
 static GCGE_BACKEND g_backend; static void *g_backend_matvec = NULL, *g_backend_lincomb = NULL;
 void GCGE_SetBackend(struct OPS_ *ops, const GCGE_BACKEND *backend)
 {
@@ -90,6 +91,7 @@ GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
 	if (getenv("GCGE_NO_BLOCK_MOVES") != NULL) b.block_moves = NULL;
 	if (getenv("GCGE_NO_RITZ_IN_PLACE") != NULL) b.ritz_in_place = NULL;
 	if (getenv("GCGE_NO_PANEL_NORMS") != NULL) b.panel_norms_sq = NULL;
+	if (getenv("GCGE_NO_START_IN_PLACE") != NULL) b.start_in_place = 0;
 	return b;
 }
 

@@ -31,6 +31,7 @@ class LINSOL_ARGS(C.Structure):
                 ("user_scale", C.POINTER(C.c_double)), ("n_user_scale", C.c_int),
                 ("rhs_scale", C.POINTER(C.c_double)),
                 ("idle_blocks", C.c_void_p), ("n_idle", C.c_int),
+                ("x_src", C.c_void_p), ("x_src_col", C.c_int),
                 ("final_residual_cols", C.c_int)]
 
 

@@ -419,6 +419,14 @@ void *gcge_hip_residual_hook (void);
 int gcge_hip_cg_pass1_mv (void *mat, void **p, int c0, int m, double *host_pw, double *host_ww);
 int gcge_hip_cg_start_mv (void *mat, void **x, int xc0, void **b, int bc0, void **r, void **p0, int rc0, int m,
 		double *host_rho);   /* r = b - A x, p0 = r, rho = column sums of r^2 (local rows) in one sweep */
+/*     the same start for b = x diag(host_scale), never read (kernel MODE 6); with b != NULL the sweep also stores the right-hand
+ *     sides it formed into b[:, bc0..) (MODE 8): x may then be columns of any block but r, p0 and b, and is only read        */
+int gcge_hip_cg_start_scaled_b_mv (void *mat, void **x, int xc0, const double *host_scale, void **r, void **p0, int rc0, int m,
+		void **b, int bc0, double *host_rho);
+/*     x[:, xc0..xc0+m) = src[:, sc0..) + sum_{q < cnt} ring_q[:, 0..m) diag(coef[q m ..]): the fused CG's x flush with its read
+ *     operand apart from the one it writes (cnt <= 16, 16-byte column pairs; host_coef: cnt * m factors); -1 declines          */
+int gcge_hip_cg_accum_x_mv (void **src, int sc0, void **x, int xc0, int m, void ***ring, int cnt, const double *host_coef);
+long gcge_hip_bpcg_start_in_place_stats (long *declined);   /* calls with an initial guess elsewhere started in one sweep / materialised first */
 int gcge_hip_cg_pass2_mv (void *mat, void **p, void **r, void **pnew, int c0, int m, const double *d_alpha,
 		const double *d_beta, const int *d_flag, double *host_rho);
 /*     the same two passes with the column sums left on the DEVICE and nothing waited for (the fused CG computes its

@@ -162,6 +162,11 @@ int        GCGE_GetLocalInnerProdReduces (void);
  *                 the driver's systems A w = (lambda + sigma) x for B == NULL, published only to a solver that takes them
  *                 (GCGE_SolverTakesScaledRhs, gcge_solver.h).  The reference forms b through MatDotMultiVec + MultiVecLinearComb
  *                 (src/ops_eig_sol_gcg.c:560-577).  NULL: b is an ordinary right-hand side.
+ *   x_src, x_src_col   the initial guess is NOT in the solver call's x: it is columns [x_src_col, x_src_col + m) of the block x_src,
+ *                 which the solver must not write; the result goes to the call's x.  Together with rhs_scale: b = x_src diag(rhs_scale),
+ *                 and the solver leaves that b in the call's b.  Published only to a back-end whose record says start_in_place;
+ *                 such a back-end accepts ANY call of this kind: where its one-sweep start does not take the operands it makes
+ *                 the copy and b itself first and goes on as if it had been handed them.  NULL: x holds the initial guess.
  *   idle_blocks   n_idle blocks the driver does not need during the call (its work blocks): scratch for the solver — the fused
  *                 HIP solver takes those that match its own blocks as further slots of its direction ring.
  *   final_residual_cols   whose residual the caller reads after the call: 0 every column's (a direct call), k > 0 only that of
@@ -173,6 +178,7 @@ typedef struct GCGE_LINSOL_ARGS_ {
 	const double *user_scale; int n_user_scale;
 	const double *rhs_scale;
 	void ***idle_blocks; int n_idle;
+	void **x_src; int x_src_col;
 	int final_residual_cols;
 } GCGE_LINSOL_ARGS;
 void       GCGE_SetLinearSolverArgs (const GCGE_LINSOL_ARGS *args);   /* copied; NULL clears */
@@ -224,6 +230,8 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *                 the same bits.  0 declines with nothing touched: more than 128 output columns, blocks in different row orders,
  *                 unaligned leading dimensions, shapes whose MultiVecLinearComb does not work row by row from registers.  GCG then
  *                 forms P before the Ritz vectors and drops the reference's ComputeX (src/ops_eig_sol_gcg.c:458-471).
+ *   start_in_place   1 when the back-end's solvers (scaled_rhs_solver, the smoother of amg_smoother_setup) honour
+ *                 GCGE_LINSOL_ARGS.x_src: GCG then leaves the W start vectors and b to the first smoothing sweep of BlockAMG (gcg.c).
  *   panel_norms_sq   out[j] = sum over the LOCAL rows of y[r, start + j]^2, j < end - start, for the panel y[:, start..end) that the
  *                 LAST call of MultiVecLinearComb wrote, summed by that call from the values it stored (no second pass over the
  *                 panel; a fixed order: the same sums on every run, rounded otherwise than MultiVecInnerProd('D')'s).  0 when that
@@ -256,6 +264,7 @@ typedef struct GCGE_BACKEND_ {
 	GCGE_BLOCK_MOVES_FN block_moves;
 	GCGE_RITZ_IN_PLACE_FN ritz_in_place;
 	GCGE_PANEL_NORMS_FN panel_norms_sq;
+	int start_in_place;
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

@@ -156,6 +156,13 @@ void GCGE_GcgBlockMoveStats (long *odd_origins, long *realigned, long *fused_mov
 /* counters since the library was loaded: launches that wrote the Ritz vectors over X and moved P in behind them
  * (GCGE_BACKEND.ritz_in_place; 0 over a table that does not offer it: the driver then keeps ComputeRitzVec / ComputeP / ComputeX) */
 void GCGE_GcgRitzInPlaceStats (long *fused_launches);
+/* ComputeW's test for leaving the W start vectors and b to the solver (GCGE_LINSOL_ARGS.x_src): 1, with the source range
+ * [*lo, *lo + *total), when the runs offset[] = {count; lo_0, hi_0, ...} are ONE contiguous range (adjacent runs count as one) and
+ * its first column, its length and startW are even; 0 otherwise (no run, a hole between runs, an odd column or length) */
+int GCGE_GcgStartInPlaceRange (const int *offset, int startW, int *lo, int *total);
+/* counters since the library was loaded: outer iterations whose W solve started from the Ritz vectors where they lie, and outer
+ * iterations of a back-end that offers it (in-place Ritz vectors, BlockAMG's scaled right-hand sides) that moved them first */
+void GCGE_GcgStartInPlaceStats (long *in_place, long *declined);
 /* counters since the library was loaded, of the "twice is enough" test of the Cholesky-QR scheme's projection (orth.c: project_out):
  * times it was made, times it asked for another pass, times the column norms came from the panel update that wrote the columns
  * (GCGE_BACKEND.panel_norms_sq) */
