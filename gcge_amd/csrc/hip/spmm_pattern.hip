@@ -610,6 +610,26 @@ static int g_chain2_xcd = 2;   // 2: runs of 4 neighbouring tiles per XCD (pass 
                                // the tiles per XCD (slower: 3.43 vs 3.19 ms at 256^3); 0: tiles in block order
 extern "C" void gcge_hip_spmm_chain2_xcd(int on) { g_chain2_xcd = on; }
 extern "C" void gcge_hip_spmm_chain2_tune(int waves) { if (waves == 0 || waves == 4 || waves == 8 || waves == 16) g_chain2_nw = waves; }
+// Waves per block of the chain + line-exchange kernel for `nrows` rows, 0: none (the chain or the plain kernel).  A candidate must
+// tile the plane (span % (nw L) == 0) and the rows must fill one group of nw lines.  Third condition, for row strips: in the FIRST
+// tile of a block the centre row a wave posts for its neighbours is loaded from its clamped row (chain2_body, it == 0), so a wave
+// whose rows lie beyond nrows posts X[nrows - 1] and the wave below it takes that as its +L row.  On a whole matrix that slot has
+// value 0; on a strip that ends inside the matrix it has not.  Later tiles get the row through the +S chain and are right.  The
+// ragged last group (nrows % (nw L) != 0) is group nrows / (nw L), and the first tiles are those of the groups below nb / (L / 8):
+// the candidate is taken only when the ragged group is not among them.  With nb = span / (8 nw) that is nrows >= span, which every
+// whole matrix with a +-span offset meets: whole matrices keep the kernel and the wave count they had.  The ring sweep
+// (gcge_hip_ring_pass) starts its rows the same way and checks the same condition on the geometry it is handed.
+static int chain2_waves(long nrows, long span, long span2, int lt) {
+  if (!(span2 <= -8 && (-span2) % 8 == 0 && lt >= 5)) return 0;
+  const long L = -span2;
+  for (int cand = g_chain2_nw; cand >= 4; cand /= 2) {
+    if (span % (cand * L) != 0 || nrows < cand * L) continue;
+    const long nb = std::min(span / (8L * cand), (((nrows + L - 1) / L + cand - 1) / cand) * (L / 8));
+    if (nrows % (cand * L) != 0 && (nrows / (cand * L)) * (L / 8) < nb) continue;   // a ragged group would be some block's first tile
+    return cand;
+  }
+  return 0;
+}
 static int g_chain_lpr = 8;    // chain variant: lanes per row = half the columns per pass (8, 16, 32)
 extern "C" void gcge_hip_spmm_chain_tune(int lanes_per_row) { if (lanes_per_row == 8 || lanes_per_row == 16 || lanes_per_row == 32) g_chain_lpr = lanes_per_row; }
 static int g_pat_line = 8;    // tuning: -1 = from the stencil's second longest offset, 8 = consecutive slices
@@ -695,6 +715,12 @@ extern "C" int gcge_hip_pattern_width(int max_row_len) {
 // CHAIN layout (slots 0,1,2 = offsets -span, 0, +span; see spmm_pattern_chain_kernel) and span is a multiple of 32;
 // span2 == -L <= -8: additionally slots 3,4 = offsets -L, +L (spmm_pattern_chain2_kernel).
 // -1: alignment contract not met.
+// Row strips: d_pid + r0, x + r0 * ldx, y + r0 * ldy (and d_rowval + 8 r0) with nrows = r1 - r0 give rows [r0, r1) of the product for
+// ANY 0 <= r0 < r1 <= rows of the matrix (mat_product.hip spmm_rows): every kernel reads X through the table's offsets from the
+// row it computes, rows outside the strip included, and stores the strip's rows only.  A chain table asks for nothing more; for a
+// chain + line-exchange table the launcher (chain2_waves) keeps the exchange away from strips whose ragged end would be the first
+// tile of a block, where a neighbour's row would come from a clamped one, and takes fewer waves, the chain or the plain kernel.
+// nrows <= 0 or ncols <= 0: 0, nothing is launched; d_dots / d_dots_yy (ncols > 0) are set to 0.
 extern "C" int gcge_hip_pattern_spmm_vals(int nrows, const unsigned short* d_pid, const void* d_tab, int npat, int lt,
                                           long span, long span2, const double* d_x, long ldx, double* d_y, long ldy, int ncols,
                                           double* d_dots, double* d_dots_yy, void* stream, long near, const double* d_rowval);
@@ -716,7 +742,11 @@ extern "C" int gcge_hip_pattern_spmm(int nrows, const unsigned short* d_pid, con
 extern "C" int gcge_hip_pattern_spmm_vals(int nrows, const unsigned short* d_pid, const void* d_tab, int npat, int lt,
                                           long span, long span2, const double* d_x, long ldx, double* d_y, long ldy, int ncols,
                                           double* d_dots, double* d_dots_yy, void* stream, long near, const double* d_rowval) {
-  if (nrows <= 0 || ncols <= 0) return 0;
+  if (nrows <= 0 || ncols <= 0) {   // no rows: the sums are 0 (nothing else is written)
+    if (ncols > 0 && d_dots) GCGE_HIP_CHECK(hipMemsetAsync(d_dots, 0, (size_t)ncols * sizeof(double), (hipStream_t)stream));
+    if (ncols > 0 && d_dots && d_dots_yy) GCGE_HIP_CHECK(hipMemsetAsync(d_dots_yy, 0, (size_t)ncols * sizeof(double), (hipStream_t)stream));
+    return 0;
+  }
   if (d_rowval != nullptr && lt > 8) return -1;
   CgArgs cgv = CgArgs{}; cgv.rowval = d_rowval;
   if ((ncols & 1) || (ldx & 1) || (ldy & 1) || ((uintptr_t)d_x & 15) || ((uintptr_t)d_y & 15)) return -1;
@@ -726,10 +756,7 @@ extern "C" int gcge_hip_pattern_spmm_vals(int nrows, const unsigned short* d_pid
   // lines of `span2` rows when they tile the matrix exactly (a plane = a whole number of 4-line groups)
   long line = 8;
   // chain layout with line exchange: L = -span2 rows per grid line, nw waves per block (the most that tile a plane)
-  int nw = 0;
-  if (span2 <= -8 && (-span2) % 8 == 0 && lt >= 5)
-    for (int cand = g_chain2_nw; cand >= 4; cand /= 2)
-      if (span % (cand * -span2) == 0 && (long)nrows >= cand * -span2) { nw = cand; break; }
+  const int nw = chain2_waves(nrows, span, span2, lt);
   if (nw > 0) {
     const long L = -span2;
     const long nbc = std::min(span / (8L * nw), ((((long)nrows + L - 1) / L + nw - 1) / nw) * (L / 8));
@@ -812,6 +839,8 @@ extern "C" int gcge_hip_pattern_spmm_vals(int nrows, const unsigned short* d_pid
 // (its table is a valid generic one).  -1: not applicable (alignment), the caller keeps the unfused recurrence.
 // near > 0: the table's slots are [-S, 0, +S, -L, +L, -1, +1] (7-point stencil) and near is the largest |offset| in it
 // (GCGE_HIP_MAT_::pat_near): modes 2 and 4 may take the LDS-ring sweep of spmm_ring.hip.
+// Row strips as in gcge_hip_pattern_spmm_vals (d_r, d_pnew, d_b advanced by r0 rows like x); nrows <= 0 or ncols <= 0 with a valid
+// mode: 0, and d_dots (mode 2: d_dots_yy too) set to 0 when there are columns.
 extern "C" int gcge_hip_pattern_cg_vals(int mode, int nrows, const unsigned short* d_pid, const void* d_tab, int npat, int lt,
                                         long span, long span2, const double* d_x, long ldx, double* d_r, long ldr, double* d_pnew,
                                         long ldp, int ncols, const double* d_alpha, const double* d_beta, const int* d_flag,
@@ -832,7 +861,11 @@ extern "C" int gcge_hip_pattern_cg_vals(int mode, int nrows, const unsigned shor
                                         const double* d_rowval) {
   if (d_rowval != nullptr && lt > 8) return -1;
   if (mode != 2 && mode != 3 && mode != 4 && mode != 5 && mode != 6 && mode != 7 && mode != 8) return -1;
-  if (nrows <= 0 || ncols <= 0) return 0;
+  if (nrows <= 0 || ncols <= 0) {   // no rows: the sums are 0 (nothing else is written)
+    if (ncols > 0 && d_dots) GCGE_HIP_CHECK(hipMemsetAsync(d_dots, 0, (size_t)ncols * sizeof(double), (hipStream_t)stream));
+    if (ncols > 0 && d_dots && mode == 2 && d_dots_yy) GCGE_HIP_CHECK(hipMemsetAsync(d_dots_yy, 0, (size_t)ncols * sizeof(double), (hipStream_t)stream));
+    return 0;
+  }
   if ((ncols & 1) || (ldx & 1) || ((uintptr_t)d_x & 15) || d_dots == nullptr) return -1;
   if ((mode == 6 || mode == 8) && d_alpha == nullptr) return -1;
   if (mode == 7 && (d_b == nullptr || (ldr & 1) || (ldp & 1) || ((uintptr_t)d_r & 15) || ((uintptr_t)d_pnew & 15) || d_pnew == d_x || d_pnew == d_r)) return -1;
@@ -842,10 +875,7 @@ extern "C" int gcge_hip_pattern_cg_vals(int mode, int nrows, const unsigned shor
   if ((size_t)npat * lt * sizeof(PatEntry) > 64 * 1024) return -1;
   hipStream_t st = (hipStream_t)stream;
   const int npass = (ncols + 15) / 16;
-  int nw = 0;
-  if (span2 <= -8 && (-span2) % 8 == 0 && lt >= 5)
-    for (int cand = g_chain2_nw; cand >= 4; cand /= 2)
-      if (span % (cand * -span2) == 0 && (long)nrows >= cand * -span2) { nw = cand; break; }
+  const int nw = chain2_waves(nrows, span, span2, lt);
   const long L = -span2;
   long nb, line = 8, cline = 0;
   if (nw > 0) { nb = std::min(span / (8L * nw), ((((long)nrows + L - 1) / L + nw - 1) / nw) * (L / 8)); cline = L; }

@@ -408,6 +408,10 @@ extern "C" int gcge_hip_ring_pass(int mode, int nrows, const unsigned short* d_p
   if (!g_ring_on || (mode != 0 && mode != 1 && mode != 2 && mode != 4) || (nrows & 7) || nrows < 8 || ((uintptr_t)d_pid & 15) || L % 8 || L < 8) return -1;
   if (((uintptr_t)d_x & 15) || (ldx & 1)) return -1;
   const long nlines = ((long)nrows + L - 1) / L, ntl = (nlines + nw - 1) / nw * (L / 8);
+  // a wave whose first slice lies beyond nrows starts on the last 8 rows and hands them to the wave below as its +L rows: right only
+  // where that slot has value 0 (the rows end the matrix).  Same rule as chain2_waves (spmm_pattern.hip): the ragged last group of
+  // nw lines must not be the first tile of a block.
+  if (nw < 1 || ((long)nrows % (nw * L) != 0 && ((long)nrows / (nw * L)) * (L / 8) < nb)) return -1;
   if (mode <= 1) {
     if (!g_ring_product || d_y == nullptr || ((uintptr_t)d_y & 15) || (ldy & 1) || ntl * nw * 8 != (long)nrows) return -1;
   }
