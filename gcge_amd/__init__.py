@@ -6,7 +6,8 @@ kernels are HIP (gcge_amd/csrc/hip), host logic is C (gcge_amd/csrc/host).
 from .lib import (CSR, RunResult, Timing, host_lib, hip_lib, build_libs,
                   make_problem, load_petsc_binary, load_matrix_market, HipBackend, run_gcg,
                   PASResult, run_pas)
+from .eigsh import EigshResult, NoConvergence, eigsh
 
 __all__ = ["CSR", "RunResult", "Timing", "host_lib", "hip_lib", "build_libs",
            "make_problem", "load_petsc_binary", "load_matrix_market", "HipBackend", "run_gcg",
-           "PASResult", "run_pas"]
+           "PASResult", "run_pas", "eigsh", "EigshResult", "NoConvergence"]

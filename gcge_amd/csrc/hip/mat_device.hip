@@ -1,5 +1,6 @@
-// Matrices from DEVICE-resident CSR arrays (gcge_hip_mat_create_device, include/gcge_hip.h) and blocks of vectors out to device memory
-// (gcge_hip_mv_to_device): the ways in and out of the back-end that never touch the host with O(n) data.
+// Matrices from DEVICE-resident CSR arrays (gcge_hip_mat_create_device, include/gcge_hip.h) and blocks of vectors out to and in from
+// device memory (gcge_hip_mv_to_device, gcge_hip_mv_from_device): the ways in and out of the back-end that never touch the host with
+// O(n) data.
 //
 // The constructor checks its input on the device (rowptr alone first, then the columns by position: nothing is addressed through a
 // value that has not been checked), copies the CSR, builds the pad-8 copy (hipcub scan of (len + 7) / 8 + a fill kernel, pads
@@ -401,19 +402,123 @@ __global__ void k_md_mv_gather(int n, int m, const double* __restrict__ src, lon
   const long r = perm != nullptr ? perm[i] : i;
   out[r * ldo + j] = src[i * ld + j];
 }
+// the block's row order on the device for one call (NULL: the caller's order); freed by the caller after its kernel is done
+static int* md_perm_upload(const GcgePerm* P, int n) {
+  if (P == nullptr) return nullptr;
+  int* d_perm = md_alloc<int>((size_t)n);
+  GCGE_HIP_CHECK(hipMemcpyAsync(d_perm, P->perm, (size_t)n * sizeof(int), hipMemcpyHostToDevice, md_stream()));
+  return d_perm;
+}
 extern "C" void gcge_hip_mv_to_device(void** mv, int c0, int c1, double* d_out, long ldo) {
   gcge_hip_apply_pending();
   GcgeHipMV* v = (GcgeHipMV*)mv;
   const int n = v->nrows, m = c1 - c0;
   GCGE_REQUIRE(c0 >= 0 && c1 <= v->ncols && m >= 0 && ldo >= m && d_out != nullptr, "gcge_hip_mv_to_device: ranges");
   if (m == 0 || n == 0) return;
-  const GcgePerm* P = real_perm(v->perm);
-  int* d_perm = nullptr;
-  if (P != nullptr) {
-    d_perm = md_alloc<int>((size_t)n);
-    GCGE_HIP_CHECK(hipMemcpyAsync(d_perm, P->perm, (size_t)n * sizeof(int), hipMemcpyHostToDevice, md_stream()));
-  }
+  int* d_perm = md_perm_upload(real_perm(v->perm), n);
   k_md_mv_gather<<<md_blocks((long)n * m, MD_BS), MD_BS, 0, md_stream()>>>(n, m, v->d + c0, v->ld, d_perm, d_out, ldo);
+  GCGE_HIP_CHECK(hipStreamSynchronize(md_stream()));
+  if (d_perm != nullptr) hipFree(d_perm);
+}
+
+// ------------------------------------------------------------------------------------------------------------------- blocks in
+// block[i * ld + c0 + j] = d_in[row(i) * row_stride + j * col_stride]; row(i) = perm[i] for a block that lives in the back-end's own
+// order (the direction of gcge_hip_mv_from_host, the inverse of k_md_mv_gather).  Three forms:
+//   rows contiguous (col_stride == 1): k_md_rows_in, the row-slab form of the block-stream kernels in vec_kernels.hip — tpr lanes walk
+//     a row, a block owns a contiguous slab of rows, four rows are in flight per lane, no division on a flattened index; a lane
+//     moves 16 bytes where source and destination columns are both 16-byte aligned (one 8-byte head lane in front of an odd first
+//     column, one behind an odd last one) and 8 bytes where their parities differ; the source row is read through perm[i], the
+//     destination rows stay in order;
+//   columns contiguous (row_stride == 1), no permutation: the padded 32 x 32 LDS transpose of the host path
+//     (gcge_hip_colmajor_to_rowmajor), both sides coalesced;
+//   everything else: k_md_elems_in, one element per thread by 2-D indexing — coalesced on the destination only.
+typedef double v2d_md __attribute__((ext_vector_type(2)));
+#define MD_IN_COLS 256           // columns per launch of the row form (one lane per column at most: tpr <= 256)
+__global__ __launch_bounds__(256) void k_md_rows_in(long n, int m, const double* __restrict__ src, long lds, const int* __restrict__ perm,
+                                                    double* __restrict__ dst, long ldd, int head, int wide, int nl, int tpr) {
+  const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
+  if (tx >= nl) return;
+  int j, w;
+  if (!wide) { j = tx; w = 1; }
+  else if (tx < head) { j = 0; w = 1; }
+  else { j = head + 2 * (tx - head); w = min(2, m - j); }
+  const long slab = (((n + gridDim.x - 1) / gridDim.x) + rpb - 1) / rpb * rpb;
+  const long rend = min(n, ((long)blockIdx.x + 1) * slab);
+  long row = (long)blockIdx.x * slab + ty;
+  if (w == 2) {
+    for (; row + 3L * rpb < rend; row += 4L * rpb) {
+      long sr[4]; v2d_md a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const long r = row + (long)u * rpb; sr[u] = perm != nullptr ? (long)perm[r] : r; }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d_md*>(src + sr[u] * lds + j));
+#pragma unroll
+      for (int u = 0; u < 4; ++u) __builtin_nontemporal_store(a[u], reinterpret_cast<v2d_md*>(dst + (row + (long)u * rpb) * ldd + j));
+    }
+    for (; row < rend; row += rpb) {
+      const long s = perm != nullptr ? (long)perm[row] : row;
+      *reinterpret_cast<v2d_md*>(dst + row * ldd + j) = *reinterpret_cast<const v2d_md*>(src + s * lds + j);
+    }
+  } else {
+    for (; row + 3L * rpb < rend; row += 4L * rpb) {
+      long sr[4]; double a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { const long r = row + (long)u * rpb; sr[u] = perm != nullptr ? (long)perm[r] : r; }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a[u] = __builtin_nontemporal_load(src + sr[u] * lds + j);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) __builtin_nontemporal_store(a[u], dst + (row + (long)u * rpb) * ldd + j);
+    }
+    for (; row < rend; row += rpb) {
+      const long s = perm != nullptr ? (long)perm[row] : row;
+      dst[row * ldd + j] = src[s * lds + j];
+    }
+  }
+}
+// the slow form: 16 x 16 threads, columns along x
+__global__ __launch_bounds__(256) void k_md_elems_in(long n, int m, const double* __restrict__ src, long rs, long cs, const int* __restrict__ perm,
+                                                     double* __restrict__ dst, long ldd) {
+  const long i = (long)blockIdx.x * 16 + threadIdx.y;
+  if (i >= n) return;
+  const long s = perm != nullptr ? (long)perm[i] : i;
+  for (int j = threadIdx.x; j < m; j += 16) dst[i * ldd + j] = src[s * rs + (long)j * cs];
+}
+static void md_rows_in(int n, int m, const double* src, long lds, const int* d_perm, double* dst, long ldd) {
+  // 16-byte lanes need even strides and the same parity of the two first columns (the block itself is 16-byte aligned)
+  const int pd = (((uintptr_t)dst & 15) == 8) ? 1 : 0, ps = (((uintptr_t)src & 15) == 8) ? 1 : 0;
+  const int wide = (lds % 2 == 0 && ldd % 2 == 0 && pd == ps && m - pd >= 2) ? 1 : 0;
+  const int head = wide ? pd : 0;
+  const int nl = wide ? head + (m - head + 1) / 2 : m;
+  int tpr = 1;
+  while (tpr < nl) tpr *= 2;
+  const int rpb = 256 / tpr;
+  const long want = ((long)n + 4L * rpb - 1) / (4L * rpb);
+  const unsigned grid = (unsigned)(want < 1 ? 1 : want > 8192 ? 8192 : want);
+  k_md_rows_in<<<grid, 256, 0, md_stream()>>>((long)n, m, src, lds, d_perm, dst, ldd, head, wide, nl, tpr);
+}
+extern "C" void gcge_hip_mv_from_device(void** mv, int c0, int c1, const double* d_in, long row_stride, long col_stride) {
+  gcge_hip_apply_pending();              // a held-back scaling is applied first and then overwritten, never applied to the new data
+  GcgeHipMV* v = (GcgeHipMV*)mv;
+  const int n = v->nrows, m = c1 - c0;
+  GCGE_REQUIRE(c0 >= 0 && c0 <= c1 && c1 <= v->ncols, "gcge_hip_mv_from_device: column range");
+  if (m == 0 || n == 0) return;
+  GCGE_REQUIRE(d_in != nullptr && ((uintptr_t)d_in & 7) == 0 && row_stride >= 1 && col_stride >= 1, "gcge_hip_mv_from_device: source and strides");
+  GCGE_REQUIRE((col_stride == 1 && row_stride >= m) || (row_stride == 1 && col_stride >= n) ||
+               row_stride / col_stride >= m || col_stride / row_stride >= n, "gcge_hip_mv_from_device: no two entries of the source alias");
+  GCGE_REQUIRE(row_stride <= (LONG_MAX / 16) / n && col_stride <= (LONG_MAX / 16) / m, "gcge_hip_mv_from_device: the source's extent");
+  const uintptr_t s0 = (uintptr_t)d_in, s1 = s0 + (size_t)(((long)(n - 1) * row_stride + (long)(m - 1) * col_stride + 1) * (long)sizeof(double));
+  const uintptr_t b0 = (uintptr_t)v->d, b1 = b0 + v->bytes;
+  GCGE_REQUIRE(s1 <= b0 || b1 <= s0, "gcge_hip_mv_from_device: the source does not overlap the block");
+  int* d_perm = md_perm_upload(real_perm(v->perm), n);
+  double* dst = v->d + c0;
+  if (col_stride == 1) {
+    for (int c = 0; c < m; c += MD_IN_COLS) md_rows_in(n, m - c < MD_IN_COLS ? m - c : MD_IN_COLS, d_in + c, row_stride, d_perm, dst + c, v->ld);
+  } else if (row_stride == 1 && d_perm == nullptr) {
+    GCGE_REQUIRE(gcge_hip_colmajor_to_rowmajor(n, m, d_in, col_stride, dst, v->ld, md_stream()) == 0, "gcge_hip_mv_from_device: kernel launch");
+  } else {
+    k_md_elems_in<<<md_blocks(n, 16), dim3(16, 16), 0, md_stream()>>>((long)n, m, d_in, row_stride, col_stride, d_perm, dst, v->ld);
+  }
+  GCGE_HIP_CHECK(hipGetLastError());
   GCGE_HIP_CHECK(hipStreamSynchronize(md_stream()));
   if (d_perm != nullptr) hipFree(d_perm);
 }

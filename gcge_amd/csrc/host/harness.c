@@ -4,6 +4,7 @@
  * comparable flag for flag (-nevConv -nevMax -blockSize -nevInit + -gcge_*).
  */
 #include <float.h>
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -179,6 +180,35 @@ int GCGE_RunGCGGiven(void *A, void *B, int flag, int argc, char *argv[], struct 
 {
 	if (evec == NULL || nevGiven < 0) return -1;
 	return run_gcg(A, B, flag, argc, argv, ops, eval_out, NULL, res, evec, nevGiven);
+}
+
+int GCGE_ResidualNorms(void *A, void *B, void **evec, int start, int end, const double *eval, double *out, struct OPS_ *ops)
+{
+	int m = end - start, s[2], e[2], idx; void **w0, **w1;
+	GCGE_RESIDUAL_FN hook;
+	if (A == NULL || evec == NULL || ops == NULL || start < 0 || m < 0 || (m > 0 && (eval == NULL || out == NULL))) return -1;
+	if (m == 0) return 0;
+	hook = GCGE_BackendOf(ops).residual_sq;
+	if (hook != NULL && hook(A, B, evec, start, end, eval, out)) {
+		GCGE_COMM *comm = GCGE_GetComm();          /* the back-end summed over its own rows */
+		if (comm != NULL) comm->allreduce_sum(out, m, comm->ctx);
+		for (idx = 0; idx < m; ++idx) out[idx] = sqrt(out[idx]);
+		return 0;
+	}
+	/* the slot sequence of CheckConvergence (gcg.c) */
+	ops->MultiVecCreateByMat(&w0, m, A, ops);
+	ops->MultiVecCreateByMat(&w1, m, A, ops);
+	s[0] = start; e[0] = end; s[1] = 0; e[1] = m;
+	ops->MatDotMultiVec(A, evec, w0, s, e, ops);
+	ops->MatDotMultiVec(B, evec, w1, s, e, ops);
+	ops->MultiVecLinearComb(NULL, w1, 0, s, e, NULL, 0, (double*)eval, 1, ops);   /* lambda B x */
+	s[0] = 0; e[0] = m;
+	ops->MultiVecAxpby(-1.0, w1, 1.0, w0, s, e, ops);                             /* A x - lambda B x */
+	ops->MultiVecInnerProd('D', w0, w0, 0, s, e, out, 1, ops);
+	for (idx = 0; idx < m; ++idx) out[idx] = sqrt(out[idx]);
+	ops->MultiVecDestroy(&w0, m, ops);
+	ops->MultiVecDestroy(&w1, m, ops);
+	return 0;
 }
 
 int TestEigenSolverGCG(void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops)

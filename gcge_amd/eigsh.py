@@ -1,0 +1,126 @@
+"""gcge_amd.eigsh: the smallest eigenpairs of A x = lambda M x from torch, with nothing of size O(n) on the host.
+
+Plumbing only: the matrices go in through HipBackend.matrix_from_device, start vectors through HipBackend.mv_from_torch, the solve is
+the harness (GCGE_RunGCG, or GCGE_RunGCGGiven with start vectors), the eigenvectors come out through HipBackend.mv_to_torch and the
+residual norms through GCGE_ResidualNorms (the back-end's residual_sq, the routine the solver's convergence check uses)."""
+import collections
+import ctypes as C
+
+EigshResult = collections.namedtuple("EigshResult", ["eigenvalues", "eigenvectors", "converged", "iterations", "seconds", "residual_norms"])
+
+
+class NoConvergence(RuntimeError):
+    """Fewer than k pairs converged; .result is the EigshResult of what the solve reached (all k columns, .converged of them done)."""
+
+    def __init__(self, message, result):
+        super().__init__(message)
+        self.result = result
+
+
+_backends = {}
+
+
+def _is_handle(a):
+    return isinstance(a, (C.c_void_p, int))
+
+
+def _device_of(*things):
+    import torch
+    for a in things:
+        for t in (a if isinstance(a, (tuple, list)) else (a,)):
+            if isinstance(t, torch.Tensor) and t.is_cuda:
+                return t.device.index
+    return torch.cuda.current_device()
+
+
+def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=()):
+    """The k smallest eigenvalues and their eigenvectors of the symmetric problem A x = lambda M x (M=None: the identity; M positive
+    definite) by GCG on the GPU.  The smallest eigenvalues are the only mode.
+
+    A, M:  a torch sparse_csr CUDA tensor, a (crow, col, val) triple of device arrays, or a matrix handle of the back-end.  Handles
+           stay the caller's; what is created here is freed here.
+    X0:    (n, j) device tensor of start vectors, j <= nev_max (a warm start: the previous eigenvectors of a nearby operator).
+    tol:   relative residual tolerance, ||A x - lambda M x|| <= tol |lambda|;  maxiter: outer iterations at most (default 500).
+    nev_max (default 2 k), block_size:  columns of the eigenvector block and of the W block, as for the harness.
+    amg_levels:  0: the W systems by the fused block CG; L >= 2: by BlockAMG over a hierarchy of at most L levels.
+    backend:  a HipBackend (default: one per device, kept for the process).
+    gcge_args:  harness options ("-gcge_compW_cg_max_iter", 40, ...), appended as they are; they win over the arguments above.
+
+    Returns EigshResult(eigenvalues (k,), eigenvectors (n, k), converged, iterations, seconds, residual_norms (k,)), tensors float64
+    on the device.  Raises NoConvergence, carrying the partial result, when fewer than k pairs converged."""
+    import numpy as np
+    import torch
+    from .lib import HipBackend, host_lib, run_gcg
+
+    k = int(k)
+    nev_max = 2 * k if nev_max is None else int(nev_max)
+    amg_levels = int(amg_levels)
+    if k < 1 or nev_max < k:
+        raise ValueError("eigsh: 1 <= k <= nev_max is required")
+    if amg_levels == 1 or amg_levels < 0:
+        raise ValueError("eigsh: amg_levels is 0 (no hierarchy) or at least 2")
+    if backend is None:
+        dev = _device_of(A, M, X0)
+        backend = _backends.get(dev)
+        if backend is None:
+            backend = _backends[dev] = HipBackend(device=dev)
+    gcge_args = [str(a) for a in gcge_args]
+    own = [("-nevConv", k), ("-nevMax", nev_max), ("-gcge_rel_tol", repr(float(tol)))]
+    if maxiter is not None:
+        own.append(("-gcge_max_niter", int(maxiter)))
+    if block_size is not None:
+        own.append(("-blockSize", int(block_size)))
+    if amg_levels > 0:
+        own.append(("-gcge_amg_levels", amg_levels))
+    args = []
+    for name, value in own:             # (the harness takes the first occurrence of an option)
+        if name not in gcge_args:
+            args += [name, value]
+    args += gcge_args
+    for i, a in enumerate(gcge_args[:-1]):
+        if a == "-nevMax":
+            nev_max = int(gcge_args[i + 1])
+
+    made = []
+
+    def handle(a):
+        if _is_handle(a):
+            return a if isinstance(a, C.c_void_p) else C.c_void_p(a)
+        m = backend.matrix_from_device(*a) if isinstance(a, (tuple, list)) else backend.matrix_from_device(a)
+        made.append(m)
+        return m
+
+    evec = None
+    try:
+        mA = handle(A)
+        mB = handle(M) if M is not None else None
+        flag = 1 if amg_levels > 0 else 0
+        if X0 is not None:
+            shape = tuple(X0.shape) if hasattr(X0, "shape") else tuple(X0.__cuda_array_interface__["shape"])
+            if len(shape) != 2 or shape[1] > nev_max:
+                raise ValueError("eigsh: X0 is an (n, j) block with j <= nev_max")
+            evec = backend.ops.mv_create(nev_max, mA)
+            backend.mv_from_torch(mA, X0, mv=evec, c0=0)
+            ev, res = run_gcg(backend.ops_handle, mA, mB, args, flag=flag, given=(evec, int(shape[1])))
+        else:
+            ev, res, evec = run_gcg(backend.ops_handle, mA, mB, args, flag=flag, keep_evec=True)
+        h = host_lib()
+        h.GCGE_ResidualNorms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), C.c_void_p]
+        lam = np.ascontiguousarray(ev[:k], dtype=np.float64)
+        rn = np.zeros(k)
+        rc = h.GCGE_ResidualNorms(mA, mB, evec, 0, k, lam.ctypes.data_as(C.POINTER(C.c_double)), rn.ctypes.data_as(C.POINTER(C.c_double)),
+                                  backend.ops_handle)
+        if rc != 0:
+            raise RuntimeError("GCGE_ResidualNorms rc=%d" % rc)
+        V = backend.mv_to_torch(evec, 0, k)
+        result = EigshResult(torch.from_numpy(lam).to(V.device), V, int(res.nevConv), int(res.numIter), float(res.seconds),
+                             torch.from_numpy(rn).to(V.device))
+    finally:
+        if evec is not None and evec.value:
+            backend.ops.mv_destroy(evec, nev_max)
+        for m in made:
+            backend.free_matrix(m)
+    if result.converged < k:
+        raise NoConvergence("eigsh: %d of %d pairs converged in %d iterations" % (result.converged, k, result.iterations), result)
+    return result

@@ -21,6 +21,11 @@ class HipBackendImpl:
         self.g.gcge_hip_mat_create_device.argtypes = [C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
         self.g.gcge_hip_mv_to_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long]
         self.g.gcge_hip_mv_nrows.argtypes = [C.c_void_p]
+        self.g.gcge_hip_mv_ncols.argtypes = [C.c_void_p]
+        self.g.gcge_hip_mv_from_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_long]
+        self.g.gcge_hip_mv_device_ptr.restype = C.c_void_p
+        self.g.gcge_hip_mv_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
+        self.g.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
         self.device = device
         if self.g.gcge_hip_init(device) != 0:
             raise RuntimeError("HIP back-end: no GPU visible (there is no CPU fallback)")
@@ -88,6 +93,63 @@ class HipBackendImpl:
         if out.numel():
             self.g.gcge_hip_mv_to_device(mv, c0, c1, out.data_ptr(), c1 - c0)
         return out
+
+    def mv_from_torch(self, mat, t, mv=None, c0=0):
+        """Columns of a block of vectors from an (n, m) tensor that lives on the GPU (gcge_hip_mv_from_device): a 2-D CUDA tensor or
+        an object with __cuda_array_interface__, rows in the caller's order.  With mv=None a new block of m columns is created for
+        `mat` and returned; otherwise columns [c0, c0 + m) of `mv` are written and `mv` is returned.  The tensor is converted to
+        float64 on the device only if it is something else and is NOT made contiguous: its two strides go to the library as they are
+        (rows contiguous: the block-stream kernel; columns contiguous: the LDS transpose) unless two of its
+        entries alias (an expanded tensor), which costs one contiguous copy.  The producer's stream is synchronised before the call
+        (torch's current stream for tensors, the whole device for other objects).  TypeError: a host tensor; ValueError: another
+        row count, a column range outside the block, a tensor that overlaps the block."""
+        import torch
+        foreign = not isinstance(t, torch.Tensor)
+        if foreign:
+            if not hasattr(t, "__cuda_array_interface__"):
+                raise TypeError("mv_from_torch: a torch device tensor or an object with __cuda_array_interface__ is required")
+            t = torch.as_tensor(t, device=torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device()))
+        if not t.is_cuda:
+            raise TypeError("mv_from_torch: the tensor must live on the GPU (HipBackend.mv_from_numpy takes host arrays)")
+        if t.dim() != 2:
+            raise ValueError("mv_from_torch: an (n, m) tensor is required")
+        n, m = int(t.shape[0]), int(t.shape[1])
+        c0 = int(c0)
+        if mv is None:
+            if c0 != 0:
+                raise ValueError("mv_from_torch: a new block is written from column 0")
+            if n != self.g.gcge_hip_mat_nrows(mat):
+                raise ValueError("mv_from_torch: the tensor has %d rows, the matrix %d" % (n, self.g.gcge_hip_mat_nrows(mat)))
+        else:
+            if n != self.g.gcge_hip_mv_nrows(mv):
+                raise ValueError("mv_from_torch: the tensor has %d rows, the block %d" % (n, self.g.gcge_hip_mv_nrows(mv)))
+            if c0 < 0 or c0 + m > self.g.gcge_hip_mv_ncols(mv):
+                raise ValueError("mv_from_torch: columns [%d, %d) are outside the block's %d" % (c0, c0 + m, self.g.gcge_hip_mv_ncols(mv)))
+        if t.dtype != torch.float64:
+            t = t.to(dtype=torch.float64)
+        if n and m:
+            rs, cs = (int(v) for v in t.stride())
+            if not (rs >= 1 and cs >= 1 and ((cs == 1 and rs >= m) or (rs == 1 and cs >= n) or rs >= m * cs or cs >= n * rs)):
+                t = t.contiguous()
+                rs, cs = m, 1
+            if mv is not None:
+                ld = C.c_long()
+                b0 = self.g.gcge_hip_mv_device_ptr(mv, C.byref(ld)) or 0
+                b1 = b0 + 8 * ld.value * n
+                s0 = t.data_ptr()
+                s1 = s0 + 8 * ((n - 1) * rs + (m - 1) * cs + 1)
+                if s0 < b1 and b0 < s1:
+                    raise ValueError("mv_from_torch: the tensor overlaps the block it is written to")
+        created = mv is None
+        if created:
+            mv = self.ops.mv_create(m, mat)
+        if n and m:
+            if foreign:
+                torch.cuda.synchronize(t.device)
+            else:
+                torch.cuda.current_stream(t.device).synchronize()
+            self.g.gcge_hip_mv_from_device(mv, c0, c0 + m, t.data_ptr(), rs, cs)
+        return mv
 
     def matrix_grid(self, csr, dims, box_of_row):
         """A matrix on a masked grid: box_of_row[r] = x + nx (y + ny z) (int32 array, ascending); see gcge_hip_mat_create_grid."""

@@ -224,6 +224,16 @@ void gcge_hip_mv_from_host (void **mv, int c0, int c1, const double *host, long 
 /* columns [c0,c1) -> DEVICE row-major array: d_out[r * ldo + (j - c0)] (ldo >= c1 - c0), rows in the caller's order whatever order the
  * block lives in; one gather kernel on gcge_hip_stream(), which the call synchronises                                              */
 void gcge_hip_mv_to_device (void **mv, int c0, int c1, double *d_out, long ldo);
+/* columns [c0,c1) <- DEVICE array with element strides: column j of the caller's row r is d_in[r * row_stride + (j - c0) * col_stride].
+ * Rows are in the caller's order whatever order the block lives in (device row i takes the caller's row perm[i], as
+ * gcge_hip_mv_from_host); only the block's own nrows rows and the columns of the range are written.  A held-back column scaling is
+ * applied first, then overwritten.  Runs on gcge_hip_stream(), which the call synchronises; the caller synchronises its producer.
+ * Required (the call aborts otherwise): 0 <= c0 <= c1 <= ncols; with work to do, d_in != NULL, both strides >= 1, no two (r, j)
+ * alias — col_stride == 1 && row_stride >= m, row_stride == 1 && col_stride >= nrows, row_stride >= m * col_stride or
+ * col_stride >= nrows * row_stride (m = c1 - c0) — and the source's address range lies outside the block's allocation.
+ * Rows contiguous (col_stride == 1) is the block-stream form; columns contiguous (row_stride == 1) of a block in the caller's order
+ * goes through an LDS transpose; every other shape takes an element kernel.                                  */
+void gcge_hip_mv_from_device (void **mv, int c0, int c1, const double *d_in, long row_stride, long col_stride);
 int  gcge_hip_mv_nrows (void **mv);
 int  gcge_hip_mv_ncols (void **mv);
 double *gcge_hip_mv_device_ptr (void **mv, long *ld);

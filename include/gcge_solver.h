@@ -187,6 +187,12 @@ int GCGE_RunGCG (void *A, void *B, int flag, int argc, char *argv[], struct OPS_
 int GCGE_RunGCGGiven (void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops,
 		double *eval, void **evec, int nevGiven, GCGE_RunResult *res);
 
+/* Residual norms of eigenpairs a solve returned: out[j - start] = || A x_j - eval[j - start] B x_j ||_2 for the columns j = start ..
+ * end - 1 of evec (B == NULL: the identity), summed over all ranks.  Through the back-end's residual_sq (GCGE_BackendOf(ops), the
+ * routine CheckConvergence uses) where it is offered and accepts; otherwise by CheckConvergence's slot sequence on two blocks of
+ * end - start columns created for the call.  Returns 0, -1 on bad arguments.                                                      */
+int GCGE_ResidualNorms (void *A, void *B, void **evec, int start, int end, const double *eval, double *out, struct OPS_ *ops);
+
 /* ---- PAS eigensolver (sets ops->EigenSolver; reference src/ops_eig_sol_pas.h) -------------------------------------
  * Rayleigh-Ritz on the coarsest level H = num_levels - 1, then per iteration: prolongate X one level (down to level 0),
  * smooth A X = Lambda B X by BlockAMG from that level down, make X B-orthogonal to range(P_H) and B-orthonormal, solve the
