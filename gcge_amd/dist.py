@@ -45,8 +45,6 @@ def grid_of(A):
     DFT Hamiltonians of BASELINE config 5), read off a CSR slab with GLOBAL columns; None: no such grid.  Host only."""
     from .lib import hip_lib
     g = hip_lib()
-    g.gcge_hip_star_grid.argtypes = [C.c_int, C.c_long, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                     C.POINTER(C.c_double), C.POINTER(C.c_long)]
     out = (C.c_long * 4)()
     if not g.gcge_hip_star_grid(A.nrows, A.row_begin, A.ncols, A.rowptr, A.colidx, A.val, out):
         return None
@@ -210,8 +208,6 @@ class Comm:
         send_cnt = (C.c_int * world)()
         rows = C.POINTER(C.c_int)()
         ns = C.c_int()
-        h.gcge_dist_plan_halo.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_int), C.c_int, C.POINTER(Transport), C.POINTER(C.c_int),
-                                          C.POINTER(C.c_int), C.POINTER(C.POINTER(C.c_int)), C.POINTER(C.c_int)]
         rc = h.gcge_dist_plan_halo(parr, gh.ctypes.data_as(C.POINTER(C.c_int)), int(gh.size), C.byref(tr), recv_cnt, send_cnt,
                                    C.byref(rows), C.byref(ns))
         if rc != 0:
@@ -300,12 +296,6 @@ class NativeComm:
     def __init__(self, hip, dist, rank, world):
         self.hip, self.rank, self.world = hip, rank, world
         g = hip.g
-        g.gcge_hip_comm_unique_id.argtypes = [C.c_void_p]
-        g.gcge_hip_comm_init.argtypes = [C.c_int, C.c_int, C.c_void_p]
-        g.gcge_hip_mat_create_slab.restype = C.c_void_p
-        g.gcge_hip_mat_create_slab.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                               C.POINTER(C.c_double), C.c_int]
-        g.gcge_hip_comm_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
         ident = C.create_string_buffer(128)
         if rank == 0 and g.gcge_hip_comm_unique_id(ident) != 0:
             raise RuntimeError("gcge_hip_comm_unique_id failed")
@@ -330,9 +320,6 @@ class NativeComm:
             dims, box_global = geometry
             bg = np.ascontiguousarray(box_global, dtype=np.int32)
             f = self.hip.g.gcge_hip_mat_create_slab_grid
-            f.restype = C.c_void_p
-            f.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int, C.c_int,
-                          C.POINTER(C.c_int)]
             m = f(parr, A.rowptr, A.colidx, A.val, cap_cols, int(dims[0]), int(dims[1]), int(dims[2]), bg.ctypes.data_as(C.POINTER(C.c_int)))
             if not m:
                 raise RuntimeError("gcge_hip_mat_create_slab_grid failed")
@@ -399,12 +386,8 @@ def hip_slab_matrix(hip, comm, A, n_global, part, cap_cols=128, geometry=None):
         dims, box_global = geometry
         bg = np.asarray(box_global, dtype=np.int32)
         box_local = np.ascontiguousarray(np.concatenate([bg[A.row_begin:A.row_begin + A.nrows], bg[np.asarray(ghosts, dtype=np.int64)]]), dtype=np.int32)
-        g.gcge_hip_star_next_geometry_cols.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         g.gcge_hip_star_next_geometry_cols(int(box_local.size), int(dims[0]), int(dims[1]), int(dims[2]), box_local.ctypes.data_as(C.POINTER(C.c_int)))
     # (the halo rows' global ids go with the arrays: a slab of a grid matrix cut on plane boundaries keeps the plane sweep)
-    g.gcge_hip_mat_create_local_ghosts.restype = C.c_void_p
-    g.gcge_hip_mat_create_local_ghosts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                                   C.POINTER(C.c_double), C.POINTER(C.c_int)]
     gh = np.ascontiguousarray(ghosts, dtype=np.int32)
     m = g.gcge_hip_mat_create_local_ghosts(A.nrows, A.ncols, n_global, A.row_begin, A.rowptr, A.colidx, A.val,
                                            gh.ctypes.data_as(C.POINTER(C.c_int)))
@@ -414,14 +397,10 @@ def hip_slab_matrix(hip, comm, A, n_global, part, cap_cols=128, geometry=None):
         raise RuntimeError("gcge_hip_mat_create_local_ghosts failed")
     mat = C.c_void_p(m)
     cb, sp, rp = comm.make_exchange(send_cnt, recv_cnt, cap_cols)
-    g.gcge_hip_mat_set_halo.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_double),
-                                        C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_void_p]
     g.gcge_hip_mat_set_halo(mat, n_global, int(send_rows.size), send_rows.ctypes.data_as(C.POINTER(C.c_int)), sp, rp,
                             cap_cols, C.cast(cb, C.c_void_p), None)
-    g.gcge_hip_mat_set_halo_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     g.gcge_hip_mat_set_halo_async(mat, C.cast(comm._begin_cb, C.c_void_p), C.cast(comm._end_cb, C.c_void_p))
     # the partition of all ranks travels with the handle: ops->MultiGridCreate coarsens a slab from it (csrc/hip/multigrid.hip)
-    g.gcge_hip_mat_set_partition.argtypes = [C.c_void_p, C.POINTER(C.c_long), C.c_int]
     g.gcge_hip_mat_set_partition(mat, (C.c_long * len(part))(*[int(v) for v in part]), len(part) - 1)
     return mat
 
@@ -440,7 +419,6 @@ def install_slab_factory(hip, comm):
         m = hip_slab_matrix(hip, comm, A, part[world], part, cap_cols=buf_cols)      # (rewrites colidx to local numbering in place)
         return m.value
     cb = FACT(_loud(factory))
-    hip.g.gcge_hip_set_slab_factory.argtypes = [C.c_void_p, C.c_void_p]
     hip.g.gcge_hip_set_slab_factory(C.cast(cb, C.c_void_p), None)
     comm._keep.append(cb)
     return cb

@@ -105,8 +105,6 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
         else:
             ev, res, evec = run_gcg(backend.ops_handle, mA, mB, args, flag=flag, keep_evec=True)
         h = host_lib()
-        h.GCGE_ResidualNorms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double),
-                                         C.POINTER(C.c_double), C.c_void_p]
         lam = np.ascontiguousarray(ev[:k], dtype=np.float64)
         rn = np.zeros(k)
         rc = h.GCGE_ResidualNorms(mA, mB, evec, 0, k, lam.ctypes.data_as(C.POINTER(C.c_double)), rn.ctypes.data_as(C.POINTER(C.c_double)),

@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from .lib import CSR, host_lib, hip_lib
+from .lib import host_lib, hip_lib
 from .ops_struct import OpsTable
 
 
@@ -11,21 +11,6 @@ class HipBackendImpl:
     def __init__(self, device=0, quiet=True):
         self.h = host_lib()
         self.g = hip_lib()
-        self.g.gcge_hip_mat_create_csr.restype = C.c_void_p
-        self.g.gcge_hip_mat_create_csr.argtypes = [C.POINTER(CSR)]
-        self.g.gcge_hip_mat_destroy.argtypes = [C.c_void_p]
-        self.g.gcge_hip_mv_to_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_long]
-        self.g.gcge_hip_mv_from_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_long]
-        self.g.gcge_hip_set_random_mode.argtypes = [C.c_int, C.c_ulonglong]
-        self.g.gcge_hip_mat_create_device.restype = C.c_void_p
-        self.g.gcge_hip_mat_create_device.argtypes = [C.c_int, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.g.gcge_hip_mv_to_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long]
-        self.g.gcge_hip_mv_nrows.argtypes = [C.c_void_p]
-        self.g.gcge_hip_mv_ncols.argtypes = [C.c_void_p]
-        self.g.gcge_hip_mv_from_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_long]
-        self.g.gcge_hip_mv_device_ptr.restype = C.c_void_p
-        self.g.gcge_hip_mv_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
-        self.g.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
         self.device = device
         if self.g.gcge_hip_init(device) != 0:
             raise RuntimeError("HIP back-end: no GPU visible (there is no CPU fallback)")
@@ -35,6 +20,11 @@ class HipBackendImpl:
         self.h.OPS_Setup(self.ops_handle)
         self.h.GCGE_SetQuiet(self.ops_handle, 1 if quiet else 0)
         self.ops = OpsTable(self.ops_handle)
+
+    def torch_device(self):
+        """The torch device this back-end runs on (torch's current one when it was opened with device < 0)."""
+        import torch
+        return torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
 
     def matrix(self, csr):
         m = self.g.gcge_hip_mat_create_csr(C.byref(csr))
@@ -59,7 +49,7 @@ class HipBackendImpl:
         elif col is None or val is None:
             raise TypeError("matrix_from_device: row pointers, columns and values are required")
         foreign = not all(isinstance(t, torch.Tensor) for t in (crow, col, val))
-        dev = torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
+        dev = self.torch_device()
 
         def on_device(t, dtype):
             if not isinstance(t, torch.Tensor):
@@ -89,7 +79,7 @@ class HipBackendImpl:
         (gcge_hip_mv_to_device): nothing passes through the host."""
         import torch
         n = self.g.gcge_hip_mv_nrows(mv)
-        out = torch.empty((n, c1 - c0), dtype=torch.float64, device=torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device()))
+        out = torch.empty((n, c1 - c0), dtype=torch.float64, device=self.torch_device())
         if out.numel():
             self.g.gcge_hip_mv_to_device(mv, c0, c1, out.data_ptr(), c1 - c0)
         return out
@@ -108,7 +98,7 @@ class HipBackendImpl:
         if foreign:
             if not hasattr(t, "__cuda_array_interface__"):
                 raise TypeError("mv_from_torch: a torch device tensor or an object with __cuda_array_interface__ is required")
-            t = torch.as_tensor(t, device=torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device()))
+            t = torch.as_tensor(t, device=self.torch_device())
         if not t.is_cuda:
             raise TypeError("mv_from_torch: the tensor must live on the GPU (HipBackend.mv_from_numpy takes host arrays)")
         if t.dim() != 2:
@@ -154,9 +144,6 @@ class HipBackendImpl:
     def matrix_grid(self, csr, dims, box_of_row):
         """A matrix on a masked grid: box_of_row[r] = x + nx (y + ny z) (int32 array, ascending); see gcge_hip_mat_create_grid."""
         g = self.g
-        g.gcge_hip_mat_create_grid.restype = C.c_void_p
-        g.gcge_hip_mat_create_grid.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                                               C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         box = np.ascontiguousarray(box_of_row, dtype=np.int32)
         m = g.gcge_hip_mat_create_grid(csr.nrows, csr.rowptr, csr.colidx, csr.val, int(dims[0]), int(dims[1]), int(dims[2]),
                                        box.ctypes.data_as(C.POINTER(C.c_int)))
@@ -170,8 +157,6 @@ class HipBackendImpl:
     def matrix_rect(self, csr):
         """A rectangular matrix (a prolongation of a multigrid hierarchy): MatDotMultiVec applies it, MatTransDotMultiVec its
         transpose (gcge_hip_mat_create_rect_csr, csrc/hip/multigrid.hip)."""
-        self.g.gcge_hip_mat_create_rect_csr.restype = C.c_void_p
-        self.g.gcge_hip_mat_create_rect_csr.argtypes = [C.POINTER(CSR)]
         m = self.g.gcge_hip_mat_create_rect_csr(C.byref(csr))
         if not m:
             raise RuntimeError("gcge_hip_mat_create_rect_csr failed")

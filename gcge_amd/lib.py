@@ -7,6 +7,8 @@ import ctypes as C
 import os
 import subprocess
 
+from . import abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 _LIBDIR = os.path.join(_HERE, "lib")
@@ -61,12 +63,9 @@ def host_lib():
         path = os.path.join(_LIBDIR, "libgcge_host.so")
         if not os.path.exists(path):
             build_libs(hip=False)
-        _host = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _host.gcge_uniform.restype = C.c_double
-        _host.gcge_uniform.argtypes = [C.c_uint64, C.c_uint64]
-        _host.GCGE_RunGCG.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                      C.POINTER(C.c_char_p), C.c_void_p,
-                                      C.POINTER(C.c_double), C.c_void_p, C.POINTER(RunResult)]
+        lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
+        abi.declare(lib, abi.HOST, "libgcge_host.so")
+        _host = lib
     return _host
 
 
@@ -78,12 +77,9 @@ def hip_lib():
         path = os.path.join(_LIBDIR, "libgcge_hip.so")
         if not os.path.exists(path):
             raise RuntimeError("libgcge_hip.so is not built: run `python -c 'import __graft_entry__ as g; g.build()'`")
-        _hip = C.CDLL(path, mode=C.RTLD_GLOBAL)
-        _hip.gcge_hip_multigrid_mode.argtypes = [C.c_int]
-        _hip.gcge_hip_multigrid_stats.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_long)]
-        _hip.gcge_hip_mg_galerkin.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.c_int, C.c_double, C.POINTER(CSR)]
-        _hip.gcge_hip_mat_to_csr.argtypes = [C.c_void_p, C.POINTER(CSR)]
-        _hip.gcge_hip_mat_to_csr_t.argtypes = [C.c_void_p, C.POINTER(CSR)]
+        lib = C.CDLL(path, mode=C.RTLD_GLOBAL)
+        abi.declare(lib, abi.HIP, "libgcge_hip.so")
+        _hip = lib
     return _hip
 
 
@@ -160,9 +156,6 @@ def mat_pattern_table(mat):
     per entry: value, column offset) — or (None, None) when the matrix has no pattern form."""
     import numpy as np
     h = hip_lib()
-    h.gcge_hip_mat_pattern_table.restype = C.c_long
-    h.gcge_hip_mat_pattern_table.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    h.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
     nt = h.gcge_hip_mat_pattern_table(mat, None, None)
     if nt == 0:
         return None, None
@@ -176,8 +169,6 @@ def mat_geometry(mat):
     (HipBackend.matrix_grid), 2 recovered at upload; box_of_row[r] = x + nx (y + ny z) as a numpy int32 array."""
     import numpy as np
     h = hip_lib()
-    h.gcge_hip_mat_geometry.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    h.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
     dims = (C.c_int * 3)()
     kind = h.gcge_hip_mat_geometry(mat, dims, None)
     if kind == 0:
@@ -199,12 +190,10 @@ def mg_aggregate_masked(dims, box_of_row, device=False):
     d = (C.c_int * 3)(*[int(v) for v in dims])
     if not device:
         f = host_lib().gcge_mg_aggregate_masked
-        f.argtypes = [C.POINTER(C.c_int * 3), ip, C.c_int, ip, C.POINTER(C.c_int * 3), ip]
         nc = f(C.byref(d), box.ctypes.data_as(ip), n, agg.ctypes.data_as(ip), C.byref(cd), cbox.ctypes.data_as(ip))
         return (nc, agg[:n], tuple(cd), cbox[:nc].copy()) if nc >= 0 else (nc, None, None, None)
     ptr, mem = np.zeros(n + 1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
     f = hip_lib().gcge_hip_mg_aggregate_masked
-    f.argtypes = [C.POINTER(C.c_int * 3), ip, C.c_int, ip, ip, ip, ip, C.POINTER(C.c_int * 3)]
     nc = f(C.byref(d), box.ctypes.data_as(ip), n, agg.ctypes.data_as(ip), ptr.ctypes.data_as(ip), mem.ctypes.data_as(ip),
            cbox.ctypes.data_as(ip), C.byref(cd))
     return (nc, agg[:n], tuple(cd), cbox[:nc].copy(), ptr[:nc + 1].copy(), mem[:n]) if nc >= 0 else (nc, None, None, None, None, None)
@@ -234,25 +223,21 @@ def mg_aggregate_graph(arrays_or_mat, theta=0.25, device=False):
         if not device:
             raise ValueError("the host routine takes (rowptr, colidx, val) arrays")
         h = hip_lib()
-        h.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
         n, mat = h.gcge_hip_mat_nrows(arrays_or_mat), arrays_or_mat
     agg = np.zeros(max(n, 1), dtype=np.int32)
     if not device:
         A = CSR(n, n, 0, len(ci), rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), va.ctypes.data_as(dp))
         f = host_lib().gcge_mg_aggregate_mis2
-        f.argtypes = [C.POINTER(CSR), C.c_double, ip]
         nc = f(C.byref(A), float(theta), agg.ctypes.data_as(ip))
         return (nc, agg[:n]) if nc >= 0 else (nc, None)
     ptr, mem = np.zeros(n + 1, dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)
     h = hip_lib()
     if mat is None:
         f = h.gcge_hip_mg_aggregate_graph_csr
-        f.argtypes = [C.c_int, ip, ip, dp, C.c_double, ip, ip, ip]
         nc = f(n, rp.ctypes.data_as(ip), ci.ctypes.data_as(ip), va.ctypes.data_as(dp), float(theta), agg.ctypes.data_as(ip),
                ptr.ctypes.data_as(ip), mem.ctypes.data_as(ip))
     else:
         f = h.gcge_hip_mg_aggregate_graph
-        f.argtypes = [C.c_void_p, C.c_double, ip, ip, ip]
         nc = f(mat, float(theta), agg.ctypes.data_as(ip), ptr.ctypes.data_as(ip), mem.ctypes.data_as(ip))
     return (nc, agg[:n], ptr[:nc + 1].copy(), mem[:n]) if nc >= 0 else (nc, None, None, None)
 
@@ -281,7 +266,6 @@ def load_petsc_binary(path, row_begin=0, row_end=-1):
     """PETSc binary Mat file (what the reference's SLEPc driver reads: test/test_app_slepc.c:416-445) -> host CSR;
     rows [row_begin, row_end) with global columns (row_end < 0: to the end)."""
     h = host_lib()
-    h.gcge_load_petsc_binary.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.POINTER(CSR)]
     A = CSR()
     rc = h.gcge_load_petsc_binary(os.fsencode(path), row_begin, row_end, C.byref(A))
     if rc != 0:
@@ -293,7 +277,6 @@ def load_matrix_market(path):
     """Matrix Market coordinate file (the form SuiteSparse ships the reference's SiO2 / Ga41As41H72 ... in) -> host CSR, full
     matrix (symmetric files are expanded), ascending columns."""
     h = host_lib()
-    h.gcge_load_matrix_market.argtypes = [C.c_char_p, C.POINTER(CSR)]
     A = CSR()
     rc = h.gcge_load_matrix_market(os.fsencode(path), C.byref(A))
     if rc != 0:
@@ -349,31 +332,32 @@ def make_argv(args):
     return len(args), arr
 
 
-def run_gcg(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False, given=None):
-    """GCGE_RunGCG through the operator table `ops` (a void* OPS handle).
-    keep_evec: also return the eigenvector multivector handle (nevMax columns; the caller destroys it).
-    given = (multivector handle with nevMax columns, nevGiven): warm start from its first nevGiven columns
-    (GCGE_RunGCGGiven); the eigenvectors come back in the same block, which stays the caller's."""
+def _solver_args(args, quiet):
+    """(argc, argv, zeroed eigenvalue array of nevMax entries) of a GCGE_Run* call: -gcge_print_usage 0 appended when quiet,
+    nevMax from -nevMax, else twice -nevConv (30 when absent)."""
     import numpy as np
-    h = host_lib()
     args = ["gcge"] + [str(a) for a in args]
     if quiet and "-gcge_print_usage" not in args:
         args += ["-gcge_print_usage", "0"]
-    argc, argv = make_argv(args)
-    nev = 30
-    nev_max = None
+    nev, nev_max = 30, None
     for i, a in enumerate(args):
         if a == "-nevConv":
             nev = int(args[i + 1])
         if a == "-nevMax":
             nev_max = int(args[i + 1])
-    nev_max = nev_max or 2 * nev
-    ev = np.zeros(nev_max)
+    return make_argv(args) + (np.zeros(nev_max or 2 * nev),)
+
+
+def run_gcg(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False, given=None):
+    """GCGE_RunGCG through the operator table `ops` (a void* OPS handle).
+    keep_evec: also return the eigenvector multivector handle (nevMax columns; the caller destroys it).
+    given = (multivector handle with nevMax columns, nevGiven): warm start from its first nevGiven columns
+    (GCGE_RunGCGGiven); the eigenvectors come back in the same block, which stays the caller's."""
+    h = host_lib()
+    argc, argv, ev = _solver_args(args, quiet)
     res = RunResult()
     evec = C.c_void_p()
     if given is not None:
-        h.GCGE_RunGCGGiven.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_int, C.c_void_p]
         rc = h.GCGE_RunGCGGiven(matA, matB, flag, argc, C.cast(argv, C.c_void_p), ops,
                                 ev.ctypes.data_as(C.c_void_p), given[0], int(given[1]), C.cast(C.byref(res), C.c_void_p))
         if rc != 0:
@@ -393,24 +377,10 @@ def run_pas(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False):
     warm-started from PAS's converged vectors unless args hold -gcge_pas_only 1.  Returns (eval, pas_result, gcg_result)
     (and the eigenvector block handle, nevMax columns, with keep_evec: the caller destroys it).  Raises on an error code
     (-7: no MultiGridCreate or fewer than 2 levels, -8: a re-ordered level, -9: B is None and the back-end has no identity)."""
-    import numpy as np
     h = host_lib()
-    args = ["gcge"] + [str(a) for a in args]
-    if quiet and "-gcge_print_usage" not in args:
-        args += ["-gcge_print_usage", "0"]
-    argc, argv = make_argv(args)
-    nev, nev_max = 30, None
-    for i, a in enumerate(args):
-        if a == "-nevConv":
-            nev = int(args[i + 1])
-        if a == "-nevMax":
-            nev_max = int(args[i + 1])
-    nev_max = nev_max or 2 * nev
-    ev = np.zeros(nev_max)
+    argc, argv, ev = _solver_args(args, quiet)
     res = PASResult()
     evec = C.c_void_p()
-    h.GCGE_RunPAS.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_char_p), C.c_void_p,
-                              C.POINTER(C.c_double), C.c_void_p, C.POINTER(PASResult)]
     rc = h.GCGE_RunPAS(matA, matB, flag, argc, argv, ops, ev.ctypes.data_as(C.POINTER(C.c_double)),
                        C.cast(C.byref(evec), C.c_void_p) if keep_evec else None, C.byref(res))
     if rc != 0:

@@ -62,7 +62,6 @@ def main():
             from gcge_amd import load_matrix_market
             from gcge_amd.lib import hip_lib
             path = os.path.join(tempfile.gettempdir(), "gcge_ballfile_%s_%d.mtx" % (os.environ.get("MASTER_PORT", "0"), ball))
-            h.gcge_save_matrix_market.argtypes = [C.c_char_p, C.POINTER(CSR), C.c_int]
             if rank == 0:
                 assert h.gcge_save_matrix_market(path.encode(), C.byref(Ag), 1) == 0
             dist.barrier()
@@ -72,7 +71,6 @@ def main():
                 os.remove(path)
             assert (L.nrows, L.nnz) == (Ag.nrows, Ag.nnz)
             gl = hip_lib()
-            gl.gcge_hip_star_infer_grid.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
             fd = (C.c_int * 3)()
             fbox = np.zeros(n_global, dtype=np.int32)
             assert gl.gcge_hip_star_infer_grid(L.nrows, L.rowptr, L.colidx, fd, fbox.ctypes.data_as(C.POINTER(C.c_int))) == 1, "no grid found in the rows of the file"
@@ -150,7 +148,6 @@ def main():
         torch.cuda.set_device(rank)
         be = HipBackend(device=rank)
         if star or ball:
-            be.g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
             be.g.gcge_hip_spmm_dense_mode(1)          # small atoms: rows of >= 24 entries may seed a block
         comm = gdist.NativeComm(be, dist, rank, world)
         mat = comm.slab_matrix(A, part, cap_cols=64 if (star or ball) else 8, geometry=geometry)
@@ -159,22 +156,15 @@ def main():
         from gcge_amd import HipBackend
         be = HipBackend(device=0)
         if star or ball:
-            be.g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
             be.g.gcge_hip_spmm_dense_mode(1)          # small atoms: rows of >= 24 entries may seed a block
         comm = gdist.install(be, dist, rank, world, stage_through_host=True)
         mat = gdist.hip_slab_matrix(be, comm, A, n_global, part, cap_cols=64 if (star or ball) else 4, geometry=geometry)   # small cap: exercises the column chunking
         be.set_random_mode(1, 777)
-        be.g.gcge_hip_mat_pattern_chain.argtypes = [C.c_void_p]
         assert sio2 or be.g.gcge_hip_mat_pattern_chain(mat) >= 1, "slab matrix with halo columns should keep the chain layout"
 
     if ball and mode in ("hip", "hip_native"):
         # every slab of the masked grid kept the plane sweep (third form through the line table: own and halo rows), and multiplies right
         g = be.g
-        g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-        g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-        g.gcge_hip_mat_star_masked_form.argtypes = [C.c_void_p]
-        g.gcge_hip_mat_star_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
-        g.gcge_hip_star_product_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
         form = g.gcge_hip_mat_spmm_form(mat).decode()
         assert form.startswith("spmm_star+spmm_dense"), (rank, form)
         assert g.gcge_hip_mat_star_masked_form(mat) == 3, "a slab of a masked grid takes the third form of the sweep"
@@ -187,9 +177,6 @@ def main():
         Yw = S @ Xw
         xw = be.mv_from_numpy(mat, Xw[part[rank]:part[rank + 1], :])
         yw = be.ops.mv_create(66, mat)
-        g.gcge_hip_spmm_dot2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
-        g.gcge_hip_set_halo_overlap.argtypes = [C.c_int]
         for overlap in (0, 1):
             # (overlap: the planes at least 6 away from a plane that holds halo lines — a neighbour's planes, or the slab's own first /
             #  last plane when the cut runs through it — are swept while the halo travels, the others after the exchange)
@@ -219,10 +206,6 @@ def main():
     if star and mode in ("hip", "hip_native"):
         # every slab took the grid form, sits where the partition put it, and sweeps its inner planes while the halo travels
         g = be.g
-        g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-        g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-        g.gcge_hip_mat_star_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
-        g.gcge_hip_star_product_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
         form = g.gcge_hip_mat_spmm_form(mat).decode()
         assert form.startswith("spmm_star+spmm_dense"), (rank, form)
         st = (C.c_long * 8)()
@@ -233,9 +216,6 @@ def main():
         Yw = S @ Xw
         xw = be.mv_from_numpy(mat, Xw[part[rank]:part[rank + 1], :])
         yw = be.ops.mv_create(66, mat)
-        g.gcge_hip_set_halo_overlap.argtypes = [C.c_int]
-        g.gcge_hip_spmm_dot2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
         for overlap in (0, 1):
             g.gcge_hip_set_halo_overlap(overlap)
             p0, s0_ = C.c_long(), C.c_long()
@@ -272,7 +252,6 @@ def main():
     assert np.max(np.abs(ip - X[:, 0:3].T @ X[:, 1:5])) < 1e-14 * n_global      # (sums of n_global products of magnitude <= 1/4)
     # 3. whole eigensolve, SPMD
     if mode in ("hip", "hip_native"):
-        be.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
         be.g.gcge_hip_bpcg_setup(be.ops_handle, 30, 1e-2, 1e-14, b"abs")
     ev, res = run_gcg(be.ops_handle, mat, None, ["-nevConv", 8, "-gcge_compW_orth_method", os.environ.get("GCGE_TEST_ORTH", "chol")], flag=1 if mode in ("hip", "hip_native") else 0)
     if sio2:

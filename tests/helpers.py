@@ -197,8 +197,6 @@ def block_amg_solve(backend, A_handles, P_handles, b, x0, max_iter, rate, tol, t
     to = (C.c_double * len(tol))(*tol)
     dbl = (C.c_double * (6 * m + 8))()
     iw = (C.c_int * (2 * m + 8))()
-    h.MultiLinearSolverSetup_BlockAMG.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_int,
-                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     h.MultiLinearSolverSetup_BlockAMG(mi, ra, to, tol_type.encode(), A_arr, P_arr, L, ws_ptrs, dbl, iw, None, backend.ops_handle)
     A0 = C.c_void_p(A_arr[0])
     mb = backend.mv_from_numpy(A0, b)
@@ -222,14 +220,12 @@ def mg_hierarchy(A, max_levels, scale=0.0, min_rows=0, B=None):
     {"A": [...], "P": [...], "PT": [...], "dims": [...], "B": [...] or None}."""
     h = host_lib()
     mg = MG()
-    h.gcge_mg_build.argtypes = [C.POINTER(CSR), C.POINTER(CSR), C.c_int, C.c_int, C.c_double, C.POINTER(MG)]
     rc = h.gcge_mg_build(C.byref(A), C.byref(B) if B is not None else None, max_levels, min_rows, scale, C.byref(mg))
     assert rc == 0, rc
     L = mg.num_levels
     out = {"A": [csr_to_scipy(mg.A[lev]) for lev in range(L)], "P": [csr_to_scipy(mg.P[lev]) for lev in range(L - 1)],
            "PT": [csr_to_scipy(mg.PT[lev]) for lev in range(L - 1)], "dims": [tuple(mg.dims[lev]) for lev in range(L)],
            "B": [csr_to_scipy(mg.B[lev]) for lev in range(L)] if B is not None else None}
-    h.gcge_mg_free.argtypes = [C.POINTER(MG)]
     h.gcge_mg_free(C.byref(mg))
     return out
 
@@ -243,15 +239,12 @@ def mg_hierarchy_slab(A_slab, dims, part, rank, max_levels, scale=0.0):
     parr = (C.c_long * (world + 1))(*[int(v) for v in part])
     d = (C.c_int * 3)(*dims)
     pl = C.POINTER(C.c_long)()
-    h.gcge_mg_build_slab.argtypes = [C.POINTER(CSR), C.POINTER(C.c_int * 3), C.POINTER(C.c_long), C.c_int, C.c_int, C.c_int, C.c_double,
-                                     C.POINTER(MG), C.POINTER(C.POINTER(C.c_long))]
     rc = h.gcge_mg_build_slab(C.byref(A_slab), C.byref(d), parr, rank, world, max_levels, scale, C.byref(mg), C.byref(pl))
     assert rc == 0, rc
     L = mg.num_levels
     out = {"A": [csr_to_scipy(mg.A[lev]) for lev in range(L)], "P": [csr_to_scipy(mg.P[lev]) for lev in range(L - 1)],
            "part": [[pl[lev * (world + 1) + r] for r in range(world + 1)] for lev in range(L)],
            "dims": [tuple(mg.dims[lev]) for lev in range(L)]}
-    h.gcge_mg_free.argtypes = [C.POINTER(MG)]
     h.gcge_mg_free(C.byref(mg))
     C.CDLL(None).free(pl)
     return out

@@ -64,7 +64,6 @@ def main():
             h.gcge_problem_lap3d_box(nx, ny, nz // 2, C.c_int64(0), C.c_int64(-1), C.byref(A))     # Dirichlet box, no halo
             mat = be.matrix(A)
         be.set_random_mode(1, 20240601)
-        be.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
         be.g.gcge_hip_bpcg_setup(be.ops_handle, 30, 1e-2, 1e-14, b"abs")
         args = ["-nevConv", 50, "-nevMax", 128, "-blockSize", 64, "-gcge_initX_orth_method", "chol", "-gcge_compW_orth_method", "chol"]
         run_gcg(be.ops_handle, mat, None, args + ["-gcge_max_niter", 2], flag=1)             # warm the pool / communicator

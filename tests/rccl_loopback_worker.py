@@ -49,7 +49,6 @@ def star_loopback(G, ball=False):
         n_loc = gdist.partition_lines(box, G, 2)[1]
     be = HipBackend(device=0)
     g = be.g
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
     g.gcge_hip_spmm_dense_mode(1)
     comm = gdist.NativeComm(be, None, 0, 1)
     A, _ = make_problem("sio2ball" if ball else "sio2", G, row_begin=0, row_end=n_loc, **kw)
@@ -59,28 +58,18 @@ def star_loopback(G, ball=False):
     assert (ball or ng >= 6 * plane) and ghosts[0] == n_loc and np.all(ghosts - n_loc < n_loc)
     if ball:
         box_local = np.ascontiguousarray(np.concatenate([box[:n_loc], box[ghosts]]), dtype=np.int32)
-        g.gcge_hip_star_next_geometry_cols.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]
         g.gcge_hip_star_next_geometry_cols(int(box_local.size), G, G, G, box_local.ctypes.data_as(C.POINTER(C.c_int)))
     P = sp.csr_matrix((np.ones(ng), (np.arange(ng), ghosts - n_loc)), shape=(ng, n_loc))
     S = (Sg[:, :n_loc] + Sg[:, ghosts] @ P).tocsr()
     ip_ = C.POINTER(C.c_int)
-    g.gcge_hip_mat_create_local_ghosts.restype = C.c_void_p
-    g.gcge_hip_mat_create_local_ghosts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip_, ip_, C.POINTER(C.c_double), ip_]
     mat = C.c_void_p(g.gcge_hip_mat_create_local_ghosts(A.nrows, A.ncols, n_global, 0, A.rowptr, A.colidx, A.val, ghosts.ctypes.data_as(ip_)))
     send_rows = np.ascontiguousarray(ghosts - n_loc, dtype=np.int32)
     peer, scnt, rcnt = (C.c_int * 2)(0, 0), (C.c_int * 2)(0, ng), (C.c_int * 2)(0, ng)
-    g.gcge_hip_mat_set_halo_rccl.argtypes = [C.c_void_p, C.c_int, C.c_int, ip_, ip_, ip_, ip_, C.c_int]
     assert g.gcge_hip_mat_set_halo_rccl(mat, n_global, 2, peer, scnt, rcnt, send_rows.ctypes.data_as(ip_), 64) == 0
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
     form = g.gcge_hip_mat_spmm_form(mat).decode()
     assert form.startswith("spmm_star+spmm_dense"), form
     if ball:
-        g.gcge_hip_mat_star_masked_form.argtypes = [C.c_void_p]
         assert g.gcge_hip_mat_star_masked_form(mat) == 3
-    g.gcge_hip_star_product_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
-    g.gcge_hip_set_halo_overlap.argtypes = [C.c_int]
-    g.gcge_hip_spmm_dot2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, ip_, ip_, C.c_void_p, C.c_void_p, C.c_void_p]
     X = uniform(5, (n_loc, 66)) - 0.5
     y = be.ops.mv_create(66, mat)
     nsplit = []
@@ -111,8 +100,6 @@ def star_loopback(G, ball=False):
     # buffers, 16 columns — the device-scalar loop must decline (gcge_hip_spmm_dot2_dev_ok) and the host-scalar loop chunk the
     # columns; it used to abort.  The loop-back operator is not symmetric, so this is no solve: five iterations of the same
     # recurrences against the same loop with 64-column buffers (one chunk), column for column.
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_release.argtypes = [C.c_void_p]
     nr = 16
     Bm = uniform(41, (n_loc, nr)) - 0.5
     sols = []
@@ -149,12 +136,6 @@ def star_loopback_full_size(G, K):
     g = be.g
     comm = gdist.NativeComm(be, None, 0, 1)
     ip_ = C.POINTER(C.c_int)
-    g.gcge_hip_mat_create_local_ghosts.restype = C.c_void_p
-    g.gcge_hip_mat_create_local_ghosts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, ip_, ip_, C.POINTER(C.c_double), ip_]
-    g.gcge_hip_mat_set_halo_rccl.argtypes = [C.c_void_p, C.c_int, C.c_int, ip_, ip_, ip_, ip_, C.c_int]
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-    g.gcge_hip_star_product_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
     part = [0, (G // 2) * plane, n]
     for r in range(2):
         A, _ = make_problem("sio2", G, row_begin=part[r], row_end=part[r + 1], **kw)
@@ -241,7 +222,6 @@ def main():
         ip_ = C.POINTER(C.c_int)
         send_rows = np.ascontiguousarray(ghosts - plane, dtype=np.int32)       # slab 1 wants the plane below its first one
         peer, scnt, rcnt = (C.c_int * 2)(0, 0), (C.c_int * 2)(0, plane), (C.c_int * 2)(0, plane)
-        be.g.gcge_hip_mat_set_halo_rccl.argtypes = [C.c_void_p, C.c_int, C.c_int, ip_, ip_, ip_, ip_, C.c_int]
         rc = be.g.gcge_hip_mat_set_halo_rccl(mat, n_global, 2, peer, scnt, rcnt, send_rows.ctypes.data_as(ip_), 64)
         assert rc == 0, rc
     else:
@@ -254,7 +234,6 @@ def main():
     Yref = S @ X
     x = be.mv_from_numpy(mat, X)
     y = be.ops.mv_create(m, mat)
-    be.g.gcge_hip_set_halo_overlap.argtypes = [C.c_int]
     for overlap in (0, 1):
         be.g.gcge_hip_set_halo_overlap(overlap)
         for rep in range(3):          # repeated: a missing stream dependency shows as a stale ghost plane
@@ -270,7 +249,6 @@ def main():
     Xl = 3.0 * X
     assert np.max(np.abs(ip - Xl[:, 0:3].T @ Xl[:, 1:5])) < 1e-10
     # 3. whole eigensolve on the loop-back operator (fused device CG: SpMM + dots with the split exchange inside)
-    be.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     be.g.gcge_hip_bpcg_setup(be.ops_handle, 30, 1e-2, 1e-14, b"abs")
     ev, res = run_gcg(be.ops_handle, mat, None, ["-nevConv", 8, "-gcge_compW_orth_method", "chol"], flag=1)
     if n_loc <= 4096:
@@ -306,7 +284,6 @@ def main():
             finally:
                 for k_ in env:
                     os.environ.pop(k_, None)
-        be.g.gcge_hip_bpcg_release.argtypes = [C.c_void_p]
         be.g.gcge_hip_bpcg_release(be.ops_handle)
         rc = be.g.gcge_hip_mat_set_halo_rccl(mat, n_global, 2, peer, scnt, rcnt, send_rows.ctypes.data_as(ip_), 64)
         assert rc == 0, rc

@@ -42,7 +42,6 @@ def main():
     hip.h.OPS_Create(C.byref(ops))
     hip.g.OPS_HIP_Set(ops)
     if a.flag == 1:
-        hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
         hip.g.gcge_hip_bpcg_setup(ops, 30, 1e-2, 1e-14, b"abs")
     hip.set_random_mode(a.rng, 20240601)
     A, B = make_problem(a.kind, a.size)
@@ -53,13 +52,11 @@ def main():
                                           C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double)]
     if a.prepare and a.flag == 1:
         like = hip.ops.mv_create(a.block, mA)
-        hip.g.gcge_hip_bpcg_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         ring = hip.g.gcge_hip_bpcg_prepare(ops, mA, like, a.block)
         assert ring >= 1, ring
         hip.ops.mv_destroy(like, a.block)
     if a.slot_timing:
         hip.g.gcge_hip_slot_timing(1)
-    hip.g.gcge_hip_bpcg_time_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_double), C.c_int]
     hip.g.gcge_hip_bpcg_time_stats(None, None, 1)
     if a.verbose:
         ref.ref_set_verbose(1)
@@ -79,10 +76,7 @@ def main():
            "eigenpairs_per_s": conv.value / sec.value}
     if a.flag == 1:   # how the fused CG ran underneath the reference's ComputeW (form, iterations, time inside the solver slot)
         its, cs_ = C.c_long(), C.c_double()
-        hip.g.gcge_hip_bpcg_time_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_double), C.c_int]
         hip.g.gcge_hip_bpcg_time_stats(C.byref(its), C.byref(cs_), 0)
-        for nm in ("recompute_iters", "device_scalar_iters", "implicit_r_iters", "surplus_iters"):
-            getattr(hip.g, "gcge_hip_bpcg_" + nm).restype = C.c_long
         out["cg"] = {"iterations": its.value, "seconds": cs_.value, "recompute_iters": hip.g.gcge_hip_bpcg_recompute_iters(),
                      "device_scalar_iters": hip.g.gcge_hip_bpcg_device_scalar_iters(),
                      "implicit_r_iters": hip.g.gcge_hip_bpcg_implicit_r_iters(), "surplus_iters": hip.g.gcge_hip_bpcg_surplus_iters()}

@@ -41,14 +41,9 @@ def main():
     hier = mg_hierarchy_slab(A, (N, N, N), part, rank, levels, scale=0.5)
     be = HipBackend(device=0)
     if os.environ.get("PROBE_DENSE_MODE"):
-        be.g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
         be.g.gcge_hip_spmm_dense_mode(int(os.environ["PROBE_DENSE_MODE"]))
     comm = gdist.install(be, dist, rank, world, stage_through_host=True)
     g = be.g
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-    g.gcge_hip_spmm_dot2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p]
-    g.gcge_hip_set_halo_overlap.argtypes = [C.c_int]
     worst, forms = 0.0, []
     for lev, (S, pl, dims) in enumerate(zip(hier["A"], hier["part"], hier["dims"])):
         S = S.tocsr(); S.sort_indices()

@@ -14,7 +14,6 @@ def orth_setup(ops_handle):
         dbl = np.zeros(200000)
         keep["dbl"] = dbl
         fn = h.MultiVecOrthSetup_BinaryGramSchmidt if method == 1 else h.MultiVecOrthSetup_ModifiedGramSchmidt
-        fn.argtypes = [C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_double), C.c_void_p]
         fn(block, reorth, zero_tol, mv_ws, dbl.ctypes.data_as(C.POINTER(C.c_double)), ops_handle)
     return setup
 
@@ -33,9 +32,6 @@ def bpcg_setup(ops_handle, tol_type=b"abs"):
     def setup(max_iter, rate, tol, ws, solve):
         dbl = np.zeros(64); iw = np.zeros(64, dtype=np.int32)
         arr = (C.c_void_p * 3)(*[w.value if isinstance(w, C.c_void_p) else w for w in ws])
-        h.MultiLinearSolverSetup_BlockPCG.argtypes = [C.c_int, C.c_double, C.c_double, C.c_char_p, C.c_void_p,
-                                                      C.POINTER(C.c_double), C.POINTER(C.c_int), C.c_void_p,
-                                                      C.c_void_p, C.c_void_p]
         h.MultiLinearSolverSetup_BlockPCG(max_iter, rate, tol, tol_type, arr, dbl.ctypes.data_as(C.POINTER(C.c_double)),
                                           iw.ctypes.data_as(C.POINTER(C.c_int)), None, None, ops_handle)
         solve()

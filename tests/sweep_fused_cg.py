@@ -1,6 +1,6 @@
 """(script, not collected by pytest: python tests/sweep_fused_cg.py)  GPU robustness sweep: GCG with the fused one-pass block CG (flag 1) against the reference-form BlockPCG over the
 HIP slots (flag 0) — converged count, iteration count, Ritz values — over problem kinds, sizes and block shapes."""
-import ctypes as C, os, sys
+import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "oracle")):     # tests/helpers.py loads the oracle
     sys.path.insert(0, _p)
@@ -9,7 +9,6 @@ import torch  # noqa
 from gcge_amd import HipBackend
 from helpers import gcg_on
 hip = HipBackend()
-hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
 hip.g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
 bad = 0
 for kind, size in (("lap3d", 16), ("lap3d", 24), ("lap3d", 32), ("fe3d", 16), ("fe3d", 24), ("fe1d", 2000), ("sio2", 12), ("sio2", 16)):

@@ -12,11 +12,7 @@ from helpers import csr_to_scipy, uniform
 from gcge_amd import HipBackend, make_problem
 
 hip = HipBackend(); g = hip.g
-g.gcge_hip_cg_pass1_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-g.gcge_hip_spmm_ring_launches.restype = C.c_long
-g.gcge_hip_spmm_ring_tune.argtypes = [C.c_int, C.c_int]
 FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
-g.gcge_hip_residual_hook.restype = C.c_void_p
 hook = FN(g.gcge_hip_residual_hook())
 bad = 0; ran = 0; ring_cases = 0
 for size in (16, 24, 32, 40, 48, 56, 64, 72, 80, 96):

@@ -1,7 +1,10 @@
 """Boundary checks that need no GPU: (1) our operator table is layout-identical to the reference's
 struct OPS_ (its layout stored under tests/golden/ops_layout.json), (2) libgcge_hip.so loads and exports every symbol
-include/gcge_hip.h declares, (3) the ctypes mirror used by the tests matches the C header."""
+include/gcge_hip.h declares, (3) the ctypes mirror used by the tests matches the C header, (4) the prototypes of gcge_amd/abi.py
+are those of the C text, every one names an exported function, and no Python file declares or calls around them."""
 import ctypes as C
+import functools
+import glob
 import json
 import os
 import re
@@ -86,6 +89,127 @@ def test_host_library_exports_solver_api():
         assert hasattr(lib, n), n
 
 
+# ---- gcge_amd/abi.py against the C text ---------------------------------------------------------------------------------------------
+_C_SCALARS = {"int": C.c_int, "unsigned": C.c_uint, "unsigned int": C.c_uint, "long": C.c_long, "int64_t": C.c_int64,
+              "uint64_t": C.c_uint64, "unsigned long long": C.c_ulonglong, "size_t": C.c_size_t, "double": C.c_double, "char": C.c_char}
+_C_POINTER_TYPEDEFS = {"gcge_halo_exchange_fn", "gcge_hip_slab_factory_fn", "GCGE_MAT_IDENTITY_FN", "GCGE_MAT_FREE_FN"}
+
+
+@functools.lru_cache(maxsize=None)
+def _c_text(path):
+    txt = re.sub(r"/\*.*?\*/", " ", open(path).read(), flags=re.S)
+    return re.sub(r"//[^\n]*", " ", txt).replace('extern "C"', " ")
+
+
+def _c_type(decl, is_return=False):
+    """One parameter or return type of a C prototype: a ctypes scalar, None (void), "ptr", or "cstr" for const char *."""
+    decl = " ".join(decl.split())
+    if "(" in decl or "[" in decl or "*" in decl:
+        return "cstr" if re.fullmatch(r"const char ?\* ?\w*", decl) else "ptr"
+    words = [w for w in decl.split() if w != "const"]
+    if not is_return and len(words) > 1 and " ".join(words) not in _C_SCALARS:
+        words = words[:-1]                               # the parameter's name
+    t = " ".join(words)
+    if t in _C_POINTER_TYPEDEFS:
+        return "ptr"
+    if t == "void" and is_return:
+        return None
+    if t not in _C_SCALARS:
+        raise KeyError("C scalar type %r (in %r) has no ctypes mapping" % (t, decl))
+    return _C_SCALARS[t]
+
+
+def _c_prototypes(name, path):
+    """(return, [parameters]) of every `return-type name ( params )` followed by ; or { in the file: declarations and definitions,
+    neither static functions nor call expressions."""
+    out = []
+    for m in re.finditer(r"([A-Za-z_][\w \t*]*?[\s*])%s\s*\(((?:[^()]|\([^()]*\))*)\)\s*[;{]" % re.escape(name), _c_text(path)):
+        if re.search(r"\b(static|return|else|do)\b", m.group(1)):
+            continue
+        params = re.sub(r"\([^()]*\)", lambda p: p.group(0).replace(",", " "), m.group(2))       # void (*end) (void *ctx, int k)
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        out.append((_c_type(m.group(1), True), [_c_type(p) for p in params]))
+    return out
+
+
+def _matches(ctype, c):
+    # widths and signedness only: on LP64 c_int64 is c_long and c_size_t is c_uint64, so int64_t / long and size_t / uint64_t pass for each other
+    if c in ("ptr", "cstr"):
+        return ctype is C.c_void_p or (c == "cstr" and ctype is C.c_char_p) or (isinstance(ctype, type) and issubclass(ctype, C._Pointer))
+    return ctype is c
+
+
+def abi_table_mismatches(root=ROOT):
+    """What is wrong between gcge_amd/abi.py and the C text under `root`, one line each (none: [])."""
+    from gcge_amd import abi
+    csrc = os.path.join(root, "gcge_amd", "csrc")
+    tiers = [sorted(glob.glob(os.path.join(root, "include", "*.h"))), [os.path.join(csrc, "hip", "gcge_hip_internal.h")],
+             sorted(glob.glob(os.path.join(csrc, "hip", "*.hip")) + glob.glob(os.path.join(csrc, "host", "*.c")))]
+    bad = []
+    for name, (restype, argtypes) in list(abi.HOST.items()) + list(abi.HIP.items()):
+        try:
+            protos = [q for tier in tiers for f in tier for q in _c_prototypes(name, f)]     # a tier without the name is fine
+        except KeyError as e:
+            bad.append("%s: %s" % (name, e.args[0]))
+            continue
+        if not protos:
+            bad.append("%s: no C prototype found" % name)
+        elif any(p != protos[0] for p in protos):
+            bad.append("%s: its C prototypes differ from one another: %r" % (name, protos))
+        else:
+            ret, params = protos[0]
+            if len(params) != len(argtypes):
+                bad.append("%s: %d parameters in C, %d in the table" % (name, len(params), len(argtypes)))
+            elif not _matches(restype, ret) or not all(_matches(a, p) for a, p in zip(argtypes, params)):
+                bad.append("%s: C says %r -> %r, the table %r -> %r" % (name, params, ret, argtypes, restype))
+    return bad
+
+
+def test_abi_table_matches_the_c_prototypes():
+    """Every entry of gcge_amd/abi.py, count and types, against the function's C prototype: the declaration in include/*.h, else
+    in csrc/hip/gcge_hip_internal.h, else the extern "C" definitions in csrc/hip/*.hip and the definitions in csrc/host/*.c."""
+    from gcge_amd import abi
+    assert len(abi.HOST) > 50 and len(abi.HIP) > 150 and not set(abi.HOST) & set(abi.HIP)
+    bad = abi_table_mismatches()
+    assert not bad, "\n".join(bad)
+
+
+def test_abi_table_names_are_exported():
+    from gcge_amd import abi
+    from gcge_amd.lib import host_lib, hip_lib
+    for lib, table in ((host_lib(), abi.HOST), (hip_lib(), abi.HIP)):          # dlopen only
+        missing = [n for n in table if not hasattr(lib, n)]
+        assert not missing, missing
+
+
+# Python attributes that share the C ABI's prefixes without being functions of the two libraries
+_NOT_IN_THE_TABLE = {
+    "OPS_ORACLE_Set",          # exported by the oracle's library (oracle/pyoracle.py declares it)
+}
+
+
+def test_no_prototype_is_declared_outside_the_table():
+    """gcge_amd/ and tests/ assign no .argtypes / .restype of their own to a function of the two libraries (those of the oracle's
+    and the reference's libraries stay), and no file calls a gcge_* / GCGE_* / OPS_* function the table does not hold."""
+    from gcge_amd import abi
+    table = set(abi.HOST) | set(abi.HIP)
+    own = sorted(set(glob.glob(os.path.join(ROOT, "gcge_amd", "**", "*.py"), recursive=True)) - {os.path.join(ROOT, "gcge_amd", "abi.py")}
+                 | set(glob.glob(os.path.join(ROOT, "tests", "**", "*.py"), recursive=True)))
+    assert len(own) > 40
+    declared, called = [], []
+    for path in own + [os.path.join(ROOT, "bench.py")] + sorted(glob.glob(os.path.join(ROOT, "tools", "*.py"))):
+        for k, line in enumerate(open(path).read().split("\n"), 1):
+            where = "%s:%d" % (os.path.relpath(path, ROOT), k)
+            if path in own and re.search(r"\.(argtypes|restype)\b[^=]*=(?!=)", line):
+                # the owner must be spelled out, lib.name, and be none of ours: an alias or a getattr could hide one
+                owners = re.findall(r"(\.?)([\w)\]]+)\.(?:argtypes|restype)\b", line)
+                declared += [where + ": " + line.strip() for dot, name in owners if not dot or not name.isidentifier() or name in table]
+            # any attribute reference, called at once or through an alias (f = lib.name; f(...))
+            called += [where + ": " + n for n in re.findall(r"\.((?:gcge_|GCGE_|OPS_)\w+)", line) if n not in table | _NOT_IN_THE_TABLE]
+    assert not declared, "prototypes belong in gcge_amd/abi.py:\n" + "\n".join(declared)
+    assert not called, "called without a prototype in gcge_amd/abi.py:\n" + "\n".join(called)
+
+
 def test_tile_upload_reproduces_the_csr_arrays():
     """Host half of the tile path (csrc/hip/spmm_tile.hip; no device call): tiles -> chunks -> ELL steps expanded back
     into (row, column, value) triples equal the CSR arrays bit for bit — bricks of a detected grid (SiO2-like: strides G
@@ -95,7 +219,6 @@ def test_tile_upload_reproduces_the_csr_arrays():
     from gcge_amd.lib import hip_lib, make_problem
     from gcge_amd import dist as gdist
     g = hip_lib()
-    g.gcge_hip_tile_selfcheck.restype = C.c_long
     xr, el, st = C.c_double(), C.c_double(), (C.c_long * 2)()
 
     def check(M):
@@ -124,7 +247,6 @@ def test_supernode_split_reproduces_the_csr_arrays():
     import ctypes as C
     from gcge_amd.lib import hip_lib, make_problem
     g = hip_lib()
-    g.gcge_hip_dense_selfcheck.restype = C.c_long
     nb, sh, fl = C.c_long(), C.c_double(), C.c_double()
 
     def check(M, min_len):
@@ -145,7 +267,6 @@ def test_star_split_reproduces_the_csr_arrays():
     import ctypes as C
     from gcge_amd.lib import hip_lib, make_problem
     g = hip_lib()
-    g.gcge_hip_star_selfcheck.restype = C.c_long
     out = (C.c_long * 5)()
 
     def check(M):
@@ -173,9 +294,6 @@ def test_star_split_on_row_slabs_cut_on_plane_boundaries():
     from gcge_amd.lib import hip_lib, make_problem
     from gcge_amd import dist as gdist
     g = hip_lib()
-    g.gcge_hip_star_selfcheck_slab.restype = C.c_long
-    g.gcge_hip_star_selfcheck_slab.argtypes = [C.c_int, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                               C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_long)]
     out = (C.c_long * 12)()
     G, kw = 24, dict(K=8, R0=1.5, R1=3.0)
     plane, n = G * G, G ** 3
@@ -226,9 +344,6 @@ def test_star_split_on_a_masked_grid():
     import numpy as np
     from gcge_amd.lib import hip_lib, make_problem, ball_geometry
     g = hip_lib()
-    g.gcge_hip_star_selfcheck_grid.restype = C.c_long
-    g.gcge_hip_star_selfcheck_grid.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_int,
-                                               C.POINTER(C.c_int), C.POINTER(C.c_long)]
     out = (C.c_long * 12)()
     ip_ = C.POINTER(C.c_int)
     for G, kw in ((24, dict(K=8, R0=1.5, R1=3.0)), (32, dict(K=30, R0=2.0, R1=5.0))):
@@ -240,7 +355,6 @@ def test_star_split_on_a_masked_grid():
         # the geometry recovered from the rows alone (a matrix read from a file names none): the true one up to a translation,
         # but for a few short lines at the rim whose ends an atom block couples (their rows stay in the remainder); the split
         # with the recovered map is as exact as with the named one
-        g.gcge_hip_star_infer_grid.argtypes = [C.c_int, ip_, ip_, ip_, ip_]
         dims, got = (C.c_int * 3)(), np.zeros(A.nrows, dtype=np.int32)
         assert g.gcge_hip_star_infer_grid(A.nrows, A.rowptr, A.colidx, dims, got.ctypes.data_as(ip_)) == 1
         nx, ny, nz = dims
@@ -259,7 +373,6 @@ def test_star_split_on_a_masked_grid():
     prp, pci = P.indptr.astype(np.int32), P.indices.astype(np.int32)
     assert g.gcge_hip_star_infer_grid(A.nrows, prp.ctypes.data_as(ip_), pci.ctypes.data_as(ip_), dims, got.ctypes.data_as(ip_)) == 0
     # without the geometry such a matrix has no constant offsets: no grid form; with a wrong one: refused
-    g.gcge_hip_star_selfcheck.restype = C.c_long
     assert g.gcge_hip_star_selfcheck(A.nrows, A.ncols, A.rowptr, A.colidx, A.val, out) == -1
     assert g.gcge_hip_star_selfcheck_grid(A.nrows, A.rowptr, A.colidx, A.val, G + 1, G, G, box.ctypes.data_as(ip_), out) == -1
 

@@ -76,8 +76,6 @@ def _fill(hip, mv, arr):
 
 def _moves(hip, ritz, V, x0, x1, runs, w0, b, b0, scale):
     g = hip_lib()
-    g.gcge_hip_block_moves_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_int,
-                                          C.POINTER(C.c_double)]
     flat = [len(runs)] + [v for r in runs for v in r]
     sc = (C.c_double * max(1, len(scale)))(*scale)
     return g.gcge_hip_block_moves_mv(ritz, V, x0, x1, (C.c_int * len(flat))(*flat), w0, b, b0, sc)
@@ -170,9 +168,6 @@ def test_axpby_on_odd_ranges_equals_the_even_aligned_call(hip, m, mode):
     rows, me = 1500, m + (m & 1)
     mA, keep = _tridiag(hip, rows)
     g = hip_lib()
-    g.gcge_hip_mv_device_ptr.restype = C.c_void_p
-    g.gcge_hip_mv_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
-    g.gcge_hip_axpby.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_int, C.c_void_p]
     alpha, beta = {"copy": (1.0, 0.0), "scale": (0.0, 0.375), "axpby": (1.7, -0.6)}[mode]
     X, Y = uniform(31, (rows, me)) - 0.5, uniform(32, (rows, me)) - 0.5
 
@@ -207,7 +202,6 @@ def _sweep_stats():
 
 def _legacy_sums():
     g = hip_lib()
-    g.gcge_hip_bpcg_legacy_start_sums.restype = C.c_long
     return g.gcge_hip_bpcg_legacy_start_sums()
 
 

@@ -30,11 +30,11 @@ Row thresholds, each derived from the launch code (cdiv = rounding-up division):
   gcge_hip_axpby         the row kernels from n >= 1024 (16-byte lanes or edge lanes), the element kernels below and at odd ld.
   gcge_hip_colscale1     nb = min(4096, cdiv(n, 1024)): capped at n > 4194304, where every thread has exactly four rows.
 """
-import ctypes as C
 
 import numpy as np
 import pytest
 
+from gcge_amd import abi
 from helpers import (EVEN_LD, IN_GUARD, LAYOUTS, OUT_BITS, OUT_GUARD, Block, bits, check_vec, draw, out_vec, vec)
 
 SMALL = [1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 31, 33, 63, 64, 65, 127, 128, 129, 255, 257, 1023, 1024, 1025]
@@ -166,27 +166,11 @@ class Lib:
         import torch
         self.torch, self.hip, g = torch, hip, hip.g
         self.g = g
-        p, i, l, d = C.c_void_p, C.c_int, C.c_long, C.c_double
-        g.gcge_hip_stream.restype = p
-        g.gcge_hip_gram.argtypes = [i, p, l, i, p, l, i, p, p]
-        g.gcge_hip_gram_tune.argtypes = [i]
-        g.gcge_hip_lincomb.argtypes = [i, p, l, i, p, i, p, p, l, p]
-        g.gcge_hip_lincomb_tune.argtypes = [i]
-        g.gcge_hip_lincomb_copy.argtypes = [i, p, l, i, p, i, p, p, l, p, l, p, l, i, p]
-        g.gcge_hip_lincomb_norms.argtypes = [i, p, l, i, p, i, p, p, l, p, p]
-        g.gcge_hip_panel_dot1.argtypes = [i, p, l, i, p, l, p, p]
-        g.gcge_hip_rank1_update.argtypes = [i, p, l, p, p, p, l, i, p]
-        g.gcge_hip_mgs_step.argtypes = [i, p, l, d, p, i, p, p]
-        g.gcge_hip_colscale1.argtypes = [i, p, l, d, p]
-        g.gcge_hip_colscale.argtypes = [i, p, l, i, p, p]
-        g.gcge_hip_coldots.argtypes = [i, p, l, p, l, i, p, p]
-        g.gcge_hip_coldots2.argtypes = [i, p, l, p, l, i, p, p]
-        g.gcge_hip_resid_sq.argtypes = [i, p, l, p, l, i, p, p, p]
-        g.gcge_hip_axpby.argtypes = [i, d, p, l, d, p, l, i, p]
         self.st = g.gcge_hip_stream()
 
     def call(self, name, *args, expect=0):
         self.torch.cuda.synchronize()
+        assert "gcge_hip_" + name in abi.HIP, name          # a name composed here escapes test_abi's source scan
         rc = getattr(self.g, "gcge_hip_" + name)(*args, self.st)
         self.hip.sync()
         assert rc == expect, (name, rc)
@@ -604,7 +588,6 @@ def test_panel_partial_sums_follow_the_slab_geometry(lib, n):
     """What panel_dot1 and mgs_step leave in the workspace, one row of sums per block, is the sums over the slabs panel_geometry
     describes — rows [b rpb, (b + 1) rpb), rpb a multiple of the rpi rows a block walks per step, the same for both kernels.
     Exact data: a slab boundary that moves changes a block's sums by integers (the totals would not notice)."""
-    lib.g.gcge_hip_partial_ws.restype, lib.g.gcge_hip_partial_ws.argtypes = C.c_void_p, [C.c_size_t]
     for li, cols in enumerate((33, 64)):
         rpb = slab_rows("panel_dot1", n, cols)[0]
         nb = cdiv(n, rpb)

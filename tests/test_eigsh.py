@@ -74,7 +74,6 @@ def test_residual_norms_through_the_slots(oracle):
     ev, res, evec = run_gcg(oracle.ops_handle, mA, mB, ["-nevConv", 4], keep_evec=True)
     assert res.nevConv >= 4
     h = host_lib()
-    h.GCGE_ResidualNorms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]
     lam, rn = np.ascontiguousarray(ev[1:4]), np.zeros(3)
     dp = C.POINTER(C.c_double)
     assert h.GCGE_ResidualNorms(mA, mB, evec, 1, 4, lam.ctypes.data_as(dp), rn.ctypes.data_as(dp), oracle.ops_handle) == 0

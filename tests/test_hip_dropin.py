@@ -31,7 +31,6 @@ def _ref_stack_on_hip(hip, c, flag):
     ref = po.ref_lib()
     ops = _fresh_hip_table(hip)
     if flag == 1:      # test_app_ccs.c:109-120: the back-end's own solver behind ops->MultiLinearSolver
-        hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
         hip.g.gcge_hip_bpcg_setup(ops, 30, 1e-2, 1e-14, b"abs")
     hip.set_random_mode(0)
     A, B = make_problem(c["kind"], c["size"], **c.get("kw", {}))
@@ -78,7 +77,6 @@ def test_reference_harness_function_over_the_hip_table(hip, key, flag):
     ref = po.ref_lib()
     ops = _fresh_hip_table(hip)
     if flag == 1:
-        hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
         hip.g.gcge_hip_bpcg_setup(ops, 30, 1e-2, 1e-14, b"abs")
     hip.set_random_mode(0)
     A, B = make_problem(c["kind"], c["size"], **c.get("kw", {}))
@@ -135,7 +133,6 @@ def test_c_main_calls_the_compiled_TestAppHIP(tmp_path):
     assert conv1 >= 30 and np.max(np.abs(ev1[:30] - ev[:30]) / ev[:30]) < 1e-9
     # a Matrix Market file -> TestAppHIP -> the same Ritz values as the generator's matrix
     h = host_lib()
-    h.gcge_save_matrix_market.argtypes = [C.c_char_p, C.POINTER(CSR), C.c_int]
     A, _ = make_problem("lap3d", 12)
     mtx = str(tmp_path / "lap12.mtx")
     assert h.gcge_save_matrix_market(mtx.encode(), C.byref(A), 1) == 0
@@ -180,7 +177,6 @@ def test_gcg_on_hip_at_baseline_solver_shapes(hip, key, variant):
         args += ["-nevMax", c["nev_max"], "-blockSize", c["block"]]
     flag = 0
     if variant == "chol+fused":
-        hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
         hip.g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
         args += ["-gcge_initX_orth_method", "chol", "-gcge_compW_orth_method", "chol"]
         flag = 1
@@ -225,8 +221,6 @@ def test_multivec_create_by_multivec_and_view(hip, capfd):
     x = hip.mv_from_numpy(mat, X)
     y = C.c_void_p()
     hip.ops.fn("MultiVecCreateByMultiVec")(C.byref(y), 4, x, hip.ops.handle)
-    hip.g.gcge_hip_mv_nrows.argtypes = [C.c_void_p]
-    hip.g.gcge_hip_mv_ncols.argtypes = [C.c_void_p]
     assert hip.g.gcge_hip_mv_nrows(y) == n and hip.g.gcge_hip_mv_ncols(y) == 4
     assert np.array_equal(hip.mv_to_numpy(y, n, 0, 4), np.zeros((n, 4)))
     hip.ops.axpby(2.0, x, 0.0, y, (1, 0), (5, 4))                # the new block works with the donor's columns
@@ -258,7 +252,6 @@ def test_petsc_binary_file_to_hip_solve(hip, tmp_path, key):
     through gcge_hip_mat_create_csr, solved on the GPU; Ritz values against the reference's run on the same pair."""
     c = GCG[key]
     h = host_lib()
-    h.gcge_load_petsc_binary.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.POINTER(CSR)]
     A0, B0 = make_problem(c["kind"], c["size"])
     loaded = []
     for tag, M in (("A", A0), ("B", B0)):
@@ -298,11 +291,6 @@ def test_masked_grid_from_a_matrix_market_file_takes_the_sweep(hip, oracle, tmp_
     plane sweep — and solved; against the CPU oracle's solve of the same file."""
     from gcge_amd import load_matrix_market
     h, g = host_lib(), hip.g
-    h.gcge_save_matrix_market.argtypes = [C.c_char_p, C.POINTER(CSR), C.c_int]
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     A, _ = make_problem("sio2ball", 22, K=8, R0=1.5, R1=3.0, seed=12345)
     path = str(tmp_path / "ball22.mtx")
     assert h.gcge_save_matrix_market(path.encode(), C.byref(A), 1) == 0
@@ -331,8 +319,6 @@ def test_ccs_triples_to_hip_solve(hip):
     """MATLAB-style CCS triples (app/app_matlab.c:80-98: jc/ir/pr, 0-based) -> gcge_csr_from_ccs -> HIP solve."""
     c = GCG["lap3d_12_nev10"]
     h = host_lib()
-    h.gcge_csr_from_ccs.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                                    C.c_int, C.POINTER(CSR)]
     A0, _ = make_problem(c["kind"], c["size"])
     S = csr_to_scipy(A0).tocsc()
     S.sort_indices()

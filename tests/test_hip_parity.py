@@ -68,11 +68,9 @@ def test_spmm_pattern_path_vs_generic_and_oracle(both, kind, size, expect, chain
     pad-8/CSR kernels and the oracle for wide, narrow and offset column ranges; irregular matrices must not qualify."""
     hip, ora = both
     A, mh, mo = _pair_mats(both, kind, size, K=8, R0=2.0, R1=3.0)
-    hip.g.gcge_hip_mat_patterns.argtypes = [C.c_void_p]
     npat = hip.g.gcge_hip_mat_patterns(mh)
     assert (npat > 0) == expect, npat
     # grids whose plane is a multiple of 32 rows get the chain layout (the +-N^2 rows stay in registers)
-    hip.g.gcge_hip_mat_pattern_chain.argtypes = [C.c_void_p]
     assert (hip.g.gcge_hip_mat_pattern_chain(mh) > 0) == chain
     n = A.nrows
     X = uniform(19, (n, 80)) - 0.5
@@ -114,7 +112,6 @@ def test_spmm_pattern_kernels_on_banded_toeplitz(hip, n, offs):
     S = (S + S.T) * 0.5 + sp.eye(n) * 3.0           # symmetric, as the back-end's contract wants
     A, keep = csr_from_scipy(S)
     mh = hip.matrix(A)
-    hip.g.gcge_hip_mat_patterns.argtypes = [C.c_void_p]
     assert hip.g.gcge_hip_mat_patterns(mh) > 0
     X = uniform(31, (n, 40)) - 0.5
     xh = hip.mv_from_numpy(mh, X)
@@ -156,7 +153,6 @@ def test_axpby_on_odd_column_ranges(hip):
     lanes (vec_kernels.hip) — against numpy, all three modes, columns outside the range untouched, copies inside one block."""
     import torch
     g = hip.g
-    g.gcge_hip_axpby.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_int, C.c_void_p]
     n, ldx, ldy = 5003, 140, 274
     X0 = np.ascontiguousarray(uniform(51, (n, ldx)) - 0.5); Y0 = np.ascontiguousarray(uniform(52, (n, ldy)) - 0.5)   # row-major blocks
     for m, xo, yo in [(9, 1, 1), (64, 3, 5), (127, 1, 3), (128, 1, 7), (128, 2, 3), (33, 0, 0), (130, 5, 141)]:
@@ -266,7 +262,6 @@ def test_fused_block_pcg_matches_reference(hip):
     P = Problems(hip)
 
     def setup(max_iter, rate, tol, ws, solve):
-        hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
         hip.g.gcge_hip_bpcg_setup(hip.ops_handle, max_iter, rate, tol, b"abs")
         solve()
         it = C.c_int()
@@ -308,7 +303,6 @@ def _fused_block_pcg_rel_cases(hip, P):
     c = load_golden("slots.json")["block_pcg"]
     n, ops, S = P.n, hip.ops, csr_to_scipy(P.A5)
     max_iter, rate, tol = 25, 1e-8, 1e-5
-    hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     cases = [(uniform(c["seed_b"], (n, 6)), np.zeros((n, 7)), c["start"], c["end"]),
              (uniform(72, (n, 8)) - 0.5, uniform(73, (n, 8)) - 0.5, [0, 0], [8, 8])]
     for Bm, X0, start, end in cases:
@@ -341,7 +335,6 @@ def _fused_block_pcg_rel_cases(hip, P):
 @pytest.mark.parametrize("key", ["lap3d_20_nev20", "fe3d_12_nev10", "sio2_12_nev10"])
 def test_gcg_with_fused_cg_matches_reference_run(hip, key):
     c = GCG[key]
-    hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     hip.g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")     # harness CG parameters
     hip.set_random_mode(0)
     ev, res = gcg_on(hip, c["kind"], c["size"], ["-nevConv", c["nev"]], flag=1, K=6, R0=1.5, R1=2.0, seed=12345)
@@ -356,7 +349,6 @@ def test_fused_cg_applies_the_shift(both):
     Checked against the reference's own shifted run (B = NULL) and, for a generalised problem, against our GCG with
     the reference-form BlockPCG on the oracle back-end: same Ritz values, same iteration count (+-2)."""
     hip, ora = both
-    hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     hip.g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
     hip.set_random_mode(0)
     c = GCG["lap3d_12_nev10_shift1"]
@@ -378,7 +370,6 @@ def test_fused_cg_applies_the_shift(both):
 def test_gcg_cholesky_qr_orth_matches_reference_run(hip):
     """Block Cholesky-QR orthonormalisation (what bench.py uses) + fused CG: same Ritz values."""
     c = GCG["fe3d_20_nev20"]
-    hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     hip.g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
     hip.set_random_mode(0)
     ev, res = gcg_on(hip, c["kind"], c["size"], ["-nevConv", c["nev"], "-gcge_initX_orth_method", "chol",
@@ -423,7 +414,6 @@ def test_full_size_spmm_properties(hip):
     ones = ops.mv_create(2, mh)
     import ctypes
     ld = ctypes.c_long()
-    hip.g.gcge_hip_mv_device_ptr.restype = ctypes.c_void_p
     # fill with ones through axpby on a zero block: y = 0*y then y += 1 via lincomb of a one-column block is awkward;
     # use set_random + scale trick instead: (u - u) + 1 is not available -> use from_host for 2 columns (268 MB)
     hones = np.ones((n, 2), order="F")
@@ -446,9 +436,6 @@ def test_full_size_config5_spmm_properties(hip, domain):
     from gcge_amd.lib import ball_geometry
     G, kw = 171, dict(K=2000, R0=2.0, R1=5.0, seed=12345)
     g = hip.g
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-    g.gcge_hip_set_spmm_path.argtypes = [C.c_int]
     if domain == "box":
         A, _ = make_problem("sio2", G, **kw)
         mh = hip.matrix(A)
@@ -500,10 +487,6 @@ def test_cg_recompute_passes_match_numpy(hip, kind, size, which, m):
     n = M.nrows
     mat = hip.matrix(M)
     g = hip.g
-    g.gcge_hip_cg_fusable.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    g.gcge_hip_cg_pass1_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    g.gcge_hip_cg_pass2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
     ncol = m + 4                                   # the passes work on columns [2, 2 + m) of wider blocks
     P = uniform(11, (n, ncol)) - 0.5
     R = uniform(12, (n, ncol)) - 0.5
@@ -557,9 +540,6 @@ def test_gcg_recompute_cg_equals_stored_product_cg(hip, nev):
     count, the Ritz values and a loose band on the count are asserted."""
     import os
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_recompute_iters.restype = C.c_long
-    g.gcge_hip_bpcg_stored_dev_iters.restype = C.c_long
     out = {}
     for tag, env in (("recompute", {}), ("stored", {"GCGE_CG_NO_RECOMPUTE": "1"}), ("stored, host scalars", {"GCGE_CG_NO_RECOMPUTE": "1", "GCGE_CG_STORED_HOST": "1"})):
         os.environ.update(env)
@@ -598,8 +578,6 @@ def test_cg_second_pass_without_stored_residual_matches_numpy(hip, kind, size, m
     n = A.nrows
     mat = hip.matrix(A)
     g = hip.g
-    g.gcge_hip_cg_pass2i_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p]
     ncol = m + 4
     P = uniform(71, (n, ncol)) - 0.5
     Q = uniform(72, (n, ncol)) - 0.5                # p_{k-1}
@@ -637,7 +615,6 @@ def test_residual_hook_matches_numpy(hip, kind, size, start, end, kw):
     columns) — odd and even column ranges, more columns than a chunk."""
     from helpers import csr_to_scipy, uniform
     g = hip.g
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
     if kind == "sio2":
         g.gcge_hip_spmm_dense_mode(1)
     try:
@@ -650,7 +627,6 @@ def test_residual_hook_matches_numpy(hip, kind, size, start, end, kw):
         x = hip.mv_from_numpy(mat, X)
         lam = uniform(22, (end - start,)) * 3.0
         FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
-        g.gcge_hip_residual_hook.restype = C.c_void_p
         fn = FN(g.gcge_hip_residual_hook())
         out = np.zeros(end - start)
         assert fn(mat, None, x, start, end, lam.ctypes.data, out.ctypes.data) == 1
@@ -670,7 +646,6 @@ def test_residual_hook_matches_numpy(hip, kind, size, start, end, kw):
 def test_gcg_residual_hook_equals_slot_path(hip):
     """Whole eigensolve with CheckConvergence through the hook and through the five slots: same locking decisions."""
     import os
-    hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     out = {}
     for tag in ("hook", "slots"):
         if tag == "slots":
@@ -727,7 +702,6 @@ def test_gcg_generalised_residual_hook_equals_slot_path(hip):
     lam = uniform(78, (21,)) * 50.0
     vx = hip.mv_from_numpy(mA, X)
     fn = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double))
-    hip.g.gcge_hip_residual_hook.restype = C.c_void_p
     hook = fn(hip.g.gcge_hip_residual_hook())
     for (s0, e0) in ((0, 21), (3, 20), (5, 6)):
         got = np.zeros(e0 - s0)
@@ -788,8 +762,6 @@ def test_cg_start_sweep_matches_numpy(hip, kind, size, m):
     n = A.nrows
     mat = hip.matrix(A)
     g = hip.g
-    g.gcge_hip_cg_start_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                       C.c_int, C.c_void_p]
     X = uniform(31, (n, m + 6)) - 0.5
     Bm = uniform(32, (n, m + 2)) - 0.5
     x, b = hip.mv_from_numpy(mat, X), hip.mv_from_numpy(mat, Bm)
@@ -818,12 +790,6 @@ def test_full_size_cg_passes_properties(hip):
     A, _ = make_problem("lap3d", N)
     mh = hip.matrix(A)
     ops, g = hip.ops, hip.g
-    g.gcge_hip_cg_pass1_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    g.gcge_hip_cg_pass2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-    g.gcge_hip_cg_start_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
-                                       C.c_int, C.c_void_p]
-    g.gcge_hip_residual_hook.restype = C.c_void_p
     hook = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p)(g.gcge_hip_residual_hook())
     p, r, r0, w, pn, t = (ops.mv_create(m, mh) for _ in range(6))
     hip.set_random_mode(1, 4711)
@@ -936,7 +902,6 @@ def test_gcg_inplace_panel_updates_equal_staged_ones(hip):
     back-end declares row-wise panel updates in place safe (GCGE_BACKEND.inplace_lincomb_cols): same arithmetic, so the
     eigensolve is identical bit for bit to the staged form (GCGE_NO_INPLACE_LINCOMB=1)."""
     import os
-    hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     hip.g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
     hip.set_random_mode(0)
     args = ["-nevConv", 20, "-blockSize", 16, "-nevMax", 48, "-gcge_initX_orth_method", "chol", "-gcge_compW_orth_method", "chol"]
@@ -962,7 +927,6 @@ def test_fused_cg_workspace_follows_the_problem_shape(hip):
     (gpurun_out/gputest3.log of round 1: a 125-row slot case followed by an 8000-row eigensolve)."""
     import scipy.sparse.linalg as sla
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     for kind, size, nrhs in [("lap3d", 5, 4), ("lap3d", 20, 20), ("fe3d", 12, 10), ("lap3d", 12, 12), ("lap3d", 20, 6),
                              ("lap3d", 5, 8)]:
         A, _ = make_problem(kind, size)
@@ -1008,7 +972,6 @@ def test_device_symmetric_eigensolver(hip, n, kind):
         A = (A + A.T) * 0.5
     lda = n + 3
     g = hip.g
-    g.gcge_hip_symeig.argtypes = [C.c_char, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     ref_w = np.linalg.eigvalsh(A)
     nrm = max(np.abs(ref_w).max(), 1e-300)
     for uplo in (b"U", b"L"):
@@ -1027,7 +990,6 @@ def test_device_symmetric_eigensolver(hip, n, kind):
     # the host solver on the same input, and both timings
     hw = np.zeros(n); hz = np.zeros((n, n), order="F"); work = np.zeros(4 * n)
     af = np.asfortranarray(A)
-    hip.h.GCGE_SymEigHost.argtypes = [C.c_char, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     t0 = time.perf_counter()
     assert hip.h.GCGE_SymEigHost(b"U", n, af.ctypes.data, n, hw.ctypes.data, hz.ctypes.data, n, work.ctypes.data) == 0
     th = time.perf_counter() - t0
@@ -1043,8 +1005,6 @@ def test_fused_cg_device_scalars_equal_host_scalars(hip):
     import os
     import scipy.sparse.linalg as sla
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_device_scalar_iters.restype = C.c_long
     A, _ = make_problem("lap3d", 16)
     S = csr_to_scipy(A); n = A.nrows
     mat = hip.matrix(A)
@@ -1093,11 +1053,7 @@ def test_merged_column_passes_equal_separate_passes(hip, kind, which, size, nrhs
     chain2 and ring kernels).  Same blocks, same partial sums: product, residual norms and a whole fused-CG solve (start
     sweep, both passes, stored and rebuilt residual) are bit-identical to the launches pass by pass, ragged widths included."""
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_spmm_pass_merge.argtypes = [C.c_int]
-    g.gcge_hip_bpcg_residual_form.argtypes = [C.c_int]
     FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
-    g.gcge_hip_residual_hook.restype = C.c_void_p
     hook = FN(g.gcge_hip_residual_hook())
     A, B = make_problem(kind, size)
     A = A if which == "A" else B         # (fe3d: the plain pattern kernel, values streamed per row for A, 16 table slots for B)
@@ -1143,8 +1099,6 @@ def test_fused_cg_small_direction_ring(hip):
     2nd / 15th / every iteration, the iterates are the same — same iteration counts, same solutions to rounding."""
     import os
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_release.argtypes = [C.c_void_p]
     A, _ = make_problem("lap3d", 16)
     n = A.nrows
     mat = hip.matrix(A)
@@ -1179,8 +1133,6 @@ def test_gcg_small_ring_takes_the_idle_blocks(hip):
     (GCGE_CG_NO_W_SLOT, GCGE_CG_NO_IDLE_SLOTS) likewise."""
     import os
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_release.argtypes = [C.c_void_p]
     hip.set_random_mode(0)
     args = ["-nevConv", 20, "-blockSize", 16, "-nevMax", 48, "-gcge_initX_orth_method", "chol", "-gcge_compW_orth_method", "chol"]
     out = {}
@@ -1218,11 +1170,7 @@ def test_ring_sweep_equals_chain_kernel_and_numpy(hip, size, m, depth, wide):
     n = A.nrows
     mat = hip.matrix(A)
     g = hip.g
-    g.gcge_hip_cg_pass1_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    g.gcge_hip_spmm_ring_launches.restype = C.c_long
-    g.gcge_hip_spmm_ring_tune.argtypes = [C.c_int, C.c_int]
     FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p)
-    g.gcge_hip_residual_hook.restype = C.c_void_p
     hook = FN(g.gcge_hip_residual_hook())
     ncol = m + 4
     P = uniform(31, (n, ncol)) - 0.5
@@ -1285,8 +1233,6 @@ def test_cg_start_from_scale_factors_equals_start_from_formed_rhs(hip, size, m):
     s = uniform(62, (m,)) * 0.2 + 0.01
     x, b = hip.mv_from_numpy(mat, X), hip.mv_from_numpy(mat, X * s)
     blk = [hip.mv_from_numpy(mat, np.zeros((n, m))) for _ in range(4)]
-    g.gcge_hip_cg_start_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    g.gcge_hip_cg_start_scaled_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     rho1, rho2 = np.zeros(m), np.zeros(m)
     assert g.gcge_hip_cg_start_mv(mat, x, 0, b, 0, blk[0], blk[1], 0, m, rho1.ctypes.data) == 0
     assert g.gcge_hip_cg_start_scaled_mv(mat, x, 0, s.ctypes.data, blk[2], blk[3], 0, m, rho2.ctypes.data) == 0
@@ -1309,8 +1255,6 @@ def test_cg_scale_factors_with_relative_tolerance_equal_the_formed_rhs(hip, size
     mat = hip.matrix(A)
     n = A.nrows
     g, h = hip.g, hip.h
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    h.GCGE_SetLinearSolverArgs.argtypes = [C.POINTER(LINSOL_ARGS)]
     X = uniform(61, (n, m)) - 0.5
     s = uniform(62, (m,)) * 0.2 + 0.01
     sc = (C.c_double * m)(*s)
@@ -1347,8 +1291,6 @@ def test_gcg_scaled_rhs_start_equals_formed_rhs(hip, extra_env):
     (here: recompute form switched off — what matrices without a pattern form get) the start is product + ONE sweep for
     r = x diag(scale) - w, p0 = r and r.r (round 4: cg_start_scaled_stored) instead of forming b."""
     import os
-    hip.g.gcge_hip_bpcg_fused_starts.restype = C.c_long
-    hip.g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     hip.g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
     hip.set_random_mode(0)
     args = ["-nevConv", 20, "-blockSize", 16, "-nevMax", 48, "-gcge_initX_orth_method", "chol", "-gcge_compW_orth_method", "chol"]
@@ -1398,14 +1340,9 @@ def test_tile_spmm_vs_oracle(both, case):
     from helpers import csr_from_scipy
     hip, ora = both
     g = hip.g
-    g.gcge_hip_spmm_tile_mode.argtypes = [C.c_int]
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
     keep = None
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
     g.gcge_hip_spmm_tile_mode(2 if case.endswith("_forced") else 1)   # 1: every matrix without a pattern form, whatever its size; 2: every matrix
     g.gcge_hip_spmm_dense_mode(1 if case.endswith("_remainder") else -1)
-    g.gcge_hip_spmm_star_mode.argtypes = [C.c_int]
     g.gcge_hip_spmm_star_mode(-1)          # (the star rows stay in the CSR arrays: this test is about the tile form)
     want_form = "spmm_dense+spmm_tile" if case.endswith("_remainder") else "spmm_tile"
     try:
@@ -1477,11 +1414,7 @@ def test_dense_block_spmm_vs_oracle(both, case):
     from helpers import csr_from_scipy
     hip, ora = both
     g = hip.g
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
     g.gcge_hip_spmm_dense_mode(1)         # rows of >= 24 entries may seed a block, however small the share of the blocks
-    g.gcge_hip_spmm_star_mode.argtypes = [C.c_int]
     g.gcge_hip_spmm_star_mode(-1)         # (the star rows stay in the CSR arrays: this test is about the block form of a whole matrix)
     keep = None
     try:
@@ -1560,10 +1493,6 @@ def test_star_sweep_spmm_vs_oracle(both, case):
     from helpers import csr_from_scipy
     hip, ora = both
     g = hip.g
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-    g.gcge_hip_mat_star_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
     g.gcge_hip_spmm_dense_mode(1)         # small atoms: rows of >= 24 entries may seed a block
     keep = None
     try:
@@ -1600,8 +1529,6 @@ def test_star_sweep_spmm_vs_oracle(both, case):
         assert np.array_equal(a, hip.mv_to_numpy(yh, n, 0, 64)), "the star sweep is not reproducible from run to run"
         # the product with its column sums, as the fused CG asks for it (x.y and y.y: summed by the sweep over its rows + a short
         # sweep over the list of the other rows)
-        g.gcge_hip_spmm_dot2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
         for m, s0, s1 in [(64, 0, 0), (30, 4, 2), (2, 8, 0)]:
             y2 = hip.mv_from_numpy(mh, uniform(9, (n, 64)))
             dots, yy = np.zeros(m), np.zeros(m)
@@ -1634,17 +1561,11 @@ def test_star_sweep_on_a_masked_grid_vs_oracle(both, G, kw, form):
     from gcge_amd.lib import ball_geometry
     hip, ora = both
     g = hip.g
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
     g.gcge_hip_spmm_dense_mode(1)
-    g.gcge_hip_spmm_star_masked_third.argtypes = [C.c_int]
-    g.gcge_hip_mat_star_masked_form.argtypes = [C.c_void_p]
     g.gcge_hip_spmm_star_masked_third(1 if form == 3 else 0)
     try:
         A, _ = make_problem("sio2ball", G, **kw)
         box = ball_geometry(G)
-        g.gcge_hip_spmm_star_infer.argtypes = [C.c_int]
         g.gcge_hip_spmm_star_infer(0)
         mp = hip.matrix(A)
         g.gcge_hip_spmm_star_infer(1)
@@ -1654,7 +1575,6 @@ def test_star_sweep_on_a_masked_grid_vs_oracle(both, G, kw, form):
         assert not g.gcge_hip_mat_spmm_form(mp).decode().startswith("spmm_star")
         assert g.gcge_hip_mat_star_masked_form(mh) == form and g.gcge_hip_mat_star_masked_form(mi) == form and g.gcge_hip_mat_star_masked_form(mp) == 0
         st, si = (C.c_long * 8)(), (C.c_long * 8)()
-        g.gcge_hip_mat_star_stats.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
         assert g.gcge_hip_mat_star_stats(mh, st) and g.gcge_hip_mat_star_stats(mi, si)
         assert si[3] == st[3] == 6 and si[4] >= 0.98 * st[4], (list(st), list(si))   # (nearly) as many clean rows as with the true geometry
         n = A.nrows
@@ -1674,8 +1594,6 @@ def test_star_sweep_on_a_masked_grid_vs_oracle(both, G, kw, form):
             _close(got, hip.mv_to_numpy(yi, n, 0, 72), tol=1e-12, what="named / recovered geometry m=%d" % m)
             _close(got[:, s1:s1 + m], S @ X[:, s0:s0 + m], tol=1e-12, what="sweep on a masked grid vs scipy m=%d" % m)
             hip.ops.mv_destroy(yh); hip.ops.mv_destroy(yp); hip.ops.mv_destroy(yi); ora.ops.mv_destroy(yo)
-        g.gcge_hip_spmm_dot2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                            C.c_void_p, C.c_void_p, C.c_void_p]
         for m, s0, s1 in [(64, 0, 0), (30, 4, 2)]:
             y2 = hip.mv_from_numpy(mh, uniform(9, (n, 64)))
             dots, yy = np.zeros(m), np.zeros(m)
@@ -1697,15 +1615,11 @@ def test_gcg_on_a_masked_grid_with_the_sweep_matches_reference_run(hip):
     from gcge_amd.lib import ball_geometry, run_gcg
     c = GCG["sio2ball_16_nev10"]
     g = hip.g
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
     g.gcge_hip_spmm_dense_mode(1)
     try:
         A, _ = make_problem("sio2ball", 16, K=6, R0=1.5, R1=2.0, seed=12345)
         mA = hip.matrix_grid(A, (16, 16, 16), ball_geometry(16))
-        g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-        g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
         form = g.gcge_hip_mat_spmm_form(mA).decode()
-        g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
         g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
         hip.set_random_mode(0)
         ev, res = run_gcg(hip.ops_handle, mA, None, ["-nevConv", c["nev"], "-gcge_initX_orth_method", "chol", "-gcge_compW_orth_method", "chol"], flag=1)
@@ -1726,8 +1640,6 @@ def test_offset_pattern_spmm_vs_oracle(both, kind, size, form):
     from helpers import perturbed_stencil
     hip, ora = both
     g = hip.g
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
     A, keep = perturbed_stencil(kind, size, 21)
     mh, mo = hip.matrix(A), ora.matrix(A)
     assert g.gcge_hip_mat_spmm_form(mh).decode() == form, g.gcge_hip_mat_spmm_form(mh).decode()
@@ -1767,13 +1679,6 @@ def test_offset_pattern_cg_passes_match_numpy(hip, size, m):
     n = A.nrows
     mat = hip.matrix(A)
     g = hip.g
-    g.gcge_hip_cg_fusable.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    g.gcge_hip_cg_pass1_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    g.gcge_hip_cg_pass2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-    g.gcge_hip_cg_pass2i_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    g.gcge_hip_cg_start_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     ncol = m + 4
     P = uniform(11, (n, ncol)) - 0.5
     R = uniform(12, (n, ncol)) - 0.5
@@ -1827,8 +1732,6 @@ def test_gcg_on_variable_coefficient_stencil_matches_oracle(both):
     from gcge_amd.lib import run_gcg
     hip, ora = both
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_recompute_iters.restype = C.c_long
     A, keep = perturbed_stencil("lap3d", 16, 33)
     mh, mo = hip.matrix(A), ora.matrix(A)
     g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
@@ -1852,7 +1755,6 @@ def test_device_eigensolver_serves_the_hip_table_only(both):
     run over the HIP table does."""
     hip, ora = both
     g = hip.g
-    g.gcge_hip_symeig_calls.restype = C.c_long
     c = load_golden("gcg_shapes.json")["c2shape_lap3d_24"]
     args = ["-nevConv", c["nev"], "-nevMax", c["nev_max"], "-blockSize", c["block"]]
     before = g.gcge_hip_symeig_calls()
@@ -1886,9 +1788,6 @@ def test_fused_cg_tight_tolerances(hip, size):
     convergence), so both are checked where that matters."""
     import scipy.sparse.linalg as sla
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_residual_form.argtypes = [C.c_int]
-    g.gcge_hip_bpcg_implicit_r_iters.restype = C.c_long
     A, _ = make_problem("lap3d", size)
     S = csr_to_scipy(A); n = A.nrows
     mat = hip.matrix(A)
@@ -1935,10 +1834,6 @@ def test_fused_cg_user_tolerance_from_solver_args_and_active_column_statistics(h
     constant): columns that retire early lower the active share, surplus iterations are counted apart."""
     from solver_setup import bpcg_setup
     g, h = hip.g, hip.h
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_column_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
-    g.gcge_hip_bpcg_surplus_iters.restype = C.c_long
-    h.GCGE_SetLinearSolverArgs.argtypes = [C.POINTER(LINSOL_ARGS)]
     A, _ = make_problem("lap3d", 16)
     S = csr_to_scipy(A); n = A.nrows
     mat = hip.matrix(A)
@@ -1977,7 +1872,6 @@ def test_gcg_auto_shift_with_the_fused_solver(hip, key):
     :483-492) travels through GCGE_LINSOL_ARGS and the fused CG solves (A + sigma B) w = (lambda + sigma) B x.
     Same converged count and Ritz values as the reference's run with its own BlockPCG."""
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
     c = load_golden("gcg.json")[key]
     g.gcge_hip_bpcg_setup(hip.ops_handle, 30, 1e-2, 1e-14, b"abs")
     hip.set_random_mode(0)
@@ -1996,12 +1890,6 @@ def test_held_back_scaling_with_raw_pointers_and_a_second_table(hip):
     OrthSelf sweep whose calls alternate between two tables — against the same sweep with the fusion off, bit for bit."""
     from gcge_amd.ops_struct import OpsTable
     g = hip.g
-    g.gcge_hip_set_mgs_fusion.argtypes = [C.c_int]
-    g.gcge_hip_mv_device_ptr.restype = C.c_void_p
-    g.gcge_hip_mv_device_ptr.argtypes = [C.c_void_p, C.POINTER(C.c_long)]
-    g.gcge_hip_coldots.argtypes = [C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
-    g.gcge_hip_axpby.argtypes = [C.c_int, C.c_double, C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_long, C.c_int, C.c_void_p]
-    g.gcge_hip_stream.restype = C.c_void_p
     import torch
     A, _ = make_problem("lap3d", 11)
     n = A.nrows
@@ -2072,8 +1960,6 @@ def test_mgs_step_fusion_equals_separate_kernels(both):
     rank-1 update is applied first, a speculative Gram column is served only to the immediately following matching call."""
     hip, ora = both
     g = hip.g
-    g.gcge_hip_set_mgs_fusion.argtypes = [C.c_int]
-    g.gcge_hip_mgs_fusion_stats.argtypes = [C.POINTER(C.c_long), C.POINTER(C.c_long)]
     A, _ = make_problem("lap3d", 11)
     n = A.nrows
     V0 = uniform(41, (n, 40)) - 0.5
@@ -2143,10 +2029,6 @@ def test_fused_cg_prepare_creates_the_blocks_before_the_solve(hip):
     solution as a solve that created its blocks itself — and a table whose MultiLinearSolver is not the fused CG is refused."""
     import torch
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_prepare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    g.gcge_hip_bpcg_release.argtypes = [C.c_void_p]
-    g.gcge_hip_pool_cached_bytes.restype = C.c_size_t
     A, _ = make_problem("lap3d", 64)                                     # 33.5 MB per 16-column block: allocations show
     n = A.nrows; nrhs = 16
     mat = hip.matrix(A)
@@ -2184,9 +2066,6 @@ def test_coldots2_equals_two_column_dot_sweeps(hip, n, m, ldx, ldy):
     matrix without a pattern form) returns, bit for bit, what two gcge_hip_coldots sweeps return, and both agree with numpy."""
     import torch
     g = hip.g
-    g.gcge_hip_coldots.argtypes = [C.c_int, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]
-    g.gcge_hip_coldots2.argtypes = g.gcge_hip_coldots.argtypes
-    g.gcge_hip_stream.restype = C.c_void_p
     st = g.gcge_hip_stream()
     gen = torch.Generator(device="cpu"); gen.manual_seed(n + m)
     X = (torch.rand((n, ldx), dtype=torch.float64, generator=gen) - 0.5).cuda()
@@ -2211,10 +2090,6 @@ def test_fused_cg_stored_product_without_stored_residual(hip, kind, size, kw):
     uses (automatic rule: not stored) and, forced, for 1e-6."""
     import scipy.sparse.linalg as sla
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_bpcg_residual_form.argtypes = [C.c_int]
-    g.gcge_hip_bpcg_implicit_r_iters.restype = C.c_long
-    g.gcge_hip_bpcg_recompute_iters.restype = C.c_long
     A, _ = make_problem(kind, size, **kw)
     S = csr_to_scipy(A); n = A.nrows
     mat = hip.matrix(A)
@@ -2223,7 +2098,6 @@ def test_fused_cg_stored_product_without_stored_residual(hip, kind, size, kw):
     nb = np.linalg.norm(Bm, axis=0)
     res = {}
     import os
-    g.gcge_hip_bpcg_stored_dev_iters.restype = C.c_long
     try:
         for rate, forms in ((1e-2, (0, 2)), (1e-6, (1, 2))):
             for form in forms:
@@ -2272,8 +2146,6 @@ def test_dense_profile_reports_the_shapes_a_solve_used(hip):
     """gcge_hip_dense_profile / gcge_hip_dense_profile_report (bench.py --dense-shapes): every Gram and panel update a solve
     launches shows up under its (k, m) with a call count, a time and a rate; switching the profile off empties it."""
     g = hip.g
-    g.gcge_hip_dense_profile.argtypes = [C.c_int]
-    g.gcge_hip_dense_profile_report.argtypes = [C.c_char_p, C.c_int]
     g.gcge_hip_dense_profile(1)
     try:
         ev, res = gcg_on(hip, "lap3d", 16, ["-nevConv", 6, "-blockSize", 4, "-nevMax", 12])
@@ -2300,14 +2172,6 @@ def test_product_profile_counts_and_algorithmic_bytes(hip):
     n, nnz, m = A.nrows, int(A.nnz), 16
     mat = hip.matrix(A)
     g = hip.g
-    g.gcge_hip_profile_enable.argtypes = [C.c_int]
-    g.gcge_hip_profile_kind.restype = C.c_long
-    g.gcge_hip_profile_kind.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    g.gcge_hip_cg_pass1_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    g.gcge_hip_cg_pass2_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_void_p]
-    g.gcge_hip_cg_pass2i_mv.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     p, r, q, pn = (hip.mv_from_numpy(mat, uniform(81 + i, (n, m)) - 0.5) for i in range(4))
     d_al, d_be, d_bp = (torch.from_numpy(uniform(91 + i, (m,)) + 0.1).cuda() for i in range(3))
     d_fl = torch.ones(m, dtype=torch.int32).cuda()

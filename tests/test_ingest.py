@@ -12,10 +12,6 @@ from helpers import csr_to_scipy
 
 def _lib():
     h = host_lib()
-    h.gcge_load_petsc_binary.argtypes = [C.c_char_p, C.c_int64, C.c_int64, C.POINTER(CSR)]
-    h.gcge_save_petsc_binary.argtypes = [C.c_char_p, C.POINTER(CSR)]
-    h.gcge_csr_from_ccs.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double),
-                                    C.c_int, C.POINTER(CSR)]
     return h
 
 
@@ -101,8 +97,6 @@ def test_matrix_market_reader(tmp_path):
     order, a duplicate; pattern; integer) against scipy; our own writer round-trips a generator matrix bit for bit; bad files."""
     import scipy.io as sio
     h = host_lib()
-    h.gcge_load_matrix_market.argtypes = [C.c_char_p, C.POINTER(CSR)]
-    h.gcge_save_matrix_market.argtypes = [C.c_char_p, C.POINTER(CSR), C.c_int]
     rng = np.random.default_rng(4)
     S = sp.random(61, 61, density=0.1, random_state=rng, format="csr")
     S = (S + S.T + sp.eye(61) * 2.25).tocsr()

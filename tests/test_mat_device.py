@@ -122,13 +122,7 @@ class G:
     """ctypes faces of the handle queries"""
 
     def __init__(self, hip):
-        g = self.g = hip.g
-        g.gcge_hip_mat_patterns.argtypes = [C.c_void_p]
-        g.gcge_hip_mat_pattern_chain.argtypes = [C.c_void_p]
-        g.gcge_hip_mat_spmm_form.restype, g.gcge_hip_mat_spmm_form.argtypes = C.c_char_p, [C.c_void_p]
-        g.gcge_hip_mat_row_order.restype, g.gcge_hip_mat_row_order.argtypes = C.c_char_p, [C.c_void_p]
-        g.gcge_hip_spmm_tile_mode.argtypes = [C.c_int]
-        g.gcge_hip_spmm_reorder_mode.argtypes = [C.c_int]
+        self.g = hip.g
 
     def facts(self, m):
         g = self.g

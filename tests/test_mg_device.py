@@ -42,7 +42,6 @@ def grid_agg(dims):
 def graph_agg(arrays, theta=0.25):
     A, keep = _host_arrays(*arrays)
     agg = np.zeros(A.nrows, dtype=np.int32)
-    host_lib().gcge_mg_aggregate_graph.argtypes = [C.POINTER(CSR), C.c_double, C.POINTER(C.c_int)]
     nc = host_lib().gcge_mg_aggregate_graph(C.byref(A), theta, agg.ctypes.data_as(C.POINTER(C.c_int)))
     return agg, nc
 
@@ -130,8 +129,6 @@ def slot_multigrid(backend, A_handle, B_handle, levels):
 
 def hierarchy_snapshot(hip, mA, mB, levels):
     g = hip_lib()
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p; g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-    g.gcge_hip_mat_row_order.restype = C.c_char_p; g.gcge_hip_mat_row_order.argtypes = [C.c_void_p]
     Ah, Bh, Ph, done = slot_multigrid(hip, mA, mB, levels)
     snap = {"L": len(Ah),
             "A": [mat_to_csr(a) for a in Ah[1:]], "B": [mat_to_csr(b) for b in Bh[1:]],

@@ -191,12 +191,10 @@ def build_levels(A, max_levels, B=None):
     """gcge_mg_build with the defaults: lists of (rowptr, colidx, val) per level for A, B, P, PT"""
     h = host_lib()
     mg = MG()
-    h.gcge_mg_build.argtypes = [C.POINTER(CSR), C.POINTER(CSR), C.c_int, C.c_int, C.c_double, C.POINTER(MG)]
     assert h.gcge_mg_build(C.byref(A), C.byref(B) if B is not None else None, max_levels, 0, 0.0, C.byref(mg)) == 0
     L = mg.num_levels
     out = {"A": [csr_arrays(mg.A[l]) for l in range(L)], "B": [csr_arrays(mg.B[l]) for l in range(L)] if B is not None else [],
            "P": [csr_arrays(mg.P[l]) for l in range(L - 1)], "PT": [csr_arrays(mg.PT[l]) for l in range(L - 1)]}
-    h.gcge_mg_free.argtypes = [C.POINTER(MG)]
     h.gcge_mg_free(C.byref(mg))
     return out
 
@@ -206,7 +204,6 @@ def host_galerkin(arrays, agg, nc, scale):
     A = as_struct(arrays)
     agg = np.ascontiguousarray(agg, dtype=np.int32)
     out = CSR()
-    h.gcge_mg_galerkin.argtypes = [C.POINTER(CSR), C.POINTER(C.c_int), C.c_int, C.c_double, C.POINTER(CSR)]
     assert h.gcge_mg_galerkin(C.byref(A), agg.ctypes.data_as(C.POINTER(C.c_int)), nc, scale, C.byref(out)) == 0
     res = csr_arrays(out)
     h.gcge_csr_free(C.byref(out))
@@ -339,7 +336,6 @@ def slot_multigrid(backend, A_handle, B_handle, levels):
 
 def row_order(h):
     g = hip_lib()
-    g.gcge_hip_mat_row_order.restype = C.c_char_p; g.gcge_hip_mat_row_order.argtypes = [C.c_void_p]
     return g.gcge_hip_mat_row_order(h).decode()
 
 
@@ -389,7 +385,6 @@ def test_multigrid_create_falls_back_to_the_host_routine_at_the_round_cap(hip):
     A, keep = csr_from_scipy(permuted("lap3d", 14))
     mA = hip.matrix(A)
     g = hip_lib()
-    g.gcge_hip_mg_graph_round_cap.argtypes = [C.c_int]
     try:
         multigrid_graph_method(1)
         full, _ = hip_levels(hip, mA, None, 4)
@@ -411,7 +406,6 @@ def test_levels_and_prolongations_agree_under_a_forced_reorder(hip, kind, size):
     form re-ordered at upload.  lap3d: the upload may recover the star grid at level 0; the geometric graph has none: level 0 takes
     reverse Cuthill-McKee and stays a matrix without a grid, whose MIS-2 levels gcge_hip_mat_create would re-order as well."""
     g = hip_lib()
-    g.gcge_hip_spmm_reorder_mode.argtypes = [C.c_int]
     A, keep = csr_from_scipy(permuted(kind, size) if kind == "lap3d" else geometric_graph(size))
     ops = hip.ops
     try:
@@ -424,7 +418,6 @@ def test_levels_and_prolongations_agree_under_a_forced_reorder(hip, kind, size):
         if kind == "geometric":
             assert "Cuthill" in row_order(mA) and g.gcge_hip_mg_graph_rounds() >= 1
         assert all(row_order(a) == "as given" for a in Ah[1:])
-        g.gcge_hip_mat_nrows.argtypes = [C.c_void_p]
         for l in range(L - 1):
             nc = g.gcge_hip_mat_nrows(Ah[l + 1])
             E = uniform(300 + l, (nc, 8)) - 0.5

@@ -82,10 +82,6 @@ def host_hierarchy(A, B, dims, box, max_levels):
     """gcge_mg_build_masked as scipy matrices and numpy box arrays"""
     h = host_lib()
     ip = C.POINTER(C.c_int)
-    h.gcge_mg_build_masked.argtypes = [C.POINTER(CSR), C.POINTER(CSR), C.POINTER(C.c_int * 3), ip, C.c_int, C.c_int, C.c_double, C.POINTER(MG)]
-    h.gcge_mg_level_box.restype = ip
-    h.gcge_mg_level_box.argtypes = [C.POINTER(MG), C.c_int]
-    h.gcge_mg_free.argtypes = [C.POINTER(MG)]
     mg = MG()
     box = np.ascontiguousarray(box, dtype=np.int32)
     rc = h.gcge_mg_build_masked(C.byref(A), C.byref(B) if B is not None else None, C.byref((C.c_int * 3)(*dims)), box.ctypes.data_as(ip),
@@ -97,7 +93,7 @@ def host_hierarchy(A, B, dims, box, max_levels):
     out = {"A": [csr_to_scipy(mg.A[l]) for l in range(L)], "B": [csr_to_scipy(mg.B[l]) for l in range(L)] if B is not None else [],
            "P": [csr_to_scipy(mg.P[l]) for l in range(L - 1)], "PT": [csr_to_scipy(mg.PT[l]) for l in range(L - 1)],
            "dims": [tuple(mg.dims[l]) for l in range(L)],
-           "box": [np.ctypeslib.as_array(h.gcge_mg_level_box(C.byref(mg), l), (mg.A[l].nrows,)).copy() for l in range(L)]}
+           "box": [np.ctypeslib.as_array(C.cast(h.gcge_mg_level_box(C.byref(mg), l), ip), (mg.A[l].nrows,)).copy() for l in range(L)]}
     assert not h.gcge_mg_level_box(C.byref(mg), L)
     h.gcge_mg_free(C.byref(mg))
     return out
@@ -209,7 +205,6 @@ def slot_multigrid(backend, A_handle, B_handle, levels):
 def snapshot(hip, mA, mB, levels):
     from gcge_amd.lib import hip_lib, mat_geometry, mat_to_csr, multigrid_stats
     g = hip_lib()
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p; g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
     Ah, Bh, Ph, done = slot_multigrid(hip, mA, mB, levels)
     snap = {"L": len(Ah), "A": [mat_to_csr(a) for a in Ah], "B": [mat_to_csr(b) for b in Bh],
             "P": [mat_to_csr(p) for p in Ph], "PT": [mat_to_csr(p, transpose=True) for p in Ph],

@@ -77,11 +77,9 @@ def test_dense_toy_multigrid_equals_the_reference():
                                                  ("fe1d", 40, (40, 1, 1), 1)])
 def test_grid_detection(kind, size, dims, arm):
     h = host_lib()
-    from gcge_amd.lib import CSR
     A, _ = make_problem(kind, size)
     d = (C.c_int * 3)()
     a = C.c_int()
-    h.gcge_mg_detect_grid.argtypes = [C.POINTER(CSR), C.POINTER(C.c_int * 3), C.POINTER(C.c_int)]
     assert h.gcge_mg_detect_grid(C.byref(A), C.byref(d), C.byref(a)) == 1
     assert tuple(d) == dims and a.value == arm
 
@@ -89,14 +87,12 @@ def test_grid_detection(kind, size, dims, arm):
 def test_grid_detection_refuses_a_permuted_matrix():
     import scipy.sparse as sp
     h = host_lib()
-    from gcge_amd.lib import CSR
     A, _ = make_problem("lap3d", 6)
     S = csr_to_scipy(A)
     p = np.random.default_rng(3).permutation(S.shape[0])
     Sp = sp.csr_matrix(S[p][:, p])
     Ap, keep = csr_from_scipy(Sp)
     d = (C.c_int * 3)()
-    h.gcge_mg_detect_grid.argtypes = [C.POINTER(CSR), C.POINTER(C.c_int * 3), C.POINTER(C.c_int)]
     assert h.gcge_mg_detect_grid(C.byref(Ap), C.byref(d), None) == 0
     # ... and the hierarchy then comes from the greedy aggregation over the graph: still P^T A P, still a partition of the rows
     lev = mg_hierarchy(Ap, 3, scale=1.0, min_rows=4)
@@ -234,9 +230,6 @@ def test_coarse_slabs_of_the_sio2_like_matrix_keep_the_grid_form(zcut, min_star)
     from gcge_amd import dist as gdist
     from gcge_amd.lib import CSR, hip_lib
     g = hip_lib()
-    g.gcge_hip_star_selfcheck_slab.restype = C.c_long
-    g.gcge_hip_star_selfcheck_slab.argtypes = [C.c_int, C.c_int, C.c_long, C.c_long, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
-                                               C.POINTER(C.c_double), C.POINTER(C.c_long)]
     N = 48
     part = [z * N * N for z in zcut]
     for r in range(3):
@@ -306,7 +299,6 @@ def _lap3d8_on(backend, via_slot):
     import scipy.sparse as sp
     g = G["lap3d8_amg"]
     h = host_lib()
-    h.gcge_mg_set_defaults.argtypes = [C.c_double, C.c_int, C.c_double]
     h.gcge_mg_set_defaults(g["scale"], g["min_rows"], -1.0)
     A, _ = make_problem("lap3d", 8)
     mA = backend.matrix(A)

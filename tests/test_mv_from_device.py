@@ -109,8 +109,6 @@ def test_block_into_a_reordered_handle(hip):
     import torch
     from test_mg_graph import geometric_graph
     g = hip.g
-    g.gcge_hip_spmm_reorder_mode.argtypes = [C.c_int]
-    g.gcge_hip_mat_row_order.restype, g.gcge_hip_mat_row_order.argtypes = C.c_char_p, [C.c_void_p]
     S = geometric_graph(3000)
     n = S.shape[0]
     A, keep = csr_from_scipy(S)

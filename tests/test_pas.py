@@ -44,7 +44,6 @@ _CALLBACKS = (_IDFN(_oracle_identity), _FREEFN(_oracle_free))
 def oracle_backend():
     """The oracle table with an identity upload registered for PAS (the oracle registers no back-end record)."""
     h = host_lib()
-    h.GCGE_PAS_SetMatIdentity.argtypes = [_IDFN, _FREEFN]
     h.GCGE_PAS_SetMatIdentity(*_CALLBACKS)
     return OracleBackend()
 
@@ -125,15 +124,11 @@ class Setup:
     def apply_dense_rows(self):
         """rows of level H, from the host builder the back-ends' MultiGridCreate runs (gcge_mg_build, same defaults)"""
         h = host_lib()
-        # own prototypes: other test modules bind these symbols with their own argtypes
-        build = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p)(
-            C.cast(h.gcge_mg_build, C.c_void_p).value)
-        free = C.CFUNCTYPE(None, C.c_void_p)(C.cast(h.gcge_mg_free, C.c_void_p).value)
         mg = MG()
-        assert build(C.addressof(self.A), None, 3, 0, 0.0, C.addressof(mg)) == 0
+        assert h.gcge_mg_build(C.byref(self.A), None, 3, 0, 0.0, C.byref(mg)) == 0
         assert mg.num_levels == 3
         n = mg.A[2].nrows
-        free(C.addressof(mg))
+        h.gcge_mg_free(C.byref(mg))
         return n
 
     def dense(self, m):
@@ -313,8 +308,6 @@ def test_pas_error_codes():
 # ---------------------------------------------------------------------------------------------------------------- GPU
 def border_call(g, QX, s, q, q0, y, y0, m, beta, t, gout):
     fn = g.gcge_hip_pas_border
-    fn.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_double,
-                   C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.c_int]
     tt = np.asfortranarray(t)
     rc = fn(QX, s, q, q0, y, y0, m, beta, tt.ctypes.data_as(C.POINTER(C.c_double)), tt.shape[0],
             gout.ctypes.data_as(C.POINTER(C.c_double)), gout.shape[0])

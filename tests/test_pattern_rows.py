@@ -39,11 +39,11 @@ difference).  So every path to an entry carries at most lt + 2 roundings, and |r
 expression formed from absolute values; the last unit covers the terms of second order ((lt + 2)^2 2^-106) and the longdouble
 reference's own rounding (2^-64 per operation).
 """
-import ctypes as C
 
 import numpy as np
 import pytest
 
+from gcge_amd import abi
 from helpers import GR, IN_GUARD, OUT_BITS, OUT_GUARD, bits, check_vec, draw, out_vec
 
 GF = 4                                               # guard rows in front of a block (even: an odd ld alone leaves row 0 on 16 bytes)
@@ -414,15 +414,6 @@ class Lib:
         import torch
         self.torch, self.hip, g = torch, hip, hip.g
         self.g = g
-        p, i, l = C.c_void_p, C.c_int, C.c_long
-        g.gcge_hip_stream.restype = p
-        g.gcge_hip_pattern_spmm_vals.argtypes = [i, p, p, i, i, l, l, p, l, p, l, i, p, p, p, l, p]
-        g.gcge_hip_pattern_cg_vals.argtypes = [i, i, p, p, i, i, l, l, p, l, p, l, p, l, i, p, p, p, p, p, p, p, l, l, p]
-        g.gcge_hip_spmm_ring_launches.restype = l
-        g.gcge_hip_spmm_ring_tune.argtypes = [i, i]
-        for name in ("spmm_pattern_tune", "spmm_pattern_tune_line", "spmm_chain_tune", "spmm_chain2_tune", "spmm_chain2_xcd", "spmm_pass_merge",
-                     "cg_pass_streams", "spmm_ring_product", "spmm_ring_wide", "spmm_ring_xcd"):
-            getattr(g, "gcge_hip_" + name).argtypes = [i]
         self.st = g.gcge_hip_stream()
         self.devs = {}
 
@@ -470,6 +461,7 @@ class Lib:
 
     def call(self, name, *args, expect=0):
         self.torch.cuda.synchronize()
+        assert "gcge_hip_pattern_" + name in abi.HIP, name          # a name composed here escapes test_abi's source scan
         rc = getattr(self.g, "gcge_hip_pattern_" + name)(*args)
         self.hip.sync()
         assert rc == expect, (name, rc, expect)

@@ -39,8 +39,6 @@ def test_grid_coordinates_come_back_from_the_star_couplings(kind, size, kw, min_
     (pairs of rows: the same |dx|, |dy|, |dz| up to a permutation of the axes) — on the box for >= 99.9 % of sampled pairs (a few
     rows deep inside large atoms have no exact stencil entry to the outside and take free positions)."""
     g = hip_lib()
-    g.gcge_hip_reorder_star_grid.restype = C.c_long
-    g.gcge_hip_reorder_star_grid.argtypes = [C.c_int, IP, IP, C.POINTER(C.c_double), IP, IP]
     Sp, _, p = permuted(kind, size, 7, **kw)
     n = Sp.shape[0]
     A, keep = csr_from_scipy(Sp)
@@ -66,11 +64,6 @@ def test_grid_coordinates_come_back_from_the_star_couplings(kind, size, kw, min_
 def test_star_recovery_refuses_what_is_no_star_grid_and_rcm_bands_it():
     import scipy.sparse as sp
     g = hip_lib()
-    g.gcge_hip_reorder_star_grid.restype = C.c_long
-    g.gcge_hip_reorder_star_grid.argtypes = [C.c_int, IP, IP, C.POINTER(C.c_double), IP, IP]
-    g.gcge_hip_reorder_rcm.argtypes = [C.c_int, IP, IP, IP]
-    g.gcge_hip_mean_bandwidth.restype = C.c_double
-    g.gcge_hip_mean_bandwidth.argtypes = [C.c_int, IP, IP, IP]
     rng = np.random.default_rng(11)
     n = 3000
     pts = rng.random((n, 3))
@@ -98,7 +91,6 @@ def test_star_recovery_refuses_what_is_no_star_grid_and_rcm_bands_it():
 # ---------------------------------------------------------------------------------------------- GPU: nothing shows at the boundary
 @pytest.fixture()
 def reorder_on(hip):
-    hip.g.gcge_hip_spmm_reorder_mode.argtypes = [C.c_int]
     hip.g.gcge_hip_spmm_reorder_mode(1)
     yield hip
     hip.g.gcge_hip_spmm_reorder_mode(0)
@@ -117,11 +109,6 @@ def test_permuted_grid_matrices_take_the_grid_kernels_again(reorder_on, kind, si
     PERMUTED arrays; with the re-ordering switched off the same handle calls give the same numbers through the generic kernels."""
     hip = reorder_on
     g = hip.g
-    g.gcge_hip_mat_spmm_form.restype = C.c_char_p
-    g.gcge_hip_mat_spmm_form.argtypes = [C.c_void_p]
-    g.gcge_hip_mat_row_order.restype = C.c_char_p
-    g.gcge_hip_mat_row_order.argtypes = [C.c_void_p]
-    g.gcge_hip_spmm_dense_mode.argtypes = [C.c_int]
     g.gcge_hip_spmm_dense_mode(1)
     try:
         Sp, _, p = permuted(kind, size, 5, **kw)
@@ -172,9 +159,6 @@ def test_gcg_on_permuted_matrices_matches_the_oracle(reorder_on, oracle, kind, s
     come back in the caller's row order (residuals recomputed with scipy)."""
     hip = reorder_on
     g = hip.g
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    g.gcge_hip_mat_row_order.restype = C.c_char_p
-    g.gcge_hip_mat_row_order.argtypes = [C.c_void_p]
     Sp, Bp, p = permuted(kind, size, 9, **kw)
     n = Sp.shape[0]
     A, keepA = csr_from_scipy(Sp)
@@ -212,8 +196,6 @@ def test_matrix_without_any_grid_gets_cuthill_mckee(reorder_on):
     from scipy.spatial import cKDTree
     hip = reorder_on
     g = hip.g
-    g.gcge_hip_mat_row_order.restype = C.c_char_p
-    g.gcge_hip_mat_row_order.argtypes = [C.c_void_p]
     rng = np.random.default_rng(2)
     n = 6000
     pts = rng.random((n, 3))

@@ -43,7 +43,6 @@ def test_gcg_on_the_oracle_keeps_the_three_steps(oracle):
 # ---------------------------------------------------------------------------------------------- HIP: the fused launch
 def _ritz_in_place(V, n0, x1, w1, coef, S, p0, np_):
     g = hip_lib()
-    g.gcge_hip_ritz_in_place_mv.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_void_p, C.c_int, C.c_int]
     return g.gcge_hip_ritz_in_place_mv(V, n0, x1, w1, coef.ctypes.data_as(C.POINTER(C.c_double)), coef.shape[0], S, p0, np_)
 
 
@@ -150,7 +149,6 @@ def test_block_moves_from_v_equal_the_moves_from_the_eigenvector_block(hip, rows
 # ---------------------------------------------------------------------------------------------- HIP: norms from the update
 def _panel_norms(y, start, end):
     g = hip_lib()
-    g.gcge_hip_panel_norms_sq_mv.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
     out = np.full(end - start, -1.0)
     return g.gcge_hip_panel_norms_sq_mv(y, start, end, out.ctypes.data_as(C.POINTER(C.c_double))), out
 

@@ -23,7 +23,6 @@ def _host_stats():
 
 def _hip_stats():
     g = hip_lib()
-    g.gcge_hip_bpcg_start_in_place_stats.restype = C.c_long
     d = C.c_long()
     return g.gcge_hip_bpcg_start_in_place_stats(C.byref(d)), d.value
 
@@ -96,10 +95,6 @@ def test_start_sweep_from_x_elsewhere_equals_moves_then_start(hip, grid, m):
     m columns.  lo = 2 runs with r and p0 the same block (the start that stores p0 alone)."""
     g = hip_lib()
     vp, ci = C.c_void_p, C.c_int
-    g.gcge_hip_cg_start_mv.argtypes = [vp, vp, ci, vp, ci, vp, vp, ci, ci, vp]
-    g.gcge_hip_cg_start_scaled_b_mv.argtypes = [vp, vp, ci, vp, vp, vp, ci, ci, vp, ci, vp]
-    g.gcge_hip_block_moves_mv.argtypes = [vp, vp, ci, ci, C.POINTER(ci), ci, vp, ci, C.POINTER(C.c_double)]
-    g.gcge_hip_cg_accum_x_mv.argtypes = [vp, ci, vp, ci, ci, C.POINTER(vp), ci, vp]
     if grid[0] == grid[1] == grid[2]:
         A, _ = make_problem("lap3d", grid[0])
         keep = None
@@ -107,7 +102,6 @@ def test_start_sweep_from_x_elsewhere_equals_moves_then_start(hip, grid, m):
         A, keep = csr_from_scipy(_lap_grid(*grid))
     mat = hip.matrix(A)
     n = A.nrows
-    g.gcge_hip_mat_pattern_chain.argtypes = [vp]
     if grid == (16, 16, 16):
         assert g.gcge_hip_mat_pattern_chain(mat) == 2          # chain + line exchange: the kernel BlockAMG's level 0 runs at the bench shape
     wv, wb, b0 = 2 * m + 12, m + 6, 2
@@ -184,8 +178,6 @@ def _solve_from_elsewhere(hip, size, iters):
     mat = hip.matrix(A)
     n, m = A.nrows, 16
     g, h = hip.g, hip.h
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    h.GCGE_SetLinearSolverArgs.argtypes = [C.POINTER(LINSOL_ARGS)]
     X0, W0 = uniform(81, (n, m + 8)) - 0.5, uniform(82, (n, m + 4)) + 2.0
     s = uniform(83, (m,)) * 0.2 + 0.01
     sc = (C.c_double * m)(*s)

@@ -15,7 +15,6 @@ from test_multigrid import slot_multigrid
 
 def _trimmed():
     g = hip_lib()
-    g.gcge_hip_bpcg_trimmed_iters.restype = C.c_long
     return g.gcge_hip_bpcg_trimmed_iters()
 
 
@@ -23,7 +22,6 @@ def _column_stats():
     g = hip_lib()
     a, b = C.c_long(), C.c_long()
     g.gcge_hip_bpcg_column_stats(C.byref(a), C.byref(b))
-    g.gcge_hip_bpcg_surplus_iters.restype = C.c_long
     return a.value, b.value, g.gcge_hip_bpcg_surplus_iters()
 
 
@@ -82,8 +80,6 @@ def test_direct_fused_cg_keeps_its_last_pass(hip, m):
     n = A.nrows
     mA = hip.matrix(A)
     g, h = hip_lib(), host_lib()
-    g.gcge_hip_bpcg_setup.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_char_p]
-    h.GCGE_SetLinearSolverArgs.argtypes = [C.c_void_p]
     b = uniform(501, (n, m)) - 0.5
     res = {}
     for cols in (0, 1, -1):
@@ -97,10 +93,8 @@ def test_direct_fused_cg_keeps_its_last_pass(hip, m):
         t0, s0 = _trimmed(), _column_stats()
         hip.ops.multi_linear_solver(mA, mb, mx, (0, 0), (m, m))
         h.GCGE_SetLinearSolverArgs(None)
-        g.gcge_hip_bpcg_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         it = C.c_int()
         g.gcge_hip_bpcg_stats(None, None, C.byref(it))
-        g.gcge_hip_bpcg_last_residual.restype = C.c_double
         res[cols] = (hip.mv_to_numpy(mx, n, 0, m), it.value, _trimmed() - t0, tuple(v - w for v, w in zip(_column_stats(), s0)),
                      g.gcge_hip_bpcg_last_residual())
         hip.ops.mv_destroy(mb, m)
