@@ -86,6 +86,9 @@ struct GCGE_HIP_MAT_ {
   // at upload (the grid form of spmm_star.hip was built on it); row r is box point h_box[r] = x + nx (y + ny z) of geom_dims, strictly ascending
   int geom_kind; int geom_dims[3]; int* h_box; int* d_box;
 };
+// The masked grid a matrix lives on, as the upload hands it to the split of spmm_star.hip (NULL: none): box[i] = x + nx (y + ny z) in an nx x ny x nz
+// box.  cols false: box[r] for the nbox = nrows rows of a whole matrix; cols true: box[c] for the nbox local columns of a row slab, own rows, then halo rows.
+struct GcgeGridGeom { int nx, ny, nz; const int* box; int nbox; bool cols; };
 // One row order per problem size and process: every matrix of n rows (A, then B of a generalised problem) and every block of vectors
 // created for them share it.  perm[new] = old, iperm[old] = new; identity: a matrix of this size was uploaded in the caller's order and
 // later ones of the same size must follow it.  Reference-counted by matrices and blocks.
@@ -231,14 +234,9 @@ const void* gcge_hip_dense_remainder_tile(const void* dm);
 void gcge_hip_dense_stats(const void* dm, long* nblocks, long* items, long* dense_nnz, long* dense_entries, long* rem_nnz);
 int gcge_hip_dense_spmm(const void* dm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, void* stream, int which);
 const int* gcge_hip_dense_row_list(const void* dm, int* nlisted);
-// spmm_star.hip
-void gcge_hip_star_next_geometry(int nrows, int nx, int ny, int nz, const int* box_of_row);
-void* gcge_hip_star_build(int nrows, int ncols_local, long row_begin, long nglobal, const int* ghost, const int* rowptr, const int* colidx, const double* val,
-                          const int** rem_rowptr, const int** rem_col, const double** rem_val);
-void gcge_hip_star_release_remainder(void);
+// spmm_star.hip (gcge_hip_star_build: star_split.h)
 void gcge_hip_star_free(void* sm);
 void gcge_hip_star_stats(const void* sm, long* out);
-const unsigned char* gcge_hip_star_host_mask(void);
 int gcge_hip_star_masked_form(const void* sm);
 int gcge_hip_star_interior(const void* sm, int* ilo, int* ihi);
 int gcge_hip_star_spmm(const void* sm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, void* stream);

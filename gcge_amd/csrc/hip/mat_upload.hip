@@ -15,6 +15,7 @@
 #include "gcge_hip.h"
 #include "gcge_hip_internal.h"
 #include "pattern_table.h"
+#include "star_split.h"
 
 #define g_spmm_path (gcge_hip_spmm_path_get())
 #define g_offset_patterns (gcge_hip_offset_patterns_get())
@@ -138,7 +139,6 @@ static void build_patterns(GCGE_HIP_MAT* A, int nrows, int ncols_local, const in
 // The masked grid a whole matrix lives on stays on the handle — named by the caller (kind 1) or recovered at upload (kind 2) —
 // independent of the K1 form: host and device copies of the box array.  A geometry that is not one (box indices out of the box or
 // not strictly ascending) is not recorded.
-static bool g_geometry_named = false;       // the upload in progress has its geometry from the caller (or from the row order search)
 static void mat_set_geometry(GCGE_HIP_MAT* A, int kind, int nx, int ny, int nz, const int* box) {
   const long nbox = (long)nx * ny * nz;
   if (A == nullptr || box == nullptr || nx < 1 || ny < 1 || nz < 1 || nbox > 2147483647L || A->nghost != 0 || A->row_begin != 0) return;
@@ -159,10 +159,11 @@ extern "C" int gcge_hip_mat_geometry(const GCGE_HIP_MAT* A, int* dims, int* box_
 
 // rows of one slab with LOCAL column indices in [0, ncols_local); columns >= nrows are halo rows.  ghost_global (may be NULL): the
 // global rows behind the halo columns, ascending — with it (and nglobal) a slab of a grid matrix cut on plane boundaries keeps the
-// plane sweep of spmm_star.hip: the planes below and above the slab are then found among the halo rows.
+// plane sweep of spmm_star.hip: the planes below and above the slab are then found among the halo rows.  geom (may be NULL): the
+// masked grid the caller names; one named for a whole matrix (cols false) also means that none is recovered for the handle.
 static double upload_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
-extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local_ghosts(int nrows, int ncols_local, int nglobal, int row_begin,
-                                                          const int* rowptr, const int* colidx, const double* val, const int* ghost_global) {
+static GCGE_HIP_MAT* mat_create_local(int nrows, int ncols_local, int nglobal, int row_begin, const int* rowptr, const int* colidx, const double* val,
+                                      const int* ghost_global, const GcgeGridGeom* geom) {
   if (gcge_hip_init(-1) != 0) return nullptr;
   const bool timing = getenv("GCGE_UPLOAD_TIMING") != nullptr;   // phases of the host-side analysis on stderr
   double t_phase = upload_now();
@@ -219,23 +220,25 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local_ghosts(int nrows, int ncols_l
   phase("pattern search");
   A->star = nullptr; A->star_rem = nullptr;
   if (A->d_pid == nullptr) {
-    const int *rr = nullptr, *rc = nullptr; const double* rv = nullptr;
     // (the sweep needs to know where the slab sits in the grid: a whole matrix, or a slab with its global size and halo rows named)
     const bool whole = row_begin == 0 && ncols_local == nrows && (nglobal <= 0 || nglobal == nrows);
     const bool slab = !whole && nglobal > 0 && (ncols_local == nrows || ghost_global != nullptr);
-    void* S = (whole || slab) ? gcge_hip_star_build(nrows, ncols_local, row_begin, whole ? nrows : nglobal, ghost_global, rowptr, colidx, val, &rr, &rc, &rv) : nullptr;
+    gcge::StarHost* H = nullptr;                    // the split behind S: ours
+    void* S = (whole || slab) ? gcge_hip_star_build(nrows, ncols_local, row_begin, whole ? nrows : nglobal, ghost_global, rowptr, colidx, val, geom, &H) : nullptr;
     phase("star split");
-    if (S != nullptr && whole && !g_geometry_named && gcge_hip_star_masked_form(S) != 0) {
-      // a masked grid nobody named: the build recovered it from the rows.  The same recovery once more, for the handle — kept
-      // whatever becomes of the grid form below
-      std::vector<int> gbox((size_t)nrows); int gd[3] = {0, 0, 0};
-      if (gcge_hip_star_infer_grid(nrows, rowptr, colidx, gd, gbox.data())) mat_set_geometry(A, 2, gd[0], gd[1], gd[2], gbox.data());
+    if (S != nullptr && whole && (geom == nullptr || geom->cols) && gcge_hip_star_masked_form(S) != 0) {
+      // a masked grid nobody named for the whole matrix: what the build recovered from the rows goes on the handle, whatever becomes of the
+      // grid form below (own_box empty: a world of ONE slab with its local columns named — the handle still carries what the rows show)
+      int* od = H->own_dims;
+      if (!H->own_box.empty() || gcge::star_infer_box(nrows, rowptr, colidx, &H->own_box, &od[0], &od[1], &od[2]))
+        mat_set_geometry(A, 2, od[0], od[1], od[2], H->own_box.data());
       phase("geometry for the handle");
     }
     if (S != nullptr) {
-      void* D = gcge_hip_dense_build_rows(nrows, ncols_local, rr, rc, rv, gcge_hip_star_host_mask());   // (its pad-8 part lists the other rows only)
+      void* D = gcge_hip_dense_build_rows(nrows, ncols_local, H->rem_rowptr.data(), H->rem_col.data(), H->rem_val.data(),
+                                          (const unsigned char*)H->clean.data());   // (its pad-8 part lists the other rows only)
       if (D != nullptr) { A->star = S; A->star_rem = D; } else gcge_hip_star_free(S);   // (no blocks among the other rows: the forms below)
-      gcge_hip_star_release_remainder();
+      delete H;
       phase("blocks + listed rows");
     }
   }
@@ -255,9 +258,18 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local_ghosts(int nrows, int ncols_l
   }
   return A;
 }
-extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local(int nrows, int ncols_local, int nglobal, int row_begin,
-                                                   const int* rowptr, const int* colidx, const double* val) {
-  return gcge_hip_mat_create_local_ghosts(nrows, ncols_local, nglobal, row_begin, rowptr, colidx, val, nullptr);
+extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local_ghosts(int nrows, int ncols_local, int nglobal, int row_begin, const int* rowptr, const int* colidx,
+                                                          const double* val, const int* ghost_global) {
+  return mat_create_local(nrows, ncols_local, nglobal, row_begin, rowptr, colidx, val, ghost_global, nullptr);
+}
+extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local(int nrows, int ncols_local, int nglobal, int row_begin, const int* rowptr, const int* colidx, const double* val) {
+  return mat_create_local(nrows, ncols_local, nglobal, row_begin, rowptr, colidx, val, nullptr, nullptr);
+}
+// a ROW SLAB of a masked grid: the box index of every local column — the own rows, then the halo rows (ascending by global row); NULL: none
+extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_local_ghosts_grid(int nrows, int ncols_local, int nglobal, int row_begin, const int* rowptr, const int* colidx,
+                                                               const double* val, const int* ghost_global, int nx, int ny, int nz, const int* box_of_local_col) {
+  const GcgeGridGeom geom = {nx, ny, nz, box_of_local_col, ncols_local, true};
+  return mat_create_local(nrows, ncols_local, nglobal, row_begin, rowptr, colidx, val, ghost_global, box_of_local_col != nullptr ? &geom : nullptr);
 }
 // ---------------------------------------------------------------------------------------------------------------- row orders
 // (round 5)  A whole matrix (one rank) that shows neither a pattern form nor a grid in the order it arrives in is
@@ -367,17 +379,11 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_beg
   gcge_hip_mat_destroy(A);
   GcgePerm* P = perm_register(nrows, perm.data());
   permute_csr(nrows, rowptr, colidx, val, P, rp, ci, va);
-  if (grid && (long)dims[0] * dims[1] * dims[2] != nrows) {   // a masked grid (ball): name the geometry for the plane sweep's row map
-    std::vector<int> bsorted((size_t)nrows);
-    for (int i = 0; i < nrows; ++i) bsorted[i] = box[perm[i]];
-    gcge_hip_star_next_geometry(nrows, dims[0], dims[1], dims[2], bsorted.data());
-    g_geometry_named = true;
-    A = gcge_hip_mat_create_local(nrows, nrows, nglobal, 0, rp.data(), ci.data(), va.data());
-    g_geometry_named = false;
-    gcge_hip_star_next_geometry(0, 0, 0, 0, nullptr);
-  } else {
-    A = gcge_hip_mat_create_local(nrows, nrows, nglobal, 0, rp.data(), ci.data(), va.data());
-  }
+  const bool masked = grid && (long)dims[0] * dims[1] * dims[2] != nrows;   // a ball: name the geometry for the plane sweep's row map
+  std::vector<int> bsorted(masked ? (size_t)nrows : 0);
+  for (int i = 0; i < nrows && masked; ++i) bsorted[i] = box[perm[i]];
+  const GcgeGridGeom geom = {dims[0], dims[1], dims[2], bsorted.data(), nrows, false};
+  A = mat_create_local(nrows, nrows, nglobal, 0, rp.data(), ci.data(), va.data(), nullptr, masked ? &geom : nullptr);
   if (A == nullptr) { gcge_hip_perm_release(gcge_hip_perm_acquire(P)); return nullptr; }
   A->perm = gcge_hip_perm_acquire(P);
   return A;
@@ -389,13 +395,12 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_beg
 // of gcge_hip_mat_create on the same arrays.
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_grid(int nrows, const int* rowptr, const int* colidx, const double* val,
                                                   int nx, int ny, int nz, const int* box_of_row) {
-  if (box_of_row != nullptr && nx > 0 && ny > 0 && nz > 0) gcge_hip_star_next_geometry(nrows, nx, ny, nz, box_of_row);
-  g_geometry_named = true;
-  GCGE_HIP_MAT* A = gcge_hip_mat_create_local(nrows, nrows, nrows, 0, rowptr, colidx, val);      // (the caller named the geometry: the rows stay as given)
-  g_geometry_named = false;
+  // (the caller named the geometry: the rows stay as given and nothing is recovered from them for the handle, even if what was named is none)
+  const bool named = box_of_row != nullptr && nx > 0 && ny > 0 && nz > 0;
+  const GcgeGridGeom geom = {nx, ny, nz, named ? box_of_row : nullptr, nrows, false};
+  GCGE_HIP_MAT* A = mat_create_local(nrows, nrows, nrows, 0, rowptr, colidx, val, nullptr, &geom);
   if (A != nullptr) { GcgePerm* P = perm_find(nrows); if (P == nullptr) P = perm_register(nrows, nullptr); if (P->identity) A->perm = gcge_hip_perm_acquire(P); }
-  gcge_hip_star_next_geometry(0, 0, 0, 0, nullptr);                   // (not consumed when the matrix took a pattern form)
-  if (A != nullptr && box_of_row != nullptr && nx > 0 && ny > 0 && nz > 0) mat_set_geometry(A, 1, nx, ny, nz, box_of_row);
+  if (A != nullptr && named) mat_set_geometry(A, 1, nx, ny, nz, box_of_row);
   return A;
 }
 // A whole matrix whose rows stay as given whatever the row order search would do and whatever order another matrix of its size lives

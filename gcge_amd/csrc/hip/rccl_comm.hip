@@ -235,19 +235,10 @@ static void rccl_exchange_int(const int* sendbuf, const int* send_cnt, int* recv
 // partitioned product needs is set up here, collectively (every rank of the communicator calls it): ghost list and
 // local renumbering, who needs which of my rows (one all-gather of the per-slab counts, then the index lists by
 // grouped send/recv), exchange buffers of buf_cols columns.  part: world + 1 row offsets, part[world] = n_global.
-// ... of a matrix on a MASKED grid (gcge_hip_mat_create_grid on one rank): box_of_global_row[r] = x + nx (y + ny z) of global row r,
+// ... of a matrix on a MASKED grid (gcge_hip_mat_create_grid on one rank): box[r] = x + nx (y + ny z) of global row r,
 // rows in scan order, the partition cut between grid LINES (gcge_dist_partition_lines) — the slab keeps the plane sweep, its halo rows
-// are found through the line table (spmm_star.hip).  NULL geometry: gcge_hip_mat_create_slab.
-static const int* g_slab_box = nullptr; static int g_slab_dims[3] = {0, 0, 0};
-extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_slab_grid(const long* part, const int* rowptr, const int* colidx_global, const double* val, int buf_cols,
-                                                       int nx, int ny, int nz, const int* box_of_global_row) {
-  g_slab_box = box_of_global_row; g_slab_dims[0] = nx; g_slab_dims[1] = ny; g_slab_dims[2] = nz;
-  GCGE_HIP_MAT* A = gcge_hip_mat_create_slab(part, rowptr, colidx_global, val, buf_cols);
-  g_slab_box = nullptr;
-  return A;
-}
-extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_slab(const long* part, const int* rowptr, const int* colidx_global,
-                                                  const double* val, int buf_cols) {
+// are found through the line table (spmm_star.hip).  NULL box: no geometry (gcge_hip_mat_create_slab).
+static GCGE_HIP_MAT* create_slab(const long* part, const int* rowptr, const int* colidx_global, const double* val, int buf_cols, int nx, int ny, int nz, const int* box) {
   if (gcge_hip_init(-1) != 0) return nullptr;
   const int world = g_world, rank = g_rank;
   const long n_global = part[world];
@@ -277,14 +268,13 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_slab(const long* part, const int* r
   if (gcge_dist_localize(&S, ghosts, ng) != 0) { gcge_free_ints(ghosts); return nullptr; }
   // (the halo rows' global ids travel with the arrays: a slab of a grid matrix cut on plane boundaries keeps the plane sweep)
   std::vector<int> box_local;
-  if (g_slab_box != nullptr) {                                       // masked grid: the box index of every local column (own rows, then halo rows)
+  if (box != nullptr) {                                              // masked grid: the box index of every local column (own rows, then halo rows)
     box_local.resize((size_t)nrows + ng);
-    for (int r = 0; r < nrows; ++r) box_local[r] = g_slab_box[part[rank] + r];
-    for (int k = 0; k < ng; ++k) box_local[(size_t)nrows + k] = g_slab_box[ghosts[k]];
-    gcge_hip_star_next_geometry_cols(nrows + ng, g_slab_dims[0], g_slab_dims[1], g_slab_dims[2], box_local.data());
+    for (int r = 0; r < nrows; ++r) box_local[r] = box[part[rank] + r];
+    for (int k = 0; k < ng; ++k) box_local[(size_t)nrows + k] = box[ghosts[k]];
   }
-  GCGE_HIP_MAT* A = gcge_hip_mat_create_local_ghosts(nrows, nrows + ng, (int)n_global, (int)part[rank], rowptr, cols.data(), val, ghosts);
-  if (g_slab_box != nullptr) gcge_hip_star_next_geometry_cols(0, 0, 0, 0, nullptr);   // (not consumed when the slab took another form)
+  GCGE_HIP_MAT* A = gcge_hip_mat_create_local_ghosts_grid(nrows, nrows + ng, (int)n_global, (int)part[rank], rowptr, cols.data(), val, ghosts, nx, ny, nz,
+                                                          box_local.empty() ? nullptr : box_local.data());
   gcge_free_ints(ghosts);
   if (A == nullptr) return nullptr;
   if (world > 1) {
@@ -294,4 +284,11 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_slab(const long* part, const int* r
   }
   gcge_hip_mat_set_partition(A, part, world);      // (MultiGridCreate coarsens a slab from it: multigrid.hip)
   return A;
+}
+extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_slab(const long* part, const int* rowptr, const int* colidx_global, const double* val, int buf_cols) {
+  return create_slab(part, rowptr, colidx_global, val, buf_cols, 0, 0, 0, nullptr);
+}
+extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_slab_grid(const long* part, const int* rowptr, const int* colidx_global, const double* val, int buf_cols,
+                                                       int nx, int ny, int nz, const int* box_of_global_row) {
+  return create_slab(part, rowptr, colidx_global, val, buf_cols, nx, ny, nz, box_of_global_row);
 }

@@ -382,17 +382,16 @@ def hip_slab_matrix(hip, comm, A, n_global, part, cap_cols=128, geometry=None):
     g = hip.g
     ghosts = localize_slab(A)
     send_rows, send_cnt, recv_cnt = comm.plan_halo(ghosts, part)
+    # (the halo rows' global ids go with the arrays: a slab of a grid matrix cut on plane boundaries keeps the plane sweep)
+    gh = np.ascontiguousarray(ghosts, dtype=np.int32)
+    slab = (A.nrows, A.ncols, n_global, A.row_begin, A.rowptr, A.colidx, A.val, gh.ctypes.data_as(C.POINTER(C.c_int)))
     if geometry is not None:
         dims, box_global = geometry
         bg = np.asarray(box_global, dtype=np.int32)
         box_local = np.ascontiguousarray(np.concatenate([bg[A.row_begin:A.row_begin + A.nrows], bg[np.asarray(ghosts, dtype=np.int64)]]), dtype=np.int32)
-        g.gcge_hip_star_next_geometry_cols(int(box_local.size), int(dims[0]), int(dims[1]), int(dims[2]), box_local.ctypes.data_as(C.POINTER(C.c_int)))
-    # (the halo rows' global ids go with the arrays: a slab of a grid matrix cut on plane boundaries keeps the plane sweep)
-    gh = np.ascontiguousarray(ghosts, dtype=np.int32)
-    m = g.gcge_hip_mat_create_local_ghosts(A.nrows, A.ncols, n_global, A.row_begin, A.rowptr, A.colidx, A.val,
-                                           gh.ctypes.data_as(C.POINTER(C.c_int)))
-    if geometry is not None:
-        g.gcge_hip_star_next_geometry_cols(0, 0, 0, 0, None)          # (not consumed when the slab took another form)
+        m = g.gcge_hip_mat_create_local_ghosts_grid(*slab, int(dims[0]), int(dims[1]), int(dims[2]), box_local.ctypes.data_as(C.POINTER(C.c_int)))
+    else:
+        m = g.gcge_hip_mat_create_local_ghosts(*slab)
     if not m:
         raise RuntimeError("gcge_hip_mat_create_local_ghosts failed")
     mat = C.c_void_p(m)

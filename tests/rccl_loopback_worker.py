@@ -56,13 +56,15 @@ def star_loopback(G, ball=False):
     ghosts = np.ascontiguousarray(gdist.localize_slab(A), dtype=np.int32)
     ng = int(ghosts.size)
     assert (ball or ng >= 6 * plane) and ghosts[0] == n_loc and np.all(ghosts - n_loc < n_loc)
-    if ball:
-        box_local = np.ascontiguousarray(np.concatenate([box[:n_loc], box[ghosts]]), dtype=np.int32)
-        g.gcge_hip_star_next_geometry_cols(int(box_local.size), G, G, G, box_local.ctypes.data_as(C.POINTER(C.c_int)))
     P = sp.csr_matrix((np.ones(ng), (np.arange(ng), ghosts - n_loc)), shape=(ng, n_loc))
     S = (Sg[:, :n_loc] + Sg[:, ghosts] @ P).tocsr()
     ip_ = C.POINTER(C.c_int)
-    mat = C.c_void_p(g.gcge_hip_mat_create_local_ghosts(A.nrows, A.ncols, n_global, 0, A.rowptr, A.colidx, A.val, ghosts.ctypes.data_as(ip_)))
+    slab = (A.nrows, A.ncols, n_global, 0, A.rowptr, A.colidx, A.val, ghosts.ctypes.data_as(ip_))
+    if ball:
+        box_local = np.ascontiguousarray(np.concatenate([box[:n_loc], box[ghosts]]), dtype=np.int32)
+        mat = C.c_void_p(g.gcge_hip_mat_create_local_ghosts_grid(*slab, G, G, G, box_local.ctypes.data_as(ip_)))
+    else:
+        mat = C.c_void_p(g.gcge_hip_mat_create_local_ghosts(*slab))
     send_rows = np.ascontiguousarray(ghosts - n_loc, dtype=np.int32)
     peer, scnt, rcnt = (C.c_int * 2)(0, 0), (C.c_int * 2)(0, ng), (C.c_int * 2)(0, ng)
     assert g.gcge_hip_mat_set_halo_rccl(mat, n_global, 2, peer, scnt, rcnt, send_rows.ctypes.data_as(ip_), 64) == 0

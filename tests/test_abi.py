@@ -260,7 +260,7 @@ def test_supernode_split_reproduces_the_csr_arrays():
 
 
 def test_star_split_reproduces_the_csr_arrays():
-    """Host half of the grid path (csrc/hip/spmm_star.hip; no device call): the rows taken as "one star stencil with a
+    """Host half of the grid path (csrc/hip/star_split.hip; no device call): the rows taken as "one star stencil with a
     diagonal of their own", rebuilt from the detected grid, the star's coefficients and the stored diagonal, and the other
     rows' remainder equal the CSR arrays bit for bit; grid and arm length are what the generator used; a slab with halo
     columns and a 7-point Laplacian small enough to be refused do not take the form."""

@@ -1609,6 +1609,46 @@ def test_star_sweep_on_a_masked_grid_vs_oracle(both, G, kw, form):
         g.gcge_hip_spmm_star_masked_third(1)
 
 
+def test_a_geometry_nobody_consumed_reaches_no_later_upload(hip):
+    """The ball matrix uploaded with its geometry named while the grid form is switched off (the split returns before it looks at
+    the geometry), then the same arrays uploaded without a geometry and with the recovery from the rows off: the second handle
+    has no grid form and carries no geometry."""
+    from gcge_amd.lib import ball_geometry, mat_geometry
+    g = hip.g
+    A, _ = make_problem("sio2ball", 24, K=8, R0=1.5, R1=3.0)
+    try:
+        g.gcge_hip_spmm_star_mode(-1)
+        m1 = hip.matrix_grid(A, (24, 24, 24), ball_geometry(24))
+        g.gcge_hip_spmm_star_mode(0)
+        g.gcge_hip_spmm_star_infer(0)
+        m2 = hip.matrix(A)
+        assert g.gcge_hip_mat_star_masked_form(m2) == 0
+        assert not g.gcge_hip_mat_spmm_form(m2).decode().startswith("spmm_star"), g.gcge_hip_mat_spmm_form(m2).decode()
+        assert g.gcge_hip_mat_geometry(m2, None, None) == 0 and mat_geometry(m2) == (0, None, None)
+        hip.free_matrix(m1); hip.free_matrix(m2)
+    finally:
+        g.gcge_hip_spmm_star_mode(0)
+        g.gcge_hip_spmm_star_infer(1)
+
+
+def test_the_handles_recovered_geometry_is_the_builds(hip):
+    """No geometry named, recovery on: what the handle carries (kind 2) is what gcge_hip_star_infer_grid finds in the same arrays,
+    dims and box array."""
+    from gcge_amd.lib import mat_geometry
+    g = hip.g
+    A, _ = make_problem("sio2ball", 24, K=8, R0=1.5, R1=3.0)
+    g.gcge_hip_spmm_star_infer(1)
+    m = hip.matrix(A)
+    try:
+        want_dims, want_box = (C.c_int * 3)(), np.zeros(A.nrows, dtype=np.int32)
+        assert g.gcge_hip_star_infer_grid(A.nrows, A.rowptr, A.colidx, want_dims, want_box.ctypes.data_as(C.POINTER(C.c_int))) == 1
+        kind, dims, box = mat_geometry(m)
+        assert kind == 2
+        assert np.array_equal(np.array(dims), np.array(list(want_dims))) and np.array_equal(box, want_box)
+    finally:
+        hip.free_matrix(m)
+
+
 def test_gcg_on_a_masked_grid_with_the_sweep_matches_reference_run(hip):
     """The reference's run on the ball matrix (tests/golden: sio2ball_16_nev10) against our driver over the HIP table with the
     geometry named, chol + fused CG (product with column sums through the mapped sweep)."""
