@@ -1,4 +1,5 @@
-// The table side of the pattern format (spmm_pattern.hip), host code only — no HIP, so it also compiles alone under a sanitizer.
+// The table side of the pattern format (spmm_pattern.hip): host code that needs no HIP, so it also compiles alone under a sanitizer
+// (the one piece kernels share, the slot rule below, is __host__ __device__ only when hipcc compiles it).
 // A pattern search has two parts:
 //   (a) every row gets the id of its class (rows equal as {(column - row, value bits)}), ids by first occurrence — done over all
 //       rows, by build_patterns on the host arrays (mat_upload.hip) or by the kernels of mat_device.hip on device arrays;
@@ -13,6 +14,31 @@
 #include <vector>
 
 struct GcgePatEntry { double val; long off; };
+
+#if defined(__HIPCC__)
+#define GCGE_PAT_HD __host__ __device__
+#else
+#define GCGE_PAT_HD
+#endif
+// The slot rule of the per-row values (d_rowval[8 r + slot], build_patterns in mat_upload.hip): the table slot that takes the entry
+// with column offset `off` of a row whose table row is e[0 .. lt).  The diagonal sits in slot 1 of a chain-layout table (where slots
+// whose address would leave the block also read offset 0); every other entry takes the first slot not used by an earlier entry of
+// its row that carries its offset and a non-zero table value.  -1: no such slot, or slot 1 taken twice.  *used: the slots taken so far.
+// Shared by the kernels of mat_values.hip and the host check in tools/pattern_values_check.cpp; build_patterns keeps its own copy.
+static inline GCGE_PAT_HD int gcge_pat_value_slot(const GcgePatEntry* e, int lt, bool chain_layout, long off, unsigned* used) {
+  int slot = -1;
+  if (chain_layout && off == 0) slot = 1;
+  else for (int k = 0; k < lt; ++k) if (!(*used >> k & 1) && e[k].off == off && e[k].val != 0.0) { slot = k; break; }
+  if (slot < 0 || slot >= lt || (*used >> slot & 1)) return -1;
+  *used |= 1u << slot;
+  return slot;
+}
+// how many slots of a table row are present (table value != 0.0): a row of the matrix whose length differs stores a +-0.0
+static inline GCGE_PAT_HD int gcge_pat_present_slots(const GcgePatEntry* e, int lt) {
+  int c = 0;
+  for (int k = 0; k < lt; ++k) c += e[k].val != 0.0 ? 1 : 0;
+  return c;
+}
 
 // gcge_hip_mat_create_device's check of its arguments before anything is launched: a positive row count, 0 <= nnz < 2^31 (the
 // pad-8 copy's octets, at most (nnz + 7 nrows) / 8, then fit an int as well), arrays that are there

@@ -38,7 +38,13 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
     definite) by GCG on the GPU.  The smallest eigenvalues are the only mode.
 
     A, M:  a torch sparse_csr CUDA tensor, a (crow, col, val) triple of device arrays, or a matrix handle of the back-end.  Handles
-           stay the caller's; what is created here is freed here.
+           stay the caller's; what is created here is freed here.  A sequence of nearby operators on one sparsity structure keeps
+           ONE handle and gives it new values between the solves (HipBackend.matrix_update_values), so no step re-creates the matrix:
+               m = hip.matrix_from_device(A0); r = eigsh(m, k, backend=hip)
+               for V in potentials:
+                   if not hip.matrix_update_values(m, values_of(V)):       # declined: nothing was written
+                       hip.free_matrix(m); m = hip.matrix_from_device(crow, col, values_of(V))
+                   r = eigsh(m, k, X0=r.eigenvectors, backend=hip)
     X0:    (n, j) device tensor of start vectors, j <= nev_max (a warm start: the previous eigenvectors of a nearby operator).
     tol:   relative residual tolerance, ||A x - lambda M x|| <= tol |lambda|;  maxiter: outer iterations at most (default 500).
     nev_max (default 2 k), block_size:  columns of the eigenvector block and of the W block, as for the harness.

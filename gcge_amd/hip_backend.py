@@ -74,6 +74,41 @@ class HipBackendImpl:
             raise ValueError("gcge_hip_mat_create_device refused the arrays")
         return C.c_void_p(m)
 
+    def matrix_update_values(self, m, values):
+        """New values for a live matrix handle, in place (gcge_hip_mat_update_values_device): `values` holds one value per stored
+        entry of the CSR arrays the handle was created from, in their order — a torch CUDA tensor, the .values() of a sparse_csr
+        tensor, or an object with __cuda_array_interface__.  Converted to float64 on the device only if it is something else; the
+        producer's stream is synchronised before the call (torch's current stream for tensors, the whole device for other objects).
+        True: every product through the handle is now that of the new values (its K1 form may have become a "+values" form).
+        False: the library declined and wrote nothing (star / dense / tile forms, slabs, re-ordered handles, a 16-slot table whose
+        classes do not stay uniform, an explicitly stored zero): free the handle and create the matrix again.
+        TypeError: a host tensor; ValueError: another count of values than the handle has entries (checked here)."""
+        import torch
+        foreign = not isinstance(values, torch.Tensor)
+        if foreign:
+            if not hasattr(values, "__cuda_array_interface__"):
+                raise TypeError("matrix_update_values: a torch device tensor or an object with __cuda_array_interface__ is required")
+            values = torch.as_tensor(values, device=self.torch_device())
+        if not values.is_cuda:
+            raise TypeError("matrix_update_values: the values must live on the GPU")
+        nnz = int(self.g.gcge_hip_mat_nnz(m))
+        if values.numel() != nnz:
+            raise ValueError("matrix_update_values: %d values for a handle of %d entries" % (values.numel(), nnz))
+        va = values.reshape(-1)
+        if va.dtype != torch.float64:
+            va = va.to(dtype=torch.float64)
+        va = va.contiguous()
+        if nnz == 0:
+            va = torch.zeros(1, dtype=torch.float64, device=va.device)     # (the library wants an array)
+        if foreign:
+            torch.cuda.synchronize(va.device)
+        else:
+            torch.cuda.current_stream(va.device).synchronize()
+        rc = self.g.gcge_hip_mat_update_values_device(m, nnz, va.data_ptr())
+        if rc < 0:
+            raise ValueError("gcge_hip_mat_update_values_device refused its arguments")
+        return rc == 0
+
     def mv_to_torch(self, mv, c0, c1):
         """Columns [c0, c1) of a block of vectors as a new (n, c1 - c0) float64 tensor on the GPU, rows in the caller's order
         (gcge_hip_mv_to_device): nothing passes through the host."""

@@ -146,6 +146,14 @@ def mat_device_stats():
     return tuple(out)
 
 
+def mat_update_stats():
+    """gcge_hip_mat_update_stats: (updates that kept the form, of those value-table rewrites, conversions to "+values", declines,
+    bad-argument returns, bytes copied device to host) of gcge_hip_mat_update_values_device since the library was loaded."""
+    out = (C.c_long * 6)()
+    hip_lib().gcge_hip_mat_update_stats(out)
+    return tuple(out)
+
+
 def mat_device_hash_bits(bits):
     """Tests: the device pattern search keeps only the low `bits` bits of its row hash (64: all of it, the default)."""
     hip_lib().gcge_hip_mat_device_hash_bits(int(bits))

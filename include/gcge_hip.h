@@ -74,6 +74,37 @@ GCGE_HIP_MAT *gcge_hip_mat_create_as_given (int nrows, const int *rowptr, const 
  * caused by a hash collision, out[3] bytes copied device to host by these constructors.                                          */
 GCGE_HIP_MAT *gcge_hip_mat_create_device (int nrows, long nnz, const int *d_rowptr, const int *d_colidx, const double *d_val);
 void gcge_hip_mat_device_stats (long out[4]);
+/* New values for a LIVE handle, in place (csrc/hip/mat_values.hip): d_val holds nnz new values for the entries of the CSR arrays the
+ * handle was created from, in the caller's order — a DEVICE array, complete when the call is made (the caller synchronises its
+ * producer).  For a sequence of nearby operators on one sparsity structure (an SCF loop, a parameter sweep): rowptr, colidx, the pad-8
+ * index arrays, pid, the table's offsets, spans and the chain layout stay; only what holds values is re-derived, on the device.  The
+ * call runs on gcge_hip_stream() and synchronises it before it returns; the array may be freed afterwards.
+ *   0    updated: every product, CG pass and residual through the handle is now that of (rowptr, colidx, d_val).
+ *   1    declined: NOTHING of the handle was written (all checks run before the first store); the caller re-creates the matrix.
+ *   < 0  bad arguments (NULL handle or array, nnz != gcge_hip_mat_nnz (A)); nothing written.
+ * One rank, a whole square matrix, rows as given or in the identity order.  What becomes of the handle:
+ *   CSR + pad-8 only (no pattern, star, dense or tile form): d_val and the pad-8 values are rewritten, any values; form unchanged.
+ *   offsets-only table + per-row values (the "+values" forms of gcge_hip_mat_spmm_form): the same, and the per-row values are
+ *     re-scattered by the slot rule of the upload (gcge_pat_value_slot, csrc/hip/pattern_table.h); form unchanged.
+ *   value table, classes still uniform (all rows of a class agree, as bits, on the new value of every present slot, none of them
+ *     +-0.0): d_val, the pad-8 values and the values of the table's present slots are rewritten; pid, offsets and spans are
+ *     untouched, so chain, chain2 and the ring sweep are kept.
+ *   value table of at most 8 slots, anything else: d_val and the pad-8 values are rewritten and the handle BECOMES the "+values" form
+ *     of the table it has (per-row values allocated and filled by the slot rule; gcge_hip_mat_spmm_form then reports
+ *     spmm_pattern+values / spmm_pattern_chain2+values).  There is no way back: a later uniform update re-scatters the per-row values.
+ *   declined (1): a value table of 16 slots whose classes do not stay uniform; a row whose count of present table slots (table value
+ *     != 0.0) differs from its length, i.e. an explicitly stored +-0.0; and, decided from the handle alone before d_val is read, a
+ *     handle with a star, dense or tile form (each has a value layout of its own behind its builder: deliberately out of scope), a
+ *     rectangular handle, a row slab (halo columns, row_begin != 0, a halo plan), a re-ordered handle.
+ * A conversion changes the K1 form between two solves.  Nothing in the back-end keeps a record of a handle's form across calls: the
+ * fused CG plans every call from the handle (cg_plan, block_pcg.hip), its parked blocks are keyed by row count and row order, and
+ * mat_product.hip reads the handle at every product.  A multigrid hierarchy built from the handle BEFORE an update belongs to the old
+ * operator; the harness creates and destroys its hierarchy inside every solve, other callers of MultiGridCreate rebuild theirs.
+ * gcge_hip_mat_update_stats: since load, out[0] updates that kept the form, out[1] of those value-table rewrites, out[2] conversions
+ * to "+values", out[3] declines, out[4] bad-argument returns, out[5] bytes copied device to host by updates — one flag word per
+ * update that has a table, whatever the size of the matrix.  gcge_hip_mat_device_stats is not touched.                              */
+int  gcge_hip_mat_update_values_device (GCGE_HIP_MAT *A, long nnz, const double *d_val);
+void gcge_hip_mat_update_stats (long out[6]);
 /* A matrix of that kind that names NO geometry (read from a file: gcge_load_matrix_market, gcge_load_petsc_binary) gets it
  * recovered at upload by gcge_hip_mat_create itself: x lines from the (r, r + 1) couplings, planes and the shifts between
  * lines / planes from the votes of the star rows' + y / + z neighbours.  A wrong guess costs speed, never the result (the
