@@ -506,6 +506,10 @@ int gcge_hip_lincomb (int nrows, const double *d_x, long ldx, int k, const doubl
 		const double *d_beta, double *d_y, long ldy, void *stream);
 void gcge_hip_lincomb_tune (int row_fragments);   /* 0 automatic (2 for m > 64 on large blocks), 1, 2: 16-row fragments per wave */
 void gcge_hip_gram_tune (int ms);                 /* K2: 4-row steps per macro-step, 1, 2 (the default) or 4; any other value is ignored */
+/*     K2 with d_q == d_p, ldq == ldp and k == m <= 64 (the Gram of a block with itself, one tile) takes a symmetric variant: one
+ *     fragment load per row, the fragments below the diagonal mirrored instead of accumulated — the same bits.  GCGE_GRAM_NO_SYM=1
+ *     in the environment (read per call) keeps the general kernel; the counter is the number of symmetric launches so far        */
+long gcge_hip_gram_sym_launches (void);
 /* K4  Y[:,0:m) = alpha X[:,0:m) + beta Y   (d_x NULL: scale only; beta == 0: no read of Y) */
 int gcge_hip_axpby (int nrows, double alpha, const double *d_x, long ldx, double beta,
 		double *d_y, long ldy, int m, void *stream);
