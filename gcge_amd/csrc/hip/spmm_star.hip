@@ -25,6 +25,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
+#include <initializer_list>
 #include <vector>
 #include "star_split.h"   // gcge_hip_internal.h; STAR_R, StarCoef, StarGeom; the upload-time analysis (star_split.hip) and its result
 
@@ -77,28 +78,24 @@ __device__ __forceinline__ v2d star2_and(v2d v, unsigned long long m) {   // m: 
 }
 constexpr int STAR2_Q = 14;
 #define S2SLOT(U, k) (((U) + (k) + STAR_R + 2 * STAR2_Q) % STAR2_Q)
-// LPP: lanes (of 16 bytes) per grid point = columns per pass / 2.  4: a 16 x 16 patch, 8 columns — 64-byte pieces of the rows;
-// 8: a 16 x 8 patch, 16 columns — 128-byte pieces, i.e. whole cache lines.  tools/seg_bench.hip: on this chip 64-byte pieces of
-// 512-byte rows come in at 3.1-3.9 TB/s (2.8 with the write-back) whatever is done, 128-byte pieces at 6.2 (5.4) TB/s, and the
-// sweep's time is proportional to its traffic (tools/star_dbg_probe.py: LDS reads and barriers cost nothing, every X row fetched
-// costs its share): the smaller patch stages 3.25 rows per row instead of 2.5 but moves them at the full rate.
-template <int LPP> struct Star2Geom {
-  static constexpr int TY = 64 / LPP;                    // lines of the patch (16 points each)
-  static constexpr int ROWS = TY + 2 * STAR_R;           // image rows
-  static constexpr int IMG = ROWS * STAR_PW * LPP;       // v2d entries of one plane image
-  static constexpr int HPTS = 2 * STAR_R * TY + 2 * STAR_R * STAR_T;   // halo points per plane: side strips, then top / bottom strips
-  static constexpr int HQ = (HPTS * LPP + 1023) / 1024;  // halo units per thread
-};
+// 4 lanes (of 16 bytes) per grid point: a 16 x 16 patch, 8-column passes, 64-byte pieces of the rows; 128-byte pieces (whole cache
+// lines, 16-column passes on a 16 x 8 patch) come in at twice the rate and won (tools/seg_bench.hip, profiles/r04_star/, profiles/r05_star/)
+// — they live in the third form below, which can afford them in registers.
+constexpr int STAR2_LPP = 4;
+constexpr int STAR2_TY = 64 / STAR2_LPP;                                    // lines of the patch (16 points each)
+constexpr int STAR2_ROWS = STAR2_TY + 2 * STAR_R;                           // image rows
+constexpr int STAR2_IMG = STAR2_ROWS * STAR_PW * STAR2_LPP;                 // v2d entries of one plane image
+constexpr int STAR2_HPTS = 2 * STAR_R * STAR2_TY + 2 * STAR_R * STAR_T;     // halo points per plane: side strips, then top / bottom strips
+constexpr int STAR2_HQ = (STAR2_HPTS * STAR2_LPP + 1023) / 1024;            // halo units per thread
 // MAPPED: a masked grid (the points inside a sphere, say): only some points of the nx x ny x nz box are rows; map[box index] = the
 // row of X / Y / diag of that point, -1 where there is none (reads as zero, nothing written).  Every access to a row then goes
 // through a 4-byte lookup requested a step before the row itself is: one more stage in the same pipeline (one rank, no halo planes).
-template <bool DOT, bool ISO, bool SLAB, int LPP, int dbg = 0, bool MAPPED = false>
+template <bool DOT, bool ISO, bool SLAB, bool MAPPED = false>
 __global__ __launch_bounds__(1024) void spmm_star2_kernel(int nx, int ny, int zs, int ze, int zmin, int zmax, long dlo, long dhi, StarCoef cf,
     const double* __restrict__ diag, const double* __restrict__ x, size_t ldx, double* __restrict__ y, size_t ldy, int ncols,
     int zlo, int zhi, int zlen, int ntx, double* __restrict__ partial, const unsigned char* __restrict__ cleanf, const int* __restrict__ map,
     const int* __restrict__ prange) {
-  typedef Star2Geom<LPP> GEO;
-  constexpr int TY = GEO::TY, IMG = GEO::IMG, HQ = GEO::HQ, SIDE = 2 * STAR_R * TY;
+  constexpr int LPP = STAR2_LPP, TY = STAR2_TY, IMG = STAR2_IMG, HPTS = STAR2_HPTS, HQ = STAR2_HQ, SIDE = 2 * STAR_R * TY;
   __shared__ v2d img[2 * IMG];                  // img[b][(row * 28 + col) * LPP + part]
   const int tid = threadIdx.x;
   const int part = tid % LPP, px = (tid / LPP) & 15, py = tid / (16 * LPP);
@@ -136,11 +133,11 @@ __global__ __launch_bounds__(1024) void spmm_star2_kernel(int nx, int ny, int zs
     const int pt = (tid + 1024 * q) / LPP;
     int xx, yy;
     if (pt < SIDE) { const int ry = pt / 12, a = pt % 12; yy = ry; xx = a < 6 ? a - 6 : 10 + a; }
-    else if (pt < GEO::HPTS) { const int j = pt - SIDE, d = j >> 4; xx = j & 15; yy = d < 6 ? d - 6 : TY - 6 + d; }
+    else if (pt < HPTS) { const int j = pt - SIDE, d = j >> 4; xx = j & 15; yy = d < 6 ? d - 6 : TY - 6 + d; }
     else { xx = 0; yy = 0; }
     const int ax = x0 + xx, ay = y0 + yy;
-    const bool ok = pt < GEO::HPTS && ax >= 0 && ax < nx && ay >= 0 && ay < ny && cvalid;
-    hdst[q] = pt < GEO::HPTS ? ((yy + STAR_R) * STAR_PW + (xx + STAR_R)) * LPP + part : -1;
+    const bool ok = pt < HPTS && ax >= 0 && ax < nx && ay >= 0 && ay < ny && cvalid;
+    hdst[q] = pt < HPTS ? ((yy + STAR_R) * STAR_PW + (xx + STAR_R)) * LPP + part : -1;
     hsrc[q] = ok ? ax + nx * ay : -1;
   }
   // lookups (MAPPED): the row of my point / of halo unit q in plane zz (clamped plane, a valid address whatever the lane)
@@ -208,7 +205,7 @@ __global__ __launch_bounds__(1024) void spmm_star2_kernel(int nx, int ny, int zs
       if (z >= z1) break;                                                                                                   \
       constexpr int CUR = ((U) & 1) * IMG, NXT = (((U) + 1) & 1) * IMG;                                                     \
       /* request: my point in plane z + 7 (first used at step z + 1); MAPPED: and the lookups of the next step */          \
-      if (!(dbg & 8)) qv[S2SLOT(U, STAR_R + 1)] = MAPPED ? ld_own_m(r7, z + STAR_R + 1) : ld_own(z + STAR_R + 1);            \
+      qv[S2SLOT(U, STAR_R + 1)] = MAPPED ? ld_own_m(r7, z + STAR_R + 1) : ld_own(z + STAR_R + 1);                           \
       int r7n = 0, rnn = 0;                                                                                                 \
       if (MAPPED) { r7n = mp_own(z + STAR_R + 2); rnn = mp_own(z + 2); }                                                    \
       const unsigned long long inn = (z + 1 < z1 ? ~0ull : 0ull) & own_m;                                                   \
@@ -219,8 +216,8 @@ __global__ __launch_bounds__(1024) void spmm_star2_kernel(int nx, int ny, int zs
       const v2d* pl = img + CUR + slot;                                                                                     \
       _Pragma("unroll") for (int k = 1; k <= STAR_R; ++k) {                                                                 \
         const v2d zsum = qv[S2SLOT(U, -k)] + qv[S2SLOT(U, k)];                                                              \
-        v2d xsum = v2d{0.0, 0.0}, ysum = v2d{0.0, 0.0};                                                                     \
-        if (!(dbg & 2)) { xsum = pl[-LPP * k] + pl[LPP * k]; ysum = pl[-LPP * k * STAR_PW] + pl[LPP * k * STAR_PW]; }        \
+        const v2d xsum = pl[-LPP * k] + pl[LPP * k];                                                                        \
+        const v2d ysum = pl[-LPP * k * STAR_PW] + pl[LPP * k * STAR_PW];                                                    \
         if (ISO) {                                                                                                          \
           const v2d s6 = (zsum + xsum) + ysum;                                                                              \
           acc.x = fma(cf.cz[k], s6.x, acc.x); acc.y = fma(cf.cz[k], s6.y, acc.y);                                            \
@@ -230,7 +227,7 @@ __global__ __launch_bounds__(1024) void spmm_star2_kernel(int nx, int ny, int zs
           acc.x = fma(cf.cy[k], ysum.x, acc.x); acc.y = fma(cf.cy[k], ysum.y, acc.y);                                        \
         }                                                                                                                   \
       }                                                                                                                     \
-      if (dg == dg && (!(dbg & 4) || acc.x == 12345.678)) {                                                                 \
+      if (dg == dg) {                                                                                                       \
         const size_t yrow = MAPPED ? (size_t)max(rcur, 0) : (size_t)(own + plane_rows * z);                                 \
         __builtin_nontemporal_store(acc, reinterpret_cast<v2d*>(y + yrow * ldy + col));                                     \
         if (DOT && cl != 0) {                                                                                               \
@@ -242,11 +239,11 @@ __global__ __launch_bounds__(1024) void spmm_star2_kernel(int nx, int ny, int zs
       /* image of plane z + 1: my value from the queue, the strips requested a step ago; then the request for plane z + 2's */ \
       img[NXT + slot] = qv[S2SLOT(U, 1)];                                                                                   \
       _Pragma("unroll") for (int q = 0; q < HQ; ++q) if (hdst[q] >= 0) img[NXT + hdst[q]] = st[q];                           \
-      if (!(dbg & 1)) { _Pragma("unroll") for (int q = 0; q < HQ; ++q) st[q] = MAPPED ? ld_halo_m(q, hrow[q], z + 2) : ld_halo(q, z + 2); } \
+      _Pragma("unroll") for (int q = 0; q < HQ; ++q) st[q] = MAPPED ? ld_halo_m(q, hrow[q], z + 2) : ld_halo(q, z + 2);     \
       if (MAPPED) { _Pragma("unroll") for (int q = 0; q < HQ; ++q) hrow[q] = mp_halo(q, z + 3); }                            \
       dg = dnext; cl = cnext;                                                                                               \
       if (MAPPED) { rcur = rnext; rnext = rnn; r7 = r7n; }                                                                  \
-      if (!(dbg & 16)) __syncthreads();                                                                                     \
+      __syncthreads();                                                                                                      \
     }
     STAR2_STEP(0) STAR2_STEP(1) STAR2_STEP(2) STAR2_STEP(3) STAR2_STEP(4) STAR2_STEP(5) STAR2_STEP(6)
     STAR2_STEP(7) STAR2_STEP(8) STAR2_STEP(9) STAR2_STEP(10) STAR2_STEP(11) STAR2_STEP(12) STAR2_STEP(13)
@@ -291,6 +288,7 @@ __global__ __launch_bounds__(1024) void spmm_star2_kernel(int nx, int ny, int zs
 // allows in flight cover the pieces issued in the current step.  No spill may exist in this kernel (a scratch access is a
 // vector-memory operation hipcc waits for at once).
 constexpr int STAR3_Q = 15;
+#define S3SLOT(U, k) (((U) + (k) + STAR_R + 2 * STAR3_Q) % STAR3_Q)   // (both third forms: #undef'd after the masked one)
 constexpr int STAR3_TY = 8, STAR3_LPP = 8;
 constexpr int STAR3_ROWS = STAR3_TY + 2 * STAR_R;                           // 20 image rows
 constexpr int STAR3_IMG = STAR3_ROWS * STAR_PW * STAR3_LPP;                 // v2d entries of the plane image (71 680 B)
@@ -298,7 +296,6 @@ constexpr int STAR3_HPTS = 2 * STAR_R * STAR3_TY + 2 * STAR_R * STAR_T;     // 2
 constexpr int STAR3_RING = STAR3_HPTS * STAR3_LPP;                          // v2d entries of one strip buffer (36 864 B)
 constexpr int STAR3_PIECES = STAR3_RING / 64;                               // 36 pieces of 64 lanes x 16 B
 constexpr unsigned STAR3_LDS = (STAR3_IMG + 2 * STAR3_RING) * 16;           // 145 408 B
-#define S3SLOT(U, k) (((U) + (k) + STAR_R + 2 * STAR3_Q) % STAR3_Q)
 __device__ __forceinline__ void star3_dma(const char* base, unsigned voff, unsigned lds_dst) {   // one piece: lane l -> lds_dst + 16 l
   unsigned keep;
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
@@ -326,9 +323,7 @@ __device__ __forceinline__ void star_block_of(int xcd, unsigned& bx, unsigned& b
 }
 template <int N> __device__ __forceinline__ void star3_vmwait() { asm volatile("s_waitcnt vmcnt(%0)" : : "n"(N) : "memory"); }
 
-// PROBE (timing only, results wrong): the own points of plane z + 2 are requested at step z — at the lead of the halo strips — instead
-// of those of plane z + 8: what a sweep that needs a plane's own points and its halo in the SAME step would request (tools/star_lead_probe.py)
-template <bool DOT, bool SLAB, bool PROBE = false>
+template <bool DOT, bool SLAB>
 __global__ __launch_bounds__(1024) void spmm_star3_kernel(int nx, int ny, int zs, int ze, int zmin, int zmax, long dlo, long dhi, StarCoef cf,
     const double* __restrict__ diag, const double* __restrict__ x, size_t ldx, double* __restrict__ y, size_t ldy, int ncols,
     int zlo, int zhi, int zlen, int ntx, double* __restrict__ partial, const unsigned char* __restrict__ cleanf, int xcd) {
@@ -436,7 +431,7 @@ __global__ __launch_bounds__(1024) void spmm_star3_kernel(int nx, int ny, int zs
       img[slot] = qv[S3SLOT(U, 0)];                                                                                         \
       __syncthreads();                                   /* B: the image of plane z is complete, strip buffer sl is free */ \
       dma_plane(z + 2, sl);                                                                                                 \
-      qv[S3SLOT(U, STAR_R + 2)] = ld_own(z + (PROBE ? 2 : STAR_R + 2));      /* first used at step z + 2 */                 \
+      qv[S3SLOT(U, STAR_R + 2)] = ld_own(z + STAR_R + 2);                    /* first used at step z + 2 */                 \
       dg3[((U) + 2) % 3] = ld_diag(z + 2);                                                                                  \
       cl3[((U) + 2) % 3] = ld_clean(z + 2);                                                                                 \
       const double dg = dg3[(U) % 3];                                                                                       \
@@ -485,7 +480,6 @@ __global__ __launch_bounds__(1024) void spmm_star3_kernel(int nx, int ny, int zs
     }
   }
 }
-#undef S3SLOT
 #undef own
 #undef own_m
 
@@ -508,7 +502,6 @@ __device__ __forceinline__ void star3_dma64(const void* addr, unsigned lds_dst) 
   asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                : "=&s"(keep) : "v"(addr), "s"(lds_dst) : "memory");
 }
-#define S3SLOT(U, k) (((U) + (k) + STAR_R + 2 * STAR3_Q) % STAR3_Q)
 template <bool DOT>
 __global__ __launch_bounds__(1024) void spmm_star3m_kernel(int nx, int ny, int nz, StarCoef cf, const double* __restrict__ diag,
     const double* __restrict__ x, size_t ldx, double* __restrict__ y, size_t ldy, int ncols, int zlo, int zhi, int zlen, int ntx,
@@ -734,18 +727,11 @@ static int g_star_infer = 1;  // 1: a matrix without a lexicographic grid is tri
 extern "C" void gcge_hip_spmm_star_infer(int on) { g_star_infer = on != 0; }
 static int g_star_form = 3;   // 2: second form of the sweep (registers stage the halo strips), 3: third form (LDS-DMA strips, 16-column passes)
 extern "C" void gcge_hip_spmm_star_form(int form) { g_star_form = form == 3 ? 3 : 2; }
-static int g_star_masked_zchunks = 0;  // masked third form: z ranges per patch (0: the rule of the other forms)
-extern "C" void gcge_hip_spmm_star_masked_zchunks(int n) { g_star_masked_zchunks = n; }
 static int g_star_masked_third = 1;   // masked grids with a line table take the third form (0: the second form with its point-wise map, round 4)
 extern "C" void gcge_hip_spmm_star_masked_third(int on) { g_star_masked_third = on != 0; }
-static int g_star_lpp = 4;    // second form: 8 = 16-column passes on 16 x 8 patches (128-byte pieces of the rows), 4 = 8 columns on 16 x 16 (64-byte pieces)
-extern "C" void gcge_hip_spmm_star_lanes(int lpp) { g_star_lpp = lpp == 4 ? 4 : 8; }
 static int g_star_xcd = 22;   // 0: workgroups in launch order; 1 / G >= 2: XCD-aware orders (star_block_of): runs of 22 patches (two patch rows of the 171^2 plane) per XCD are 2 % faster than launch order (2.78 against 2.84 ms, profiles/r04_star/16, gpurun_out/r5/09)
 extern "C" void gcge_hip_spmm_star_xcd(int on) { g_star_xcd = on < 0 ? 0 : on; }
-static int g_star_dbg = 0;    // measurement only: 1 no halo loads, 2 no LDS arm reads, 4 no stores, 8 no own-plane loads (results are wrong then)
-extern "C" void gcge_hip_spmm_star_dbg(int bits) { g_star_dbg = bits; }
 extern "C" void gcge_hip_spmm_star_mode(int mode) { g_star_mode = mode; }
-extern "C" int gcge_hip_spmm_star_mode_get(void) { return g_star_mode; }
 
 extern "C" void gcge_hip_star_free(void* sm) {
   StarMat* S = (StarMat*)sm;
@@ -883,6 +869,17 @@ extern "C" int gcge_hip_star_interior(const void* sm, int* ilo, int* ihi) {
   return (g.zmin < g.zs || g.ze < g.zmax) && hi > lo;
 }
 
+// Raise the dynamic-LDS limit of `kernels` to `bytes`, once per device (done[device]: a process may drive several);
+// refused: abort, naming `what` they are for.
+static void star_raise_lds(bool (&done)[64], std::initializer_list<const void*> kernels, unsigned bytes, const char* what) {
+  int dev = 0; (void)hipGetDevice(&dev);
+  if (done[dev & 63]) return;
+  bool ok = true;
+  for (const void* k : kernels) ok &= hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+  if (!ok) { (void)hipGetLastError(); fprintf(stderr, "gcge_hip: %u bytes of LDS refused for %s\n", bytes, what); abort(); }
+  done[dev & 63] = true;
+}
+
 // one launch over the output planes [zlo, zhi); returns the number of partial rows it writes behind `part` (DOT) or 0
 static int star_launch(const StarMat* S, const double* d_x, long ldx, double* d_y, long ldy, int ncols, int zlo, int zhi, double* part, bool count_only,
                        hipStream_t stream) {
@@ -890,20 +887,19 @@ static int star_launch(const StarMat* S, const double* d_x, long ldx, double* d_
   if (nzl <= 0) return 0;
   const StarGeom& g = S->g;
   const bool slab = g.zmin < g.zs || g.ze < g.zmax, iso = S->iso;
-  // 8 lanes per point = 16-column passes on 16 x 8 patches, 4 = 8-column passes on 16 x 16 patches (see the kernel)
   const bool mapped = S->d_map != nullptr;
   // third form (LDS-DMA strips, two planes of prefetch): one coefficient set, every grid point a row, lane offsets of a plane in 32 bits
   const bool third = g_star_form == 3 && iso && !mapped && (double)g.nx * g.ny * (double)ldx * 8.0 < 4.0e9;
   // ... and on a masked grid with a line table (spmm_star3m_kernel: 64-bit lane addresses, no size limit)
   const bool third_m = iso && mapped && S->d_lines != nullptr && ldx < (1L << 31) && (S->masked_slab || (g_star_form == 3 && g_star_masked_third));
-  const int lpp = (third || third_m) ? 8 : (!iso || mapped || g_star_lpp == 4) ? 4 : 8;   // (per-axis coefficients / masked grids: the 8-column form, which needs fewer registers)
+  // lanes per point: 8 = 16-column passes on 16 x 8 patches (the third forms), 4 = 8-column passes on 16 x 16 patches (the second)
+  const int lpp = (third || third_m) ? STAR3_LPP : STAR2_LPP;
   const int ty = 64 / lpp;
   const int ntx = (g.nx + STAR_T - 1) / STAR_T, nty = (g.ny + ty - 1) / ty, npass = (ncols + 2 * lpp - 1) / (2 * lpp);
   // z ranges: ONE where the patches x passes already give every CU two workgroups' worth of work (each range re-reads 12 planes
   // of warm-up: 171^3, 64 columns: 1 / 2 / 3 / 4 ranges = 3.93 / 4.26 / 4.35 / 4.47 ms for the whole product), otherwise enough
   // ranges of at least 24 planes to get there
   int zchunks = (int)std::max(1L, std::min((long)nzl / 24, (2L * 256 + (long)ntx * nty * npass - 1) / ((long)ntx * nty * npass)));
-  if (third_m && g_star_masked_zchunks > 0) zchunks = std::max(1, std::min(g_star_masked_zchunks, nzl / 24));
   const int zlen = (nzl + zchunks - 1) / zchunks;
   zchunks = (nzl + zlen - 1) / zlen;
   const int npatch = third_m ? S->npatch3 : ntx * nty;                 // (masked third form: only the patches that have rows)
@@ -918,49 +914,24 @@ static int star_launch(const StarMat* S, const double* d_x, long ldx, double* d_
   const unsigned char* cv = (const unsigned char*)((uintptr_t)S->d_clean + (uintptr_t)shift);
   const long dlo = g.lo_off - g.mid_off, dhi = g.hi_off - g.mid_off;
 #define STAR_ARGS g.nx, g.ny, g.zs, g.ze, g.zmin, g.zmax, dlo, dhi, S->c, dv, xv, (size_t)ldx, yv, (size_t)ldy, ncols, zlo, zhi, zlen, ntx, part, cv, (const int*)S->d_map, (const int*)S->d_prange
-#define STAR_LAUNCH2(DOT, ISO, SLAB, LPP) hipLaunchKernelGGL((spmm_star2_kernel<DOT, ISO, SLAB, LPP>), grid, dim3(1024), 0, stream, STAR_ARGS)
-#define STAR_DBG(B) case B: hipLaunchKernelGGL((spmm_star2_kernel<false, true, false, 8, B>), grid, dim3(1024), 0, stream, STAR_ARGS); return nb;
-  if (g_star_dbg != 0 && part == nullptr && iso && lpp == 8 && !slab)
-    switch (g_star_dbg) { STAR_DBG(1) STAR_DBG(2) STAR_DBG(8) STAR_DBG(3) STAR_DBG(9) STAR_DBG(16) default: break; }
+#define STAR_LAUNCH2(DOT, ISO, SLAB) hipLaunchKernelGGL((spmm_star2_kernel<DOT, ISO, SLAB>), grid, dim3(1024), 0, stream, STAR_ARGS)
   const bool dot = part != nullptr;
   if (third) {
-    static bool attr_dev[64] = {};                                    // per device: a process may drive several
-    int dev_ = 0; (void)hipGetDevice(&dev_);
-    bool& attr_set = attr_dev[dev_ & 63];
-    if (!attr_set) {
-      bool ok = true;
-      ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_star3_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAR3_LDS) == hipSuccess;
-      ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_star3_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAR3_LDS) == hipSuccess;
-      ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_star3_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAR3_LDS) == hipSuccess;
-      ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_star3_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAR3_LDS) == hipSuccess;
-      if (!ok) { (void)hipGetLastError(); fprintf(stderr, "gcge_hip: %u bytes of LDS refused for the third form of the sweep\n", STAR3_LDS); abort(); }
-      attr_set = true;
-    }
+    static bool lds_set[64] = {};
+    star_raise_lds(lds_set, {reinterpret_cast<const void*>(&spmm_star3_kernel<false, false>), reinterpret_cast<const void*>(&spmm_star3_kernel<false, true>),
+                             reinterpret_cast<const void*>(&spmm_star3_kernel<true, false>), reinterpret_cast<const void*>(&spmm_star3_kernel<true, true>)},
+                   STAR3_LDS, "the third form of the sweep");
 #define STAR_LAUNCH3(DOT, SLAB) hipLaunchKernelGGL((spmm_star3_kernel<DOT, SLAB>), grid, dim3(1024), STAR3_LDS, stream, g.nx, g.ny, g.zs, g.ze, g.zmin, g.zmax, \
                                                    dlo, dhi, S->c, dv, xv, (size_t)ldx, yv, (size_t)ldy, ncols, zlo, zhi, zlen, ntx, part, cv, g_star_xcd)
-    if (g_star_dbg == 32 && !dot && !slab) {
-      static bool probe_dev[64] = {};
-      bool& probe_attr = probe_dev[dev_ & 63];
-      if (!probe_attr) { GCGE_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_star3_kernel<false, false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAR3_LDS)); probe_attr = true; }
-      hipLaunchKernelGGL((spmm_star3_kernel<false, false, true>), grid, dim3(1024), STAR3_LDS, stream, g.nx, g.ny, g.zs, g.ze, g.zmin, g.zmax,
-                         dlo, dhi, S->c, dv, xv, (size_t)ldx, yv, (size_t)ldy, ncols, zlo, zhi, zlen, ntx, part, cv, g_star_xcd);
-      return nb;
-    }
     if (dot) { if (slab) STAR_LAUNCH3(true, true); else STAR_LAUNCH3(true, false); }
     else     { if (slab) STAR_LAUNCH3(false, true); else STAR_LAUNCH3(false, false); }
 #undef STAR_LAUNCH3
     return nb;
   }
   if (third_m) {
-    static bool attr_mdev[64] = {};
-    int dev_ = 0; (void)hipGetDevice(&dev_);
-    bool& attr_m = attr_mdev[dev_ & 63];
-    if (!attr_m) {
-      bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_star3m_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAR3M_LDS) == hipSuccess;
-      ok &= hipFuncSetAttribute(reinterpret_cast<const void*>(&spmm_star3m_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)STAR3M_LDS) == hipSuccess;
-      if (!ok) { (void)hipGetLastError(); fprintf(stderr, "gcge_hip: %u bytes of LDS refused for the third form of the sweep (masked grids)\n", STAR3M_LDS); abort(); }
-      attr_m = true;
-    }
+    static bool lds_set[64] = {};
+    star_raise_lds(lds_set, {reinterpret_cast<const void*>(&spmm_star3m_kernel<false>), reinterpret_cast<const void*>(&spmm_star3m_kernel<true>)},
+                   STAR3M_LDS, "the third form of the sweep (masked grids)");
     if (dot) hipLaunchKernelGGL((spmm_star3m_kernel<true>), grid, dim3(1024), STAR3M_LDS, stream, g.nx, g.ny, g.nz, S->c, (const double*)S->d_diag, d_x, (size_t)ldx, d_y, (size_t)ldy,
                                 ncols, zlo, zhi, zlen, ntx, part, (const unsigned char*)S->d_clean, (const unsigned long long*)S->d_lines, (const int*)S->d_prange3, (const int*)S->d_order3, (int)S->nrows);
     else     hipLaunchKernelGGL((spmm_star3m_kernel<false>), grid, dim3(1024), STAR3M_LDS, stream, g.nx, g.ny, g.nz, S->c, (const double*)S->d_diag, d_x, (size_t)ldx, d_y, (size_t)ldy,
@@ -969,17 +940,15 @@ static int star_launch(const StarMat* S, const double* d_x, long ldx, double* d_
   }
   if (mapped) {          // masked grid: one rank, one coefficient set (checked at upload)
     if (S->masked_slab) { fprintf(stderr, "gcge_hip: a row slab of a masked grid has the third form of the sweep only (leading dimension %ld)\n", ldx); abort(); }
-    if (dot) hipLaunchKernelGGL((spmm_star2_kernel<true, true, false, 4, 0, true>), grid, dim3(1024), 0, stream, STAR_ARGS);
-    else     hipLaunchKernelGGL((spmm_star2_kernel<false, true, false, 4, 0, true>), grid, dim3(1024), 0, stream, STAR_ARGS);
+    if (dot) hipLaunchKernelGGL((spmm_star2_kernel<true, true, false, true>), grid, dim3(1024), 0, stream, STAR_ARGS);
+    else     hipLaunchKernelGGL((spmm_star2_kernel<false, true, false, true>), grid, dim3(1024), 0, stream, STAR_ARGS);
     return nb;
   }
-#define STAR_PICK(ISO, LPP)                                                                                          \
-  do { if (dot) { if (slab) STAR_LAUNCH2(true, ISO, true, LPP); else STAR_LAUNCH2(true, ISO, false, LPP); }          \
-       else     { if (slab) STAR_LAUNCH2(false, ISO, true, LPP); else STAR_LAUNCH2(false, ISO, false, LPP); } } while (0)
-  if (iso) { if (lpp == 8) STAR_PICK(true, 8); else STAR_PICK(true, 4); }
-  else STAR_PICK(false, 4);
+#define STAR_PICK(ISO)                                                                                     \
+  do { if (dot) { if (slab) STAR_LAUNCH2(true, ISO, true); else STAR_LAUNCH2(true, ISO, false); }          \
+       else     { if (slab) STAR_LAUNCH2(false, ISO, true); else STAR_LAUNCH2(false, ISO, false); } } while (0)
+  if (iso) STAR_PICK(true); else STAR_PICK(false);
 #undef STAR_PICK
-#undef STAR_DBG
 #undef STAR_LAUNCH2
 #undef STAR_ARGS
   return nb;
@@ -1020,9 +989,6 @@ extern "C" int gcge_hip_star_spmm_part(const void* sm, const double* d_x, long l
   g_star_part1_rows = 0;
   gcge_hip_reduce_partials(ws, n_all, 2 * ncols, d_dots, stream);
   return (int)hipGetLastError();
-}
-extern "C" int gcge_hip_star_spmm_dots(const void* sm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, double* d_dots, void* stream) {
-  return gcge_hip_star_spmm_part(sm, d_x, ldx, d_y, ldy, ncols, d_dots, stream, 0);
 }
 extern "C" int gcge_hip_star_spmm(const void* sm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, void* stream) {
   return gcge_hip_star_spmm_part(sm, d_x, ldx, d_y, ldy, ncols, nullptr, stream, 0);

@@ -1483,17 +1483,22 @@ def _star_grid_csr(nx, ny, nz, R, seed, natoms, radius):
     return S
 
 
-@pytest.mark.parametrize("case", ["sio2_24", "sio2_20_big_atoms", "box_40x19x15_R3", "box_17x33x14_R6"])
-def test_star_sweep_spmm_vs_oracle(both, case):
+@pytest.mark.parametrize("case,form", [pytest.param("sio2_24", 3, id="sio2_24"), pytest.param("sio2_24", 2, id="sio2_24-form2"),
+                                       pytest.param("sio2_20_big_atoms", 3, id="sio2_20_big_atoms"),
+                                       pytest.param("box_40x19x15_R3", 3, id="box_40x19x15_R3"), pytest.param("box_17x33x14_R6", 3, id="box_17x33x14_R6")])
+def test_star_sweep_spmm_vs_oracle(both, case, form):
     """K1, grid path (spmm_star.hip: rows that are exactly a star stencil leave the CSR arrays and are multiplied by a plane
     sweep — z-neighbours in registers, x / y arms from LDS; the other rows keep every entry and take the block form) against
     the CPU oracle, scipy and the pad-8 kernel on the whole matrix: grids that are no multiple of the 16 x 16 patch, arm
     lengths 3 and 6 with different coefficients per axis, a diagonal of its own in every row, z ranges split over
-    workgroups, widths from 2 to 130 columns (more than one 8-column pass, a last pass of 2), column offsets."""
+    workgroups, widths from 2 to 130 columns (more than one 8-column pass, a last pass of 2), column offsets.  form 3: the third
+    form of the sweep (default); form 2: the second form on a grid with ONE coefficient set, which nothing but the switch and
+    planes too large for the third form select (the box_* cases have per-axis coefficients and take the second form anyway)."""
     from helpers import csr_from_scipy
     hip, ora = both
     g = hip.g
     g.gcge_hip_spmm_dense_mode(1)         # small atoms: rows of >= 24 entries may seed a block
+    g.gcge_hip_spmm_star_form(form)
     keep = None
     try:
         if case == "sio2_24":
@@ -1505,8 +1510,8 @@ def test_star_sweep_spmm_vs_oracle(both, case):
         else:
             A, keep = csr_from_scipy(_star_grid_csr(17, 33, 14, 6, 6, 5, 3.1)); dims = (17, 33, 14, 6)
         mh, mo = hip.matrix(A), ora.matrix(A)
-        form = g.gcge_hip_mat_spmm_form(mh).decode()
-        assert form in ("spmm_star+spmm_dense+spmm_pad8", "spmm_star+spmm_dense+spmm_tile"), form
+        kform = g.gcge_hip_mat_spmm_form(mh).decode()
+        assert kform in ("spmm_star+spmm_dense+spmm_pad8", "spmm_star+spmm_dense+spmm_tile"), kform
         st = (C.c_long * 8)()
         assert g.gcge_hip_mat_star_stats(mh, st) == 1 and tuple(st[:4]) == dims and st[5] == A.nrows and 2 * st[4] >= A.nrows, list(st)
         n = A.nrows
@@ -1544,6 +1549,7 @@ def test_star_sweep_spmm_vs_oracle(both, case):
         _close(a, hip.mv_to_numpy(yh, n, 0, 64), tol=1e-12, what="star rows + blocks vs pad-8 on the whole matrix")
         hip.free_matrix(mh)
     finally:
+        g.gcge_hip_spmm_star_form(3)
         g.gcge_hip_set_spmm_path(0)
         g.gcge_hip_spmm_dense_mode(0)
 

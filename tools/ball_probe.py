@@ -66,23 +66,3 @@ for tag in ("with the geometry", "with the geometry, second form of the sweep", 
 ref = res[("without", 3)]
 for k, v in res.items():
     print("max |%s, path %d - pad-8| / max = %.2e" % (k[0], k[1], float(np.max(np.abs(v - ref)) / np.max(np.abs(ref)))))
-
-# z ranges per patch of the masked third form (balance against the planes of warm-up every range re-reads)
-g.gcge_hip_spmm_star_masked_zchunks.argtypes = [C.c_int]
-g.gcge_hip_spmm_star_infer(1); g.gcge_hip_spmm_star_masked_third(1)
-mA = hip.matrix_grid(A, (G, G, G), box)
-V = hip.mv_from_numpy(mA, X); W = ops.mv_create(m, mA)
-for zc in (1, 2, 3, 4):
-    g.gcge_hip_spmm_star_masked_zchunks(zc)
-    ops.spmm(mA, V, W, (0, 0), (m, m)); hip.sync()
-    g.gcge_hip_profile_enable(1)
-    for _ in range(12):
-        ops.spmm(mA, V, W, (0, 0), (m, m))
-    hip.sync()
-    ms, by = C.c_double(), C.c_double()
-    cnt = g.gcge_hip_profile_spmm(m, C.byref(ms), C.byref(by))
-    g.gcge_hip_profile_enable(0)
-    t = ms.value / cnt
-    err = float(np.max(np.abs(hip.mv_to_numpy(W, A.nrows, 0, 8) - ref)) / np.max(np.abs(ref)))
-    print("third form, %d z range(s) per patch: %.3f ms (%.1f %% of 8 TB/s), max rel diff vs pad-8 %.1e" % (zc, t, by.value / cnt / t * 1e-6 / 80, err), flush=True)
-g.gcge_hip_spmm_star_masked_zchunks(0)

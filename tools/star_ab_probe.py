@@ -11,7 +11,6 @@ m = int(sys.argv[3]) if len(sys.argv) > 3 else 64
 hip = HipBackend(); g = hip.g
 if os.environ.get("GCGE_STAR_XCD") is not None:      # 0: workgroups in launch order (before round 4's XCD-aware order)
     g.gcge_hip_spmm_star_xcd.argtypes = [C.c_int]; g.gcge_hip_spmm_star_xcd(int(os.environ["GCGE_STAR_XCD"]))
-g.gcge_hip_spmm_star_lanes.argtypes = [C.c_int]
 g.gcge_hip_spmm_star_form.argtypes = [C.c_int]
 g.gcge_hip_profile_enable.argtypes = [C.c_int]
 g.gcge_hip_profile_spmm.restype = C.c_long
@@ -29,10 +28,9 @@ if g.gcge_hip_mat_form_stats(mA, st):
 hip.set_random_mode(1, 7)
 ops = hip.ops
 V = ops.mv_create(m, mA); ops.set_random(V, 0, m)
-W = {2: ops.mv_create(m, mA), 3: ops.mv_create(m, mA), 4: ops.mv_create(m, mA)}
-for which in (2, 3, 4, 2, 3, 4):
-    g.gcge_hip_spmm_star_lanes(4 if which == 2 else 8)           # 2: 8-column passes on 16 x 16 patches; 3: 16-column passes on 16 x 8 patches
-    g.gcge_hip_spmm_star_form(3 if which == 4 else 2)            # 4: third form (LDS-DMA strips)
+W = {2: ops.mv_create(m, mA), 3: ops.mv_create(m, mA)}
+for which in (2, 3, 2, 3):
+    g.gcge_hip_spmm_star_form(which)      # 2: 8-column passes on 16 x 16 patches, strips through registers; 3: 16-column passes on 16 x 8 patches, LDS-DMA strips
     ops.spmm(mA, V, W[which], (0, 0), (m, m)); hip.sync()
     g.gcge_hip_profile_enable(1)
     for _ in range(6):
@@ -51,9 +49,7 @@ for which in (2, 3, 4, 2, 3, 4):
     g.gcge_hip_profile_enable(0)
     print("form %d: product %.3f ms = %.1f %% of 8 TB/s on the CSR bytes; with column sums %.3f ms" % (which, t, by.value / cnt / t * 1e-6 / 80, ms2.value / cnt2), flush=True)
 a = hip.mv_to_numpy(W[2], A.nrows, 0, m); b = hip.mv_to_numpy(W[3], A.nrows, 0, m)
-print("max |16-column form - 8-column form| / max =", float(np.max(np.abs(a - b)) / np.max(np.abs(a))))
-b = hip.mv_to_numpy(W[4], A.nrows, 0, m)
-print("max |third form - 8-column form| / max =", float(np.max(np.abs(a - b)) / np.max(np.abs(a))))
+print("max |third form - second form| / max =", float(np.max(np.abs(a - b)) / np.max(np.abs(a))))
 g.gcge_hip_spmm_star_form(2)
 g.gcge_hip_set_spmm_path.argtypes = [C.c_int]
 g.gcge_hip_set_spmm_path(3)
