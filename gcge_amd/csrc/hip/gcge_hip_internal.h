@@ -85,7 +85,18 @@ struct GCGE_HIP_MAT_ {
   // MultiGridCreate coarsens by 2 x 2 x 2 cells.  geom_kind 0: none, 1: named by the caller (gcge_hip_mat_create_grid), 2: recovered
   // at upload (the grid form of spmm_star.hip was built on it); row r is box point h_box[r] = x + nx (y + ny z) of geom_dims, strictly ascending
   int geom_kind; int geom_dims[3]; int* h_box; int* d_box;
+  // value maps of the star split (mat_values_forms.hip; NULL: none kept — gcge_hip_mat_keep_value_maps was off at creation, or no grid
+  // form); those of the block form live behind star_rem / dense
+  struct GcgeStarMaps* star_maps;
 };
+// mat_values_forms.hip: the device copy of a split's maps (H->keep_maps), and the two halves of an update of a star / dense handle
+extern "C" struct GcgeStarMaps* gcge_hip_star_maps_create(const void* star_host, long nnz);
+extern "C" void gcge_hip_star_maps_free(struct GcgeStarMaps* M);
+extern "C" long gcge_hip_star_maps_bytes(const struct GcgeStarMaps* M);
+extern "C" int gcge_hip_mat_has_value_form(const struct GCGE_HIP_MAT_* A);
+extern "C" int gcge_hip_mat_holds_value_maps(const struct GCGE_HIP_MAT_* A);                            // by their presence, whatever their size
+extern "C" int gcge_hip_mat_forms_check(struct GCGE_HIP_MAT_* A, const double* d_val, long* d2h);      // 0: go on and write, 1: declined
+extern "C" void gcge_hip_mat_forms_write(struct GCGE_HIP_MAT_* A, const double* d_val);
 // The masked grid a matrix lives on, as the upload hands it to the split of spmm_star.hip (NULL: none): box[i] = x + nx (y + ny z) in an nx x ny x nz
 // box.  cols false: box[r] for the nbox = nrows rows of a whole matrix; cols true: box[c] for the nbox local columns of a row slab, own rows, then halo rows.
 struct GcgeGridGeom { int nx, ny, nz; const int* box; int nbox; bool cols; };
@@ -226,9 +237,14 @@ int gcge_hip_spmm_tile_mode_get(void);
 void gcge_hip_tile_stats(const void* tm, long* ntiles, long* ov_nnz, double* xrows_per_row, double* ell_per_nnz, int* brick, long* strides);
 int gcge_hip_tile_spmm(const void* tm, const double* d_x, long ldx, double* d_y, long ldy, int ncols, void* stream);
 // spmm_dense.hip
-void* gcge_hip_dense_build(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val);
-void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed);
+void* gcge_hip_dense_build(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, int keep_maps);
+void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed,
+                                int keep_maps);
 void gcge_hip_dense_free(void* dm);
+// value maps of a block form (value_maps.h; 0: it holds none): bytes of maps; one map entry per slot of the block values and of the pad-8
+// remainder, indices into the nsrc values the form was built from
+long gcge_hip_dense_value_maps(const void* dm, const int** d_vmap, double** d_vals, long* nvals, const int** d_pmap, double** d_pval, long* npval,
+                               long* nsrc);
 int gcge_hip_dense_remainder_is_tiled(const void* dm);
 const void* gcge_hip_dense_remainder_tile(const void* dm);
 void gcge_hip_dense_stats(const void* dm, long* nblocks, long* items, long* dense_nnz, long* dense_entries, long* rem_nnz);
@@ -236,6 +252,7 @@ int gcge_hip_dense_spmm(const void* dm, const double* d_x, long ldx, double* d_y
 const int* gcge_hip_dense_row_list(const void* dm, int* nlisted);
 // spmm_star.hip (gcge_hip_star_build: star_split.h)
 void gcge_hip_star_free(void* sm);
+double* gcge_hip_star_diag(void* sm);
 void gcge_hip_star_stats(const void* sm, long* out);
 int gcge_hip_star_masked_form(const void* sm);
 int gcge_hip_star_interior(const void* sm, int* ilo, int* ihi);

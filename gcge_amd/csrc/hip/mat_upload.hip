@@ -161,6 +161,17 @@ extern "C" int gcge_hip_mat_geometry(const GCGE_HIP_MAT* A, int* dims, int* box_
 // global rows behind the halo columns, ascending — with it (and nglobal) a slab of a grid matrix cut on plane boundaries keeps the
 // plane sweep of spmm_star.hip: the planes below and above the slab are then found among the halo rows.  geom (may be NULL): the
 // masked grid the caller names; one named for a whole matrix (cols false) also means that none is recovered for the handle.
+// Value maps (value_maps.h, mat_values_forms.hip): with the switch on when a matrix is created, a handle that takes the star or the dense form
+// also keeps, on the device, where each of its stored values came from — what gcge_hip_mat_update_values_device needs to give such a
+// handle new values in place.  The forms and every stored array are those of the switch off; the maps cost about 4 bytes per block slot
+// and remainder slot plus 1 byte per CSR entry under a star (gcge_hip_mat_value_maps).  Default 0.
+static int g_keep_value_maps = 0;
+extern "C" int gcge_hip_mat_keep_value_maps(int on) { const int was = g_keep_value_maps; g_keep_value_maps = on != 0; return was; }   // returns the setting it replaces
+extern "C" long gcge_hip_mat_value_maps(const GCGE_HIP_MAT* A) {
+  if (A == nullptr || !gcge_hip_mat_holds_value_maps(A)) return 0;
+  const void* DM = A->star != nullptr ? A->star_rem : A->dense;
+  return gcge_hip_star_maps_bytes(A->star_maps) + gcge_hip_dense_value_maps(DM, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
 static double upload_now() { struct timespec ts; clock_gettime(CLOCK_MONOTONIC, &ts); return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec; }
 static GCGE_HIP_MAT* mat_create_local(int nrows, int ncols_local, int nglobal, int row_begin, const int* rowptr, const int* colidx, const double* val,
                                       const int* ghost_global, const GcgeGridGeom* geom) {
@@ -219,12 +230,14 @@ static GCGE_HIP_MAT* mat_create_local(int nrows, int ncols_local, int nglobal, i
   // arrays for the plane sweep of spmm_star.hip, the others (rows inside dense blocks, ...) keep every entry and take the block form
   phase("pattern search");
   A->star = nullptr; A->star_rem = nullptr;
+  // (maps only where an update can use them: a whole matrix on one rank — a row slab declines every update)
+  const int keep_maps = g_keep_value_maps && row_begin == 0 && ncols_local == nrows && (nglobal <= 0 || nglobal == nrows);
   if (A->d_pid == nullptr) {
     // (the sweep needs to know where the slab sits in the grid: a whole matrix, or a slab with its global size and halo rows named)
     const bool whole = row_begin == 0 && ncols_local == nrows && (nglobal <= 0 || nglobal == nrows);
     const bool slab = !whole && nglobal > 0 && (ncols_local == nrows || ghost_global != nullptr);
     gcge::StarHost* H = nullptr;                    // the split behind S: ours
-    void* S = (whole || slab) ? gcge_hip_star_build(nrows, ncols_local, row_begin, whole ? nrows : nglobal, ghost_global, rowptr, colidx, val, geom, &H) : nullptr;
+    void* S = (whole || slab) ? gcge_hip_star_build(nrows, ncols_local, row_begin, whole ? nrows : nglobal, ghost_global, rowptr, colidx, val, geom, &H, keep_maps) : nullptr;
     phase("star split");
     if (S != nullptr && whole && (geom == nullptr || geom->cols) && gcge_hip_star_masked_form(S) != 0) {
       // a masked grid nobody named for the whole matrix: what the build recovered from the rows goes on the handle, whatever becomes of the
@@ -236,14 +249,15 @@ static GCGE_HIP_MAT* mat_create_local(int nrows, int ncols_local, int nglobal, i
     }
     if (S != nullptr) {
       void* D = gcge_hip_dense_build_rows(nrows, ncols_local, H->rem_rowptr.data(), H->rem_col.data(), H->rem_val.data(),
-                                          (const unsigned char*)H->clean.data());   // (its pad-8 part lists the other rows only)
+                                          (const unsigned char*)H->clean.data(), keep_maps);   // (its pad-8 part lists the other rows only)
       if (D != nullptr) { A->star = S; A->star_rem = D; } else gcge_hip_star_free(S);   // (no blocks among the other rows: the forms below)
+      if (D != nullptr && keep_maps) A->star_maps = gcge_hip_star_maps_create(H, A->nnz);
       delete H;
       phase("blocks + listed rows");
     }
   }
   // matrices without a pattern form: dense row blocks (supernodes) on MFMA + remainder CSR, where such blocks exist
-  A->dense = (A->d_pid == nullptr && A->star == nullptr) ? gcge_hip_dense_build(nrows, ncols_local, rowptr, colidx, val) : nullptr;
+  A->dense = (A->d_pid == nullptr && A->star == nullptr) ? gcge_hip_dense_build(nrows, ncols_local, rowptr, colidx, val, keep_maps) : nullptr;
   // ... and, where switched on, row tiles with LDS-staged X rows
   A->tile = ((A->d_pid == nullptr && A->star == nullptr) || gcge_hip_spmm_tile_mode_get() == 2) ? gcge_hip_tile_build(nrows, ncols_local, rowptr, colidx, val) : nullptr;
   // interior rows: none of them references a halo column (slabs: everything but the first and the last plane)
@@ -448,6 +462,7 @@ extern "C" void gcge_hip_mat_destroy(GCGE_HIP_MAT* A) {
   if (A->dense != nullptr) gcge_hip_dense_free(A->dense);
   if (A->star_rem != nullptr) gcge_hip_dense_free(A->star_rem);
   if (A->star != nullptr) gcge_hip_star_free(A->star);
+  if (A->star_maps != nullptr) gcge_hip_star_maps_free(A->star_maps);
   if (A->native_halo != nullptr) gcge_hip_halo_native_free(A);   // RCCL plan + the exchange buffers it owns (rccl_comm.hip)
   free(A->h_ghost_global); free(A->h_part);
   free(A->h_box); if (A->d_box) hipFree(A->d_box);

@@ -14,6 +14,8 @@
 // count of present table slots against its length (an explicitly stored +-0.0), every entry placed by the slot rule, and for a value
 // table the row's new values against those of the first row of its class, entry by entry as bits (rows of one class carry the same
 // offsets in the same order, so equal entries are equal slots), none of them +-0.0.  One flag word comes back.
+// A handle with a star or a dense form that kept its value maps (gcge_hip_mat_keep_value_maps) takes the check and the write of
+// mat_values_forms.hip around k_mv_values instead; without maps it is declined from the handle alone, as every tile form is.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -133,8 +135,10 @@ __global__ void k_mv_table(int npat, int lt, int chain_layout, const int* __rest
 
 extern "C" int gcge_hip_mat_update_values_device(GCGE_HIP_MAT* A, long nnz, const double* d_val) {
   if (A == nullptr || d_val == nullptr || nnz != A->nnz) { g_mu_stats[4] += 1; return -1; }
-  // declined from the handle alone: forms with a value layout of their own, rectangular handles, row slabs, re-ordered handles
-  if (A->star != nullptr || A->star_rem != nullptr || A->dense != nullptr || A->tile != nullptr || A->rect_ncols > 0 || A->nghost > 0 ||
+  // declined from the handle alone: tile forms, star / dense forms without value maps (gcge_hip_mat_forms_check), rectangular handles,
+  // row slabs, re-ordered handles
+  const bool forms = gcge_hip_mat_has_value_form(A) != 0;
+  if (A->tile != nullptr || A->rect_ncols > 0 || A->nghost > 0 ||
       A->row_begin != 0 || (A->nglobal > 0 && A->nglobal != A->nrows) || A->exchange != nullptr || A->exchange_begin != nullptr ||
       A->native_halo != nullptr || A->d_send_rows != nullptr || real_perm(A->perm) != nullptr || A->d_orp == nullptr ||
       (A->d_pid != nullptr && (A->d_tab == nullptr || A->pat_lt < 1 || A->pat_lt > 16 || A->npat < 1 || (A->d_rowval != nullptr && A->pat_lt > 8)))) {
@@ -143,6 +147,15 @@ extern "C" int gcge_hip_mat_update_values_device(GCGE_HIP_MAT* A, long nnz, cons
   }
   hipStream_t st = (hipStream_t)gcge_hip_stream();
   const int n = A->nrows, lt = A->pat_lt, npat = A->npat;
+  if (forms) {
+    if (A->d_pid != nullptr || gcge_hip_mat_forms_check(A, d_val, &g_mu_stats[5]) != 0) { g_mu_stats[3] += 1; return 1; }
+    if (n > 0) k_mv_values<<<mv_blocks(8L * n, MV_BS), MV_BS, 0, st>>>(n, A->d_rowptr, A->d_orp, d_val, A->d_val, A->d_pval);
+    gcge_hip_mat_forms_write(A, d_val);
+    GCGE_HIP_CHECK(hipGetLastError());
+    GCGE_HIP_CHECK(hipStreamSynchronize(st));
+    g_mu_stats[0] += 1;
+    return 0;
+  }
   const int chain_layout = A->pat_span2 <= -1 ? 1 : 0;
   const GcgePatEntry* tab = (const GcgePatEntry*)A->d_tab;
   const bool value_table = A->d_pid != nullptr && A->d_rowval == nullptr;

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <vector>
 #include "gcge_hip_internal.h"
+#include "value_maps.h"
 
 extern "C" int gcge_hip_pad8_spmm(int nrows, const int* d_orp, const int* d_pcol, const double* d_pval, const double* d_x,
                                   long ldx, double* d_y, long ldy, int ncols, void* stream);
@@ -54,12 +55,15 @@ struct DenseMat {
   int* d_padlist; int npad;
   int nlayers; int layer_item[9];                        // blocks of layer l: items [layer_item[l], layer_item[l + 1]); one launch per layer, in order                              // ... of them the rows whose remainder is NOT empty: what the pad-8 kernel walks (ADDING to Y)
   void* rem_tile;                                        // remainder in tile form (spmm_tile.hip) when that path is switched on
+  int* d_vmap; int* d_pmap; long nsrc;                   // value maps (value_maps.h; NULL: not kept): per slot of d_vals / d_pval the index into the nsrc values the form was built from
 };
 
 struct DenseHost {
   std::vector<DenseSn> sn; std::vector<DenseItem> items; std::vector<int> rows, cols; std::vector<double> vals;
   std::vector<int> rem_rowptr, rem_col; std::vector<double> rem_val;
   long dense_nnz = 0;
+  bool maps = false;                                     // value maps wanted (value_maps.h): per slot of vals / per remainder entry the index into the
+  std::vector<int> val_src, rem_src;                     // ... builder's input values (through `prov` of dense_build_host: into the FIRST layer's input)
 };
 
 // One wave per 32 rows of a block and pass of up to 64 columns.  (Two consecutive 32-row blocks per wave — 16 MFMAs per X row
@@ -160,7 +164,7 @@ __global__ __launch_bounds__(256, FULL ? 3 : 2) void spmm_dense_kernel(
 
 // ------------------------------------------------------------------------------------------------ detection (host)
 static bool dense_build_host(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, int min_len,
-                             DenseHost* H, int min_rows = 16) {
+                             DenseHost* H, int min_rows = 16, const int* prov = nullptr) {   // prov (maps only): where val[p] came from, NULL: p itself
   std::vector<int> seeds;
   for (int r = 0; r < nrows; ++r) if (rowptr[r + 1] - rowptr[r] >= min_len) seeds.push_back(r);
   if (seeds.empty()) return false;
@@ -209,7 +213,9 @@ static bool dense_build_host(int nrows, int ncols_local, const int* rowptr, cons
     for (int k = 0; k < 4 * ng; ++k) H->cols.push_back(k < (int)C.size() ? C[k] : C[0]);   // padding: a valid column, zero values
     for (size_t k = 0; k < C.size(); ++k) pos[C[k]] = (int)k;
     H->vals.resize(H->vals.size() + (size_t)nb * ng * 128, 0.0);
+    if (H->maps) H->val_src.resize(H->vals.size(), -1);
     double* D = H->vals.data() + S.val_off;
+    int* DS = H->maps ? H->val_src.data() + S.val_off : nullptr;
     for (size_t ir = 0; ir < R.size(); ++ir) {
       const int r = R[ir]; assigned[r] = sn;
       const size_t b = ir / 32, f = (ir % 32) / 16, i = ir % 16;
@@ -218,6 +224,7 @@ static bool dense_build_host(int nrows, int ncols_local, const int* rowptr, cons
         if (stamp[c] != id) continue;
         const size_t k = (size_t)pos[c], g = k / 4, kq = k % 4;
         D[((b * ng + g) * 64 + kq * 16 + i) * 2 + f] = val[p];
+        if (DS != nullptr) DS[((b * ng + g) * 64 + kq * 16 + i) * 2 + f] = prov != nullptr ? prov[p] : p;
         ++H->dense_nnz;
       }
     }
@@ -243,9 +250,11 @@ static bool dense_build_host(int nrows, int ncols_local, const int* rowptr, cons
     H->rem_rowptr[r + 1] = H->rem_rowptr[r] + c;
   }
   H->rem_col.resize((size_t)H->rem_rowptr[nrows]); H->rem_val.resize((size_t)H->rem_rowptr[nrows]);
+  if (H->maps) H->rem_src.resize((size_t)H->rem_rowptr[nrows]);
   for (int r = 0; r < nrows; ++r) {
     int o = H->rem_rowptr[r];
-    for (int p = rowptr[r]; p < rowptr[r + 1]; ++p) if (!in_block[p]) { H->rem_col[o] = colidx[p]; H->rem_val[o] = val[p]; ++o; }
+    for (int p = rowptr[r]; p < rowptr[r + 1]; ++p)
+      if (!in_block[p]) { H->rem_col[o] = colidx[p]; H->rem_val[o] = val[p]; if (H->maps) H->rem_src[o] = prov != nullptr ? prov[p] : p; ++o; }
   }
   return true;
 }
@@ -317,6 +326,8 @@ extern "C" void gcge_hip_dense_free(void* dm) {
   if (!D) return;
   hipFree(D->d_sn); hipFree(D->d_items); hipFree(D->d_rows); hipFree(D->d_cols); hipFree(D->d_vals);
   hipFree(D->d_orp); hipFree(D->d_pcol); hipFree(D->d_pval);
+  if (D->d_vmap) hipFree(D->d_vmap);
+  if (D->d_pmap) hipFree(D->d_pmap);
   if (D->d_rowmap) hipFree(D->d_rowmap);
   if (D->d_padlist) hipFree(D->d_padlist);
   if (D->rem_tile) gcge_hip_tile_free(D->rem_tile);
@@ -331,50 +342,94 @@ static T* to_device(const std::vector<T>& v) {
   return d;
 }
 
-// NULL: no block worth forming (the matrix keeps the generic kernels alone)
-extern "C" void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed);
-extern "C" void* gcge_hip_dense_build(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val) {
-  return gcge_hip_dense_build_rows(nrows, ncols_local, rowptr, colidx, val, nullptr);
-}
-// not_listed != NULL: rows with not_listed[r] != 0 are EMPTY in these arrays and belong to another kernel (spmm_star.hip): the
-// pad-8 part of the remainder then walks a list of the other rows only and leaves those rows of Y alone
-extern "C" void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed) {
-  if (g_dense_mode < 0 || nrows <= 0) return nullptr;
+// Host half of gcge_hip_dense_build_rows, part 1: blocks, layers and what is left (H), the items of every layer.  false: no block worth forming.
+static bool dense_layers_host(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed,
+                              bool maps, DenseHost& H, std::vector<int>& layer_item) {
+  if (g_dense_mode < 0 || nrows <= 0) return false;
   if (const char* e = getenv("GCGE_DENSE_LAYERS")) g_dense_layers = atoi(e) >= 1 ? atoi(e) : g_dense_layers;   // (measurements / bisection)
   const int min_len = g_dense_mode == 1 ? 24 : g_dense_min_len;
-  DenseHost H;
   const long nnz = rowptr[nrows];
+  H.maps = maps;
   bool blocks = dense_build_host(nrows, ncols_local, rowptr, colidx, val, min_len, &H);
-  if (blocks && not_listed == nullptr && g_dense_mode == 0 && 10 * H.dense_nnz < nnz) return nullptr;   // blocks hold less than a tenth of the matrix: not worth a second launch
+  if (blocks && not_listed == nullptr && g_dense_mode == 0 && 10 * H.dense_nnz < nnz) return false;   // blocks hold less than a tenth of the matrix: not worth a second launch
   if (!blocks) {
-    if (not_listed == nullptr) return nullptr;
+    if (not_listed == nullptr) return false;
     // the rows a sweep leaves, and no block among them (a star with a few irregular rows, or none): all of it is the listed remainder
     H = DenseHost();
+    H.maps = maps;
     H.rem_rowptr.assign(rowptr, rowptr + nrows + 1); H.rem_col.assign(colidx, colidx + nnz); H.rem_val.assign(val, val + nnz);
+    if (maps) { H.rem_src.resize((size_t)nnz); for (long k = 0; k < nnz; ++k) H.rem_src[(size_t)k] = (int)k; }
   }
   // LAYERS.  No row lies in two blocks of one launch (that is what makes Y[R] += block safe without atomics), so a row inside two
   // overlapping atom balls leaves the entries of the second ball to the remainder: a few rows with hundreds of entries each, and the
   // pad-8 list walks a row with ONE wave — on the SiO2-like matrix of config 5 the list's 4.9e6 non-zeros took 0.43 ms, all of it the
   // tail of its longest rows.  The remainder is therefore searched again (shorter seeds, smaller row sets) and what it yields becomes a
   // second, third ... launch of the block kernel, ordered behind the first by the stream: one owner per row and launch, still bit-reproducible.
-  std::vector<int> layer_item = {0, (int)H.items.size()};
+  layer_item = {0, (int)H.items.size()};
   // (only under the sweep: there the remainder holds nothing but what differs from the star; on a whole matrix every stencil row of
   //  >= 32 entries would be tried as a seed again in every layer — 20 s of upload at 2·10⁶ rows for nothing)
   if (blocks && g_dense_layers > 1 && not_listed != nullptr) {
     for (int l = 1; l < g_dense_layers && l < 8; ++l) {
       DenseHost H2;
-      if (!dense_build_host(nrows, ncols_local, H.rem_rowptr.data(), H.rem_col.data(), H.rem_val.data(), g_dense_layer_len, &H2, 8)) break;
+      H2.maps = maps;                                       // (the maps compose: a later layer's sources are the previous remainder's)
+      if (!dense_build_host(nrows, ncols_local, H.rem_rowptr.data(), H.rem_col.data(), H.rem_val.data(), g_dense_layer_len, &H2, 8,
+                            maps ? H.rem_src.data() : nullptr)) break;
       const int sn0 = (int)H.sn.size(), row0 = (int)H.rows.size(), col0 = (int)H.cols.size(); const long val0 = (long)H.vals.size();
       for (DenseSn S : H2.sn) { S.row_off += row0; S.col_off += col0; S.val_off += val0; H.sn.push_back(S); }
       for (DenseItem it : H2.items) { it.sn += sn0; H.items.push_back(it); }
       H.rows.insert(H.rows.end(), H2.rows.begin(), H2.rows.end());
       H.cols.insert(H.cols.end(), H2.cols.begin(), H2.cols.end());
       H.vals.insert(H.vals.end(), H2.vals.begin(), H2.vals.end());
+      if (maps) H.val_src.insert(H.val_src.end(), H2.val_src.begin(), H2.val_src.end());
       H.dense_nnz += H2.dense_nnz;
-      H.rem_rowptr.swap(H2.rem_rowptr); H.rem_col.swap(H2.rem_col); H.rem_val.swap(H2.rem_val);
+      H.rem_rowptr.swap(H2.rem_rowptr); H.rem_col.swap(H2.rem_col); H.rem_val.swap(H2.rem_val); H.rem_src.swap(H2.rem_src);
       layer_item.push_back((int)H.items.size());
     }
   }
+  return true;
+}
+// ... part 2: the remainder in pad-8 form: every row padded to a multiple of 8 entries with (own column, 0.0)
+// With a list the remainder is ADDED to what the sweep wrote: rows whose remainder is empty (every entry inside their block: most
+// rows of a block) are not walked at all — each would cost a read and a write of its Y row for nothing; `all` (every row that is
+// not `not_listed`) stays the list of the column sums over those rows (gcge_hip_dense_row_list).
+struct DensePad8Host { std::vector<int> list, all, orp, pc, pmap; std::vector<double> pv; size_t noct = 0; };
+static void dense_pad8_host(int nrows, const unsigned char* not_listed, const DenseHost& H, DensePad8Host& P) {
+  std::vector<int>& list = P.list; std::vector<int>& all = P.all;
+  for (int r = 0; r < nrows; ++r)
+    if (not_listed == nullptr) list.push_back(r);
+    else if (!not_listed[r]) { all.push_back(r); if (H.rem_rowptr[r + 1] > H.rem_rowptr[r]) list.push_back(r); }
+  const int nl = (int)list.size();
+  std::vector<int>& orp = P.orp;
+  orp.resize((size_t)nl + 1);
+  size_t noct = 0;
+  for (int i = 0; i < nl; ++i) { const int r = list[i]; orp[i] = (int)noct; noct += ((size_t)(H.rem_rowptr[r + 1] - H.rem_rowptr[r]) + 7) / 8; }
+  orp[nl] = (int)noct;
+  P.noct = noct;
+  std::vector<int>& pc = P.pc; std::vector<double>& pv = P.pv;
+  pc.resize(noct * 8); pv.resize(noct * 8);
+  if (H.maps) P.pmap.assign(noct * 8, -1);
+  for (int i = 0; i < nl; ++i) {
+    const int r = list[i];
+    size_t o = (size_t)orp[i] * 8;
+    for (int k = H.rem_rowptr[r]; k < H.rem_rowptr[r + 1]; ++k, ++o) { pc[o] = H.rem_col[k]; pv[o] = H.rem_val[k]; if (H.maps) P.pmap[o] = H.rem_src[k]; }
+    for (; o < (size_t)orp[i + 1] * 8; ++o) { pc[o] = r; pv[o] = 0.0; }
+  }
+}
+
+// NULL: no block worth forming (the matrix keeps the generic kernels alone)
+extern "C" void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed,
+                                           int keep_maps);
+extern "C" void* gcge_hip_dense_build(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, int keep_maps) {
+  return gcge_hip_dense_build_rows(nrows, ncols_local, rowptr, colidx, val, nullptr, keep_maps);
+}
+// not_listed != NULL: rows with not_listed[r] != 0 are EMPTY in these arrays and belong to another kernel (spmm_star.hip): the
+// pad-8 part of the remainder then walks a list of the other rows only and leaves those rows of Y alone.  keep_maps: the form keeps,
+// on the device, where every stored value came from in `val` (value_maps.h) — the stored arrays are the same with and without
+extern "C" void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed,
+                                           int keep_maps) {
+  DenseHost H;
+  std::vector<int> layer_item;
+  if (!dense_layers_host(nrows, ncols_local, rowptr, colidx, val, not_listed, keep_maps != 0, H, layer_item)) return nullptr;
   DenseMat* D = new DenseMat();
   D->nlayers = (int)layer_item.size() - 1;
   for (int l = 0; l <= D->nlayers; ++l) D->layer_item[l] = layer_item[l];
@@ -383,35 +438,71 @@ extern "C" void* gcge_hip_dense_build_rows(int nrows, int ncols_local, const int
   D->d_sn = to_device(H.sn); D->d_items = to_device(H.items); D->d_rows = to_device(H.rows); D->d_cols = to_device(H.cols);
   D->d_vals = to_device(H.vals);
   std::vector<double>().swap(H.vals);
-  // remainder in pad-8 form: every row padded to a multiple of 8 entries with (own column, 0.0)
-  // With a list the remainder is ADDED to what the sweep wrote: rows whose remainder is empty (every entry inside their block: most
-  // rows of a block) are not walked at all — each would cost a read and a write of its Y row for nothing; `all` (every row that is
-  // not `not_listed`) stays the list of the column sums over those rows (gcge_hip_dense_row_list).
-  std::vector<int> list, all;
-  for (int r = 0; r < nrows; ++r)
-    if (not_listed == nullptr) list.push_back(r);
-    else if (!not_listed[r]) { all.push_back(r); if (H.rem_rowptr[r + 1] > H.rem_rowptr[r]) list.push_back(r); }
-  const int nl = (int)list.size();
-  std::vector<int> orp((size_t)nl + 1);
-  size_t noct = 0;
-  for (int i = 0; i < nl; ++i) { const int r = list[i]; orp[i] = (int)noct; noct += ((size_t)(H.rem_rowptr[r + 1] - H.rem_rowptr[r]) + 7) / 8; }
-  orp[nl] = (int)noct;
-  std::vector<int> pc(noct * 8); std::vector<double> pv(noct * 8);
-  for (int i = 0; i < nl; ++i) {
-    const int r = list[i];
-    size_t o = (size_t)orp[i] * 8;
-    for (int k = H.rem_rowptr[r]; k < H.rem_rowptr[r + 1]; ++k, ++o) { pc[o] = H.rem_col[k]; pv[o] = H.rem_val[k]; }
-    for (; o < (size_t)orp[i + 1] * 8; ++o) { pc[o] = r; pv[o] = 0.0; }
-  }
-  D->noct = (long)noct;
-  D->d_orp = to_device(orp); D->d_pcol = to_device(pc); D->d_pval = to_device(pv);
-  D->nlisted = not_listed != nullptr ? (int)all.size() : nl;
-  D->d_rowmap = not_listed != nullptr ? to_device(all) : nullptr;
+  D->d_vmap = nullptr; D->d_pmap = nullptr; D->nsrc = rowptr[nrows];
+  if (H.maps) { D->d_vmap = to_device(H.val_src); std::vector<int>().swap(H.val_src); }
+  DensePad8Host P;
+  dense_pad8_host(nrows, not_listed, H, P);
+  const int nl = (int)P.list.size();
+  D->noct = (long)P.noct;
+  D->d_orp = to_device(P.orp); D->d_pcol = to_device(P.pc); D->d_pval = to_device(P.pv);
+  if (H.maps) D->d_pmap = to_device(P.pmap);
+  D->nlisted = not_listed != nullptr ? (int)P.all.size() : nl;
+  D->d_rowmap = not_listed != nullptr ? to_device(P.all) : nullptr;
   D->npad = nl;
-  D->d_padlist = not_listed != nullptr ? to_device(list) : nullptr;
+  D->d_padlist = not_listed != nullptr ? to_device(P.list) : nullptr;
   // (a listed remainder stays with the pad-8 kernel: a tile writes all of its rows)
   D->rem_tile = not_listed != nullptr ? nullptr : gcge_hip_tile_build_for(nrows, ncols_local, H.rem_rowptr.data(), H.rem_col.data(), H.rem_val.data(), 1);   // NULL: pad-8
   return D;
+}
+extern "C" long gcge_hip_dense_value_maps(const void* dm, const int** d_vmap, double** d_vals, long* nvals, const int** d_pmap, double** d_pval, long* npval,
+                                          long* nsrc) {
+  const DenseMat* D = (const DenseMat*)dm;
+  if (D == nullptr || D->d_vmap == nullptr || D->d_pmap == nullptr) return 0;
+  if (d_vmap) *d_vmap = D->d_vmap;
+  if (d_vals) *d_vals = D->d_vals;
+  if (nvals) *nvals = D->dense_entries;
+  if (d_pmap) *d_pmap = D->d_pmap;
+  if (d_pval) *d_pval = D->d_pval;
+  if (npval) *npval = D->noct * 8;
+  if (nsrc) *nsrc = D->nsrc;
+  return (long)sizeof(int) * (D->dense_entries + D->noct * 8);
+}
+// Host only (the self-check of the value maps, mat_values_forms.hip): the form built from (rowptr, colidx, val) with its maps, the maps
+// replayed on `src` (one value per entry of `val`), every stored value appended to its row of `got` as (column, value) — blocks (zeros
+// included only where a map entry names a source), then the pad-8 remainder.  -1: no form; otherwise map entries outside [-1, nnz).
+// out[0] layers of blocks (0: no block at all), out[1] bytes of maps.
+long gcge_dense_maps_expand(int nrows, int ncols_local, const int* rowptr, const int* colidx, const double* val, const unsigned char* not_listed,
+                            const double* src, std::vector<std::vector<std::pair<int, double>>>& got, long* out) {
+  DenseHost H;
+  std::vector<int> layer_item;
+  if (!dense_layers_host(nrows, ncols_local, rowptr, colidx, val, not_listed, true, H, layer_item)) return -1;
+  const long nnz = rowptr[nrows];
+  long bad = 0;
+  if (H.val_src.size() != H.vals.size()) return -1;
+  for (size_t s = 0; s < H.sn.size(); ++s) {
+    const DenseSn& S = H.sn[s];
+    for (int ir = 0; ir < S.nrows; ++ir) {
+      const int r = H.rows[(size_t)S.row_off + ir];
+      const size_t b = ir / 32, f = (ir % 32) / 16, i = ir % 16;
+      for (int k = 0; k < 4 * S.ng; ++k) {
+        const size_t slot = (size_t)S.val_off + ((b * S.ng + k / 4) * 64 + (k % 4) * 16 + i) * 2 + f;
+        const int m = H.val_src[slot];
+        if (m < -1 || m >= nnz) { ++bad; continue; }
+        if (m >= 0) got[(size_t)r].emplace_back(H.cols[(size_t)S.col_off + k], gcge_vm_gather(src, m));
+      }
+    }
+  }
+  DensePad8Host P;
+  dense_pad8_host(nrows, not_listed, H, P);
+  if (P.pmap.size() != P.pv.size()) return -1;
+  for (size_t i = 0; i < P.list.size(); ++i)
+    for (size_t o = (size_t)P.orp[i] * 8; o < (size_t)P.orp[i + 1] * 8; ++o) {
+      const int m = P.pmap[o];
+      if (m < -1 || m >= nnz) { ++bad; continue; }
+      if (m >= 0) got[(size_t)P.list[i]].emplace_back(P.pc[o], gcge_vm_gather(src, m));
+    }
+  if (out) { out[0] = H.sn.empty() ? 0 : (long)layer_item.size() - 1; out[1] = (long)sizeof(int) * (long)(H.val_src.size() + P.pmap.size()); }
+  return bad;
 }
 
 extern "C" const int* gcge_hip_dense_row_list(const void* dm, int* nlisted) {   // the rows its pad-8 part walks (NULL: all rows)

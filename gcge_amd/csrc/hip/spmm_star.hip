@@ -748,10 +748,11 @@ extern "C" void gcge_hip_star_free(void* sm) {
 // (ascending; NULL on one rank).  geom (NULL, or box NULL: none): the masked grid the rows live on — of a whole matrix (one rank, no
 // halo columns) or of a row slab (cols: the own rows, then the halo rows ascending by global row); one that fits neither is ignored.
 extern "C" void* gcge_hip_star_build(int nrows, int ncols_local, long row_begin, long nglobal, const int* ghost, const int* rowptr,
-                                     const int* colidx, const double* val, const GcgeGridGeom* geom, StarHost** host) {
+                                     const int* colidx, const double* val, const GcgeGridGeom* geom, StarHost** host, int keep_maps) {
   *host = nullptr;
   if (g_star_mode < 0 || nrows <= 0) return nullptr;
   StarHost* H = new StarHost();
+  H->keep_maps = keep_maps != 0;                                       // (value_maps.h: the provenance of diag / rem_val, for the caller)
   StarRows M = {nrows, ncols_local, row_begin, nglobal, ghost, rowptr, colidx, val};
   if (geom != nullptr && geom->box != nullptr &&
       (geom->cols ? geom->nbox == ncols_local : geom->nbox == nrows && ncols_local == nrows && row_begin == 0)) {
@@ -762,6 +763,7 @@ extern "C" void* gcge_hip_star_build(int nrows, int ncols_local, long row_begin,
   if (!ok && M.box == nullptr && g_star_infer && ncols_local == nrows && row_begin == 0 && nglobal == nrows) {
     // no lexicographic grid: the points of a masked one in scan order?  (the geometry recovered from the rows)
     delete H; H = new StarHost();
+    H->keep_maps = keep_maps != 0;
     int* od = H->own_dims;
     if (star_infer_box(nrows, rowptr, colidx, &H->own_box, &od[0], &od[1], &od[2])) {
       M.box = H->own_box.data(); M.bnx = od[0]; M.bny = od[1]; M.bnz = od[2]; M.nglobal = (long)od[0] * od[1] * od[2];
@@ -845,6 +847,7 @@ extern "C" int gcge_hip_star_masked_form(const void* sm) {
   if (S->d_map == nullptr) return 0;
   return (S->iso && S->d_lines != nullptr && (S->masked_slab || (g_star_form == 3 && g_star_masked_third))) ? 3 : 2;
 }
+extern "C" double* gcge_hip_star_diag(void* sm) { return ((StarMat*)sm)->d_diag; }   // the stored diagonal, nrows doubles (mat_values_forms.hip rewrites it)
 extern "C" void gcge_hip_star_stats(const void* sm, long* out) {   // nx, ny, nz, arm length, clean rows, rows, first / last + 1 plane of the slab
   const StarMat* S = (const StarMat*)sm;
   out[0] = S->g.nx; out[1] = S->g.ny; out[2] = S->g.nz; out[3] = S->R; out[4] = S->nclean; out[5] = S->nrows; out[6] = S->g.zs; out[7] = S->g.ze;

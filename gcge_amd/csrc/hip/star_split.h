@@ -19,6 +19,11 @@ struct StarHost {
   std::vector<int> inv;                                               // masked domains: grid point -> row (-1: none)
   std::vector<int> own_box; int own_dims[3] = {0, 0, 0};              // masked domains whose geometry was recovered here (star_infer_box): box index of every row; nx, ny, nz
   std::vector<int> rem_rowptr, rem_col; std::vector<double> rem_val;  // every entry of the rows that are not clean (local columns)
+  // value maps (value_maps.h), built only when keep_maps is set before star_build_host: where diag / rem_val came from in the CSR values
+  bool keep_maps = false;
+  std::vector<int> diag_src;                                          // [row] CSR index of the stored diagonal entry, -1: none
+  std::vector<int> rem_src; std::vector<unsigned char> rem_code;      // [remainder entry] CSR index (-1: taken back), coefficient code
+  std::vector<unsigned char> pin;                                     // [CSR entry] see value_maps.h
 };
 
 // The rows of one slab: local rows [0, nrows) are global rows row_begin + r; local column c < nrows is global column row_begin + c,
@@ -39,5 +44,5 @@ bool star_infer_box(int nrows, const int* rowptr, const int* colidx, std::vector
 }  // namespace gcge
 // spmm_star.hip: the sweep's device object (NULL: none) and, through *host, the split behind it — the caller's to read and delete
 extern "C" void* gcge_hip_star_build(int nrows, int ncols_local, long row_begin, long nglobal, const int* ghost, const int* rowptr, const int* colidx,
-                                     const double* val, const GcgeGridGeom* geom, gcge::StarHost** host);
+                                     const double* val, const GcgeGridGeom* geom, gcge::StarHost** host, int keep_maps);
 #endif

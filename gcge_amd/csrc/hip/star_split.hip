@@ -6,8 +6,10 @@
 #include <algorithm>
 #include <unordered_map>
 #include "star_split.h"
+#include "value_maps.h"
 
 namespace gcge {
+static_assert(GCGE_VM_ARM == STAR_R, "value_maps.h codes the coefficients of a star of arm length STAR_R");
 
 static inline uint64_t star_bits(double v) { uint64_t b; memcpy(&b, &v, 8); return b; }
 
@@ -127,6 +129,8 @@ bool star_build_host(const StarRows& M, StarHost* H) {
   const long sy = nx, sz = (long)nx * ny;
   H->diag.assign((size_t)nrows, 0.0);
   H->rem_rowptr.assign((size_t)nrows + 1, 0);
+  const bool maps = H->keep_maps;
+  if (maps) { H->diag_src.assign((size_t)nrows, -1); H->pin.assign((size_t)rowptr[nrows], 0); }
   uint64_t cb[3][STAR_R + 1]; double cv[3][STAR_R + 1];
   for (int k = 0; k <= STAR_R; ++k) {
     cv[0][k] = H->c.cx[k]; cv[1][k] = H->c.cy[k]; cv[2][k] = H->c.cz[k];
@@ -155,11 +159,14 @@ bool star_build_host(const StarRows& M, StarHost* H) {
   // rows are independent: contiguous chunks, one thread each, every chunk with its own remainder arrays (joined in order below)
   const int nt = gcge_upload_threads();
   std::vector<std::vector<int>> crc((size_t)nt); std::vector<std::vector<double>> crv((size_t)nt);
+  std::vector<std::vector<int>> crs((size_t)nt); std::vector<std::vector<unsigned char>> crk((size_t)nt);   // (maps: source and code of every remainder entry)
   std::vector<long> cclean((size_t)nt, 0); std::vector<int> cfail((size_t)nt, 0);
   std::vector<int>& rcnt = H->rem_rowptr;                             // [r + 1] = entries of row r for now, prefix-summed below
   gcge_parallel_chunks(nrows, nt, [&](int chunk, long rb, long re) {
-  std::vector<std::pair<int, double>> rem;                             // remainder of the row being looked at
+  struct RemEntry { int first; double second; int src; int code; };   // column, value; where the value came from (value_maps.h): it rides through the sort
+  std::vector<RemEntry> rem;                                           // remainder of the row being looked at
   std::vector<int>& rc = crc[chunk]; std::vector<double>& rv = crv[chunk];
+  std::vector<int>& rs = crs[chunk]; std::vector<unsigned char>& rk = crk[chunk];
   long nclean = 0;
   for (int r = (int)rb; r < (int)re; ++r) {
     const long gr = M.gpos(r);
@@ -172,10 +179,10 @@ bool star_build_host(const StarRows& M, StarHost* H) {
     };
     bool seen[3][2][STAR_R + 1] = {};
     rem.clear();
-    bool have_diag = false; double dv = 0.0;
+    bool have_diag = false; double dv = 0.0; int dq = -1;
     for (int q = rowptr[r]; q < rowptr[r + 1]; ++q) {
       const long o = M.gcol(colidx[q]) - gr;
-      if (o == 0 && !have_diag) { have_diag = true; dv = val[q]; continue; }
+      if (o == 0 && !have_diag) { have_diag = true; dv = val[q]; dq = q; continue; }
       const long ao = o < 0 ? -o : o; const int sgn = o < 0 ? 0 : 1;
       int a = -1, k = 0;
       if (ao >= 1 && ao <= STAR_R) { a = 0; k = (int)ao; }
@@ -183,9 +190,10 @@ bool star_build_host(const StarRows& M, StarHost* H) {
       else if (ao % sy == 0 && ao / sy >= 1 && ao / sy <= STAR_R) { a = 1; k = (int)(ao / sy); }
       // a star position: the neighbour k steps along axis a exists in the grid and the star reaches that far
       const bool star_pos = a >= 0 && cb[a][k] != 0 && !seen[a][sgn][k] && exists(a, sgn, k);
-      if (!star_pos) { rem.emplace_back(colidx[q], val[q]); continue; }
+      if (!star_pos) { rem.push_back(RemEntry{colidx[q], val[q], q, 0}); continue; }
       seen[a][sgn][k] = true;
-      if (star_bits(val[q]) != cb[a][k]) rem.emplace_back(colidx[q], val[q] - cv[a][k]);
+      if (star_bits(val[q]) != cb[a][k]) rem.push_back(RemEntry{colidx[q], val[q] - cv[a][k], q, gcge_vm_code(a, k)});
+      else if (maps) H->pin[q] = (unsigned char)gcge_vm_code(a, k);   // the star carries this entry: new values must keep it
     }
     for (int a = 0; a < 3; ++a)
       for (int k = 1; k <= STAR_R; ++k) {
@@ -196,15 +204,17 @@ bool star_build_host(const StarRows& M, StarHost* H) {
           const long gq = gr + (sgn ? 1 : -1) * k * stride[a];
           const int zz = (int)(gq / sz);
           if (zz < gm.zmin || zz >= gm.zmax) { cfail[chunk] = 1; return; }   // (cannot happen: zmin / zmax cover the star's reach)
-          rem.emplace_back((int)xcol(gq), -cv[a][k]);
+          rem.push_back(RemEntry{(int)xcol(gq), -cv[a][k], -1, gcge_vm_code(a, k)});
         }
       }
     if (dv != dv) { cfail[chunk] = 1; return; }                        // a NaN on the diagonal: not for this form
     H->diag[r] = dv;
+    if (maps && dq >= 0) { H->diag_src[r] = dq; H->pin[dq] = GCGE_VM_PIN_DIAG; }
     if (rem.empty()) { clean[r] = 1; ++nclean; }
     else {
-      std::sort(rem.begin(), rem.end(), [](const std::pair<int, double>& p, const std::pair<int, double>& q) { return p.first < q.first; });
+      std::sort(rem.begin(), rem.end(), [](const RemEntry& p, const RemEntry& q) { return p.first < q.first; });
       for (auto& e : rem) { rc.push_back(e.first); rv.push_back(e.second); }
+      if (maps) for (auto& e : rem) { rs.push_back(e.src); rk.push_back((unsigned char)e.code); }
     }
     rcnt[r + 1] = (int)rem.size();
   }
@@ -223,6 +233,12 @@ bool star_build_host(const StarRows& M, StarHost* H) {
       std::vector<int>().swap(crc[c]); std::vector<double>().swap(crv[c]);
     }
     if (off != rc.size()) return false;
+  }
+  if (maps) {
+    H->rem_src.clear(); H->rem_code.clear();
+    H->rem_src.reserve(rc.size()); H->rem_code.reserve(rc.size());
+    for (int c = 0; c < nt; ++c) { H->rem_src.insert(H->rem_src.end(), crs[c].begin(), crs[c].end()); H->rem_code.insert(H->rem_code.end(), crk[c].begin(), crk[c].end()); }
+    if (H->rem_src.size() != rc.size()) return false;
   }
   H->nclean = nclean;
   if (2 * nclean < nrows) return false;

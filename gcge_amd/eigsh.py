@@ -40,11 +40,13 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
     A, M:  a torch sparse_csr CUDA tensor, a (crow, col, val) triple of device arrays, or a matrix handle of the back-end.  Handles
            stay the caller's; what is created here is freed here.  A sequence of nearby operators on one sparsity structure keeps
            ONE handle and gives it new values between the solves (HipBackend.matrix_update_values), so no step re-creates the matrix:
-               m = hip.matrix_from_device(A0); r = eigsh(m, k, backend=hip)
+               m = hip.matrix_from_device(A0, updatable=True); r = eigsh(m, k, backend=hip)
                for V in potentials:
                    if not hip.matrix_update_values(m, values_of(V)):       # declined: nothing was written
-                       hip.free_matrix(m); m = hip.matrix_from_device(crow, col, values_of(V))
+                       hip.free_matrix(m); m = hip.matrix_from_device(crow, col, values_of(V), updatable=True)
                    r = eigsh(m, k, X0=r.eigenvectors, backend=hip)
+           (updatable=True matters for real-space Hamiltonians — a Laplacian star, a local potential on the diagonal, atom blocks:
+           their handles keep the provenance of their stored values only on request; the star's coefficients must not change.)
     X0:    (n, j) device tensor of start vectors, j <= nev_max (a warm start: the previous eigenvectors of a nearby operator).
     tol:   relative residual tolerance, ||A x - lambda M x|| <= tol |lambda|;  maxiter: outer iterations at most (default 500).
     nev_max (default 2 k), block_size:  columns of the eigenvector block and of the W block, as for the harness.

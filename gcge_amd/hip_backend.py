@@ -1,4 +1,5 @@
 """Python handle on the HIP back-end (libgcge_hip.so).  Plumbing only."""
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -26,18 +27,36 @@ class HipBackendImpl:
         import torch
         return torch.device("cuda", self.device if self.device >= 0 else torch.cuda.current_device())
 
-    def matrix(self, csr):
-        m = self.g.gcge_hip_mat_create_csr(C.byref(csr))
+    @contextlib.contextmanager
+    def _keeping_value_maps(self, updatable):
+        """gcge_hip_mat_keep_value_maps(1) around one creation (the switch is process-wide and off by default); afterwards the setting
+        that was in force before is back"""
+        if not updatable:
+            yield
+            return
+        was = self.g.gcge_hip_mat_keep_value_maps(1)
+        try:
+            yield
+        finally:
+            self.g.gcge_hip_mat_keep_value_maps(was)
+
+    def matrix(self, csr, updatable=False):
+        """updatable=True: a handle that takes the star or the dense form also keeps where its stored values came from (about 4 bytes
+        per block and remainder slot on the device, gcge_hip_mat_value_maps), so that matrix_update_values can give it new values in
+        place; without it such a handle declines every update.  The forms and the products are the same either way."""
+        with self._keeping_value_maps(updatable):
+            m = self.g.gcge_hip_mat_create_csr(C.byref(csr))
         if not m:
             raise RuntimeError("gcge_hip_mat_create_csr failed")
         return C.c_void_p(m)
 
-    def matrix_from_device(self, crow, col=None, val=None, nrows=None):
+    def matrix_from_device(self, crow, col=None, val=None, nrows=None, updatable=False):
         """A whole square matrix from CSR arrays that live on the GPU (gcge_hip_mat_create_device): a torch sparse_csr tensor alone,
         three torch device tensors, or three objects with __cuda_array_interface__ (row pointers, ascending columns, values).
         Indices are converted to int32 and values to float64 on the device where needed; the producer's stream is synchronised
         before the call (torch's current stream for tensors, the whole device for other objects); the handle owns copies and
-        nothing of the caller's is kept.  ValueError: the arrays are not a matrix (the library says why on stderr)."""
+        nothing of the caller's is kept.  updatable: as for HipBackend.matrix.  ValueError: the arrays are not a matrix (the library
+        says why on stderr)."""
         import torch
         if col is None and val is None:
             if not (isinstance(crow, torch.Tensor) and crow.layout == torch.sparse_csr):
@@ -69,7 +88,8 @@ class HipBackendImpl:
             torch.cuda.synchronize(rp.device)
         else:
             torch.cuda.current_stream(rp.device).synchronize()
-        m = self.g.gcge_hip_mat_create_device(int(nrows), int(va.numel()), rp.data_ptr(), ci.data_ptr(), va.data_ptr())
+        with self._keeping_value_maps(updatable):
+            m = self.g.gcge_hip_mat_create_device(int(nrows), int(va.numel()), rp.data_ptr(), ci.data_ptr(), va.data_ptr())
         if not m:
             raise ValueError("gcge_hip_mat_create_device refused the arrays")
         return C.c_void_p(m)
@@ -80,8 +100,12 @@ class HipBackendImpl:
         tensor, or an object with __cuda_array_interface__.  Converted to float64 on the device only if it is something else; the
         producer's stream is synchronised before the call (torch's current stream for tensors, the whole device for other objects).
         True: every product through the handle is now that of the new values (its K1 form may have become a "+values" form).
-        False: the library declined and wrote nothing (star / dense / tile forms, slabs, re-ordered handles, a 16-slot table whose
-        classes do not stay uniform, an explicitly stored zero): free the handle and create the matrix again.
+        A handle with a star or a dense form (real-space Hamiltonians: a Laplacian star, a diagonal, atom blocks) takes new values
+        when it was created with updatable=True: the diagonal and every entry the star does not carry may change, the star's
+        coefficients stay (an entry that equalled its coefficient at creation must keep it).
+        False: the library declined and wrote nothing (a star / dense handle created without updatable=True or given other star
+        coefficients or a NaN diagonal, tile forms, slabs, re-ordered handles, a 16-slot table whose classes do not stay uniform,
+        an explicitly stored zero): free the handle and create the matrix again.
         TypeError: a host tensor; ValueError: another count of values than the handle has entries (checked here)."""
         import torch
         foreign = not isinstance(values, torch.Tensor)
@@ -176,12 +200,14 @@ class HipBackendImpl:
             self.g.gcge_hip_mv_from_device(mv, c0, c0 + m, t.data_ptr(), rs, cs)
         return mv
 
-    def matrix_grid(self, csr, dims, box_of_row):
-        """A matrix on a masked grid: box_of_row[r] = x + nx (y + ny z) (int32 array, ascending); see gcge_hip_mat_create_grid."""
+    def matrix_grid(self, csr, dims, box_of_row, updatable=False):
+        """A matrix on a masked grid: box_of_row[r] = x + nx (y + ny z) (int32 array, ascending); see gcge_hip_mat_create_grid.
+        updatable: as for HipBackend.matrix."""
         g = self.g
         box = np.ascontiguousarray(box_of_row, dtype=np.int32)
-        m = g.gcge_hip_mat_create_grid(csr.nrows, csr.rowptr, csr.colidx, csr.val, int(dims[0]), int(dims[1]), int(dims[2]),
-                                       box.ctypes.data_as(C.POINTER(C.c_int)))
+        with self._keeping_value_maps(updatable):
+            m = g.gcge_hip_mat_create_grid(csr.nrows, csr.rowptr, csr.colidx, csr.val, int(dims[0]), int(dims[1]), int(dims[2]),
+                                           box.ctypes.data_as(C.POINTER(C.c_int)))
         if not m:
             raise RuntimeError("gcge_hip_mat_create_grid failed")
         return C.c_void_p(m)

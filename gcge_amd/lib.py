@@ -154,6 +154,14 @@ def mat_update_stats():
     return tuple(out)
 
 
+def mat_update_form_stats():
+    """gcge_hip_mat_update_form_stats: (star handles updated, dense handles updated, declines by a pinned entry, declines by a NaN
+    diagonal) of gcge_hip_mat_update_values_device since the library was loaded."""
+    out = (C.c_long * 4)()
+    hip_lib().gcge_hip_mat_update_form_stats(out)
+    return tuple(out)
+
+
 def mat_device_hash_bits(bits):
     """Tests: the device pattern search keeps only the low `bits` bits of its row hash (64: all of it, the default)."""
     hip_lib().gcge_hip_mat_device_hash_bits(int(bits))

@@ -92,19 +92,51 @@ void gcge_hip_mat_device_stats (long out[4]);
  *   value table of at most 8 slots, anything else: d_val and the pad-8 values are rewritten and the handle BECOMES the "+values" form
  *     of the table it has (per-row values allocated and filled by the slot rule; gcge_hip_mat_spmm_form then reports
  *     spmm_pattern+values / spmm_pattern_chain2+values).  There is no way back: a later uniform update re-scatters the per-row values.
+ *   star + blocks, or blocks alone (spmm_star+spmm_dense+spmm_pad8, spmm_dense+spmm_pad8), created while gcge_hip_mat_keep_value_maps
+ *     was on: the handle kept, on the device, where each stored value came from (csrc/hip/value_maps.h), and the update replays that
+ *     (csrc/hip/mat_values_forms.hip): d_val and the pad-8 copy as above, the star's diagonal gathered, the star's remainder formed in a
+ *     scratch as "entry minus coefficient" with the rounding of the upload, the block values of every layer and the pad-8 remainder
+ *     gathered from it (without a star: from d_val), pads +0.0.  Form, split, blocks, layers and lists are unchanged.  The star's
+ *     coefficients are fixed for the life of the handle: an entry that sits at a star position and equalled the coefficient at
+ *     creation (it has no slot of its own) must keep those bits.  Every other entry is free, the diagonal any value but NaN.
  *   declined (1): a value table of 16 slots whose classes do not stay uniform; a row whose count of present table slots (table value
- *     != 0.0) differs from its length, i.e. an explicitly stored +-0.0; and, decided from the handle alone before d_val is read, a
- *     handle with a star, dense or tile form (each has a value layout of its own behind its builder: deliberately out of scope), a
- *     rectangular handle, a row slab (halo columns, row_begin != 0, a halo plan), a re-ordered handle.
+ *     != 0.0) differs from its length, i.e. an explicitly stored +-0.0; under a star, a pinned entry whose new value differs in bits
+ *     from its coefficient (a rescaled Laplacian, say) or a NaN on the diagonal; and, decided from the handle alone before d_val is
+ *     read, a star or dense handle WITHOUT value maps (the switch was off at creation: the default), a dense form whose remainder is
+ *     tiled, any handle with a tile form, a rectangular handle, a row slab (halo columns, row_begin != 0, a halo plan), a re-ordered
+ *     handle.
  * A conversion changes the K1 form between two solves.  Nothing in the back-end keeps a record of a handle's form across calls: the
  * fused CG plans every call from the handle (cg_plan, block_pcg.hip), its parked blocks are keyed by row count and row order, and
  * mat_product.hip reads the handle at every product.  A multigrid hierarchy built from the handle BEFORE an update belongs to the old
  * operator; the harness creates and destroys its hierarchy inside every solve, other callers of MultiGridCreate rebuild theirs.
  * gcge_hip_mat_update_stats: since load, out[0] updates that kept the form, out[1] of those value-table rewrites, out[2] conversions
  * to "+values", out[3] declines, out[4] bad-argument returns, out[5] bytes copied device to host by updates — one flag word per
- * update that has a table, whatever the size of the matrix.  gcge_hip_mat_device_stats is not touched.                              */
+ * update that has a table or a star, whatever the size of the matrix.  gcge_hip_mat_device_stats is not touched.  An accepted update
+ * of a star or dense handle counts in out[0], a decline in out[3]; gcge_hip_mat_update_form_stats adds out[0] star handles updated,
+ * out[1] dense handles updated, out[2] declines by a pinned entry, out[3] declines by a NaN diagonal (an update that shows both counts
+ * in both).                                                                                                                          */
 int  gcge_hip_mat_update_values_device (GCGE_HIP_MAT *A, long nnz, const double *d_val);
 void gcge_hip_mat_update_stats (long out[6]);
+void gcge_hip_mat_update_form_stats (long out[4]);
+/* Value maps, kept on request only.  gcge_hip_mat_keep_value_maps (on): process-wide, read when a matrix is created (like
+ * gcge_hip_spmm_reorder_mode), default 0; returns the setting it replaces.  With 0 nothing is kept and a star or dense handle
+ * declines every update.  With 1 a handle
+ * that takes the star or the dense form also keeps the provenance of its stored values on the device; forms, split, blocks, layers,
+ * lists and every stored value array are bit-identical to those of the switch off.  Only a whole matrix on one rank keeps maps (a
+ * row slab declines every update).  gcge_hip_mat_value_maps: the bytes of maps a handle holds (0: none) — 4 per block slot and
+ * pad-8 remainder slot; under a star also 1 per CSR entry, 4 per row and 5 per entry of the star's remainder.  The first update of a
+ * star handle also allocates, and keeps, a scratch of 8 bytes per entry of the star's remainder.
+ * gcge_hip_value_maps_selfcheck (host only, no device; tests): the forms and maps built from val0 (dense_mode: gcge_hip_spmm_dense_mode
+ * for the duration of the call), the maps replayed on val1 through value_maps.h, star + diagonal + blocks + remainder expanded back into
+ * per-row sums per column and compared with the CSR rows of val1.  Returns the number of differing entries, (row, column) pairs
+ * (0: equal), -1: neither a star nor a dense form, -2: an update to val1 would be declined.  out[0] forms found (1 star, 2 blocks, 3 both), out[1] layers of blocks,
+ * out[2] pinned entries, out[3] bytes of maps.  _grid: with the masked grid of gcge_hip_mat_create_grid named.                        */
+int  gcge_hip_mat_keep_value_maps (int on);
+long gcge_hip_mat_value_maps (const GCGE_HIP_MAT *A);
+long gcge_hip_value_maps_selfcheck (int nrows, const int *rowptr, const int *colidx, const double *val0, const double *val1, int dense_mode,
+                                    long out[4]);
+long gcge_hip_value_maps_selfcheck_grid (int nrows, const int *rowptr, const int *colidx, const double *val0, const double *val1, int dense_mode,
+                                         int nx, int ny, int nz, const int *box_of_row, long out[4]);
 /* A matrix of that kind that names NO geometry (read from a file: gcge_load_matrix_market, gcge_load_petsc_binary) gets it
  * recovered at upload by gcge_hip_mat_create itself: x lines from the (r, r + 1) couplings, planes and the shifts between
  * lines / planes from the votes of the star rows' + y / + z neighbours.  A wrong guess costs speed, never the result (the

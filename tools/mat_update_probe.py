@@ -6,7 +6,13 @@ Both calls synchronise before they return, so a host clock round them times the 
 on one handle, then the median of `reps`.  GB/s counts the bytes an update has to move: 8 nnz + 2 n read, 8 nnz + 64 noct written, and
 64 n more where the per-row values are written (the check pass reads the values and columns once more on handles with a table: that
 is the kernels' own traffic, not counted).
-    python tools/mat_update_probe.py N [N ...] [--out FILE]"""
+    python tools/mat_update_probe.py N [N ...] [--out FILE]
+With --star G K the star case runs instead: make_problem("sio2", G, K=K, R0=2.0, R1=5.0) (G = 171, K = 2000 is BASELINE config 5's
+matrix, as in tools/tile_probe.py), uploaded through gcge_hip_mat_create_csr:
+    create, maps off / on     the upload with gcge_hip_mat_keep_value_maps 0 / 1 (the host analysis: star split, blocks, layers, pad-8)
+    free + create             what an SCF step costs without the update: gcge_hip_mat_destroy + the upload of the new values
+    update D / O              a new diagonal in every row / the creation values again, in place (GB/s counts 16 bytes per CSR entry only)
+and the bytes of maps the handle holds.  A library without the switch (an earlier commit) runs the "maps off" rows only."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -18,7 +24,10 @@ argv = list(sys.argv[1:])
 out_path = None
 if "--out" in argv:
     i = argv.index("--out"); out_path = argv[i + 1]; del argv[i:i + 2]
-sizes = [int(a) for a in argv] or [128]
+star_case = None
+if "--star" in argv:
+    i = argv.index("--star"); star_case = (int(argv[i + 1]), int(argv[i + 2])); del argv[i:i + 3]
+sizes = [int(a) for a in argv] or ([] if star_case else [128])
 hip = HipBackend(); g = hip.g
 results = []
 
@@ -40,7 +49,71 @@ def report(name, N, n, nnz, t, nbytes):
                                                                             "%8.1f GB/s" % gbs if gbs else ""), flush=True)
 
 
+def star_probe(G, K):
+    import ctypes as C
+    t0 = time.perf_counter()
+    A = make_problem("sio2", G, K=K, R0=2.0, R1=5.0)[0]
+    rp, ci, va = csr_arrays(A)
+    n, nnz = A.nrows, int(va.size)
+    print("sio2 %d, K %d: n %d, nnz %d, generated in %.1f s" % (G, K, n, nnz, time.perf_counter() - t0), flush=True)
+    has_switch = hasattr(g, "gcge_hip_mat_keep_value_maps")
+
+    def create(on):
+        if has_switch:
+            g.gcge_hip_mat_keep_value_maps(1 if on else 0)
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter(); m = g.gcge_hip_mat_create_csr(C.byref(A)); t = time.perf_counter() - t0
+        finally:
+            if has_switch:
+                g.gcge_hip_mat_keep_value_maps(0)
+        assert m
+        return C.c_void_p(m), t
+
+    def one(name, ts, nbytes=0):
+        report(name, G, n, nnz, (float(np.median(ts)), min(ts), max(ts)), nbytes)
+
+    m, t_first = create(False)
+    form = g.gcge_hip_mat_spmm_form(m).decode()
+    print("form:", form, flush=True)
+    ts = []
+    for _ in range(2):                                             # free + create from the same values, maps off
+        torch.cuda.synchronize()
+        t0 = time.perf_counter(); g.gcge_hip_mat_destroy(m); m, t = create(False); ts.append(time.perf_counter() - t0)
+    one("free + create, maps off (%s)" % form, ts)
+    one("create, maps off", [t_first, t])
+    g.gcge_hip_mat_destroy(m)
+    if not has_switch:
+        return
+    ts, tc = [], []
+    m, t = create(True); tc.append(t)
+    for _ in range(2):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter(); g.gcge_hip_mat_destroy(m); m, t = create(True); ts.append(time.perf_counter() - t0); tc.append(t)
+    one("free + create, maps on", ts)
+    one("create, maps on", tc)
+    nmap = int(g.gcge_hip_mat_value_maps(m))
+    print("bytes of maps: %d (%.2f per stored entry)" % (nmap, nmap / nnz), flush=True)
+    results.append({"case": "bytes of maps", "N": G, "n": n, "nnz": nnz, "bytes": nmap})
+    assert nmap > 0 and g.gcge_hip_mat_spmm_form(m).decode() == form
+    d_va = torch.from_numpy(va).cuda()
+    d_rp, d_ci = torch.from_numpy(rp).cuda(), torch.from_numpy(ci).cuda()
+    rows = torch.repeat_interleave(torch.arange(n, device="cuda", dtype=torch.int32), (d_rp[1:] - d_rp[:-1]).to(torch.int64))
+    diag = rows == d_ci
+    d_d = d_va + torch.where(diag, torch.rand(n, dtype=torch.float64, device="cuda")[rows.to(torch.int64)], torch.zeros((), dtype=torch.float64, device="cuda"))
+    del rows, d_rp, d_ci
+    torch.cuda.synchronize()
+    s0 = mat_update_stats()
+    report("update D (a new diagonal)", G, n, nnz, timed(lambda: g.gcge_hip_mat_update_values_device(m, nnz, d_d.data_ptr()), 1, 5), 16 * nnz)
+    report("update O (the creation values again)", G, n, nnz, timed(lambda: g.gcge_hip_mat_update_values_device(m, nnz, d_va.data_ptr()), 1, 5), 16 * nnz)
+    s1 = mat_update_stats()
+    assert s1[0] - s0[0] == 12 and s1[3] == s0[3], (s0, s1)
+    g.gcge_hip_mat_destroy(m)
+
+
 print("device:", torch.cuda.get_device_name(0), flush=True)
+if star_case:
+    star_probe(*star_case)
 for N in sizes:
     rp, ci, va = csr_arrays(make_problem("lap3d", N)[0])
     n, nnz = rp.size - 1, int(va.size)
