@@ -126,6 +126,9 @@ extern "C" void gcge_hip_mg_agg_grid_device(const int dims[3], int* d_agg, int* 
 extern "C" int gcge_hip_mg_galerkin_device(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
                                            const int* d_ptr, const int* d_mem, double scale, int** d_rp_out, int** d_ci_out, double** d_va_out,
                                            long* nnz_out, long* d2h);
+extern "C" int gcge_hip_mg_galerkin_values_into(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
+                                                const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c,
+                                                double* d_va_c, long* d2h);     // (rows that fit are written even when it returns 1)
 extern "C" int gcge_hip_mg_agg_masked_device(const int dims[3], const int* d_box, int nf, int* d_agg, int* d_mem, int** d_ptr_out, int** d_cbox_out,
                                              int cdims[3], long* d2h);
 // mg_aggregate.hip: MIS-2 aggregation (gcge_mg_aggregate_mis2) of an n-row device CSR; agg / mem: the caller's, *d_ptr_out allocated

@@ -130,9 +130,10 @@ __device__ inline int mg_lookup(const MgRowLds& s, int c) {
 }
 
 // walk the entries of coarse row I in the host's order: fn(c, v, i, n) per chunk of n <= 64 entries, lane i holds entry i (c = -1:
-// no entry / a column >= nf); every lane calls fn the same number of times (block = one wave, __syncthreads orders LDS)
-template <class F>
-__device__ inline void mg_walk_row(MgRowLds& s, int I, int nf, const int* __restrict__ ptr, const int* __restrict__ mem, const int* __restrict__ rowptr,
+// no entry / a column >= nf); every lane calls fn the same number of times (block = one wave, __syncthreads orders LDS).  S: the
+// kernel's LDS record, of which the walk uses mbeg / moff
+template <class S, class F>
+__device__ inline void mg_walk_row(S& s, int I, int nf, const int* __restrict__ ptr, const int* __restrict__ mem, const int* __restrict__ rowptr,
                                    const int* __restrict__ colidx, const double* __restrict__ val, const int* __restrict__ agg, bool want_val, F fn) {
   const int lane = threadIdx.x;
   const int q0 = ptr[I], q1 = ptr[I + 1];
@@ -202,6 +203,52 @@ __global__ void __launch_bounds__(MG_WAVE) k_mg_galerkin(int nc, int nf, const i
       if (scale != 1.0) a *= scale;
       val_c[base + r] = a;
     }
+    __syncthreads();
+  }
+}
+
+// Values only, for a coarse structure that exists (gcge_hip_mg_galerkin_values_device: the refresh of a live hierarchy, multigrid.hip):
+// the row's ascending coarse columns staged in LDS, every entry's place among them by binary search — no hash, no count pass —, then the
+// sums of k_mg_galerkin<true>: the lane that owns a rank adds its values one by one in walk order from 0.0, times scale at the end when
+// scale != 1.0.  7.3 KB of LDS per wave.  A row is written whole or not at all: an entry whose coarse column the row does not hold, or
+// a row of more than MG_DCAP columns, sets the flag and leaves the row's values alone.
+struct MgValLds {
+  int col[MG_DCAP];      // the coarse row's columns, ascending
+  double acc[MG_DCAP];   // sums by rank
+  int mbeg[MG_WAVE], moff[MG_WAVE + 1];
+  int cr[MG_WAVE]; double cv[MG_WAVE];
+  int miss;
+};
+__global__ void __launch_bounds__(MG_WAVE) k_mg_galerkin_values(int nc, int nf, const int* __restrict__ ptr, const int* __restrict__ mem,
+    const int* __restrict__ rowptr, const int* __restrict__ colidx, const double* __restrict__ val, const int* __restrict__ agg, double scale,
+    const int* __restrict__ rowptr_c, const int* __restrict__ colidx_c, double* __restrict__ val_c, int* __restrict__ flag) {
+  __shared__ MgValLds s;
+  const int lane = threadIdx.x;
+  for (int I = blockIdx.x; I < nc; I += gridDim.x) {
+    const int base = rowptr_c[I], nd = rowptr_c[I + 1] - base;
+    if (nd < 0 || nd > MG_DCAP) { if (lane == 0) *flag = 1; continue; }       // (uniform over the wave)
+    for (int j = lane; j < nd; j += MG_WAVE) { s.col[j] = colidx_c[base + j]; s.acc[j] = 0.0; }
+    if (lane == 0) s.miss = 0;
+    __syncthreads();
+    mg_walk_row(s, I, nf, ptr, mem, rowptr, colidx, val, agg, true, [&](int c, double v, int i, int n) {
+      int r = -1;
+      if (c >= 0) {
+        int lo = 0, hi = nd;                          // first column >= c
+        while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (s.col[mid] < c) lo = mid + 1; else hi = mid; }
+        if (lo < nd && s.col[lo] == c) r = lo; else s.miss = 1;
+      }
+      s.cr[i] = r; s.cv[i] = v;
+      __syncthreads();
+      for (int t = 0; t < n; ++t) { const int q = s.cr[t]; if (q >= 0 && (q & (MG_WAVE - 1)) == lane) s.acc[q] += s.cv[t]; }
+      __syncthreads();
+    });
+    if (s.miss) { if (lane == 0) *flag = 1; }
+    else
+      for (int j = lane; j < nd; j += MG_WAVE) {
+        double a = s.acc[j];
+        if (scale != 1.0) a *= scale;
+        val_c[base + j] = a;
+      }
     __syncthreads();
   }
 }
@@ -415,6 +462,48 @@ extern "C" int gcge_hip_mg_galerkin_device(int nf, const int* d_rowptr, const in
   return 0;
 }
 
+// The values of Ac = scale P^T A P for a coarse structure that exists (d_rp_c / d_ci_c: nc rows, ascending columns — what
+// gcge_hip_mg_galerkin_device made of a matrix of this structure), straight into d_va_c: the doubles gcge_hip_mg_galerkin_device and the
+// host's gcge_mg_galerkin give for these values.  Returns 0, or 1 when an entry's coarse column is not in its coarse row (the structure is
+// not this matrix's) or a coarse row holds more than MG_DCAP columns: such rows keep what d_va_c held, the others are written.  One word
+// comes back.
+extern "C" int gcge_hip_mg_galerkin_values_into(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
+                                                const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c,
+                                                double* d_va_c, long* d2h) {
+  if (nc <= 0) return 0;
+  int* d_flag = (int*)gcge_hip_stage_d(1);              // (a word of the back-end's staging block: nothing else runs between the two calls)
+  GCGE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int), mg_stream()));
+  const unsigned grid = (unsigned)(nc < 65536 * 16 ? nc : 65536 * 16);
+  hipLaunchKernelGGL(k_mg_galerkin_values, dim3(grid), dim3(MG_WAVE), 0, mg_stream(), nc, nf, d_ptr, d_mem, d_rowptr, d_colidx, d_val, d_agg, scale,
+                     d_rp_c, d_ci_c, d_va_c, d_flag);
+  GCGE_HIP_CHECK(hipGetLastError());
+  int flag = 0;
+  GCGE_HIP_CHECK(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, mg_stream()));
+  GCGE_HIP_CHECK(hipStreamSynchronize(mg_stream()));
+  if (d2h) *d2h += (long)sizeof flag;
+  return flag != 0;
+}
+// ... into d_va_c_out only when the whole product fits the structure: on a return of 1 d_va_c_out is as it was (the values go through
+// a block of the pool)
+extern "C" int gcge_hip_mg_galerkin_values_device(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
+                                                  const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c,
+                                                  double* d_va_c_out) {
+  if (nc <= 0) return 0;
+  int nnz = 0;
+  GCGE_HIP_CHECK(hipStreamSynchronize(mg_stream()));
+  GCGE_HIP_CHECK(hipMemcpy(&nnz, d_rp_c + nc, sizeof nnz, hipMemcpyDeviceToHost));
+  if (nnz <= 0) return 0;
+  const size_t bytes = (size_t)nnz * sizeof(double);
+  double* tmp = (double*)gcge_hip_pool_alloc(bytes);
+  const int rc = gcge_hip_mg_galerkin_values_into(nf, d_rowptr, d_colidx, d_val, d_agg, nc, d_ptr, d_mem, scale, d_rp_c, d_ci_c, tmp, nullptr);
+  if (rc == 0) {
+    GCGE_HIP_CHECK(hipMemcpyAsync(d_va_c_out, tmp, bytes, hipMemcpyDeviceToDevice, mg_stream()));
+    GCGE_HIP_CHECK(hipStreamSynchronize(mg_stream()));
+  }
+  gcge_hip_pool_free(tmp, bytes);
+  return rc;
+}
+
 // P (rowptr[r] = r, colidx = agg, 1.0) and P^T (the members, 1.0) from device arrays: what gcge_hip_mat_create_rect makes from the
 // host arrays of gcge_mg_prolongation.  The arrays are copied; the caller keeps its own.
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_rect_device(int nf, int nc, const int* d_agg, const int* d_ptr, const int* d_mem) {
@@ -494,5 +583,33 @@ extern "C" int gcge_hip_mg_galerkin(const GCGE_HIP_MAT* A, const int* agg_host, 
   if (rc != 0) { memset(Ac_out, 0, sizeof *Ac_out); return 1; }
   rc = gcge_hip_mg_download_csr(nc, nc, nnz, d_rp, d_ci, d_va, Ac_out, nullptr);
   hipFree(d_rp); hipFree(d_ci); hipFree(d_va);
+  return rc;
+}
+
+// the values-only product on A's device CSR for a host agg and a host coarse structure (nc rows): va_c goes up as it is, comes back as
+// gcge_hip_mg_galerkin_values_device left it, and its return value is returned — tests and tools
+extern "C" int gcge_hip_mg_galerkin_values(const GCGE_HIP_MAT* A, const int* agg_host, int nc, double scale, const int* rp_c, const int* ci_c,
+                                           double* va_c) {
+  if (A == nullptr || agg_host == nullptr || rp_c == nullptr || ci_c == nullptr || va_c == nullptr || A->rect_ncols > 0 || nc < 1) return -1;
+  const int nf = A->nrows;
+  for (int r = 0; r < nf; ++r) if (agg_host[r] < 0 || agg_host[r] >= nc) return -2;
+  if (rp_c[0] != 0) return -2;
+  for (int I = 0; I < nc; ++I) if (rp_c[I + 1] < rp_c[I]) return -2;
+  const size_t nnz = (size_t)rp_c[nc];
+  for (size_t k = 0; k < nnz; ++k) if (ci_c[k] < 0 || ci_c[k] >= nc) return -2;
+  std::vector<int> ptr, mem;
+  gcge_hip_mg_members_host(agg_host, nf, nc, ptr, mem);
+  auto up = [](const void* h, size_t bytes) { void* d = nullptr; GCGE_HIP_CHECK(hipMalloc(&d, bytes ? bytes : 8)); GCGE_HIP_CHECK(hipMemcpy(d, h, bytes, hipMemcpyHostToDevice)); return d; };
+  GCGE_HIP_CHECK(hipStreamSynchronize(mg_stream()));
+  int* d_agg = (int*)up(agg_host, (size_t)nf * sizeof(int));
+  int* d_ptr = (int*)up(ptr.data(), ptr.size() * sizeof(int));
+  int* d_mem = (int*)up(mem.data(), (size_t)nf * sizeof(int));
+  int* d_rp = (int*)up(rp_c, ((size_t)nc + 1) * sizeof(int));
+  int* d_ci = (int*)up(ci_c, nnz * sizeof(int));
+  double* d_va = (double*)up(va_c, nnz * sizeof(double));
+  const int rc = gcge_hip_mg_galerkin_values_device(nf, A->d_rowptr, A->d_colidx, A->d_val, d_agg, nc, d_ptr, d_mem, scale, d_rp, d_ci, d_va);
+  GCGE_HIP_CHECK(hipStreamSynchronize(mg_stream()));
+  if (nnz > 0) GCGE_HIP_CHECK(hipMemcpy(va_c, d_va, nnz * sizeof(double), hipMemcpyDeviceToHost));
+  hipFree(d_agg); hipFree(d_ptr); hipFree(d_mem); hipFree(d_rp); hipFree(d_ci); hipFree(d_va);
   return rc;
 }

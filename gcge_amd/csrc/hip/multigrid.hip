@@ -63,7 +63,9 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_rect_csr(const GCGE_CSR* P) {
 
 
 // one hierarchy per MultiGridCreate call; found again through the A_array pointer MultiGridDestroy hands back
-struct MgHold { void** A_array; std::vector<GCGE_HIP_MAT*> owned; };
+// (scale, slab: what gcge_hip_multigrid_refresh needs to know of the build — the factor of its Galerkin products, and whether the levels
+// are row slabs, which it leaves alone)
+struct MgHold { void** A_array; std::vector<GCGE_HIP_MAT*> owned; int num_levels = 0; double scale = 0.5; bool slab = false; };
 static std::vector<MgHold> g_mg;
 static double g_mg_seconds = 0.0;
 extern "C" double gcge_hip_multigrid_seconds(void) { return g_mg_seconds; }   // host + upload time of the last MultiGridCreate
@@ -132,7 +134,8 @@ static void mg_install(const MgSlot& s, const MgBuilt& b) {
         fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, grid %d x %d x %d, K1 form %s%s\n", l, m->nrows, m->nnz, d[0], d[1], d[2],
                 gcge_hip_mat_spmm_form(m), b.how);
     }
-  h.A_array = *s.A_array;
+  h.A_array = *s.A_array; h.num_levels = L; h.slab = b.world > 0;
+  gcge_mg_get_defaults(&h.scale, nullptr, nullptr);       // (every build takes the defaults in force when it runs)
   g_mg.push_back(h);
   *s.num_levels = L;
 }
@@ -458,4 +461,57 @@ extern "C" void gcge_hip_multigrid_destroy(void*** A_array, void*** B_array, voi
   free(*A_array); *A_array = nullptr;
   free(*P_array); *P_array = nullptr;
   if (B_array != nullptr && *B_array != nullptr) { free(*B_array); *B_array = nullptr; }
+}
+
+// ------------------------------------------------------------------------------------------------------------ refresh in place
+// A live hierarchy after level 0 took new values (gcge_hip_mat_update_values_device): level by level the values of A_{l+1} = scale P_l^T
+// A_l P_l — the numeric half of the Galerkin product (k_mg_galerkin_values, mg_device.hip) on what the handles hold: level l's CSR, the
+// aggregates P_l keeps (agg = its columns, ptr / mem = its transpose) and level l + 1's own structure — into a block of the pool, then
+// through the in-place update of the coarse handle, which re-derives every stored copy of the values (pad-8, table or row values, star
+// diagonal, blocks).  The structure of a Galerkin product does not depend on the values and the sums are those of the build, so a
+// refreshed hierarchy is the fresh one bit for bit.  Nothing is all-or-nothing across levels: the first level that declines ends the
+// call, and the hierarchy is then stale from that level on (see include/gcge_hip.h).
+static long g_mr_stats[4] = {0, 0, 0, 0};
+extern "C" void gcge_hip_multigrid_refresh_stats(long out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_mr_stats[i]; }
+
+static bool mr_level_ok(const GCGE_HIP_MAT_* m) {
+  return m != nullptr && m->rect_ncols == 0 && m->nghost == 0 && m->row_begin == 0 && real_perm(m->perm) == nullptr && m->d_rowptr != nullptr;
+}
+// 0: level l + 1 of `arr` now holds scale P^T (level l) P; 1: declined, the level is as it was
+static int mr_level(void** arr, int l, const GCGE_HIP_MAT_* P, double scale) {
+  const GCGE_HIP_MAT_* f = (const GCGE_HIP_MAT_*)arr[l];
+  GCGE_HIP_MAT_* c = (GCGE_HIP_MAT_*)arr[l + 1];
+  const size_t bytes = (size_t)(c->nnz > 0 ? c->nnz : 1) * sizeof(double);
+  double* work = (double*)gcge_hip_pool_alloc(bytes);
+  long u0[6], u1[6];
+  gcge_hip_mat_update_stats(u0);
+  int rc = gcge_hip_mg_galerkin_values_into(f->nrows, f->d_rowptr, f->d_colidx, f->d_val, P->d_colidx, P->rect_ncols, P->d_t_rowptr, P->d_t_colidx,
+                                            scale, c->d_rowptr, c->d_colidx, work, &g_mr_stats[3]);
+  if (rc == 0) rc = gcge_hip_mat_update_values_device(c, c->nnz, work) != 0;
+  gcge_hip_mat_update_stats(u1);
+  g_mr_stats[3] += u1[5] - u0[5];
+  gcge_hip_pool_free(work, bytes);
+  if (rc == 0) g_mr_stats[2] += 1;
+  return rc;
+}
+extern "C" int gcge_hip_multigrid_refresh(void** A_array, void** B_array, void** P_array, int num_levels) {
+  const MgHold* h = nullptr;
+  for (const MgHold& k : g_mg) if (k.A_array == A_array) h = &k;
+  if (h == nullptr || A_array == nullptr || P_array == nullptr || num_levels != h->num_levels || h->slab) return -1;
+  const bool withB = B_array != nullptr && B_array[0] != nullptr;
+  for (int l = 0; l < num_levels; ++l) {
+    if (!mr_level_ok((const GCGE_HIP_MAT_*)A_array[l]) || (withB && !mr_level_ok((const GCGE_HIP_MAT_*)B_array[l]))) return -1;
+    if (withB && ((const GCGE_HIP_MAT_*)B_array[l])->nrows != ((const GCGE_HIP_MAT_*)A_array[l])->nrows) return -1;
+    if (l == 0) continue;
+    const GCGE_HIP_MAT_* P = (const GCGE_HIP_MAT_*)P_array[l - 1];
+    if (P == nullptr || !P->rect_one_per_row || P->d_t_rowptr == nullptr || P->nrows != ((const GCGE_HIP_MAT_*)A_array[l - 1])->nrows ||
+        P->rect_ncols != ((const GCGE_HIP_MAT_*)A_array[l])->nrows) return -1;
+  }
+  GCGE_HIP_CHECK(hipStreamSynchronize((hipStream_t)gcge_hip_stream()));
+  for (int l = 0; l + 1 < num_levels; ++l) {
+    const GCGE_HIP_MAT_* P = (const GCGE_HIP_MAT_*)P_array[l];
+    if (mr_level(A_array, l, P, h->scale) != 0 || (withB && mr_level(B_array, l, P, 1.0) != 0)) { g_mr_stats[1] += 1; return l + 1; }
+  }
+  g_mr_stats[0] += 1;
+  return 0;
 }

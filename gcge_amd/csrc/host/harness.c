@@ -69,6 +69,13 @@ void GCGE_AMGDestroy(GCGE_AMG **pamg, struct OPS_ *ops)
 	free(amg); *pamg = NULL;
 }
 
+int GCGE_AMGRefresh(GCGE_AMG *amg, struct OPS_ *ops)
+{
+	const GCGE_BACKEND be = GCGE_BackendOf(ops);
+	if (amg == NULL || be.multigrid_refresh == NULL) return -1;
+	return be.multigrid_refresh(amg->A_array, amg->B_array, amg->P_array, amg->num_levels);
+}
+
 /* evec_in != NULL: a block of nevMax columns owned by the caller whose first nevGiven columns are start vectors
  * (the `nevGiven` argument of ops->EigenSolver, reference src/ops_eig_sol_gcg.c:101-158) */
 static int run_gcg(void *A, void *B, int flag, int argc, char *argv[], struct OPS_ *ops,

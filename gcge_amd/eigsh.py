@@ -33,24 +33,31 @@ def _device_of(*things):
     return torch.cuda.current_device()
 
 
-def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=()):
+def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None):
     """The k smallest eigenvalues and their eigenvectors of the symmetric problem A x = lambda M x (M=None: the identity; M positive
     definite) by GCG on the GPU.  The smallest eigenvalues are the only mode.
 
     A, M:  a torch sparse_csr CUDA tensor, a (crow, col, val) triple of device arrays, or a matrix handle of the back-end.  Handles
            stay the caller's; what is created here is freed here.  A sequence of nearby operators on one sparsity structure keeps
            ONE handle and gives it new values between the solves (HipBackend.matrix_update_values), so no step re-creates the matrix:
-               m = hip.matrix_from_device(A0, updatable=True); r = eigsh(m, k, backend=hip)
+               m = hip.matrix_from_device(A0, updatable=True); h = hip.multigrid(m, levels=6, block_size=b)
+               r = eigsh(m, k, amg=h, backend=hip)
                for V in potentials:
-                   if not hip.matrix_update_values(m, values_of(V)):       # declined: nothing was written
-                       hip.free_matrix(m); m = hip.matrix_from_device(crow, col, values_of(V), updatable=True)
-                   r = eigsh(m, k, X0=r.eigenvectors, backend=hip)
+                   hip.matrix_update_values(m, values_of(V)) or recreate(...)    # declined: nothing was written; free m and h, create both again
+                   h.refresh()                                                   # the coarse levels follow, in place (False: built again)
+                   r = eigsh(m, k, X0=r.eigenvectors, amg=h, backend=hip)
            (updatable=True matters for real-space Hamiltonians — a Laplacian star, a local potential on the diagonal, atom blocks:
-           their handles keep the provenance of their stored values only on request; the star's coefficients must not change.)
+           their handles keep the provenance of their stored values only on request; the star's coefficients must not change.
+           Without a hierarchy the loop is the same minus the lines that name h.)
     X0:    (n, j) device tensor of start vectors, j <= nev_max (a warm start: the previous eigenvectors of a nearby operator).
     tol:   relative residual tolerance, ||A x - lambda M x|| <= tol |lambda|;  maxiter: outer iterations at most (default 500).
     nev_max (default 2 k), block_size:  columns of the eigenvector block and of the W block, as for the harness.
-    amg_levels:  0: the W systems by the fused block CG; L >= 2: by BlockAMG over a hierarchy of at most L levels.
+    amg_levels:  0: the W systems by the fused block CG; L >= 2: by BlockAMG over a hierarchy of at most L levels, built and freed
+           inside this call.
+    amg:   a Hierarchy (HipBackend.multigrid) built on the handles A (and M): the W systems by BlockAMG over it, as it is — nothing is
+           built here; Hierarchy.refresh() keeps it in step with new values.  block_size=None then means the hierarchy's block size.
+           ValueError: amg_levels given as well, A (or M) is not the handle the hierarchy was built on, a larger block_size than the
+           hierarchy's, a hierarchy of another back-end.
     backend:  a HipBackend (default: one per device, kept for the process).
     gcge_args:  harness options ("-gcge_compW_cg_max_iter", 40, ...), appended as they are; they win over the arguments above.
 
@@ -67,6 +74,19 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
         raise ValueError("eigsh: 1 <= k <= nev_max is required")
     if amg_levels == 1 or amg_levels < 0:
         raise ValueError("eigsh: amg_levels is 0 (no hierarchy) or at least 2")
+    if amg is not None:
+        as_int = lambda a: (a.value if isinstance(a, C.c_void_p) else a) if _is_handle(a) else None
+        if amg_levels > 0:
+            raise ValueError("eigsh: amg (a hierarchy that exists) and amg_levels (one built inside the call) exclude each other")
+        if as_int(A) is None or as_int(A) != amg.A.value or as_int(M) != (amg.M.value if amg.M is not None else None):
+            raise ValueError("eigsh: amg was not built on these matrix handles")
+        if block_size is not None and int(block_size) > amg.block_size:
+            raise ValueError("eigsh: block_size %d exceeds the hierarchy's %d" % (int(block_size), amg.block_size))
+        if backend is not None and backend is not amg.backend:
+            raise ValueError("eigsh: amg belongs to another back-end")
+        backend = amg.backend
+        if block_size is None:
+            block_size = amg.block_size
     if backend is None:
         dev = _device_of(A, M, X0)
         backend = _backends.get(dev)
@@ -102,7 +122,9 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
     try:
         mA = handle(A)
         mB = handle(M) if M is not None else None
-        flag = 1 if amg_levels > 0 else 0
+        flag = 1 if amg_levels > 0 or amg is not None else 0
+        if amg is not None:
+            amg.install()
         if X0 is not None:
             shape = tuple(X0.shape) if hasattr(X0, "shape") else tuple(X0.__cuda_array_interface__["shape"])
             if len(shape) != 2 or shape[1] > nev_max:

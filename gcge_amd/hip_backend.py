@@ -133,6 +133,15 @@ class HipBackendImpl:
             raise ValueError("gcge_hip_mat_update_values_device refused its arguments")
         return rc == 0
 
+    def multigrid(self, A, M=None, levels=6, block_size=8, cycles=1, smooth0=5, smooth=4, rate=1e-2, refreshable=True):
+        """A BlockAMG hierarchy over the matrix handle A (and M), kept by the caller across solves (GCGE_AMGCreate): at most `levels`
+        levels, work blocks of `block_size` columns per level, `cycles` V-cycles of smooth0 (level 0) / smooth (coarse levels) CG
+        iterations, level 0 smoothed to `rate`.  eigsh(A, k, M, amg=h) solves its W systems with it.  refreshable=True creates the
+        coarse levels with their value maps kept (as updatable=True does for a matrix), so that Hierarchy.refresh() can give a coarse
+        level with a star or dense form new values in place; the hierarchy and its products are the same either way.  The handles stay
+        the caller's and must outlive the hierarchy."""
+        return Hierarchy(self, A, M, int(levels), int(block_size), int(cycles), int(smooth0), int(smooth), float(rate), bool(refreshable))
+
     def mv_to_torch(self, mv, c0, c1):
         """Columns [c0, c1) of a block of vectors as a new (n, c1 - c0) float64 tensor on the GPU, rows in the caller's order
         (gcge_hip_mv_to_device): nothing passes through the host."""
@@ -243,3 +252,82 @@ class HipBackendImpl:
 
     def sync(self):
         self.g.gcge_hip_sync()
+
+
+class _AMGHead(C.Structure):
+    """The leading fields of GCGE_AMG (include/gcge_solver.h)."""
+    _fields_ = [("A_array", C.POINTER(C.c_void_p)), ("B_array", C.POINTER(C.c_void_p)), ("P_array", C.POINTER(C.c_void_p)),
+                ("num_levels", C.c_int), ("block_size", C.c_int), ("own_smoother", C.c_int)]
+
+
+class Hierarchy:
+    """What HipBackend.multigrid returns: a live GCGE_AMG (hierarchy, work blocks, parameter arrays) over the handles A and M.
+    .num_levels, .block_size, .A, .M; refresh() after the handles took new values in place; close() (or a with block) frees it."""
+
+    def __init__(self, backend, A, M, levels, block_size, cycles, smooth0, smooth, rate, refreshable):
+        if levels < 2 or block_size < 1:
+            raise ValueError("multigrid: at least 2 levels and a block of at least 1 column are required")
+        as_handle = lambda a: a if isinstance(a, C.c_void_p) or a is None else C.c_void_p(a)
+        self.backend, self.A, self.M = backend, as_handle(A), as_handle(M)
+        self._args = (levels, block_size, cycles, smooth0, smooth, rate)
+        self._refreshable = refreshable
+        self._graph_method = backend.h.gcge_mg_get_graph_method()
+        self._amg = None
+        self._create()
+
+    def _create(self):
+        b = self.backend
+        before = b.h.gcge_mg_get_graph_method()
+        b.h.gcge_mg_set_graph_method(self._graph_method)
+        try:
+            with b._keeping_value_maps(self._refreshable):
+                amg = b.h.GCGE_AMGCreate(self.A, self.M, *self._args, b.ops_handle)
+        finally:
+            b.h.gcge_mg_set_graph_method(before)
+        if not amg:
+            raise RuntimeError("GCGE_AMGCreate failed")
+        self._amg = C.c_void_p(amg)
+        head = C.cast(self._amg, C.POINTER(_AMGHead)).contents
+        self.num_levels, self.block_size = int(head.num_levels), int(head.block_size)
+
+    def _head(self):
+        if self._amg is None:
+            raise ValueError("the hierarchy is closed")
+        return C.cast(self._amg, C.POINTER(_AMGHead)).contents
+
+    def level_handles(self):
+        """(A handles of all levels, M handles of all levels ([] without M), P handles): the back-end's, valid until the next
+        refresh() that returns False or close()."""
+        h = self._head()
+        L = h.num_levels
+        Ah = [C.c_void_p(h.A_array[l]) for l in range(L)]
+        Bh = [C.c_void_p(h.B_array[l]) for l in range(L)] if self.M is not None and h.B_array else []
+        return Ah, Bh, [C.c_void_p(h.P_array[l]) for l in range(L - 1)]
+
+    def refresh(self):
+        """After A (and M) took new values in place (HipBackend.matrix_update_values): the coarse levels recomputed where they are
+        (GCGE_AMGRefresh).  True: refreshed in place.  False: a level declined or the back-end wrote nothing — the hierarchy was
+        destroyed and built again from the same handles and arguments.  Either way it now belongs to the present values."""
+        self._head()
+        if self.backend.h.GCGE_AMGRefresh(self._amg, self.backend.ops_handle) == 0:
+            return True
+        self.close()
+        self._create()
+        return False
+
+    def install(self):
+        """BlockAMG over this hierarchy into the back-end's table (GCGE_AMGInstall): the solver of a harness run with flag 1."""
+        self._head()
+        self.backend.h.GCGE_AMGInstall(self._amg, self.backend.ops_handle)
+
+    def close(self):
+        if self._amg is not None:
+            self.backend.h.GCGE_AMGDestroy(C.byref(self._amg), self.backend.ops_handle)
+            self._amg = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

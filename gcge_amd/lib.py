@@ -269,6 +269,32 @@ def mg_galerkin_device(mat, agg, nc, scale):
     return _take_csr(out)
 
 
+def mg_galerkin_values_device(mat, agg, nc, scale, rowptr_c, colidx_c, out):
+    """The values of scale P^T A P on the device for a HIP matrix handle, an aggregate map and a coarse structure that exists
+    (gcge_hip_mg_galerkin_values_device through gcge_hip_mg_galerkin_values): `out` (numpy float64, one value per coarse entry) goes
+    up as it is and comes back as the device function left it.  Returns 0 (written) or 1 (an entry's coarse column is not in its
+    coarse row: out is unchanged)."""
+    import numpy as np
+    ip = C.POINTER(C.c_int)
+    agg = np.ascontiguousarray(agg, dtype=np.int32)
+    rp, ci = np.ascontiguousarray(rowptr_c, dtype=np.int32), np.ascontiguousarray(colidx_c, dtype=np.int32)
+    if out.dtype != np.float64 or not out.flags.c_contiguous or len(out) != len(ci) or len(rp) != int(nc) + 1:
+        raise ValueError("mg_galerkin_values_device: nc + 1 row pointers and a contiguous float64 value per coarse entry are required")
+    rc = hip_lib().gcge_hip_mg_galerkin_values(mat, agg.ctypes.data_as(ip), int(nc), float(scale), rp.ctypes.data_as(ip), ci.ctypes.data_as(ip),
+                                               out.ctypes.data_as(C.POINTER(C.c_double)))
+    if rc < 0:
+        raise RuntimeError("gcge_hip_mg_galerkin_values failed: %d" % rc)
+    return rc
+
+
+def multigrid_refresh_stats():
+    """gcge_hip_multigrid_refresh_stats: (refreshes completed in place, calls that ended in a decline, levels written, bytes copied
+    device to host) since the library was loaded."""
+    out = (C.c_long * 4)()
+    hip_lib().gcge_hip_multigrid_refresh_stats(out)
+    return tuple(out)
+
+
 def mat_to_csr(mat, transpose=False):
     """A HIP matrix handle's device CSR (P^T of a rectangular handle with transpose=True) as numpy (rowptr, colidx, val)."""
     out = CSR()

@@ -108,7 +108,8 @@ void gcge_hip_mat_device_stats (long out[4]);
  * A conversion changes the K1 form between two solves.  Nothing in the back-end keeps a record of a handle's form across calls: the
  * fused CG plans every call from the handle (cg_plan, block_pcg.hip), its parked blocks are keyed by row count and row order, and
  * mat_product.hip reads the handle at every product.  A multigrid hierarchy built from the handle BEFORE an update belongs to the old
- * operator; the harness creates and destroys its hierarchy inside every solve, other callers of MultiGridCreate rebuild theirs.
+ * operator until gcge_hip_multigrid_refresh (below) has given its coarse levels the new Galerkin products; the harness creates and
+ * destroys its hierarchy inside every solve.
  * gcge_hip_mat_update_stats: since load, out[0] updates that kept the form, out[1] of those value-table rewrites, out[2] conversions
  * to "+values", out[3] declines, out[4] bad-argument returns, out[5] bytes copied device to host by updates — one flag word per
  * update that has a table or a star, whatever the size of the matrix.  gcge_hip_mat_device_stats is not touched.  An accepted update
@@ -227,6 +228,40 @@ void gcge_hip_multigrid_stats (double *seconds6, long *d2h_bytes);
 /*     the device Galerkin product scale P^T A P on A's device CSR for a host aggregate map agg[nrows] (0 <= agg < nc): a host CSR
  *     (gcge_csr_free); 0 on success, 1 when it is out of the kernels' reach, < 0 bad arguments                                     */
 int  gcge_hip_mg_galerkin (const GCGE_HIP_MAT *A, const int *agg_host, int nc, double scale, GCGE_CSR *Ac_out);
+/*     The numeric half alone, for a coarse structure that exists: the values of scale P^T A P into d_va_c_out, entry by entry where
+ *     d_rp_c / d_ci_c (nc rows, ascending columns) name them — the doubles gcge_hip_mg_galerkin_device and the host's gcge_mg_galerkin
+ *     give for these values (one wave per coarse row, its columns staged in LDS and searched, the sums in walk order; no float atomics).
+ *     A (nf rows) as device CSR, d_agg / d_ptr / d_mem the aggregate of every row and the members of every aggregate, device arrays.
+ *     0: written.  1: an entry's coarse column is not in its coarse row — the structure does not belong to this matrix — or a coarse
+ *     row holds more than 512 columns; d_va_c_out is then as it was.  One flag word comes back.
+ *     gcge_hip_mg_galerkin_values: the same on A's device CSR for a host aggregate map and a host structure; va_c goes up as it is and
+ *     comes back as the device function left it (< 0: bad arguments) — tests and tools.                                            */
+int  gcge_hip_mg_galerkin_values_device (int nf, const int *d_rowptr, const int *d_colidx, const double *d_val, const int *d_agg, int nc,
+		const int *d_ptr, const int *d_mem, double scale, const int *d_rp_c, const int *d_ci_c, double *d_va_c_out);
+int  gcge_hip_mg_galerkin_values (const GCGE_HIP_MAT *A, const int *agg_host, int nc, double scale, const int *rp_c, const int *ci_c,
+		double *va_c);
+/*     A live hierarchy of MultiGridCreate after its level 0 took new values in place (gcge_hip_mat_update_values_device on A_array[0],
+ *     and on B_array[0]): for l = 0 .. num_levels - 2 the values of level l + 1 are computed from level l's present values, P_l's
+ *     aggregates and level l + 1's own structure (gcge_hip_mg_galerkin_values_device, with the scale the build used) and handed to
+ *     gcge_hip_mat_update_values_device (A_{l+1}); the same for B with scale 1.0 when B_array is not NULL and holds a level 0.
+ *     Nothing else of the hierarchy changes: P, P^T, structures, forms (but a value table that becomes "+values"), row orders.
+ *       0     every level holds the Galerkin product of the level above it over the aggregates the hierarchy has.  On a grid or a
+ *             masked grid, whose cells do not depend on the values, that is the hierarchy a fresh MultiGridCreate gives, bit for bit;
+ *             aggregation over the graph (greedy or MIS-2) reads the off-diagonal values, so there a fresh build is the same
+ *             hierarchy only while the off-diagonals are (a new diagonal) and may otherwise choose other aggregates.
+ *       l>=1  level l was the first to decline — its in-place update (a star or dense level built without
+ *             gcge_hip_mat_keep_value_maps (1) in force, a pinned star coefficient that moved, an explicit zero in a table row ...)
+ *             or the structure check.  The levels below l are refreshed, those from l on keep their old values: still a usable
+ *             preconditioner of a nearby operator, no longer the Galerkin hierarchy (with a B, A of level l may have been written
+ *             when it is B that declines).  The caller destroys it and creates it again.
+ *       -1    nothing was written: A_array is not a hierarchy of this back-end, num_levels is not its level count, a hierarchy of row
+ *             slabs, a level whose handle re-ordered its rows.
+ *     Nothing outside the handles holds values derived from a level's matrix (the smoother's parked blocks are work space keyed by row
+ *     count and row order), so a refreshed hierarchy needs no other reset.  gcge_hip_multigrid_refresh_stats: since load, out[0]
+ *     refreshes that returned 0, out[1] calls that ended in a decline (l >= 1), out[2] levels written (A and B count separately),
+ *     out[3] bytes copied device to host (one flag word per product, plus those of the in-place updates).                          */
+int  gcge_hip_multigrid_refresh (void **A_array, void **B_array, void **P_array, int num_levels);
+void gcge_hip_multigrid_refresh_stats (long out[4]);
 /*     a handle's device CSR (square, or P of a rectangular one) / the P^T triple of a rectangular one as a host copy (gcge_csr_free) */
 int  gcge_hip_mat_to_csr (const GCGE_HIP_MAT *A, GCGE_CSR *out);
 int  gcge_hip_mat_to_csr_t (const GCGE_HIP_MAT *A, GCGE_CSR *out);

@@ -235,7 +235,10 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *   panel_norms_sq   out[j] = sum over the LOCAL rows of y[r, start + j]^2, j < end - start, for the panel y[:, start..end) that the
  *                 LAST call of MultiVecLinearComb wrote, summed by that call from the values it stored (no second pass over the
  *                 panel; a fixed order: the same sums on every run, rounded otherwise than MultiVecInnerProd('D')'s).  0 when that
- *                 call did not collect them, or wrote another panel, or any other call came in between. */
+ *                 call did not collect them, or wrote another panel, or any other call came in between.
+ *   multigrid_refresh   the coarse levels of a live hierarchy of ops->MultiGridCreate recomputed in place after level 0 took new
+ *                 values for the same structure: 0 done, l >= 1 the first level that declined (those below it are refreshed), -1
+ *                 nothing written (GCGE_AMGRefresh, gcge_solver.h; the HIP back-end's gcge_hip_multigrid_refresh, gcge_hip.h). */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -265,6 +268,7 @@ typedef struct GCGE_BACKEND_ {
 	GCGE_RITZ_IN_PLACE_FN ritz_in_place;
 	GCGE_PANEL_NORMS_FN panel_norms_sq;
 	int start_in_place;
+	int  (*multigrid_refresh) (void **A_array, void **B_array, void **P_array, int num_levels);
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

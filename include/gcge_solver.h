@@ -104,6 +104,11 @@ GCGE_AMG *GCGE_AMGCreate (void *A, void *B, int max_levels, int block_size, int 
 		struct OPS_ *ops);
 void GCGE_AMGInstall (GCGE_AMG *amg, struct OPS_ *ops);
 void GCGE_AMGDestroy (GCGE_AMG **amg, struct OPS_ *ops);
+/*     After A (and B) took new values in place for the same structure: the coarse levels of amg's hierarchy recomputed where they are,
+ *     through the back-end's multigrid_refresh (GCGE_BACKEND, gcge_ops.h), whose return value this is — 0: the hierarchy of the new
+ *     values; l >= 1: level l declined, the caller destroys the hierarchy and creates it again; -1: nothing was written, also when
+ *     the back-end of `ops` offers no refresh.  Work blocks, parameter arrays and the installed solver are not touched.          */
+int  GCGE_AMGRefresh (GCGE_AMG *amg, struct OPS_ *ops);
 
 /* ---- GCG eigensolver (sets ops->EigenSolver) -------------------------------- */
 typedef struct GCGSolver_ {

@@ -5,6 +5,7 @@ total set-up time, for one problem of the existing generators.
   python tools/mg_setup_probe.py ball <G> <K> [levels] [solve]
   python tools/mg_setup_probe.py perm <size> [levels] [solve]
   python tools/mg_setup_probe.py delaunay <points> [levels] [solve]
+  python tools/mg_setup_probe.py refresh <lap3d|sio2> <size> [levels] [K]
 
 ball: the masked grid of BASELINE config 5 (the ball in the G^3 box, K atoms, R0 = 2.0, R1 = 5.0 as in bench.py --config c5), its
 geometry named; each mode is run with the cells of the box and with the graph branch (gcge_hip_multigrid_masked_cells).  With `solve`: one GCG solve (nev 10, block 64 columns of W) with BlockAMG over each of the
@@ -18,6 +19,11 @@ rounds of every level); with `solve` one GCG solve (nev 10) with BlockAMG over e
 hostlevels (any kind): gcge_hip_multigrid_device_levels(0) — the device build downloads every coarse level for the host constructors
 instead of handing it to gcge_hip_mat_create_device.
 
+refresh: a live hierarchy refreshed in place (gcge_hip_multigrid_refresh) against MultiGridCreate on the same handle, in one process:
+an updatable handle (sio2: K atoms, R0 = 2.0, R1 = 5.0 as in bench.py --config c5; default K 2000), a new diagonal for level 0 through
+gcge_hip_mat_update_values_device before every timed call, every timed call bracketed by a stream synchronise, one warm-up, then the
+median of 5 (min and max beside it); the phase split of the fresh build, the bytes each copies device to host, one JSON line at the end.
+
 Mode 0 builds the hierarchy on the device (csrc/hip/mg_device.hip), mode 1 on the host (csrc/host/multigrid.c); both give the same
 hierarchy.  Each mode is timed on a fresh MultiGridCreate after one warm-up call; the rows, K1 form and row order of its levels are listed."""
 import ctypes as C
@@ -28,7 +34,100 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def refresh_leg(argv):
+    import json
+    import statistics
+    import torch
+    from gcge_amd import HipBackend
+    from gcge_amd.lib import csr_arrays, hip_lib, make_problem, multigrid_refresh_stats, multigrid_stats
+    from gcge_amd.ops_struct import OPS
+    kind, size = argv[0], int(argv[1])
+    levels = int(argv[2]) if len(argv) > 2 else 6
+    K = int(argv[3]) if len(argv) > 3 else 2000
+    hip = HipBackend()
+    g = hip_lib()
+    A, _ = make_problem(kind, size, **(dict(K=K, R0=2.0, R1=5.0, seed=12345) if kind == "sio2" else {}))
+    t = time.perf_counter()
+    m = hip.matrix(A, updatable=True)
+    hip.sync()
+    print("%s %d: %d rows, %d non-zeros; upload with value maps kept %.2f s, K1 form %s" % (
+        kind, size, A.nrows, A.nnz, time.perf_counter() - t, g.gcge_hip_mat_spmm_form(m).decode()))
+    rp, ci, va = (torch.from_numpy(a).cuda() for a in csr_arrays(A))
+    rows = torch.repeat_interleave(torch.arange(A.nrows, device=rp.device, dtype=torch.int32), (rp[1:] - rp[:-1]).long())
+    diag = (rows == ci).nonzero().reshape(-1)
+    pot = 0.25 * (1.0 + (rows[diag] % 11).double())
+    del rows, rp, ci
+
+    def values(step):                       # the creation values with step * pot on the diagonal
+        v = va.clone()
+        v[diag] += step * pot
+        return v
+    st = C.cast(hip.ops_handle, C.POINTER(OPS)).contents
+    create = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_void_p)(st.MultiGridCreate)
+    destroy = C.CFUNCTYPE(None, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p)(st.MultiGridDestroy)
+
+    def build(keep_maps):
+        A_arr, P_arr, nl = C.c_void_p(), C.c_void_p(), C.c_int(levels)
+        with hip._keeping_value_maps(keep_maps):
+            create(C.byref(A_arr), None, C.byref(P_arr), C.byref(nl), m, None, hip.ops_handle)
+        return A_arr, P_arr, nl
+
+    def free(hier):
+        destroy(C.byref(hier[0]), None, C.byref(hier[1]), C.byref(hier[2]), hip.ops_handle)
+
+    def med(ts):
+        return {"median_s": statistics.median(ts), "min_s": min(ts), "max_s": max(ts), "calls": len(ts)}
+    out = {"kind": kind, "size": size, "K": K if kind == "sio2" else None, "levels_asked": levels, "rows": A.nrows, "nnz": int(A.nnz)}
+    assert hip.matrix_update_values(m, values(1)), "level 0 declined the new diagonal"
+    for keep_maps in (True, False):
+        ts = []
+        for rep in range(6):
+            hip.sync()
+            t = time.perf_counter()
+            hier = build(keep_maps)
+            hip.sync()
+            ts.append(time.perf_counter() - t)
+            secs, d2h = multigrid_stats()
+            free(hier)
+        key = "fresh_build_maps_kept" if keep_maps else "fresh_build"
+        out[key] = dict(med(ts[1:]), phases_s=secs, d2h_bytes=d2h)
+        print("MultiGridCreate, value maps %s: median %.4f s (min %.4f, max %.4f) of 5 after a warm-up  [%s]  device->host %d bytes" % (
+            "kept" if keep_maps else "not kept", out[key]["median_s"], out[key]["min_s"], out[key]["max_s"],
+            "  ".join("%s %.4f" % kv for kv in secs.items()), d2h))
+    hier = build(True)
+    L = hier[2].value
+    out["levels"] = []
+    for lev, a in enumerate(C.cast(hier[0], C.POINTER(C.c_void_p * L)).contents):
+        out["levels"].append({"rows": g.gcge_hip_mat_nrows(a), "nnz": g.gcge_hip_mat_nnz(a), "form": g.gcge_hip_mat_spmm_form(a).decode()})
+        print("  level %d: %d rows, %d non-zeros, K1 form %s" % (lev, out["levels"][-1]["rows"], out["levels"][-1]["nnz"], out["levels"][-1]["form"]))
+    ts, tu, rcs, moved = [], [], [], []
+    for rep in range(6):
+        v = values(2 + rep % 2)
+        hip.sync()
+        t = time.perf_counter()
+        assert hip.matrix_update_values(m, v)
+        hip.sync()
+        tu.append(time.perf_counter() - t)
+        s0 = multigrid_refresh_stats()
+        t = time.perf_counter()
+        rc = g.gcge_hip_multigrid_refresh(hier[0], None, hier[1], L)
+        hip.sync()
+        ts.append(time.perf_counter() - t)
+        rcs.append(rc)
+        moved.append(multigrid_refresh_stats()[3] - s0[3])
+    free(hier)
+    out["refresh"] = dict(med(ts[1:]), returned=rcs, d2h_bytes=moved[-1])
+    out["level0_update"] = med(tu[1:])
+    print("gcge_hip_multigrid_refresh: median %.4f s (min %.4f, max %.4f) of 5 after a warm-up, returned %s, device->host %d bytes; "
+          "the update of level 0 before it: median %.4f s" % (out["refresh"]["median_s"], out["refresh"]["min_s"], out["refresh"]["max_s"], rcs,
+                                                              moved[-1], out["level0_update"]["median_s"]))
+    print(json.dumps(out))
+    hip.free_matrix(m)
+
+
 def main():
+    if sys.argv[1] == "refresh":
+        return refresh_leg(sys.argv[2:])
     import torch  # noqa: F401  (one libamdhip64, shared with torch)
     from gcge_amd import HipBackend
     from gcge_amd.lib import (CSR, ball_geometry, csr_to_scipy, hip_lib, make_problem, multigrid_graph_method, multigrid_masked_cells,
