@@ -88,6 +88,9 @@ struct GCGE_HIP_MAT_ {
   // value maps of the star split (mat_values_forms.hip; NULL: none kept — gcge_hip_mat_keep_value_maps was off at creation, or no grid
   // form); those of the block form live behind star_rem / dense
   struct GcgeStarMaps* star_maps;
+  // entry map of a re-ordered handle (mat_upload.hip "row orders"; NULL: none kept — the rows are as given, or
+  // gcge_hip_mat_keep_value_maps was off at creation): d_val[q] holds the caller's entry d_emap[q]; nnz ints
+  int* d_emap;
 };
 // mat_values_forms.hip: the device copy of a split's maps (H->keep_maps), and the two halves of an update of a star / dense handle
 extern "C" struct GcgeStarMaps* gcge_hip_star_maps_create(const void* star_host, long nnz);

@@ -327,24 +327,59 @@ extern "C" GcgePerm* gcge_hip_perm_identity(int n) {
   if (P == nullptr) P = perm_register(n, nullptr);
   return P->identity ? P : nullptr;
 }
-// P A P^T as CSR with ascending columns: new row i = old row perm[i], old column c -> iperm[c]
-static void permute_csr(int n, const int* rowptr, const int* colidx, const double* val, const GcgePerm* P,
-                        std::vector<int>& rp, std::vector<int>& ci, std::vector<double>& va) {
-  rp.resize((size_t)n + 1); ci.resize((size_t)rowptr[n] ? (size_t)rowptr[n] : 1); va.resize(ci.size());
+// P A P^T as CSR with ascending columns: new row i = old row perm[i], old column c -> iperm[c].  Each entry rides through the sort
+// with its index in the caller's arrays (the columns of a row are distinct: the order is decided by them alone); emap (may be NULL)
+// takes it: emap[q] = k, the entry of the caller's arrays that sits at position q of the new ones — what an update of the values in
+// place needs (mat_values.hip).  val and va may be NULL together: the structure alone.
+static void permute_csr_into(int n, const int* rowptr, const int* colidx, const double* val, const int* perm, const int* iperm,
+                             int* rp, int* ci, double* va, int* emap) {
   rp[0] = 0;
-  for (int i = 0; i < n; ++i) rp[i + 1] = rp[i] + (rowptr[P->perm[i] + 1] - rowptr[P->perm[i]]);
+  for (int i = 0; i < n; ++i) rp[i + 1] = rp[i] + (rowptr[perm[i] + 1] - rowptr[perm[i]]);
   gcge_parallel_chunks(n, gcge_upload_threads(), [&](int, long r0, long r1) {
-    std::vector<std::pair<int, double>> tmp;
+    std::vector<std::pair<int, int>> tmp;             // (new column, the caller's entry)
     for (long i = r0; i < r1; ++i) {
-      const int o = P->perm[i];
+      const int o = perm[i];
       tmp.clear();
-      for (int k = rowptr[o]; k < rowptr[o + 1]; ++k) tmp.emplace_back(P->iperm[colidx[k]], val[k]);
-      std::sort(tmp.begin(), tmp.end(), [](const std::pair<int, double>& a, const std::pair<int, double>& b) { return a.first < b.first; });
+      for (int k = rowptr[o]; k < rowptr[o + 1]; ++k) tmp.emplace_back(iperm[colidx[k]], k);
+      std::sort(tmp.begin(), tmp.end(), [](const std::pair<int, int>& a, const std::pair<int, int>& b) { return a.first < b.first; });
       int q = rp[i];
-      for (auto& e : tmp) { ci[q] = e.first; va[q] = e.second; ++q; }
+      for (auto& e : tmp) {
+        ci[q] = e.first;
+        if (va != nullptr) va[q] = val[e.second];
+        if (emap != nullptr) emap[q] = e.second;
+        ++q;
+      }
     }
   });
 }
+static void permute_csr(int n, const int* rowptr, const int* colidx, const double* val, const GcgePerm* P,
+                        std::vector<int>& rp, std::vector<int>& ci, std::vector<double>& va, std::vector<int>* emap) {
+  rp.resize((size_t)n + 1); ci.resize((size_t)rowptr[n] ? (size_t)rowptr[n] : 1); va.resize(ci.size());
+  if (emap != nullptr) emap->resize(ci.size());
+  permute_csr_into(n, rowptr, colidx, val, P->perm, P->iperm, rp.data(), ci.data(), va.data(), emap != nullptr ? emap->data() : nullptr);
+}
+// tests: the routine above on the caller's arrays, no device.  perm[new] = old; rowptr_new: n + 1 ints, colidx_new and emap: rowptr[n]
+// ints each.  0: done; -1: perm is no permutation of [0, n), or n < 0
+extern "C" int gcge_hip_reorder_entry_map(int n, const int* rowptr, const int* colidx, const int* perm, int* rowptr_new, int* colidx_new, int* emap) {
+  if (n < 0 || rowptr_new == nullptr) return -1;
+  if (n == 0) { rowptr_new[0] = 0; return 0; }
+  if (rowptr == nullptr || perm == nullptr || colidx_new == nullptr || emap == nullptr || (colidx == nullptr && rowptr[n] > 0)) return -1;
+  std::vector<int> iperm((size_t)n, -1);
+  for (int i = 0; i < n; ++i) {
+    if (perm[i] < 0 || perm[i] >= n || iperm[perm[i]] >= 0) return -1;
+    iperm[perm[i]] = i;
+  }
+  permute_csr_into(n, rowptr, colidx, nullptr, perm, iperm.data(), rowptr_new, colidx_new, nullptr, emap);
+  return 0;
+}
+// The entry map of a re-ordered handle goes to the device when gcge_hip_mat_keep_value_maps is on at creation (4 bytes per entry: too
+// much to keep unasked); with the switch off the handle is what it is without this record.
+static void mat_keep_entry_map(GCGE_HIP_MAT* A, const std::vector<int>& emap) {
+  if (A == nullptr) return;
+  GCGE_HIP_CHECK(hipMalloc(&A->d_emap, (size_t)(A->nnz > 0 ? A->nnz : 1) * sizeof(int)));
+  GCGE_HIP_CHECK(hipMemcpy(A->d_emap, emap.data(), (size_t)A->nnz * sizeof(int), hipMemcpyHostToDevice));
+}
+extern "C" long gcge_hip_mat_entry_map(const GCGE_HIP_MAT* A) { return (A != nullptr && A->d_emap != nullptr) ? (long)A->nnz * (long)sizeof(int) : 0; }
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_begin, const int* rowptr,
                                              const int* colidx, const double* val) {
   if (row_begin != 0 || nrows != nglobal) {
@@ -353,16 +388,20 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_beg
   }
   const bool timing = getenv("GCGE_UPLOAD_TIMING") != nullptr;
   std::vector<int> rp, ci; std::vector<double> va;
-  // a matrix of this size lives in this process already: the new one shares its row order (B after A of a generalised problem)
+  std::vector<int> em;                                      // the entry map, recorded only where an update in place was asked for
+  std::vector<int>* emap = g_keep_value_maps ? &em : nullptr;
+  // a matrix of this size lives in this process already: the new one shares its row order (B after A of a generalised problem; its
+  // structure is its own, and so is its entry map)
   if (GcgePerm* P = perm_find(nrows)) {
     if (P->identity) {
       GCGE_HIP_MAT* A = gcge_hip_mat_create_local(nrows, nrows, nglobal, 0, rowptr, colidx, val);
       if (A != nullptr) A->perm = gcge_hip_perm_acquire(P);
       return A;
     }
-    permute_csr(nrows, rowptr, colidx, val, P, rp, ci, va);
+    permute_csr(nrows, rowptr, colidx, val, P, rp, ci, va, emap);
     GCGE_HIP_MAT* A = gcge_hip_mat_create_local(nrows, nrows, nglobal, 0, rp.data(), ci.data(), va.data());
     if (A != nullptr) A->perm = gcge_hip_perm_acquire(P);
+    if (A != nullptr && emap != nullptr) mat_keep_entry_map(A, em);
     return A;
   }
   GCGE_HIP_MAT* A = gcge_hip_mat_create_local(nrows, nrows, nglobal, 0, rowptr, colidx, val);
@@ -392,7 +431,7 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_beg
   if (!have) { A->perm = gcge_hip_perm_acquire(perm_register(nrows, nullptr)); return A; }
   gcge_hip_mat_destroy(A);
   GcgePerm* P = perm_register(nrows, perm.data());
-  permute_csr(nrows, rowptr, colidx, val, P, rp, ci, va);
+  permute_csr(nrows, rowptr, colidx, val, P, rp, ci, va, emap);
   const bool masked = grid && (long)dims[0] * dims[1] * dims[2] != nrows;   // a ball: name the geometry for the plane sweep's row map
   std::vector<int> bsorted(masked ? (size_t)nrows : 0);
   for (int i = 0; i < nrows && masked; ++i) bsorted[i] = box[perm[i]];
@@ -400,6 +439,7 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create(int nrows, int nglobal, int row_beg
   A = mat_create_local(nrows, nrows, nglobal, 0, rp.data(), ci.data(), va.data(), nullptr, masked ? &geom : nullptr);
   if (A == nullptr) { gcge_hip_perm_release(gcge_hip_perm_acquire(P)); return nullptr; }
   A->perm = gcge_hip_perm_acquire(P);
+  if (emap != nullptr) mat_keep_entry_map(A, em);
   return A;
 }
 // A matrix on a MASKED grid (one rank): row r is grid point box_of_row[r] = x + nx (y + ny z) of an nx x ny x nz box, rows in scan
@@ -463,6 +503,7 @@ extern "C" void gcge_hip_mat_destroy(GCGE_HIP_MAT* A) {
   if (A->star_rem != nullptr) gcge_hip_dense_free(A->star_rem);
   if (A->star != nullptr) gcge_hip_star_free(A->star);
   if (A->star_maps != nullptr) gcge_hip_star_maps_free(A->star_maps);
+  if (A->d_emap != nullptr) hipFree(A->d_emap);
   if (A->native_halo != nullptr) gcge_hip_halo_native_free(A);   // RCCL plan + the exchange buffers it owns (rccl_comm.hip)
   free(A->h_ghost_global); free(A->h_part);
   free(A->h_box); if (A->d_box) hipFree(A->d_box);

@@ -474,8 +474,10 @@ extern "C" void gcge_hip_multigrid_destroy(void*** A_array, void*** B_array, voi
 static long g_mr_stats[4] = {0, 0, 0, 0};
 extern "C" void gcge_hip_multigrid_refresh_stats(long out[4]) { for (int i = 0; i < 4; ++i) out[i] = g_mr_stats[i]; }
 
-static bool mr_level_ok(const GCGE_HIP_MAT_* m) {
-  return m != nullptr && m->rect_ncols == 0 && m->nghost == 0 && m->row_begin == 0 && real_perm(m->perm) == nullptr && m->d_rowptr != nullptr;
+// Level 0 may live in a row order of the back-end's own (mat_upload.hip "row orders"): the hierarchy was built from the handle's CSR, in
+// the handle's order, and P_0's rows are numbered like it.  A re-ordered coarse level would contradict its prolongation.
+static bool mr_level_ok(const GCGE_HIP_MAT_* m, int level) {
+  return m != nullptr && m->rect_ncols == 0 && m->nghost == 0 && m->row_begin == 0 && (level == 0 || real_perm(m->perm) == nullptr) && m->d_rowptr != nullptr;
 }
 // 0: level l + 1 of `arr` now holds scale P^T (level l) P; 1: declined, the level is as it was
 static int mr_level(void** arr, int l, const GCGE_HIP_MAT_* P, double scale) {
@@ -500,7 +502,7 @@ extern "C" int gcge_hip_multigrid_refresh(void** A_array, void** B_array, void**
   if (h == nullptr || A_array == nullptr || P_array == nullptr || num_levels != h->num_levels || h->slab) return -1;
   const bool withB = B_array != nullptr && B_array[0] != nullptr;
   for (int l = 0; l < num_levels; ++l) {
-    if (!mr_level_ok((const GCGE_HIP_MAT_*)A_array[l]) || (withB && !mr_level_ok((const GCGE_HIP_MAT_*)B_array[l]))) return -1;
+    if (!mr_level_ok((const GCGE_HIP_MAT_*)A_array[l], l) || (withB && !mr_level_ok((const GCGE_HIP_MAT_*)B_array[l], l))) return -1;
     if (withB && ((const GCGE_HIP_MAT_*)B_array[l])->nrows != ((const GCGE_HIP_MAT_*)A_array[l])->nrows) return -1;
     if (l == 0) continue;
     const GCGE_HIP_MAT_* P = (const GCGE_HIP_MAT_*)P_array[l - 1];

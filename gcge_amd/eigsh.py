@@ -47,7 +47,9 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
                    h.refresh()                                                   # the coarse levels follow, in place (False: built again)
                    r = eigsh(m, k, X0=r.eigenvectors, amg=h, backend=hip)
            (updatable=True matters for real-space Hamiltonians — a Laplacian star, a local potential on the diagonal, atom blocks:
-           their handles keep the provenance of their stored values only on request; the star's coefficients must not change.
+           their handles keep the provenance of their stored values only on request; the star's coefficients must not change —
+           and for matrices in a numbering that shows no grid, which the back-end re-orders inside the handle: such a handle is
+           declined only when it was created without updatable=True; the values stay in the caller's entry order.
            Without a hierarchy the loop is the same minus the lines that name h.)
     X0:    (n, j) device tensor of start vectors, j <= nev_max (a warm start: the previous eigenvectors of a nearby operator).
     tol:   relative residual tolerance, ||A x - lambda M x|| <= tol |lambda|;  maxiter: outer iterations at most (default 500).

@@ -43,7 +43,9 @@ class HipBackendImpl:
     def matrix(self, csr, updatable=False):
         """updatable=True: a handle that takes the star or the dense form also keeps where its stored values came from (about 4 bytes
         per block and remainder slot on the device, gcge_hip_mat_value_maps), so that matrix_update_values can give it new values in
-        place; without it such a handle declines every update.  The forms and the products are the same either way."""
+        place; without it such a handle declines every update.  The forms and the products are the same either way.  A handle that
+        re-orders its rows keeps, under the same switch, which of the caller's entries sits at each of its own positions (4 bytes
+        per entry, gcge_hip_mat_entry_map), and declines every update without it."""
         with self._keeping_value_maps(updatable):
             m = self.g.gcge_hip_mat_create_csr(C.byref(csr))
         if not m:
@@ -103,9 +105,12 @@ class HipBackendImpl:
         A handle with a star or a dense form (real-space Hamiltonians: a Laplacian star, a diagonal, atom blocks) takes new values
         when it was created with updatable=True: the diagonal and every entry the star does not carry may change, the star's
         coefficients stay (an entry that equalled its coefficient at creation must keep it).
-        False: the library declined and wrote nothing (a star / dense handle created without updatable=True or given other star
-        coefficients or a NaN diagonal, tile forms, slabs, re-ordered handles, a 16-slot table whose classes do not stay uniform,
-        an explicitly stored zero): free the handle and create the matrix again.
+        A handle that re-ordered its rows (a matrix that shows no grid in the numbering it arrives in) takes new values when it was
+        created with updatable=True as well: it then keeps which of the caller's entries sits where (4 bytes per entry on the
+        device), `values` stays in the CALLER's entry order, and the call gathers it through a transient block of 8 bytes per entry.
+        False: the library declined and wrote nothing (a star / dense handle or a re-ordered handle created without updatable=True,
+        other star coefficients or a NaN diagonal, tile forms, slabs, a 16-slot table whose classes do not stay uniform, an
+        explicitly stored zero): free the handle and create the matrix again.
         TypeError: a host tensor; ValueError: another count of values than the handle has entries (checked here)."""
         import torch
         foreign = not isinstance(values, torch.Tensor)
@@ -307,7 +312,9 @@ class Hierarchy:
     def refresh(self):
         """After A (and M) took new values in place (HipBackend.matrix_update_values): the coarse levels recomputed where they are
         (GCGE_AMGRefresh).  True: refreshed in place.  False: a level declined or the back-end wrote nothing — the hierarchy was
-        destroyed and built again from the same handles and arguments.  Either way it now belongs to the present values."""
+        destroyed and built again from the same handles and arguments.  Either way it now belongs to the present values.  A level 0
+        that re-ordered its rows is refreshed like any other (it took its values in place only if created with updatable=True);
+        hierarchies of row slabs are built again."""
         self._head()
         if self.backend.h.GCGE_AMGRefresh(self._amg, self.backend.ops_handle) == 0:
             return True

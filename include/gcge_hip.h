@@ -82,7 +82,8 @@ void gcge_hip_mat_device_stats (long out[4]);
  *   0    updated: every product, CG pass and residual through the handle is now that of (rowptr, colidx, d_val).
  *   1    declined: NOTHING of the handle was written (all checks run before the first store); the caller re-creates the matrix.
  *   < 0  bad arguments (NULL handle or array, nnz != gcge_hip_mat_nnz (A)); nothing written.
- * One rank, a whole square matrix, rows as given or in the identity order.  What becomes of the handle:
+ * One rank, a whole square matrix.  Its rows may be as given or re-ordered inside the handle (gcge_hip_spmm_reorder_mode; its own bullet below);
+ * d_val is in the CALLER's entry order either way.  What becomes of the handle:
  *   CSR + pad-8 only (no pattern, star, dense or tile form): d_val and the pad-8 values are rewritten, any values; form unchanged.
  *   offsets-only table + per-row values (the "+values" forms of gcge_hip_mat_spmm_form): the same, and the per-row values are
  *     re-scattered by the slot rule of the upload (gcge_pat_value_slot, csrc/hip/pattern_table.h); form unchanged.
@@ -99,12 +100,18 @@ void gcge_hip_mat_device_stats (long out[4]);
  *     gathered from it (without a star: from d_val), pads +0.0.  Form, split, blocks, layers and lists are unchanged.  The star's
  *     coefficients are fixed for the life of the handle: an entry that sits at a star position and equalled the coefficient at
  *     creation (it has no slot of its own) must keep those bits.  Every other entry is free, the diagonal any value but NaN.
+ *   a handle that re-ordered its rows (gcge_hip_mat_row_order is not "as given"), created while gcge_hip_mat_keep_value_maps was on: it
+ *     kept, on the device, which entry of the caller's arrays sits at each position of its own CSR (gcge_hip_mat_entry_map bytes, 4 per
+ *     entry).  The update gathers d_val through that map into a block of nnz doubles from the back-end's pool — a TRANSIENT 8 bytes per
+ *     entry, for the duration of the call — and then proceeds by the bullet above that fits the handle's form, on that block; the gather
+ *     writes the block only, so a decline still leaves the handle untouched.  The block returns to the pool after the call's last
+ *     synchronisation.
  *   declined (1): a value table of 16 slots whose classes do not stay uniform; a row whose count of present table slots (table value
  *     != 0.0) differs from its length, i.e. an explicitly stored +-0.0; under a star, a pinned entry whose new value differs in bits
  *     from its coefficient (a rescaled Laplacian, say) or a NaN on the diagonal; and, decided from the handle alone before d_val is
  *     read, a star or dense handle WITHOUT value maps (the switch was off at creation: the default), a dense form whose remainder is
  *     tiled, any handle with a tile form, a rectangular handle, a row slab (halo columns, row_begin != 0, a halo plan), a re-ordered
- *     handle.
+ *     handle WITHOUT an entry map (the switch was off at creation).
  * A conversion changes the K1 form between two solves.  Nothing in the back-end keeps a record of a handle's form across calls: the
  * fused CG plans every call from the handle (cg_plan, block_pcg.hip), its parked blocks are keyed by row count and row order, and
  * mat_product.hip reads the handle at every product.  A multigrid hierarchy built from the handle BEFORE an update belongs to the old
@@ -131,9 +138,18 @@ void gcge_hip_mat_update_form_stats (long out[4]);
  * for the duration of the call), the maps replayed on val1 through value_maps.h, star + diagonal + blocks + remainder expanded back into
  * per-row sums per column and compared with the CSR rows of val1.  Returns the number of differing entries, (row, column) pairs
  * (0: equal), -1: neither a star nor a dense form, -2: an update to val1 would be declined.  out[0] forms found (1 star, 2 blocks, 3 both), out[1] layers of blocks,
- * out[2] pinned entries, out[3] bytes of maps.  _grid: with the masked grid of gcge_hip_mat_create_grid named.                        */
+ * out[2] pinned entries, out[3] bytes of maps.  _grid: with the masked grid of gcge_hip_mat_create_grid named.
+ * The same switch makes a handle that RE-ORDERS its rows (gcge_hip_mat_create under gcge_hip_spmm_reorder_mode, a later matrix of the
+ * same size that adopts the live order, the host path gcge_hip_mat_create_device falls back to) keep its entry map on the device:
+ * 4 bytes per entry (1.4 GB at 350 M entries), freed with the handle.  gcge_hip_mat_entry_map: the bytes of entry map a handle holds
+ * (0: none); gcge_hip_mat_value_maps does not count them.  With the switch off such a handle is what it is without this record.
+ * gcge_hip_reorder_entry_map (host only, no device; tests): the routine the upload re-orders with, on the caller's arrays: perm[new]
+ * = old (n ints); rowptr_new (n + 1 ints) / colidx_new (rowptr[n] ints): P A P^T with ascending columns; emap[q] (rowptr[n] ints):
+ * the index in colidx of the entry at position q of colidx_new.  0: done (n = 0: rowptr_new[0] = 0); -1: perm is no permutation.    */
 int  gcge_hip_mat_keep_value_maps (int on);
 long gcge_hip_mat_value_maps (const GCGE_HIP_MAT *A);
+long gcge_hip_mat_entry_map (const GCGE_HIP_MAT *A);
+int  gcge_hip_reorder_entry_map (int n, const int *rowptr, const int *colidx, const int *perm, int *rowptr_new, int *colidx_new, int *emap);
 long gcge_hip_value_maps_selfcheck (int nrows, const int *rowptr, const int *colidx, const double *val0, const double *val1, int dense_mode,
                                     long out[4]);
 long gcge_hip_value_maps_selfcheck_grid (int nrows, const int *rowptr, const int *colidx, const double *val0, const double *val1, int dense_mode,
@@ -255,7 +271,8 @@ int  gcge_hip_mg_galerkin_values (const GCGE_HIP_MAT *A, const int *agg_host, in
  *             preconditioner of a nearby operator, no longer the Galerkin hierarchy (with a B, A of level l may have been written
  *             when it is B that declines).  The caller destroys it and creates it again.
  *       -1    nothing was written: A_array is not a hierarchy of this back-end, num_levels is not its level count, a hierarchy of row
- *             slabs, a level whose handle re-ordered its rows.
+ *             slabs, a COARSE level whose handle re-ordered its rows (level 0 may: the hierarchy was built from its CSR in its own order
+ *             and P_0's rows are numbered like it; it takes its new values as gcge_hip_mat_update_values_device states).
  *     Nothing outside the handles holds values derived from a level's matrix (the smoother's parked blocks are work space keyed by row
  *     count and row order), so a refreshed hierarchy needs no other reset.  gcge_hip_multigrid_refresh_stats: since load, out[0]
  *     refreshes that returned 0, out[1] calls that ended in a decline (l >= 1), out[2] levels written (A and B count separately),
