@@ -774,6 +774,7 @@ extern "C" void OPS_HIP_Set(struct OPS_* ops) {
   be.block_moves = HIP_BlockMoves;            // GCG's X / W start / b moves of an outer iteration in one sweep
   be.ritz_in_place = HIP_RitzInPlace;         // GCG's Ritz vectors written over X, P moved in behind them: no ComputeX
   be.panel_norms_sq = HIP_PanelNormsSq;       // column norms summed by the panel update that wrote the columns
+  be.multigrid_refresh_check = gcge_hip_multigrid_refresh_check;
   be.multigrid_refresh = gcge_hip_multigrid_refresh;   // a live hierarchy after level 0 took new values in place (multigrid.hip)
   be.mat_identity = HIP_MatIdentity; be.mat_free = HIP_MatFree; be.mat_rows_as_given = HIP_MatRowsAsGiven;
   GCGE_SetBackend(ops, &be);

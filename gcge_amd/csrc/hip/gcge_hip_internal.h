@@ -112,6 +112,7 @@ extern "C" void gcge_hip_perm_release(struct GcgePerm* p);
 extern "C" struct GcgePerm* gcge_hip_perm_live(int n);          // mat_upload.hip: the live order of size n (NULL: none); no reference taken
 extern "C" struct GcgePerm* gcge_hip_perm_identity(int n);      // ... the identity order of size n, registered if none is live (NULL: a re-ordered one is)
 extern "C" void gcge_hip_halo_native_free(struct GCGE_HIP_MAT_* A);
+extern "C" void gcge_hip_comm_transfer_sync(void);              // rccl_comm.hip: the split exchange's transfer stream has drained
 // mat_device.hip: gcge_hip_mat_create_device whose fall-back is gcge_hip_mat_create_as_given and which runs beside a re-ordered matrix of
 // its size (the coarse levels of a MIS-2 hierarchy, multigrid.hip)
 extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_device_as_given(int nrows, long nnz, const int* d_rowptr, const int* d_colidx, const double* d_val);
@@ -132,6 +133,9 @@ extern "C" int gcge_hip_mg_galerkin_device(int nf, const int* d_rowptr, const in
 extern "C" int gcge_hip_mg_galerkin_values_into(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
                                                 const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c,
                                                 double* d_va_c, long* d2h);     // (rows that fit are written even when it returns 1)
+extern "C" int gcge_hip_mg_galerkin_values_slab_into(int ncols_f, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_colagg,
+                                                     int nc, const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c,
+                                                     double* d_va_c, int nlo, long* d2h);     // a level of a row-slab hierarchy
 extern "C" int gcge_hip_mg_agg_masked_device(const int dims[3], const int* d_box, int nf, int* d_agg, int* d_mem, int** d_ptr_out, int** d_cbox_out,
                                              int cdims[3], long* d2h);
 // mg_aggregate.hip: MIS-2 aggregation (gcge_mg_aggregate_mis2) of an n-row device CSR; agg / mem: the caller's, *d_ptr_out allocated

@@ -230,8 +230,9 @@ static GCGE_HIP_MAT* mat_create_local(int nrows, int ncols_local, int nglobal, i
   // arrays for the plane sweep of spmm_star.hip, the others (rows inside dense blocks, ...) keep every entry and take the block form
   phase("pattern search");
   A->star = nullptr; A->star_rem = nullptr;
-  // (maps only where an update can use them: a whole matrix on one rank — a row slab declines every update)
-  const int keep_maps = g_keep_value_maps && row_begin == 0 && ncols_local == nrows && (nglobal <= 0 || nglobal == nrows);
+  // (a row slab keeps them like a whole matrix: the maps index the CSR entries of the local arrays, which are the caller's entries —
+  //  gcge_dist_localize only renames columns —, and every stored value of a slab derives from the rank's own rows)
+  const int keep_maps = g_keep_value_maps;
   if (A->d_pid == nullptr) {
     // (the sweep needs to know where the slab sits in the grid: a whole matrix, or a slab with its global size and halo rows named)
     const bool whole = row_begin == 0 && ncols_local == nrows && (nglobal <= 0 || nglobal == nrows);

@@ -18,6 +18,8 @@
 // mat_values_forms.hip around k_mv_values instead; without maps it is declined from the handle alone, as every tile form is.
 // A re-ordered handle that kept its entry map (the same switch) first gathers the caller's values into its own order
 // (k_mv_gather_entries) and then takes the update above on that block; without the map it is declined from the handle alone.
+// A row slab (halo columns, a halo plan) takes all of the above on its own rows: nothing here indexes by column, the offsets of the
+// pattern rule are those of the local columns the table was built from.  The call is rank-local: no collective, no exchange.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <stdint.h>
@@ -216,13 +218,19 @@ static int mv_update(GCGE_HIP_MAT* A, const double* d_val) {
 extern "C" int gcge_hip_mat_update_values_device(GCGE_HIP_MAT* A, long nnz, const double* d_val) {
   if (A == nullptr || d_val == nullptr || nnz != A->nnz) { g_mu_stats[4] += 1; return -1; }
   // declined from the handle alone: tile forms, star / dense forms without value maps (gcge_hip_mat_forms_check), rectangular handles,
-  // row slabs, re-ordered handles without an entry map
-  if (A->tile != nullptr || A->rect_ncols > 0 || A->nghost > 0 ||
-      A->row_begin != 0 || (A->nglobal > 0 && A->nglobal != A->nrows) || A->exchange != nullptr || A->exchange_begin != nullptr ||
-      A->native_halo != nullptr || A->d_send_rows != nullptr || (real_perm(A->perm) != nullptr && A->d_emap == nullptr) || A->d_orp == nullptr ||
+  // re-ordered handles without an entry map.  A row slab is taken like a whole matrix: its d_val is in the caller's entry order
+  // (gcge_dist_localize only renames columns; a slab never has a row order of its own) and every stored copy of a value derives from
+  // the rank's own rows, so the call stays rank-local and collective-free.
+  if (A->tile != nullptr || A->rect_ncols > 0 || (real_perm(A->perm) != nullptr && A->d_emap == nullptr) || A->d_orp == nullptr ||
       (A->d_pid != nullptr && (A->d_tab == nullptr || A->pat_lt < 1 || A->pat_lt > 16 || A->npat < 1 || (A->d_rowval != nullptr && A->pat_lt > 8)))) {
     g_mu_stats[3] += 1;
     return 1;
+  }
+  // a slab's halo exchange moves X, not matrix values, but a split product may still be reading the handle: the back-end's stream and,
+  // where the exchange runs over a transfer stream of the back-end's own, that stream drain before the first store
+  if (A->nghost > 0 || A->exchange != nullptr || A->exchange_begin != nullptr || A->native_halo != nullptr) {
+    GCGE_HIP_CHECK(hipStreamSynchronize((hipStream_t)gcge_hip_stream()));
+    if (A->native_halo != nullptr) gcge_hip_comm_transfer_sync();
   }
   if (A->d_emap == nullptr) return mv_update(A, d_val);
   // a re-ordered handle: the caller's values in the handle's order, in a block of the pool, then the update as it is.  The gather writes

@@ -271,6 +271,76 @@ static long value_maps_selfcheck(int nrows, const int* rowptr, const int* colidx
   }
   return bad;
 }
+// The same question for a ROW SLAB (local columns, halo columns >= nrows behind `ghost`; box_of_local_col != NULL: a slab of a masked
+// grid, the box index of every local column), asked of the stored values themselves: the split and the block form built from val0 with
+// their maps, the maps replayed on val1 — diagonal, the star's remainder, every block slot and pad-8 slot — against the split and the
+// block form built directly from val1, value for value as bits, structure for structure.  Returns the number of differing stored
+// values (0: the update in place leaves what a creation from val1 stores), -1: neither a star nor a dense form, -2: the update would
+// be declined (a pinned entry moved, a NaN on the diagonal).  out[0] forms found (1 star, 2 dense, 3 both), out[1] layers of blocks,
+// out[2] pinned entries, out[3] halo columns among the star's remainder (a slab's maps must reach them).
+extern "C" long gcge_hip_value_maps_selfcheck_slab(int nrows, int ncols_local, long row_begin, long nglobal, const int* ghost, const int* rowptr,
+                                                   const int* colidx, const double* val0, const double* val1, int dense_mode, int nx, int ny,
+                                                   int nz, const int* box_of_local_col, long* out) {
+  const long nnz = rowptr[nrows];
+  const int saved_mode = gcge_hip_spmm_dense_mode_get();
+  gcge_hip_spmm_dense_mode(dense_mode);
+  struct Restore { int m; ~Restore() { gcge_hip_spmm_dense_mode(m); } } restore{saved_mode};
+  typedef std::vector<std::vector<std::pair<int, double>>> Rows;
+  auto differing = [&](const Rows& a, const Rows& b) -> long {
+    long bad = 0;
+    for (int r = 0; r < nrows; ++r) {
+      const auto &x = a[(size_t)r], &y = b[(size_t)r];
+      if (x.size() != y.size()) { bad += (long)std::max(x.size(), y.size()); continue; }
+      for (size_t i = 0; i < x.size(); ++i) bad += x[i].first != y[i].first || vm_bits(x[i].second) != vm_bits(y[i].second);
+    }
+    return bad;
+  };
+  StarHost H0, H1;
+  H0.keep_maps = true;
+  StarRows M0 = {nrows, ncols_local, row_begin, nglobal, ghost, rowptr, colidx, val0};
+  if (box_of_local_col != nullptr && nx > 0 && ny > 0 && nz > 0) {
+    M0.box = box_of_local_col; M0.bnx = nx; M0.bny = ny; M0.bnz = nz; M0.nglobal = (long)nx * ny * nz; M0.box_cols = ncols_local != nrows;
+  }
+  StarRows M1 = M0;
+  M1.val = val1;
+  Rows got0((size_t)nrows), got1((size_t)nrows);
+  long d0[2] = {0, 0}, d1[2] = {0, 0}, bad = 0, pinned = 0, halo = 0;
+  if (star_build_host(M0, &H0)) {
+    const GcgeVmCoef coef = vm_coef(H0.c);
+    for (long q = 0; q < nnz; ++q) {                    // the update's check
+      const int p = H0.pin[(size_t)q];
+      pinned += p != 0 && p != GCGE_VM_PIN_DIAG;
+      if (gcge_vm_check(val1[q], p, coef.c) != 0) return -2;
+    }
+    if (!star_build_host(M1, &H1)) return nrows + 1;
+    if (memcmp(&H0.c, &H1.c, sizeof H0.c) != 0 || H0.rem_rowptr != H1.rem_rowptr || H0.rem_col != H1.rem_col || H0.clean != H1.clean) return nrows + 2;
+    for (int r = 0; r < nrows; ++r) bad += vm_bits(gcge_vm_gather(val1, H0.diag_src[(size_t)r])) != vm_bits(H1.diag[(size_t)r]);
+    std::vector<double> rem1(H0.rem_val.size());
+    for (size_t e = 0; e < rem1.size(); ++e) {
+      if (H0.rem_src[e] < -1 || H0.rem_src[e] >= nnz || H0.rem_code[e] >= GCGE_VM_NCODE) return nrows + 1;
+      rem1[e] = gcge_vm_replay(val1, H0.rem_src[e], H0.rem_code[e], coef.c);
+      bad += vm_bits(rem1[e]) != vm_bits(H1.rem_val[e]);
+      halo += H0.rem_col[e] >= nrows;
+    }
+    const long b0 = gcge_dense_maps_expand(nrows, ncols_local, H0.rem_rowptr.data(), H0.rem_col.data(), H0.rem_val.data(), (const unsigned char*)H0.clean.data(),
+                                           rem1.data(), got0, d0);
+    const long b1 = gcge_dense_maps_expand(nrows, ncols_local, H1.rem_rowptr.data(), H1.rem_col.data(), H1.rem_val.data(), (const unsigned char*)H1.clean.data(),
+                                           H1.rem_val.data(), got1, d1);
+    if (b0 == 0 && b1 == 0) {
+      if (out) { out[0] = 1 | (d0[0] > 0 ? 2 : 0); out[1] = d0[0]; out[2] = pinned; out[3] = halo; }
+      return bad + differing(got0, got1);
+    }
+    if (b0 > 0 || b1 > 0) return nrows + 1;
+    for (auto& g : got0) g.clear();                     // (no block form under the star: the upload drops the star then)
+    for (auto& g : got1) g.clear();
+  }
+  const long b0 = gcge_dense_maps_expand(nrows, ncols_local, rowptr, colidx, val0, nullptr, val1, got0, d0);
+  const long b1 = gcge_dense_maps_expand(nrows, ncols_local, rowptr, colidx, val1, nullptr, val1, got1, d1);
+  if (b0 < 0 || b1 < 0) return -1;
+  if (b0 > 0 || b1 > 0) return nrows + 1;
+  if (out) { out[0] = 2; out[1] = d0[0]; out[2] = 0; out[3] = 0; }
+  return differing(got0, got1);
+}
 extern "C" long gcge_hip_value_maps_selfcheck(int nrows, const int* rowptr, const int* colidx, const double* val0, const double* val1, int dense_mode,
                                               long* out) {
   return value_maps_selfcheck(nrows, rowptr, colidx, val0, val1, dense_mode, 0, 0, 0, nullptr, out);

@@ -212,6 +212,12 @@ __global__ void __launch_bounds__(MG_WAVE) k_mg_galerkin(int nc, int nf, const i
 // sums of k_mg_galerkin<true>: the lane that owns a rank adds its values one by one in walk order from 0.0, times scale at the end when
 // scale != 1.0.  7.3 KB of LDS per wave.  A row is written whole or not at all: an entry whose coarse column the row does not hold, or
 // a row of more than MG_DCAP columns, sets the flag and leaves the row's values alone.
+// SLAB (a level of a row-slab hierarchy, multigrid.hip): agg is the level's colagg — one entry per LOCAL column, halo columns included
+// (nf counts them all) — and the coarse row lists its columns in ascending GLOBAL order under local names: own columns [0, nown), then
+// the halo columns, of which the first nlo lie below the slab.  mg_slab_key turns a local column into its rank in that global order, so
+// the staged row is ascending again and the search is the same; the sums are the build's (gcge_mg_build_slab adds a coarse entry's
+// contributions in walk order from 0.0, then times scale).
+__device__ inline int mg_slab_key(int c, int nown, int nlo) { return c < nown ? c + nlo : (c - nown < nlo ? c - nown : c); }
 struct MgValLds {
   int col[MG_DCAP];      // the coarse row's columns, ascending
   double acc[MG_DCAP];   // sums by rank
@@ -219,19 +225,21 @@ struct MgValLds {
   int cr[MG_WAVE]; double cv[MG_WAVE];
   int miss;
 };
+template <bool SLAB>
 __global__ void __launch_bounds__(MG_WAVE) k_mg_galerkin_values(int nc, int nf, const int* __restrict__ ptr, const int* __restrict__ mem,
     const int* __restrict__ rowptr, const int* __restrict__ colidx, const double* __restrict__ val, const int* __restrict__ agg, double scale,
-    const int* __restrict__ rowptr_c, const int* __restrict__ colidx_c, double* __restrict__ val_c, int* __restrict__ flag) {
+    const int* __restrict__ rowptr_c, const int* __restrict__ colidx_c, double* __restrict__ val_c, int* __restrict__ flag, int nown, int nlo) {
   __shared__ MgValLds s;
   const int lane = threadIdx.x;
   for (int I = blockIdx.x; I < nc; I += gridDim.x) {
     const int base = rowptr_c[I], nd = rowptr_c[I + 1] - base;
     if (nd < 0 || nd > MG_DCAP) { if (lane == 0) *flag = 1; continue; }       // (uniform over the wave)
-    for (int j = lane; j < nd; j += MG_WAVE) { s.col[j] = colidx_c[base + j]; s.acc[j] = 0.0; }
+    for (int j = lane; j < nd; j += MG_WAVE) { const int cj = colidx_c[base + j]; s.col[j] = SLAB ? mg_slab_key(cj, nown, nlo) : cj; s.acc[j] = 0.0; }
     if (lane == 0) s.miss = 0;
     __syncthreads();
     mg_walk_row(s, I, nf, ptr, mem, rowptr, colidx, val, agg, true, [&](int c, double v, int i, int n) {
       int r = -1;
+      if (SLAB && c >= 0) c = mg_slab_key(c, nown, nlo);
       if (c >= 0) {
         int lo = 0, hi = nd;                          // first column >= c
         while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (s.col[mid] < c) lo = mid + 1; else hi = mid; }
@@ -467,21 +475,38 @@ extern "C" int gcge_hip_mg_galerkin_device(int nf, const int* d_rowptr, const in
 // host's gcge_mg_galerkin give for these values.  Returns 0, or 1 when an entry's coarse column is not in its coarse row (the structure is
 // not this matrix's) or a coarse row holds more than MG_DCAP columns: such rows keep what d_va_c held, the others are written.  One word
 // comes back.
-extern "C" int gcge_hip_mg_galerkin_values_into(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
-                                                const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c,
-                                                double* d_va_c, long* d2h) {
+static int mg_galerkin_values_into(bool slab, int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
+                                   const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c, double* d_va_c,
+                                   int nlo, long* d2h) {
   if (nc <= 0) return 0;
   int* d_flag = (int*)gcge_hip_stage_d(1);              // (a word of the back-end's staging block: nothing else runs between the two calls)
   GCGE_HIP_CHECK(hipMemsetAsync(d_flag, 0, sizeof(int), mg_stream()));
   const unsigned grid = (unsigned)(nc < 65536 * 16 ? nc : 65536 * 16);
-  hipLaunchKernelGGL(k_mg_galerkin_values, dim3(grid), dim3(MG_WAVE), 0, mg_stream(), nc, nf, d_ptr, d_mem, d_rowptr, d_colidx, d_val, d_agg, scale,
-                     d_rp_c, d_ci_c, d_va_c, d_flag);
+  if (slab)
+    hipLaunchKernelGGL(k_mg_galerkin_values<true>, dim3(grid), dim3(MG_WAVE), 0, mg_stream(), nc, nf, d_ptr, d_mem, d_rowptr, d_colidx, d_val, d_agg, scale,
+                       d_rp_c, d_ci_c, d_va_c, d_flag, nc, nlo);
+  else
+    hipLaunchKernelGGL(k_mg_galerkin_values<false>, dim3(grid), dim3(MG_WAVE), 0, mg_stream(), nc, nf, d_ptr, d_mem, d_rowptr, d_colidx, d_val, d_agg, scale,
+                       d_rp_c, d_ci_c, d_va_c, d_flag, nc, 0);
   GCGE_HIP_CHECK(hipGetLastError());
   int flag = 0;
   GCGE_HIP_CHECK(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, mg_stream()));
   GCGE_HIP_CHECK(hipStreamSynchronize(mg_stream()));
   if (d2h) *d2h += (long)sizeof flag;
   return flag != 0;
+}
+extern "C" int gcge_hip_mg_galerkin_values_into(int nf, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_agg, int nc,
+                                                const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c,
+                                                double* d_va_c, long* d2h) {
+  return mg_galerkin_values_into(false, nf, d_rowptr, d_colidx, d_val, d_agg, nc, d_ptr, d_mem, scale, d_rp_c, d_ci_c, d_va_c, 0, d2h);
+}
+// ... on one level of a row-slab hierarchy: the nrows_f own rows of the fine slab (d_ptr / d_mem: the members of the nc own coarse rows)
+// over its ncols_f LOCAL columns, d_colagg[ncols_f] the local coarse column of each (gcge_mg_slab_colagg), nlo of the coarse slab's halo
+// columns below it; the coarse structure is the coarse slab's own, local columns.  Same returns.
+extern "C" int gcge_hip_mg_galerkin_values_slab_into(int ncols_f, const int* d_rowptr, const int* d_colidx, const double* d_val, const int* d_colagg,
+                                                     int nc, const int* d_ptr, const int* d_mem, double scale, const int* d_rp_c, const int* d_ci_c,
+                                                     double* d_va_c, int nlo, long* d2h) {
+  return mg_galerkin_values_into(true, ncols_f, d_rowptr, d_colidx, d_val, d_colagg, nc, d_ptr, d_mem, scale, d_rp_c, d_ci_c, d_va_c, nlo, d2h);
 }
 // ... into d_va_c_out only when the whole product fits the structure: on a return of 1 d_va_c_out is as it was (the values go through
 // a block of the pool)

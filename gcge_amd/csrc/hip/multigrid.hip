@@ -64,8 +64,13 @@ extern "C" GCGE_HIP_MAT* gcge_hip_mat_create_rect_csr(const GCGE_CSR* P) {
 
 // one hierarchy per MultiGridCreate call; found again through the A_array pointer MultiGridDestroy hands back
 // (scale, slab: what gcge_hip_multigrid_refresh needs to know of the build — the factor of its Galerkin products, and whether the levels
-// are row slabs, which it leaves alone)
-struct MgHold { void** A_array; std::vector<GCGE_HIP_MAT*> owned; int num_levels = 0; double scale = 0.5; bool slab = false; };
+// are row slabs; of a slab hierarchy also, per level l < num_levels - 1, colagg[l]: a device array of nrows_l + nghost_l ints, the LOCAL
+// column of level l + 1 every local column of level l aggregates into (gcge_mg_slab_colagg), and nlo[l]: the halo columns of level l + 1
+// that lie below its slab.  Empty: the halo rows of some level were not named, the hierarchy cannot be refreshed.  Freed with it.)
+struct MgHold {
+  void** A_array; std::vector<GCGE_HIP_MAT*> owned; int num_levels = 0; double scale = 0.5; bool slab = false;
+  std::vector<int*> colagg; std::vector<int> nlo;
+};
 static std::vector<MgHold> g_mg;
 static double g_mg_seconds = 0.0;
 extern "C" double gcge_hip_multigrid_seconds(void) { return g_mg_seconds; }   // host + upload time of the last MultiGridCreate
@@ -105,6 +110,7 @@ struct MgBuilt {
   std::vector<std::array<int, 3>> dims;
   bool masked = false; const char* how = "";       // how: " (device build)", " (host build)" or nothing
   int rank = 0, world = 0; std::vector<long> global_rows;       // a row slab: the rows of all ranks, level by level
+  std::vector<int*> colagg; std::vector<int> nlo;               // ... and what MgHold keeps for a refresh
 };
 
 static void mg_install(const MgSlot& s, const MgBuilt& b) {
@@ -134,7 +140,7 @@ static void mg_install(const MgSlot& s, const MgBuilt& b) {
         fprintf(stderr, "MultiGridCreate: level %d: %d rows, %ld non-zeros, grid %d x %d x %d, K1 form %s%s\n", l, m->nrows, m->nnz, d[0], d[1], d[2],
                 gcge_hip_mat_spmm_form(m), b.how);
     }
-  h.A_array = *s.A_array; h.num_levels = L; h.slab = b.world > 0;
+  h.A_array = *s.A_array; h.num_levels = L; h.slab = b.world > 0; h.colagg = b.colagg; h.nlo = b.nlo;
   gcge_mg_get_defaults(&h.scale, nullptr, nullptr);       // (every build takes the defaults in force when it runs)
   g_mg.push_back(h);
   *s.num_levels = L;
@@ -195,6 +201,24 @@ static void multigrid_create_slab(const MgSlot& s, const GCGE_HIP_MAT_* mA) {
     if (a->h_part == nullptr) gcge_hip_mat_set_partition(a, pl, world);
     return a;
   });
+  // what a refresh in place needs of the neighbours, while the host still knows it: where every local column of a level — the halo
+  // columns through their owners' pairing and the coarse slab's halo list — lands among the local columns of the next one
+  bool named = true;
+  for (int l = 0; l + 1 < mg.num_levels && named; ++l) {
+    const GCGE_HIP_MAT_* f = l == 0 ? mA : built.As[(size_t)l - 1];
+    const GCGE_HIP_MAT_* c = built.As[(size_t)l];
+    if ((f->nghost > 0 && f->h_ghost_global == nullptr) || (c->nghost > 0 && c->h_ghost_global == nullptr)) { named = false; break; }
+    std::vector<int> colagg((size_t)f->nrows + f->nghost + 1);
+    int nlo = 0;
+    if (gcge_mg_slab_colagg(mg.dims[l], parts + (size_t)l * (world + 1), rank, world, f->h_ghost_global, f->nghost, c->h_ghost_global, c->nghost,
+                            colagg.data(), &nlo) != 0) { named = false; break; }
+    for (int k = 0; k < f->nrows + f->nghost; ++k) GCGE_REQUIRE(colagg[(size_t)k] >= 0 && colagg[(size_t)k] < c->nrows + c->nghost, "MultiGridCreate on a row slab: a local column of the coarse slab");
+    int* d = nullptr;
+    GCGE_HIP_CHECK(hipMalloc(&d, colagg.size() * sizeof(int)));
+    GCGE_HIP_CHECK(hipMemcpy(d, colagg.data(), colagg.size() * sizeof(int), hipMemcpyHostToDevice));
+    built.colagg.push_back(d); built.nlo.push_back(nlo);
+  }
+  if (!named) { for (int* d : built.colagg) hipFree(d); built.colagg.clear(); built.nlo.clear(); }
   gcge_mg_free(&mg);
   free(parts);
   mg_install(s, built);
@@ -455,6 +479,7 @@ extern "C" void gcge_hip_multigrid_destroy(void*** A_array, void*** B_array, voi
   for (size_t i = 0; i < g_mg.size(); ++i) {
     if (g_mg[i].A_array != *A_array) continue;
     for (GCGE_HIP_MAT* m : g_mg[i].owned) gcge_hip_mat_destroy(m);
+    for (int* d : g_mg[i].colagg) hipFree(d);
     g_mg.erase(g_mg.begin() + (long)i);
     break;
   }
@@ -476,19 +501,25 @@ extern "C" void gcge_hip_multigrid_refresh_stats(long out[4]) { for (int i = 0; 
 
 // Level 0 may live in a row order of the back-end's own (mat_upload.hip "row orders"): the hierarchy was built from the handle's CSR, in
 // the handle's order, and P_0's rows are numbered like it.  A re-ordered coarse level would contradict its prolongation.
+// A hierarchy of row slabs (multigrid_create_slab) is refreshed like one of whole matrices, every rank its own levels: each coarse row of a
+// slab level is scale x the sum over fine rows the rank owns (aggregates never cross a cut), its halo columns only have to know which
+// coarse column they fall into (MgHold::colagg), and the coarse slab takes its values through the same in-place update.  Nothing here is
+// collective — the ranks agree on the outcome in GCGE_AMGRefresh (csrc/host/harness.c).  No B below level 0 on slabs: A's levels only.
 static bool mr_level_ok(const GCGE_HIP_MAT_* m, int level) {
-  return m != nullptr && m->rect_ncols == 0 && m->nghost == 0 && m->row_begin == 0 && (level == 0 || real_perm(m->perm) == nullptr) && m->d_rowptr != nullptr;
+  return m != nullptr && m->rect_ncols == 0 && (level == 0 || real_perm(m->perm) == nullptr) && m->d_rowptr != nullptr;
 }
 // 0: level l + 1 of `arr` now holds scale P^T (level l) P; 1: declined, the level is as it was
-static int mr_level(void** arr, int l, const GCGE_HIP_MAT_* P, double scale) {
+static int mr_level(const MgHold* h, void** arr, int l, const GCGE_HIP_MAT_* P, double scale) {
   const GCGE_HIP_MAT_* f = (const GCGE_HIP_MAT_*)arr[l];
   GCGE_HIP_MAT_* c = (GCGE_HIP_MAT_*)arr[l + 1];
   const size_t bytes = (size_t)(c->nnz > 0 ? c->nnz : 1) * sizeof(double);
   double* work = (double*)gcge_hip_pool_alloc(bytes);
   long u0[6], u1[6];
   gcge_hip_mat_update_stats(u0);
-  int rc = gcge_hip_mg_galerkin_values_into(f->nrows, f->d_rowptr, f->d_colidx, f->d_val, P->d_colidx, P->rect_ncols, P->d_t_rowptr, P->d_t_colidx,
-                                            scale, c->d_rowptr, c->d_colidx, work, &g_mr_stats[3]);
+  int rc = h->slab ? gcge_hip_mg_galerkin_values_slab_into(f->nrows + f->nghost, f->d_rowptr, f->d_colidx, f->d_val, h->colagg[(size_t)l], P->rect_ncols,
+                                                           P->d_t_rowptr, P->d_t_colidx, scale, c->d_rowptr, c->d_colidx, work, h->nlo[(size_t)l], &g_mr_stats[3])
+                   : gcge_hip_mg_galerkin_values_into(f->nrows, f->d_rowptr, f->d_colidx, f->d_val, P->d_colidx, P->rect_ncols, P->d_t_rowptr, P->d_t_colidx,
+                                                      scale, c->d_rowptr, c->d_colidx, work, &g_mr_stats[3]);
   if (rc == 0) rc = gcge_hip_mat_update_values_device(c, c->nnz, work) != 0;
   gcge_hip_mat_update_stats(u1);
   g_mr_stats[3] += u1[5] - u0[5];
@@ -496,23 +527,36 @@ static int mr_level(void** arr, int l, const GCGE_HIP_MAT_* P, double scale) {
   if (rc == 0) g_mr_stats[2] += 1;
   return rc;
 }
-extern "C" int gcge_hip_multigrid_refresh(void** A_array, void** B_array, void** P_array, int num_levels) {
-  const MgHold* h = nullptr;
-  for (const MgHold& k : g_mg) if (k.A_array == A_array) h = &k;
-  if (h == nullptr || A_array == nullptr || P_array == nullptr || num_levels != h->num_levels || h->slab) return -1;
-  const bool withB = B_array != nullptr && B_array[0] != nullptr;
+static const MgHold* mr_hold(void** A_array) {
+  for (const MgHold& k : g_mg) if (k.A_array == A_array) return &k;
+  return nullptr;
+}
+// what a refresh decides from the handles alone, before anything is written: 0 go on, -1 (GCGE_BACKEND.multigrid_refresh_check)
+extern "C" int gcge_hip_multigrid_refresh_check(void** A_array, void** B_array, void** P_array, int num_levels) {
+  const MgHold* h = mr_hold(A_array);
+  if (h == nullptr || A_array == nullptr || P_array == nullptr || num_levels != h->num_levels) return -1;
+  if (h->slab && num_levels > 1 && ((int)h->colagg.size() != num_levels - 1 || (int)h->nlo.size() != num_levels - 1)) return -1;
+  const bool withB = !h->slab && B_array != nullptr && B_array[0] != nullptr;
   for (int l = 0; l < num_levels; ++l) {
-    if (!mr_level_ok((const GCGE_HIP_MAT_*)A_array[l], l) || (withB && !mr_level_ok((const GCGE_HIP_MAT_*)B_array[l], l))) return -1;
-    if (withB && ((const GCGE_HIP_MAT_*)B_array[l])->nrows != ((const GCGE_HIP_MAT_*)A_array[l])->nrows) return -1;
+    const GCGE_HIP_MAT_* a = (const GCGE_HIP_MAT_*)A_array[l];
+    if (!mr_level_ok(a, l) || (withB && !mr_level_ok((const GCGE_HIP_MAT_*)B_array[l], l))) return -1;
+    if (!h->slab && (a->nghost != 0 || a->row_begin != 0)) return -1;       // (a level with halo columns outside a slab hierarchy: no colagg)
+    if (withB && ((const GCGE_HIP_MAT_*)B_array[l])->nrows != a->nrows) return -1;
     if (l == 0) continue;
     const GCGE_HIP_MAT_* P = (const GCGE_HIP_MAT_*)P_array[l - 1];
     if (P == nullptr || !P->rect_one_per_row || P->d_t_rowptr == nullptr || P->nrows != ((const GCGE_HIP_MAT_*)A_array[l - 1])->nrows ||
-        P->rect_ncols != ((const GCGE_HIP_MAT_*)A_array[l])->nrows) return -1;
+        P->rect_ncols != a->nrows) return -1;
   }
+  return 0;
+}
+extern "C" int gcge_hip_multigrid_refresh(void** A_array, void** B_array, void** P_array, int num_levels) {
+  if (gcge_hip_multigrid_refresh_check(A_array, B_array, P_array, num_levels) != 0) return -1;
+  const MgHold* h = mr_hold(A_array);
+  const bool withB = !h->slab && B_array != nullptr && B_array[0] != nullptr;
   GCGE_HIP_CHECK(hipStreamSynchronize((hipStream_t)gcge_hip_stream()));
   for (int l = 0; l + 1 < num_levels; ++l) {
     const GCGE_HIP_MAT_* P = (const GCGE_HIP_MAT_*)P_array[l];
-    if (mr_level(A_array, l, P, h->scale) != 0 || (withB && mr_level(B_array, l, P, 1.0) != 0)) { g_mr_stats[1] += 1; return l + 1; }
+    if (mr_level(h, A_array, l, P, h->scale) != 0 || (withB && mr_level(h, B_array, l, P, 1.0) != 0)) { g_mr_stats[1] += 1; return l + 1; }
   }
   g_mr_stats[0] += 1;
   return 0;

@@ -155,6 +155,10 @@ static void rccl_exchange_end(void* ctx) {
   GCGE_HIP_CHECK(hipStreamWaitEvent((hipStream_t)gcge_hip_stream(), g_ev_arrived, 0));
 }
 
+// the transfer stream of the split exchange has drained (no communicator: nothing to wait for) — mat_values.hip, before an update in place
+extern "C" void gcge_hip_comm_transfer_sync(void) {
+  if (g_cs != nullptr) GCGE_HIP_CHECK(hipStreamSynchronize(g_cs));
+}
 extern "C" void gcge_hip_halo_native_free(GCGE_HIP_MAT_* A) {
   if (A->native_halo == nullptr) return;
   GCGE_HIP_CHECK(hipDeviceSynchronize());

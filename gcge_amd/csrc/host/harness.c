@@ -72,8 +72,32 @@ void GCGE_AMGDestroy(GCGE_AMG **pamg, struct OPS_ *ops)
 int GCGE_AMGRefresh(GCGE_AMG *amg, struct OPS_ *ops)
 {
 	const GCGE_BACKEND be = GCGE_BackendOf(ops);
-	if (amg == NULL || be.multigrid_refresh == NULL) return -1;
-	return be.multigrid_refresh(amg->A_array, amg->B_array, amg->P_array, amg->num_levels);
+	GCGE_COMM *comm = GCGE_GetComm();
+	enum { MAXL = 64 };
+	double votes[MAXL + 1];
+	int rc, l;
+	if (be.multigrid_refresh == NULL) return -1;       /* (the table's, so the same answer on every rank) */
+	/* The back-end's refresh is rank-local.  Over a communicator the ranks agree on its outcome by two all-reduces that EVERY rank
+	 * reaches, whatever it found itself: the first on what can be decided from the handles, before anything is written — a -1
+	 * anywhere is a -1 everywhere with every hierarchy untouched —, the second after the level loop, on the smallest level that
+	 * declined on any rank.  No collective sits behind a predicate only one rank evaluates. */
+	rc = amg == NULL || amg->num_levels > MAXL ? -1
+	     : be.multigrid_refresh_check != NULL ? be.multigrid_refresh_check(amg->A_array, amg->B_array, amg->P_array, amg->num_levels) : 0;
+	if (comm != NULL) {
+		votes[0] = rc != 0 ? 1.0 : 0.0;
+		comm->allreduce_sum(votes, 1, comm->ctx);
+		if (votes[0] != 0.0) rc = -1;
+	}
+	if (rc == 0) rc = be.multigrid_refresh(amg->A_array, amg->B_array, amg->P_array, amg->num_levels);
+	else rc = -1;
+	if (comm == NULL) return rc;
+	/* votes[0]: ranks that wrote nothing; votes[l]: ranks whose level l was the first to decline */
+	for (l = 0; l <= MAXL; ++l) votes[l] = 0.0;
+	if (rc < 0 || rc > MAXL) votes[0] = 1.0; else if (rc > 0) votes[rc] = 1.0;
+	comm->allreduce_sum(votes, MAXL + 1, comm->ctx);
+	if (votes[0] != 0.0) return -1;
+	for (l = 1; l <= MAXL; ++l) if (votes[l] != 0.0) return l;
+	return 0;
 }
 
 /* evec_in != NULL: a block of nevMax columns owned by the caller whose first nevGiven columns are start vectors

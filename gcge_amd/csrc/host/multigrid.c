@@ -547,6 +547,43 @@ static int slab_coarsenable(const int d[3], const long *part, int world)
 	}
 	return two;
 }
+/* first fine / coarse plane of every rank at one level (zf, zc: world + 1 entries each) and the coarse partition (pc, may be NULL) */
+static void slab_planes(const int d[3], const long *pf, int world, long *zf, long *zc, long *pc)
+{
+	const long plane = (long)d[0] * d[1], cplane = (long)((d[0] + 1) / 2) * ((d[1] + 1) / 2); int r;
+	zc[0] = 0;
+	for (r = 0; r <= world; ++r) zf[r] = pf[r] / plane;
+	for (r = 0; r < world; ++r) zc[r + 1] = zc[r] + (zf[r + 1] - zf[r] + 1) / 2;       /* every rank pairs its own planes */
+	if (pc != NULL) for (r = 0; r <= world; ++r) pc[r] = zc[r] * cplane;
+}
+int gcge_mg_slab_colagg(const int dims[3], const long *part, int rank, int world, const int *ghost, int nghost, const int *ghost_c,
+		int nghost_c, int *colagg, int *nlo_c)
+{
+	const int cx = (dims[0] + 1) / 2, cy = (dims[1] + 1) / 2;
+	long *zf, *zc, *pc, rb, nf, nc, c; int k, nlo = 0, rc = 0;
+	if (world < 1 || rank < 0 || rank >= world || nghost < 0 || nghost_c < 0 || colagg == NULL || !slab_coarsenable(dims, part, world)) return -2;
+	if ((long)dims[0] * dims[1] * dims[2] != part[world]) return -2;
+	zf = (long*)calloc(3 * ((size_t)world + 1), sizeof(long));
+	if (zf == NULL) return -3;
+	zc = zf + world + 1; pc = zc + world + 1;
+	slab_planes(dims, part, world, zf, zc, pc);
+	rb = part[rank]; nf = part[rank + 1] - rb; nc = pc[rank + 1] - pc[rank];
+	for (c = 0; c < nf; ++c) colagg[c] = (int)(slab_agg(rb + c, dims, cx, cy, zf, zc, world) - pc[rank]);
+	for (k = 0; k < nghost_c; ++k) nlo += ghost_c[k] < pc[rank];
+	for (k = 0; k < nghost && rc == 0; ++k) {
+		long g;
+		int lo = 0, hi = nghost_c;                                     /* first entry of ghost_c >= g */
+		if (ghost[k] < 0 || ghost[k] >= part[world] || (ghost[k] >= rb && ghost[k] < rb + nf)) { rc = -2; break; }
+		g = slab_agg(ghost[k], dims, cx, cy, zf, zc, world);
+		while (lo < hi) { const int mid = lo + (hi - lo) / 2; if (ghost_c[mid] < g) lo = mid + 1; else hi = mid; }
+		if (lo >= nghost_c || ghost_c[lo] != g) rc = -2;
+		else colagg[nf + k] = (int)(nc + lo);
+	}
+	if (nlo_c != NULL) *nlo_c = nlo;
+	free(zf);
+	return rc;
+}
+
 int gcge_mg_build_slab(const GCGE_CSR *A, const int dims[3], const long *part, int rank, int world, int max_levels, double scale,
 		GCGE_MG *mg, long **part_levels_out)
 {
@@ -570,10 +607,7 @@ int gcge_mg_build_slab(const GCGE_CSR *A, const int dims[3], const long *part, i
 		GCGE_CSR *Ac = &mg->A[l + 1];
 		int r, nc, *agg, *ptr = NULL, *mem = NULL, I, rc = 0; int64_t tot = 0;
 		if (!slab_coarsenable(d, pf, world)) break;
-		zc[0] = 0;
-		for (r = 0; r <= world; ++r) zf[r] = pf[r] / plane;
-		for (r = 0; r < world; ++r) zc[r + 1] = zc[r] + (zf[r + 1] - zf[r] + 1) / 2;       /* every rank pairs its own planes */
-		for (r = 0; r <= world; ++r) pc[r] = zc[r] * cplane;
+		slab_planes(d, pf, world, zf, zc, pc);
 		cz = (int)zc[world];
 		if (zf[world] != d[2] || cz >= d[2]) { rc = -2; goto fail; }
 		nc = (int)(pc[rank + 1] - pc[rank]);

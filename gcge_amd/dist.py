@@ -163,6 +163,15 @@ class Comm:
     def uninstall(self):
         host_lib().GCGE_SetComm(None)
 
+    def allreduce_sum_host(self, arr):
+        """In-place sum over the ranks of a contiguous float64 host array (what HipBackend.matrix_update_values(agree=) asks of a
+        comm object)."""
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        self._allreduce(a.ctypes.data_as(C.POINTER(C.c_double)), int(a.size), None)
+        if a is not arr:
+            arr[...] = a.reshape(np.shape(arr))
+        return arr
+
     # ---- halo planning ------------------------------------------------------------------------
     def plan_halo(self, ghosts, part):
         """ghosts: ascending global row ids this rank needs.  Returns (send_rows, send_cnt, recv_cnt): local rows to ship grouped by
@@ -312,19 +321,34 @@ class NativeComm:
         self.hip.g.gcge_hip_comm_stats(C.byref(a), C.byref(e))
         return a.value
 
-    def slab_matrix(self, A, part, cap_cols=128, geometry=None):
+    def allreduce_sum_host(self, arr):
+        """In-place sum over the ranks of a contiguous float64 host array, through the communicator gcge_hip_comm_init installed
+        (a world of one rank keeps none: the array is the sum)."""
+        a = np.ascontiguousarray(arr, dtype=np.float64)
+        p = host_lib().GCGE_GetComm()
+        if p:
+            c = C.cast(p, C.POINTER(GcgeComm)).contents
+            ALLREDUCE_FN(c.allreduce_sum)(a.ctypes.data_as(C.POINTER(C.c_double)), int(a.size), c.ctx)
+        if a is not arr:
+            arr[...] = a.reshape(np.shape(arr))
+        return arr
+
+    def slab_matrix(self, A, part, cap_cols=128, geometry=None, updatable=False):
         """A: CSR slab with GLOBAL column indices (rows part[rank] .. part[rank+1]).  Collective.  geometry = (dims, box_global): a
-        matrix on a masked grid, cuts between grid lines (partition_lines): gcge_hip_mat_create_slab_grid."""
+        matrix on a masked grid, cuts between grid lines (partition_lines): gcge_hip_mat_create_slab_grid.  updatable: as for
+        HipBackend.matrix — a slab with a star or dense form keeps its value maps and takes HipBackend.matrix_update_values."""
         parr = (C.c_long * (self.world + 1))(*part)
         if geometry is not None:
             dims, box_global = geometry
             bg = np.ascontiguousarray(box_global, dtype=np.int32)
             f = self.hip.g.gcge_hip_mat_create_slab_grid
-            m = f(parr, A.rowptr, A.colidx, A.val, cap_cols, int(dims[0]), int(dims[1]), int(dims[2]), bg.ctypes.data_as(C.POINTER(C.c_int)))
+            with self.hip._keeping_value_maps(updatable):
+                m = f(parr, A.rowptr, A.colidx, A.val, cap_cols, int(dims[0]), int(dims[1]), int(dims[2]), bg.ctypes.data_as(C.POINTER(C.c_int)))
             if not m:
                 raise RuntimeError("gcge_hip_mat_create_slab_grid failed")
             return C.c_void_p(m)
-        m = self.hip.g.gcge_hip_mat_create_slab(parr, A.rowptr, A.colidx, A.val, cap_cols)
+        with self.hip._keeping_value_maps(updatable):
+            m = self.hip.g.gcge_hip_mat_create_slab(parr, A.rowptr, A.colidx, A.val, cap_cols)
         if not m:
             raise RuntimeError("gcge_hip_mat_create_slab failed")
         return C.c_void_p(m)
@@ -376,9 +400,11 @@ def partition_lines(box_global, nx, world):
     return part
 
 
-def hip_slab_matrix(hip, comm, A, n_global, part, cap_cols=128, geometry=None):
+def hip_slab_matrix(hip, comm, A, n_global, part, cap_cols=128, geometry=None, updatable=False):
     """Upload a CSR slab (GLOBAL columns on entry) and install its halo plan.  geometry = (dims, box_global): the matrix lives on a
-    masked grid (box index of every GLOBAL row); with cuts between grid lines (partition_lines) the slab keeps the plane sweep."""
+    masked grid (box index of every GLOBAL row); with cuts between grid lines (partition_lines) the slab keeps the plane sweep.
+    updatable: as for HipBackend.matrix — a slab with a star or dense form keeps its value maps, so that
+    HipBackend.matrix_update_values gives it new values in place (one value per entry of A, in A's order)."""
     g = hip.g
     ghosts = localize_slab(A)
     send_rows, send_cnt, recv_cnt = comm.plan_halo(ghosts, part)
@@ -389,9 +415,11 @@ def hip_slab_matrix(hip, comm, A, n_global, part, cap_cols=128, geometry=None):
         dims, box_global = geometry
         bg = np.asarray(box_global, dtype=np.int32)
         box_local = np.ascontiguousarray(np.concatenate([bg[A.row_begin:A.row_begin + A.nrows], bg[np.asarray(ghosts, dtype=np.int64)]]), dtype=np.int32)
-        m = g.gcge_hip_mat_create_local_ghosts_grid(*slab, int(dims[0]), int(dims[1]), int(dims[2]), box_local.ctypes.data_as(C.POINTER(C.c_int)))
+        with hip._keeping_value_maps(updatable):
+            m = g.gcge_hip_mat_create_local_ghosts_grid(*slab, int(dims[0]), int(dims[1]), int(dims[2]), box_local.ctypes.data_as(C.POINTER(C.c_int)))
     else:
-        m = g.gcge_hip_mat_create_local_ghosts(*slab)
+        with hip._keeping_value_maps(updatable):
+            m = g.gcge_hip_mat_create_local_ghosts(*slab)
     if not m:
         raise RuntimeError("gcge_hip_mat_create_local_ghosts failed")
     mat = C.c_void_p(m)
@@ -433,9 +461,9 @@ def weak_scaling_box(N, world):
     return dims.get(world, (N, N, N * world))
 
 
-def lap3d_slab(hip, dims, rank, world, comm=None):
+def lap3d_slab(hip, dims, rank, world, comm=None, updatable=False):
     """Slab of the 7-point Laplacian on an Nx x Ny x Nz grid: rank r owns Nz/world planes (rows in natural order).
-    comm: NativeComm (RCCL in the back-end) or Comm (torch.distributed callbacks)."""
+    comm: NativeComm (RCCL in the back-end) or Comm (torch.distributed callbacks).  updatable: as for hip_slab_matrix."""
     h = host_lib()
     nx, ny, nz = dims
     n_global = nx * ny * nz
@@ -446,7 +474,7 @@ def lap3d_slab(hip, dims, rank, world, comm=None):
     if rc != 0:
         raise RuntimeError("gcge_problem_lap3d_box failed")
     if isinstance(comm, NativeComm):
-        mat = comm.slab_matrix(A, part)
+        mat = comm.slab_matrix(A, part, updatable=updatable)
     else:
-        mat = hip_slab_matrix(hip, comm, A, n_global, part)
+        mat = hip_slab_matrix(hip, comm, A, n_global, part, updatable=updatable)
     return A, mat

@@ -96,7 +96,7 @@ class HipBackendImpl:
             raise ValueError("gcge_hip_mat_create_device refused the arrays")
         return C.c_void_p(m)
 
-    def matrix_update_values(self, m, values):
+    def matrix_update_values(self, m, values, agree=None):
         """New values for a live matrix handle, in place (gcge_hip_mat_update_values_device): `values` holds one value per stored
         entry of the CSR arrays the handle was created from, in their order — a torch CUDA tensor, the .values() of a sparse_csr
         tensor, or an object with __cuda_array_interface__.  Converted to float64 on the device only if it is something else; the
@@ -108,9 +108,15 @@ class HipBackendImpl:
         A handle that re-ordered its rows (a matrix that shows no grid in the numbering it arrives in) takes new values when it was
         created with updatable=True as well: it then keeps which of the caller's entries sits where (4 bytes per entry on the
         device), `values` stays in the CALLER's entry order, and the call gathers it through a transient block of 8 bytes per entry.
+        A row slab (gcge_amd.dist.hip_slab_matrix, NativeComm.slab_matrix, lap3d_slab; updatable=True there for star and dense
+        slabs) takes new values the same way: one value per entry of the slab's own CSR arrays, in their order.  The library call
+        is rank-local and collective-free, so its answer is this rank's alone; agree=comm (a gcge_amd.dist.Comm or NativeComm:
+        anything with allreduce_sum_host) makes the returned bool the AND over the ranks by one all-reduce every rank reaches.  If
+        it is False, EVERY rank frees its slab and creates it again (a rank that accepted holds the new values, one that declined
+        the old ones; creation is collective).
         False: the library declined and wrote nothing (a star / dense handle or a re-ordered handle created without updatable=True,
-        other star coefficients or a NaN diagonal, tile forms, slabs, a 16-slot table whose classes do not stay uniform, an
-        explicitly stored zero): free the handle and create the matrix again.
+        other star coefficients or a NaN diagonal, tile forms, a 16-slot table whose classes do not stay uniform, an
+        explicitly stored zero) — or, with agree=, some rank's did: free the handle and create the matrix again.
         TypeError: a host tensor; ValueError: another count of values than the handle has entries (checked here)."""
         import torch
         foreign = not isinstance(values, torch.Tensor)
@@ -134,9 +140,12 @@ class HipBackendImpl:
         else:
             torch.cuda.current_stream(va.device).synchronize()
         rc = self.g.gcge_hip_mat_update_values_device(m, nnz, va.data_ptr())
+        if agree is not None:
+            votes = np.array([1.0 if rc != 0 else 0.0])          # (before any exception: every rank reaches the all-reduce)
+            agree.allreduce_sum_host(votes)
         if rc < 0:
             raise ValueError("gcge_hip_mat_update_values_device refused its arguments")
-        return rc == 0
+        return rc == 0 and (agree is None or float(votes[0]) == 0.0)
 
     def multigrid(self, A, M=None, levels=6, block_size=8, cycles=1, smooth0=5, smooth=4, rate=1e-2, refreshable=True):
         """A BlockAMG hierarchy over the matrix handle A (and M), kept by the caller across solves (GCGE_AMGCreate): at most `levels`
@@ -313,8 +322,9 @@ class Hierarchy:
         """After A (and M) took new values in place (HipBackend.matrix_update_values): the coarse levels recomputed where they are
         (GCGE_AMGRefresh).  True: refreshed in place.  False: a level declined or the back-end wrote nothing — the hierarchy was
         destroyed and built again from the same handles and arguments.  Either way it now belongs to the present values.  A level 0
-        that re-ordered its rows is refreshed like any other (it took its values in place only if created with updatable=True);
-        hierarchies of row slabs are built again."""
+        that re-ordered its rows is refreshed like any other (it took its values in place only if created with updatable=True).
+        A hierarchy of row slabs is refreshed the same way, every rank its own levels; GCGE_AMGRefresh agrees on the outcome over
+        the communicator, so every rank gets the same answer here and the rebuild (collective) happens on all ranks or on none."""
         self._head()
         if self.backend.h.GCGE_AMGRefresh(self._amg, self.backend.ops_handle) == 0:
             return True

@@ -82,7 +82,8 @@ void gcge_hip_mat_device_stats (long out[4]);
  *   0    updated: every product, CG pass and residual through the handle is now that of (rowptr, colidx, d_val).
  *   1    declined: NOTHING of the handle was written (all checks run before the first store); the caller re-creates the matrix.
  *   < 0  bad arguments (NULL handle or array, nnz != gcge_hip_mat_nnz (A)); nothing written.
- * One rank, a whole square matrix.  Its rows may be as given or re-ordered inside the handle (gcge_hip_spmm_reorder_mode; its own bullet below);
+ * A whole square matrix on one rank, or a ROW SLAB (halo columns, row_begin != 0, a halo plan of any kind: its own bullet below).  The
+ * rows of a whole matrix may be as given or re-ordered inside the handle (gcge_hip_spmm_reorder_mode; its own bullet below);
  * d_val is in the CALLER's entry order either way.  What becomes of the handle:
  *   CSR + pad-8 only (no pattern, star, dense or tile form): d_val and the pad-8 values are rewritten, any values; form unchanged.
  *   offsets-only table + per-row values (the "+values" forms of gcge_hip_mat_spmm_form): the same, and the per-row values are
@@ -106,12 +107,21 @@ void gcge_hip_mat_device_stats (long out[4]);
  *     entry, for the duration of the call — and then proceeds by the bullet above that fits the handle's form, on that block; the gather
  *     writes the block only, so a decline still leaves the handle untouched.  The block returns to the pool after the call's last
  *     synchronisation.
+ *   a row slab: d_val holds one value per entry of the LOCAL arrays the slab was created from, in their order (gcge_dist_localize only
+ *     renames columns, a slab never re-orders its rows), and the update proceeds by the bullet above that fits the handle's form: every
+ *     stored copy of a value on a slab derives from the rank's own rows.  A star or dense slab needs its value maps like a whole matrix
+ *     (gcge_hip_mat_keep_value_maps on when the slab was created, by whichever constructor).  The call is RANK-LOCAL and
+ *     COLLECTIVE-FREE: no exchange, no all-reduce, and its return value is this rank's alone.  The rule for callers: reduce the return
+ *     codes over the ranks, and if ANY rank declined, EVERY rank frees its slab and creates it again (creation is collective; a rank
+ *     that accepted holds the new values, one that declined the old ones).  A halo exchange moves X, not matrix values, but an update
+ *     must not overlap a split product: the back-end's stream and, under a native (RCCL) halo plan, its transfer stream are
+ *     synchronised before the first store.
  *   declined (1): a value table of 16 slots whose classes do not stay uniform; a row whose count of present table slots (table value
  *     != 0.0) differs from its length, i.e. an explicitly stored +-0.0; under a star, a pinned entry whose new value differs in bits
  *     from its coefficient (a rescaled Laplacian, say) or a NaN on the diagonal; and, decided from the handle alone before d_val is
  *     read, a star or dense handle WITHOUT value maps (the switch was off at creation: the default), a dense form whose remainder is
- *     tiled, any handle with a tile form, a rectangular handle, a row slab (halo columns, row_begin != 0, a halo plan), a re-ordered
- *     handle WITHOUT an entry map (the switch was off at creation).
+ *     tiled, any handle with a tile form, a rectangular handle, a re-ordered handle WITHOUT an entry map (the switch was off at
+ *     creation).  Every check runs before the first store: a decline has written nothing on that rank.
  * A conversion changes the K1 form between two solves.  Nothing in the back-end keeps a record of a handle's form across calls: the
  * fused CG plans every call from the handle (cg_plan, block_pcg.hip), its parked blocks are keyed by row count and row order, and
  * mat_product.hip reads the handle at every product.  A multigrid hierarchy built from the handle BEFORE an update belongs to the old
@@ -130,8 +140,8 @@ void gcge_hip_mat_update_form_stats (long out[4]);
  * gcge_hip_spmm_reorder_mode), default 0; returns the setting it replaces.  With 0 nothing is kept and a star or dense handle
  * declines every update.  With 1 a handle
  * that takes the star or the dense form also keeps the provenance of its stored values on the device; forms, split, blocks, layers,
- * lists and every stored value array are bit-identical to those of the switch off.  Only a whole matrix on one rank keeps maps (a
- * row slab declines every update).  gcge_hip_mat_value_maps: the bytes of maps a handle holds (0: none) — 4 per block slot and
+ * lists and every stored value array are bit-identical to those of the switch off.  Row slabs keep them like whole matrices (the maps
+ * index the entries of the local arrays; halo columns and the box of a masked grid only decide WHERE a value is stored).  gcge_hip_mat_value_maps: the bytes of maps a handle holds (0: none) — 4 per block slot and
  * pad-8 remainder slot; under a star also 1 per CSR entry, 4 per row and 5 per entry of the star's remainder.  The first update of a
  * star handle also allocates, and keeps, a scratch of 8 bytes per entry of the star's remainder.
  * gcge_hip_value_maps_selfcheck (host only, no device; tests): the forms and maps built from val0 (dense_mode: gcge_hip_spmm_dense_mode
@@ -139,6 +149,11 @@ void gcge_hip_mat_update_form_stats (long out[4]);
  * per-row sums per column and compared with the CSR rows of val1.  Returns the number of differing entries, (row, column) pairs
  * (0: equal), -1: neither a star nor a dense form, -2: an update to val1 would be declined.  out[0] forms found (1 star, 2 blocks, 3 both), out[1] layers of blocks,
  * out[2] pinned entries, out[3] bytes of maps.  _grid: with the masked grid of gcge_hip_mat_create_grid named.
+ * _slab: a row slab with LOCAL columns (the arguments of gcge_hip_star_selfcheck_slab; box_of_local_col != NULL: a slab of a masked grid,
+ * the box index of every local column, own rows then halo rows), asked of the stored values themselves: everything the maps built from
+ * val0 give on val1 — diagonal, the star's remainder, every block and pad-8 slot — against the split and block form built directly
+ * from val1, as bits.  Returns the number of differing stored values; -1 / -2 as above; out[3] = entries of the star's remainder that
+ * sit in halo columns.
  * The same switch makes a handle that RE-ORDERS its rows (gcge_hip_mat_create under gcge_hip_spmm_reorder_mode, a later matrix of the
  * same size that adopts the live order, the host path gcge_hip_mat_create_device falls back to) keep its entry map on the device:
  * 4 bytes per entry (1.4 GB at 350 M entries), freed with the handle.  gcge_hip_mat_entry_map: the bytes of entry map a handle holds
@@ -154,6 +169,9 @@ long gcge_hip_value_maps_selfcheck (int nrows, const int *rowptr, const int *col
                                     long out[4]);
 long gcge_hip_value_maps_selfcheck_grid (int nrows, const int *rowptr, const int *colidx, const double *val0, const double *val1, int dense_mode,
                                          int nx, int ny, int nz, const int *box_of_row, long out[4]);
+long gcge_hip_value_maps_selfcheck_slab (int nrows, int ncols_local, long row_begin, long nglobal, const int *ghost, const int *rowptr,
+                                         const int *colidx, const double *val0, const double *val1, int dense_mode, int nx, int ny, int nz,
+                                         const int *box_of_local_col, long out[4]);
 /* A matrix of that kind that names NO geometry (read from a file: gcge_load_matrix_market, gcge_load_petsc_binary) gets it
  * recovered at upload by gcge_hip_mat_create itself: x lines from the (r, r + 1) couplings, planes and the shifts between
  * lines / planes from the votes of the star rows' + y / + z neighbours.  A wrong guess costs speed, never the result (the
@@ -270,14 +288,25 @@ int  gcge_hip_mg_galerkin_values (const GCGE_HIP_MAT *A, const int *agg_host, in
  *             or the structure check.  The levels below l are refreshed, those from l on keep their old values: still a usable
  *             preconditioner of a nearby operator, no longer the Galerkin hierarchy (with a B, A of level l may have been written
  *             when it is B that declines).  The caller destroys it and creates it again.
- *       -1    nothing was written: A_array is not a hierarchy of this back-end, num_levels is not its level count, a hierarchy of row
- *             slabs, a COARSE level whose handle re-ordered its rows (level 0 may: the hierarchy was built from its CSR in its own order
- *             and P_0's rows are numbered like it; it takes its new values as gcge_hip_mat_update_values_device states).
+ *       -1    nothing was written: A_array is not a hierarchy of this back-end, num_levels is not its level count, a COARSE level whose
+ *             handle re-ordered its rows (level 0 may: the hierarchy was built from its CSR in its own order and P_0's rows are numbered
+ *             like it; it takes its new values as gcge_hip_mat_update_values_device states), a hierarchy of row slabs one of whose
+ *             levels was created without the global rows behind its halo columns (gcge_hip_mat_create_local without _ghosts).
+ *             gcge_hip_multigrid_refresh_check answers this much alone, 0 or -1, and writes nothing.
+ *     A hierarchy of ROW SLABS is refreshed the same way, every rank its own levels: each coarse row of a slab level is scale x the sum
+ *     over fine rows the rank owns (aggregates never cross a cut), so nothing is exchanged; MultiGridCreate keeps, per level, where every
+ *     local column — halo columns through their owners' pairing — lands among the next level's local columns (gcge_mg_slab_colagg,
+ *     include/gcge_multigrid.h: 4 bytes per local column on the device, freed with the hierarchy), and the numeric product uses the
+ *     build's summation order: bit for bit the coarse slabs of a fresh build.  Coarse slabs with a star or dense form need their value
+ *     maps (the switch on around MultiGridCreate).  No B below level 0 on slabs: A's levels only.  The call is RANK-LOCAL and
+ *     COLLECTIVE-FREE and its return is this rank's; GCGE_AMGRefresh (include/gcge_solver.h) is the collective form: it agrees on the
+ *     check before any rank writes and on the smallest declining level afterwards, so every rank sees the same return.
  *     Nothing outside the handles holds values derived from a level's matrix (the smoother's parked blocks are work space keyed by row
  *     count and row order), so a refreshed hierarchy needs no other reset.  gcge_hip_multigrid_refresh_stats: since load, out[0]
  *     refreshes that returned 0, out[1] calls that ended in a decline (l >= 1), out[2] levels written (A and B count separately),
  *     out[3] bytes copied device to host (one flag word per product, plus those of the in-place updates).                          */
 int  gcge_hip_multigrid_refresh (void **A_array, void **B_array, void **P_array, int num_levels);
+int  gcge_hip_multigrid_refresh_check (void **A_array, void **B_array, void **P_array, int num_levels);
 void gcge_hip_multigrid_refresh_stats (long out[4]);
 /*     a handle's device CSR (square, or P of a rectangular one) / the P^T triple of a rectangular one as a host copy (gcge_csr_free) */
 int  gcge_hip_mat_to_csr (const GCGE_HIP_MAT *A, GCGE_CSR *out);

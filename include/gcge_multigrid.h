@@ -124,6 +124,16 @@ const int *gcge_mg_level_box (const GCGE_MG *mg, int level);     /* NULL: the le
 int gcge_mg_build_slab (const GCGE_CSR *A, const int dims[3], const long *part, int rank, int world, int max_levels, double scale,
 		GCGE_MG *mg, long **part_levels_out);
 
+/* Where every LOCAL column of one level of that hierarchy goes (what a refresh of the coarse slab's values in place needs, and all it
+ * needs of the neighbours): dims / part are those of level l (part = part_levels + l * (world + 1)), ghost[nghost] the ascending global
+ * rows behind level l's halo columns, ghost_c[nghost_c] those of level l + 1.  colagg[c], c < nrows_l + nghost: the LOCAL column of
+ * level l + 1 that fine column c aggregates into — an own row through the rank's own pairing (P_l's column), a halo row through its
+ * owner's pairing and its place in ghost_c (nrows_{l+1} + index).  *nlo_c (may be NULL): how many of ghost_c lie below the coarse slab
+ * (a localized row lists them after its own columns although they come first in global order).  Returns 0; -2: the level is not
+ * coarsened (gcge_mg_build_slab would stop here), or a halo row's aggregate is not among ghost_c.                                  */
+int gcge_mg_slab_colagg (const int dims[3], const long *part, int rank, int world, const int *ghost, int nghost, const int *ghost_c,
+		int nghost_c, int *colagg, int *nlo_c);
+
 /* process-wide defaults the back-ends' MultiGridCreate slots use (the slot's signature has no room for them,
  * src/ops.h:134): scale as above (default 0.5), min_rows (default 64), theta of the graph aggregation (default 0.25) */
 void gcge_mg_set_defaults (double scale, int min_rows, double theta);

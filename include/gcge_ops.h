@@ -238,7 +238,11 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *                 call did not collect them, or wrote another panel, or any other call came in between.
  *   multigrid_refresh   the coarse levels of a live hierarchy of ops->MultiGridCreate recomputed in place after level 0 took new
  *                 values for the same structure: 0 done, l >= 1 the first level that declined (those below it are refreshed), -1
- *                 nothing written (GCGE_AMGRefresh, gcge_solver.h; the HIP back-end's gcge_hip_multigrid_refresh, gcge_hip.h). */
+ *                 nothing written (GCGE_AMGRefresh, gcge_solver.h; the HIP back-end's gcge_hip_multigrid_refresh, gcge_hip.h).
+ *                 Rank-local: it calls nothing collective.
+ *   multigrid_refresh_check   what multigrid_refresh decides from the handles alone, before it writes: 0 it would go on, -1 it would
+ *                 return -1.  Rank-local and free of side effects; GCGE_AMGRefresh agrees on it over the ranks before any rank
+ *                 writes.  NULL: multigrid_refresh is asked alone. */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -269,6 +273,7 @@ typedef struct GCGE_BACKEND_ {
 	GCGE_PANEL_NORMS_FN panel_norms_sq;
 	int start_in_place;
 	int  (*multigrid_refresh) (void **A_array, void **B_array, void **P_array, int num_levels);
+	int  (*multigrid_refresh_check) (void **A_array, void **B_array, void **P_array, int num_levels);
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

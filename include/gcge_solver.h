@@ -107,7 +107,11 @@ void GCGE_AMGDestroy (GCGE_AMG **amg, struct OPS_ *ops);
 /*     After A (and B) took new values in place for the same structure: the coarse levels of amg's hierarchy recomputed where they are,
  *     through the back-end's multigrid_refresh (GCGE_BACKEND, gcge_ops.h), whose return value this is — 0: the hierarchy of the new
  *     values; l >= 1: level l declined, the caller destroys the hierarchy and creates it again; -1: nothing was written, also when
- *     the back-end of `ops` offers no refresh.  Work blocks, parameter arrays and the installed solver are not touched.          */
+ *     the back-end of `ops` offers no refresh.  Work blocks, parameter arrays and the installed solver are not touched.
+ *     Over a communicator (GCGE_SetComm: a hierarchy of row slabs) the call is COLLECTIVE and every rank gets the same return: the
+ *     back-end's refresh is rank-local, and the ranks agree by two all-reduces every rank reaches unconditionally — one on what the
+ *     back-end decides from the handles alone (multigrid_refresh_check), before any rank writes, so a -1 anywhere is a -1 everywhere
+ *     with nothing written; one after the level loop, whose result is the smallest level that declined on any rank, or 0.          */
 int  GCGE_AMGRefresh (GCGE_AMG *amg, struct OPS_ *ops);
 
 /* ---- GCG eigensolver (sets ops->EigenSolver) -------------------------------- */
