@@ -770,6 +770,7 @@ extern "C" void OPS_HIP_Set(struct OPS_* ops) {
   be.symeig = gcge_hip_symeig; be.symeig_min_n = 192;
   gcge_hip_product_slots(ops, &be);           // MatDotMultiVec / MatTransDotMultiVec, the residual hook, the V-cycle's fused sweeps
   gcge_hip_bpcg_backend(&be);                 // the fused device CG: BlockAMG's smoother, and the solver of unformed b = x diag(scale)
+  gcge_hip_pcg_backend(&be);                  // the sweeps of GCGE_PCGSolve's step, one launch each (pcg_sweeps.hip)
   be.pas_border = gcge_hip_pas_border;        // PAS: y += QX t and g = QX^T q in one pass over QX
   be.block_moves = HIP_BlockMoves;            // GCG's X / W start / b moves of an outer iteration in one sweep
   be.ritz_in_place = HIP_RitzInPlace;         // GCG's Ritz vectors written over X, P moved in behind them: no ComputeX

@@ -410,21 +410,7 @@ __global__ __launch_bounds__(256) void cg_scalars_b(int m, const double* __restr
 
 using namespace gcge;
 
-static bool cg_vec_ok(int m, std::initializer_list<const double*> ptrs, std::initializer_list<long> lds) {
-  if (m & 1) return false;
-  for (const double* q : ptrs) if ((uintptr_t)q & 15) return false;
-  for (long l : lds) if (l & 1) return false;
-  return true;
-}
-static int cg_tpr(int m) { int t = 1; while (t < m / 2) t *= 2; return t; }   // threads per row (m <= 512)
-
-// the row split of every sweep that leaves partial sums: nb workgroups of rpb rows each (a multiple of 4)
-struct CgGrid { long nb, rpb; };
-static CgGrid cg_grid(long n) {
-  long nb = (n + 255) / 256; if (nb > 2048) nb = 2048;
-  const long rpb = ((n + nb - 1) / nb + 3) / 4 * 4;
-  return {(n + rpb - 1) / rpb, rpb};
-}
+// (cg_vec_ok, cg_tpr, cg_grid: gcge_hip_internal.h, shared with pcg_sweeps.hip)
 
 static void launch_update_xp(long n, const double* r, long ldr, double* p, long ldp, double* x, long ldx, int mw,
                              const double* beta, const double* aprev, const int* flag, hipStream_t st) {

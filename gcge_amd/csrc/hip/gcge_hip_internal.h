@@ -147,6 +147,26 @@ extern "C" int gcge_hip_mg_download_csr(int nrows, int ncols, long nnz, const in
 void gcge_hip_mg_members_host(const int* agg, int nf, int nc, std::vector<int>& ptr, std::vector<int>& mem);
 // block_pcg.hip: the fused CG's part of the back-end record OPS_HIP_Set registers (the BlockAMG smoother, the scaled-rhs solver)
 extern "C" void gcge_hip_bpcg_backend(GCGE_BACKEND* be);
+// pcg_sweeps.hip: the three sweeps of GCGE_PCGSolve's step (pcg_step / pcg_dots / pcg_direction) and the fused CG's iteration count
+extern "C" void gcge_hip_pcg_backend(GCGE_BACKEND* be);
+// What the block sweeps of block_pcg.hip and pcg_sweeps.hip share.  16-byte lanes (column pairs) need an even width, 16-byte aligned
+// column origins and even leading dimensions; cg_tpr: threads per row of such a sweep (m <= 512)
+#include <initializer_list>
+#include <stdint.h>
+static inline bool cg_vec_ok(int m, std::initializer_list<const double*> ptrs, std::initializer_list<long> lds) {
+  if (m & 1) return false;
+  for (const double* q : ptrs) if ((uintptr_t)q & 15) return false;
+  for (long l : lds) if (l & 1) return false;
+  return true;
+}
+static inline int cg_tpr(int m) { int t = 1; while (t < m / 2) t *= 2; return t; }
+// the row split of every sweep that leaves partial sums: nb workgroups of rpb rows each (a multiple of 4)
+struct CgGrid { long nb, rpb; };
+static inline CgGrid cg_grid(long n) {
+  long nb = (n + 255) / 256; if (nb > 2048) nb = 2048;
+  const long rpb = ((n + nb - 1) / nb + 3) / 4 * 4;
+  return {(n + rpb - 1) / rpb, rpb};
+}
 // A column scaling the slots hold back (column-wise Gram-Schmidt, app_hip.hip) is applied now.  First statement of every EXPORTED
 // raw kernel that takes device pointers: the caller may have fetched its pointer before the scaling was held back.
 extern "C" void gcge_hip_apply_pending(void);

@@ -59,7 +59,8 @@ void **GCGE_GetRealignedRhs(int *b0) { if (b0 != NULL) *b0 = g_realigned_b0; ret
  *   GCGE_NO_RESIDUAL_HOOK    residual_sq                                    (CheckConvergence through the slots)
  *   GCGE_NO_INPLACE_LINCOMB  inplace_lincomb_cols                           (panel updates staged through a work block)
  *   GCGE_EIG_HOST            symeig                                         (projected eigenproblems on the host)
- *   GCGE_AMG_HOST_SMOOTHER   amg_smoother_setup, amg_smoother_residual      (BlockAMG smooths with BlockPCG over the slots)
+ *   GCGE_AMG_HOST_SMOOTHER   amg_smoother_setup, amg_smoother_residual,     (BlockAMG smooths with BlockPCG over the slots)
+ *                            amg_smoother_niter
  *   GCGE_AMG_NO_FUSIONS      amg_residual, amg_prolong_add, amg_form_rhs,   (the V-cycle's slot calls;
  *                            amg_final_cols                                  every smoothing call runs its last pass whole)
  *   GCGE_AMG_FULL_LAST_PASS  amg_final_cols                                 (the same, alone)
@@ -67,7 +68,8 @@ void **GCGE_GetRealignedRhs(int *b0) { if (b0 != NULL) *b0 = g_realigned_b0; ret
  *   GCGE_NO_BLOCK_MOVES      block_moves                                    (X, the W start vectors and b moved one by one)
  *   GCGE_NO_RITZ_IN_PLACE    ritz_in_place                                  (Ritz vectors into the eigenvector block, then ComputeX)
  *   GCGE_NO_PANEL_NORMS      panel_norms_sq                                 (column norms by a sweep of their own)
- *   GCGE_NO_START_IN_PLACE   start_in_place                                 (the W start vectors and b moved before the solve) */
+ *   GCGE_NO_START_IN_PLACE   start_in_place                                 (the W start vectors and b moved before the solve)
+ *   GCGE_NO_PCG_SWEEPS       pcg_step, pcg_dots, pcg_direction              (GCGE_PCGSolve's sweeps through the slots) */
 static GCGE_BACKEND g_backend; static void *g_backend_matvec = NULL, *g_backend_lincomb = NULL;
 void GCGE_SetBackend(struct OPS_ *ops, const GCGE_BACKEND *backend)
 {
@@ -84,7 +86,7 @@ GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
 	if (getenv("GCGE_NO_RESIDUAL_HOOK") != NULL) b.residual_sq = NULL;
 	if (getenv("GCGE_NO_INPLACE_LINCOMB") != NULL) b.inplace_lincomb_cols = 0;
 	if (getenv("GCGE_EIG_HOST") != NULL) b.symeig = NULL;
-	if (getenv("GCGE_AMG_HOST_SMOOTHER") != NULL) { b.amg_smoother_setup = NULL; b.amg_smoother_residual = NULL; b.amg_final_cols = 0; }
+	if (getenv("GCGE_AMG_HOST_SMOOTHER") != NULL) { b.amg_smoother_setup = NULL; b.amg_smoother_residual = NULL; b.amg_smoother_niter = NULL; b.amg_final_cols = 0; }
 	if (getenv("GCGE_AMG_NO_FUSIONS") != NULL) { b.amg_residual = NULL; b.amg_prolong_add = NULL; b.amg_form_rhs = NULL; b.amg_final_cols = 0; }
 	if (getenv("GCGE_AMG_FULL_LAST_PASS") != NULL) b.amg_final_cols = 0;
 	if (getenv("GCGE_NO_RHS_SCALE") != NULL) { b.scaled_rhs_solver = NULL; b.amg_form_rhs = NULL; }
@@ -92,6 +94,7 @@ GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
 	if (getenv("GCGE_NO_RITZ_IN_PLACE") != NULL) b.ritz_in_place = NULL;
 	if (getenv("GCGE_NO_PANEL_NORMS") != NULL) b.panel_norms_sq = NULL;
 	if (getenv("GCGE_NO_START_IN_PLACE") != NULL) b.start_in_place = 0;
+	if (getenv("GCGE_NO_PCG_SWEEPS") != NULL) { b.pcg_step = NULL; b.pcg_dots = NULL; b.pcg_direction = NULL; }
 	return b;
 }
 

@@ -156,6 +156,14 @@ class HipBackendImpl:
         the caller's and must outlive the hierarchy."""
         return Hierarchy(self, A, M, int(levels), int(block_size), int(cycles), int(smooth0), int(smooth), float(rate), bool(refreshable))
 
+    def linear_solver(self, A, amg=None, max_cols=8):
+        """A LinearSolver for A X = B on the matrix handle A with up to `max_cols` right-hand sides per solve (GCGE_PCGCreate): flexible
+        block CG preconditioned by one V-cycle of the Hierarchy `amg` (HipBackend.multigrid, built on A), or with amg=None the fused
+        block CG alone.  The handle and the hierarchy stay the caller's and must outlive the solver; new values in the handle
+        (matrix_update_values, then amg.refresh()) need no new solver.  ValueError: amg was built on another handle or belongs to
+        another back-end."""
+        return LinearSolver(self, A, amg, int(max_cols))
+
     def mv_to_torch(self, mv, c0, c1):
         """Columns [c0, c1) of a block of vectors as a new (n, c1 - c0) float64 tensor on the GPU, rows in the caller's order
         (gcge_hip_mv_to_device): nothing passes through the host."""
@@ -341,6 +349,132 @@ class Hierarchy:
         if self._amg is not None:
             self.backend.h.GCGE_AMGDestroy(C.byref(self._amg), self.backend.ops_handle)
             self._amg = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+
+class LinearSolver:
+    """What HipBackend.linear_solver returns: a live GCGE_PCG (include/gcge_solver.h) with its work blocks and a right-hand-side and a
+    solution block of max_cols columns.  solve(b, ...) as often as wanted; close() (or a with block) frees it.  .column_iterations: the
+    iteration count of every column of the last solve (numpy int32)."""
+
+    def __init__(self, backend, A, amg, max_cols):
+        as_handle = lambda a: a if isinstance(a, C.c_void_p) else C.c_void_p(a)
+        if max_cols < 1:
+            raise ValueError("linear_solver: at least one column is required")
+        if amg is not None:
+            if amg.backend is not backend:
+                raise ValueError("linear_solver: amg belongs to another back-end")
+            if as_handle(A).value != amg.A.value:
+                raise ValueError("linear_solver: amg was not built on this matrix handle")
+        self.backend, self.A, self.amg, self.max_cols = backend, as_handle(A), amg, max_cols
+        self.n = int(backend.g.gcge_hip_mat_nrows(self.A))
+        self._s = self._b = self._x = self.column_iterations = None
+        self._b = backend.ops.mv_create(max_cols, self.A)
+        self._x = backend.ops.mv_create(max_cols, self.A)
+        try:
+            self._create()
+        except Exception:
+            self.close()
+            raise
+
+    def _create(self):
+        b = self.backend
+        if self._s is not None:
+            b.h.GCGE_PCGDestroy(C.byref(self._s), b.ops_handle)
+            self._s = None
+        if self.amg is not None:
+            self.amg._head()                                           # ValueError: the hierarchy is closed
+        self._amg_ptr = self.amg._amg.value if self.amg is not None else None
+        s = b.h.GCGE_PCGCreate(self.A, self.amg._amg if self.amg is not None else None, self.max_cols, b.ops_handle)
+        if not s:
+            raise RuntimeError("GCGE_PCGCreate failed")
+        self._s = C.c_void_p(s)
+
+    def _block(self, t, what):
+        """(2-D device tensor, was 1-D) of a right-hand side or a start block"""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            if not hasattr(t, "__cuda_array_interface__"):
+                raise TypeError("solve: %s must be a torch device tensor or an object with __cuda_array_interface__" % what)
+            t = torch.as_tensor(t, device=self.backend.torch_device())
+            torch.cuda.synchronize(t.device)                           # (a producer torch knows nothing of)
+        if not t.is_cuda:
+            raise TypeError("solve: %s must live on the GPU" % what)
+        flat = t.dim() == 1
+        if flat:
+            t = t.reshape(-1, 1)
+        if t.dim() != 2 or t.shape[1] < 1:
+            raise ValueError("solve: %s is an (n, m) or (n,) block" % what)
+        if t.shape[0] != self.n:
+            raise ValueError("solve: %s has %d rows, the matrix %d" % (what, t.shape[0], self.n))
+        if t.shape[1] > self.max_cols:
+            raise ValueError("solve: %d columns, the solver was created for %d" % (t.shape[1], self.max_cols))
+        return t, flat
+
+    def solve(self, b, x0=None, tol=1e-8, maxiter=200):
+        """A X = b to the relative residual |b_j - A x_j| <= tol |b_j| in every column, within `maxiter` outer iterations (V-cycles per
+        column; without a hierarchy: iterations of the block CG).  b: an (n, m) or (n,) CUDA tensor or an object with
+        __cuda_array_interface__, m <= max_cols, rows in the caller's order, any strides (mv_from_torch); x0: likewise, or None for a
+        zero start.  Returns SolveResult(x, converged, iterations, residual_norms, seconds): x a float64 device tensor of b's shape,
+        converged a bool tensor per column, iterations the largest count of any column, residual_norms the TRUE relative residuals
+        |b_j - A x_j| / |b_j| the library formed after its last step.  Raises gcge_amd.NoConvergence, carrying that result, when a
+        column did not converge.  TypeError: a host tensor; ValueError: another row count, more than max_cols columns, x0 of
+        another shape than b."""
+        import time
+        import numpy as np
+        import torch
+        from .eigsh import NoConvergence
+        from .solve import SolveResult
+        if self._s is None:
+            raise ValueError("the solver is closed")
+        if self.amg is not None and self.amg._amg is None:
+            raise ValueError("the hierarchy is closed")
+        bk = self.backend
+        bt, flat = self._block(b, "b")
+        m = int(bt.shape[1])
+        if x0 is not None:
+            xt, _ = self._block(x0, "x0")
+            if tuple(xt.shape) != tuple(bt.shape):
+                raise ValueError("solve: x0 has another shape than b")
+        if self.amg is not None and self.amg._amg.value != self._amg_ptr:   # refresh() built the hierarchy again
+            self._create()
+        bk.mv_from_torch(self.A, bt, mv=self._b, c0=0)
+        if x0 is not None:
+            bk.mv_from_torch(self.A, xt, mv=self._x, c0=0)
+        rel, it = np.zeros(m), np.zeros(m, dtype=np.int32)
+        bk.sync()
+        t0 = time.perf_counter()
+        rc = bk.h.GCGE_PCGSolve(self._s, self._b, 0, self._x, 0, m, float(tol), int(maxiter), 1 if x0 is None else 0,
+                                rel.ctypes.data_as(C.c_void_p), it.ctypes.data_as(C.c_void_p), bk.ops_handle)
+        bk.sync()
+        seconds = time.perf_counter() - t0
+        self.column_iterations = it.copy()                             # per column: V-cycles (amg=None: the one call's count)
+        if rc < 0:
+            raise RuntimeError("GCGE_PCGSolve rc=%d%s" % (rc, " (a communicator is set: single rank only)" if rc == -2 else ""))
+        x = bk.mv_to_torch(self._x, 0, m)
+        if flat:
+            x = x.reshape(-1)
+        result = SolveResult(x, torch.from_numpy(rel <= tol).to(x.device), int(it.max()), torch.from_numpy(rel).to(x.device), seconds)
+        if rc < m:
+            raise NoConvergence("solve: %d of %d columns converged in %d iterations" % (rc, m, result.iterations), result)
+        return result
+
+    def close(self):
+        b = self.backend
+        if self._s is not None:
+            b.h.GCGE_PCGDestroy(C.byref(self._s), b.ops_handle)
+            self._s = None
+        for name in ("_b", "_x"):
+            mv = getattr(self, name)
+            if mv is not None and mv.value:
+                b.ops.mv_destroy(mv, self.max_cols)
+            setattr(self, name, None)
 
     def __enter__(self):
         return self

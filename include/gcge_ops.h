@@ -242,7 +242,19 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *                 Rank-local: it calls nothing collective.
  *   multigrid_refresh_check   what multigrid_refresh decides from the handles alone, before it writes: 0 it would go on, -1 it would
  *                 return -1.  Rank-local and free of side effects; GCGE_AMGRefresh agrees on it over the ranks before any rank
- *                 writes.  NULL: multigrid_refresh is asked alone. */
+ *                 writes.  NULL: multigrid_refresh is asked alone.
+ *   pcg_step      one step of the preconditioned CG of GCGE_PCGSolve (gcge_solver.h) on a window of m columns, in one sweep:
+ *                 x[:, x0..) += p[:, p0..) diag(alpha) ;  r[:, r0..) -= w[:, w0..) diag(alpha) ;  rr[j] = sum over the LOCAL rows of
+ *                 r_new[r, j]^2 — for the columns with flag[j] != 0 only; a column without a flag keeps the bits of its x and r (its
+ *                 rr[j] is 0).  alpha, flag, rr: host arrays of m entries.  The slots take, per flagged column, two MultiVecAxpby,
+ *                 then MultiVecLocalInnerProd('D') over the window: 4 reads + 2 writes + 2 reads.  0 declines, nothing touched.
+ *   pcg_dots      zr[j] = sum z[r, j] r[r, j] and zw[j] = sum z[r, j] w[r, j] over the LOCAL rows, j < m, from ONE read of z, r and w
+ *                 (the slots: two MultiVecLocalInnerProd('D'), 4 reads).  Host arrays.  0 declines.
+ *   pcg_direction p[:, p0..) = z[:, z0..) + p diag(beta) for the columns with flag[j] == 1, p = z for those with flag[j] == 2 (p is
+ *                 not read: it may hold anything), and a column with flag[j] == 0 keeps its bits (the slots: one MultiVecAxpby per
+ *                 flagged column).  beta, flag: host arrays of m entries.  0 declines, nothing touched.
+ *   amg_smoother_niter   the iteration count of the last call of the smoother of amg_smoother_setup (what BlockPCGSolver.niter would
+ *                 hold): GCGE_PCGSolve without a hierarchy reports it.  NULL: that solve takes BlockPCG over the slots. */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -256,6 +268,10 @@ typedef int    (*GCGE_BLOCK_MOVES_FN) (void **ritz, void **V, int x0, int x1, co
 typedef int    (*GCGE_RITZ_IN_PLACE_FN) (void **V, int n0, int x1, int w1, const double *coef, int ldc, void **S, int p0, int np,
 		struct OPS_ *ops);
 typedef int    (*GCGE_PANEL_NORMS_FN) (void **y, int start, int end, double *out, struct OPS_ *ops);
+typedef int    (*GCGE_PCG_STEP_FN) (void **p, int p0, void **w, int w0, void **x, int x0, void **r, int r0, int m, const double *alpha,
+		const int *flag, double *rr, struct OPS_ *ops);
+typedef int    (*GCGE_PCG_DOTS_FN) (void **z, int z0, void **r, int r0, void **w, int w0, int m, double *zr, double *zw, struct OPS_ *ops);
+typedef int    (*GCGE_PCG_DIRECTION_FN) (void **z, int z0, void **p, int p0, int m, const double *beta, const int *flag, struct OPS_ *ops);
 typedef struct GCGE_BACKEND_ {
 	GCGE_RESIDUAL_FN residual_sq;
 	int inplace_lincomb_cols;
@@ -274,6 +290,8 @@ typedef struct GCGE_BACKEND_ {
 	int start_in_place;
 	int  (*multigrid_refresh) (void **A_array, void **B_array, void **P_array, int num_levels);
 	int  (*multigrid_refresh_check) (void **A_array, void **B_array, void **P_array, int num_levels);
+	GCGE_PCG_STEP_FN pcg_step; GCGE_PCG_DOTS_FN pcg_dots; GCGE_PCG_DIRECTION_FN pcg_direction;
+	int  (*amg_smoother_niter) (struct OPS_ *ops);
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

@@ -114,6 +114,29 @@ void GCGE_AMGDestroy (GCGE_AMG **amg, struct OPS_ *ops);
  *     with nothing written; one after the level loop, whose result is the smallest level that declined on any rank, or 0.          */
 int  GCGE_AMGRefresh (GCGE_AMG *amg, struct OPS_ *ops);
 
+/* ---- linear systems A X = B, converged to a tolerance (csrc/host/block_fpcg.c) -------
+ * Flexible preconditioned block CG, every column with its own alpha and beta as in BlockPCG; the preconditioner z = V(r) is one call
+ * of BlockAMG over `amg` from z = 0 (installed as GCGE_AMGInstall does and called through ops->MultiLinearSolver with cleared
+ * GCGE_LINSOL_ARGS; the slot, its workspace pointer and what was published are put back before GCGE_PCGSolve returns):
+ *     alpha_j = (z.r)_j / (p.w)_j ;  x += alpha p ;  r -= alpha w ;  beta_j = -alpha_j (z_new.w)_j / (z_old.r_old)_j ;  p = z + beta p
+ * A column stops at |r_j| <= tol |b_j| (|b_j| = 0: x_j = 0, rel_res 0) and is retired with alpha = 0 and no flag: its x, r, p keep their
+ * bits; the V-cycle runs over the contiguous window of the columns still active.  m > amg->block_size: chunks of block_size columns,
+ * each solved as a call of its own would.  When the recurrence is through with a chunk, b - A x is formed (the back-end's amg_residual,
+ * else the slots); a column whose TRUE relative residual is above tol starts again from it, within max_iter.  rel_res[j] is always
+ * that true value, col_iters[j] the V-cycles column j saw (at most max_iter).
+ * amg == NULL: one call of the block CG that exists — the back-end's amg_smoother_setup(max_iter, 0, tol, "rel") where it is offered,
+ * BlockPCG on the solver's blocks otherwise —, then the same true-residual report; col_iters[j] is that call's iteration count.
+ * The sweeps go through GCGE_BACKEND.pcg_step / pcg_dots / pcg_direction (gcge_ops.h) where the back-end offers them.
+ * GCGE_PCGCreate: four blocks of max_cols columns created by A (r, z, p, w) and the scalar arrays; NULL on bad arguments, among
+ * them a hierarchy whose level 0 is not A.  GCGE_PCGSolve: zero_start != 0 starts from x = 0 whatever x holds; returns the number
+ * of columns with rel_res <= tol, -1 on bad arguments (m > max_cols among them), -2 while a communicator of more than one rank is
+ * set (single rank only) — nothing is written then.                                                                              */
+typedef struct GCGE_PCG_ GCGE_PCG;
+GCGE_PCG *GCGE_PCGCreate (void *A, GCGE_AMG *amg, int max_cols, struct OPS_ *ops);
+int  GCGE_PCGSolve (GCGE_PCG *s, void **b, int b0, void **x, int x0, int m, double tol, int max_iter, int zero_start,
+		double *rel_res, int *col_iters, struct OPS_ *ops);
+void GCGE_PCGDestroy (GCGE_PCG **s, struct OPS_ *ops);
+
 /* ---- GCG eigensolver (sets ops->EigenSolver) -------------------------------- */
 typedef struct GCGSolver_ {
 	void   *A; void *B; double sigma;
