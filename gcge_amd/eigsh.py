@@ -63,11 +63,62 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
     backend:  a HipBackend (default: one per device, kept for the process).
     gcge_args:  harness options ("-gcge_compW_cg_max_iter", 40, ...), appended as they are; they win over the arguments above.
 
+    Gradients: when A (or M) is given as a sparse_csr tensor or a (crow, col, val) triple whose values require grad, and grad mode is
+    on, `eigenvalues` comes back attached to the graph and backward gives d loss / d values on the stored entries
+    (gcge_amd.grad.eigenvalue_grads: d lambda_c / d A_ij = x_ic x_jc, d lambda_c / d M_ij = -lambda_c x_ic x_jc, one kernel call per
+    matrix); the matrix is created from the detached values.  `eigenvectors` and `residual_norms` are marked non-differentiable:
+    gradients through eigenvectors need deflated solves and are not implemented.  Double backward raises.  With handles, or
+    without a tensor that requires grad, nothing is attached and nothing else changes.
+
     Returns EigshResult(eigenvalues (k,), eigenvectors (n, k), converged, iterations, seconds, residual_norms (k,)), tensors float64
     on the device.  Raises NoConvergence, carrying the partial result, when fewer than k pairs converged."""
+    import torch
+    dA, dM = _differentiable(A), _differentiable(M)
+    kw = dict(X0=X0, tol=tol, maxiter=maxiter, nev_max=nev_max, block_size=block_size, amg_levels=amg_levels, gcge_args=gcge_args, amg=amg)
+    if dA is None and dM is None:
+        return _eigsh(A, k, M, backend=backend, **kw)
+    from .grad import _function
+    backend = _backend_for(backend, A, M, X0)
+    detached = lambda a, d: a if d is None else (a.detach() if isinstance(a, torch.Tensor) else (a[0], a[1], a[2].detach()) + tuple(a[3:]))
+    box = {}
+
+    def run():
+        box["result"] = _eigsh(detached(A, dA), k, detached(M, dM) if M is not None else None, backend=backend, **kw)
+        return box["result"]
+
+    lam, V, rn = _function(0).apply(dA[2] if dA is not None else None, dM[2] if dM is not None else None, run, backend,
+                                      dA[:2] if dA is not None else None, dM[:2] if dM is not None else None)
+    return box["result"]._replace(eigenvalues=lam, eigenvectors=V, residual_norms=rn)
+
+
+def _differentiable(a):
+    """(crow, col, val) when `a` is a matrix given as tensors whose values require grad while grad mode is on, else None"""
+    import torch
+    if a is None or _is_handle(a) or not torch.is_grad_enabled():
+        return None
+    if isinstance(a, torch.Tensor):
+        return (a.crow_indices(), a.col_indices(), a.values()) if a.layout == torch.sparse_csr and a.requires_grad else None
+    if isinstance(a, (tuple, list)) and len(a) >= 3 and isinstance(a[2], torch.Tensor) and a[2].requires_grad:
+        return (a[0], a[1], a[2])
+    return None
+
+
+def _backend_for(backend, *things):
+    """`backend`, or the HipBackend kept for the device of the first CUDA tensor among `things` (torch's current device without one)"""
+    from .lib import HipBackend
+    if backend is None:
+        dev = _device_of(*things)
+        backend = _backends.get(dev)
+        if backend is None:
+            backend = _backends[dev] = HipBackend(device=dev)
+    return backend
+
+
+def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None):
+    """eigsh on detached inputs: see there"""
     import numpy as np
     import torch
-    from .lib import HipBackend, host_lib, run_gcg
+    from .lib import host_lib, run_gcg
 
     k = int(k)
     nev_max = 2 * k if nev_max is None else int(nev_max)
@@ -89,11 +140,7 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
         backend = amg.backend
         if block_size is None:
             block_size = amg.block_size
-    if backend is None:
-        dev = _device_of(A, M, X0)
-        backend = _backends.get(dev)
-        if backend is None:
-            backend = _backends[dev] = HipBackend(device=dev)
+    backend = _backend_for(backend, A, M, X0)
     gcge_args = [str(a) for a in gcge_args]
     own = [("-nevConv", k), ("-nevMax", nev_max), ("-gcge_rel_tol", repr(float(tol)))]
     if maxiter is not None:

@@ -231,6 +231,48 @@ class HipBackendImpl:
             self.g.gcge_hip_mv_from_device(mv, c0, c0 + m, t.data_ptr(), rs, cs)
         return mv
 
+    def sample_outer(self, crow, col, U, V, weights=None, alpha=1.0):
+        """The rank-k product U diag(weights) V^T on the stored entries of a CSR pattern (gcge_hip_csr_sample_outer): an (nnz,)
+        float64 device tensor with out[e] = alpha sum_c weights[c] U[i, c] V[col[e], c] for every entry e of row i, in the entry order
+        of `crow`, `col` — never in a handle's.  crow (n + 1), col (nnz): device index tensors, converted to int32 on the device if
+        they are something else; U (n, k), V (rows for every column index, k): 2-D CUDA tensors, converted to float64 if they are
+        something else, taken as they are when their rows are contiguous (any row stride >= k) and copied once otherwise; U and V
+        may be the same tensor; weights: k values (None: all ones).  The producer's stream (torch's current one) is synchronised
+        before the call, the kernel runs on the library's stream and has finished on return.  TypeError: a host tensor;
+        ValueError: shapes that do not belong together."""
+        import torch
+        for name, t in (("crow", crow), ("col", col), ("U", U), ("V", V)) + ((("weights", weights),) if weights is not None else ()):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise TypeError("sample_outer: %s must be a torch tensor that lives on the GPU" % name)
+        if U.dim() != 2 or V.dim() != 2 or U.shape[1] != V.shape[1] or U.shape[1] < 1:
+            raise ValueError("sample_outer: U and V are (n, k) and (ncols, k) blocks of the same k >= 1 columns")
+        n, k = int(U.shape[0]), int(U.shape[1])
+        rp = crow.reshape(-1).to(dtype=torch.int32).contiguous()
+        ci = col.reshape(-1).to(dtype=torch.int32).contiguous()
+        if rp.numel() != n + 1:
+            raise ValueError("sample_outer: %d row pointers for a U of %d rows" % (rp.numel(), n))
+        if weights is not None and weights.numel() != k:
+            raise ValueError("sample_outer: %d weights for %d columns" % (weights.numel(), k))
+
+        def rows_contiguous(t):
+            t = t.to(dtype=torch.float64)
+            return t if t.stride(1) == 1 and (t.stride(0) >= k or t.shape[0] <= 1) else t.contiguous()
+
+        Ud, Vd = rows_contiguous(U), rows_contiguous(V)
+        w = weights.reshape(-1).to(dtype=torch.float64).contiguous() if weights is not None else None
+        nnz = int(ci.numel())
+        out = torch.empty(nnz, dtype=torch.float64, device=Ud.device)
+        if n == 0 or nnz == 0:
+            return out
+        torch.cuda.current_stream(Ud.device).synchronize()
+        rc = self.g.gcge_hip_csr_sample_outer(n, rp.data_ptr(), ci.data_ptr(), Ud.data_ptr(), max(int(Ud.stride(0)), k), Vd.data_ptr(),
+                                              max(int(Vd.stride(0)), k), k, w.data_ptr() if w is not None else None, float(alpha),
+                                              out.data_ptr(), self.g.gcge_hip_stream())
+        self.sync()
+        if rc != 0:
+            raise RuntimeError("gcge_hip_csr_sample_outer rc=%d" % rc)
+        return out
+
     def matrix_grid(self, csr, dims, box_of_row, updatable=False):
         """A matrix on a masked grid: box_of_row[r] = x + nx (y + ny z) (int32 array, ascending); see gcge_hip_mat_create_grid.
         updatable: as for HipBackend.matrix."""
@@ -425,7 +467,18 @@ class LinearSolver:
         converged a bool tensor per column, iterations the largest count of any column, residual_norms the TRUE relative residuals
         |b_j - A x_j| / |b_j| the library formed after its last step.  Raises gcge_amd.NoConvergence, carrying that result, when a
         column did not converge.  TypeError: a host tensor; ValueError: another row count, more than max_cols columns, x0 of
-        another shape than b."""
+        another shape than b.
+        When b is a tensor that requires grad and grad mode is on, x comes back attached to the graph: backward solves
+        A Z = d loss / d x with this solver, the same tol and maxiter (NoConvergence when that solve does not converge), and Z is
+        the gradient with respect to b.  The solver must then be open when backward runs.  Double backward raises."""
+        import torch
+        if isinstance(b, torch.Tensor) and b.requires_grad and torch.is_grad_enabled():
+            from .grad import _solve_attached
+            return _solve_attached(self, b, x0, tol, maxiter)
+        return self._solve(b, x0, tol, maxiter)
+
+    def _solve(self, b, x0, tol, maxiter):
+        """solve on a detached b: see there"""
         import time
         import numpy as np
         import torch

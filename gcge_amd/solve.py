@@ -7,7 +7,7 @@ alone), the solution comes out through HipBackend.mv_to_torch.  HipBackend.linea
 import collections
 import ctypes as C
 
-from .eigsh import NoConvergence, _backends, _device_of, _is_handle  # noqa: F401
+from .eigsh import NoConvergence, _backends, _device_of, _differentiable, _is_handle  # noqa: F401
 
 SolveResult = collections.namedtuple("SolveResult", ["x", "converged", "iterations", "residual_norms", "seconds"])
 
@@ -26,7 +26,14 @@ def solve(A, b, x0=None, tol=1e-8, maxiter=200, amg=None, amg_levels=0, backend=
 
     Returns SolveResult(x, converged, iterations, residual_norms, seconds) as LinearSolver.solve does (x of b's shape, converged a
     bool tensor per column, residual_norms the true relative residuals); raises NoConvergence, carrying the result, when a column
-    did not converge.  A sequence of solves on one handle keeps a solver instead: HipBackend.linear_solver(A, amg=h)."""
+    did not converge.  A sequence of solves on one handle keeps a solver instead: HipBackend.linear_solver(A, amg=h).
+
+    Gradients: when b requires grad, or A is given as a sparse_csr tensor or a (crow, col, val) triple whose values require grad, and
+    grad mode is on, x comes back attached to the graph.  Backward solves A Z = d loss / d x with the same solver, hierarchy, tol
+    and maxiter (NoConvergence when that solve does not converge) and gives Z for b and -Z_i . x_j on the stored entries for the
+    values (gcge_amd.grad.solve_grads); with a handle for A the gradient with respect to b alone.  The matrix is created from the
+    detached values; what this call created is then freed when backward has run or the graph is freed, not on return.  Double
+    backward raises."""
     from .lib import HipBackend
 
     amg_levels = int(amg_levels)
@@ -53,6 +60,11 @@ def solve(A, b, x0=None, tol=1e-8, maxiter=200, amg=None, amg_levels=0, backend=
     if m < 1:
         raise ValueError("solve: at least one right-hand side is required")
 
+    import torch
+    dA = _differentiable(A)
+    attached = dA is not None or (isinstance(b, torch.Tensor) and b.requires_grad and torch.is_grad_enabled())
+    if dA is not None:                                                  # the matrix is created from the detached values
+        A = A.detach() if isinstance(A, torch.Tensor) else (A[0], A[1], A[2].detach()) + tuple(A[3:])
     made, built, solver = None, None, None
     try:
         if _is_handle(A):
@@ -62,7 +74,18 @@ def solve(A, b, x0=None, tol=1e-8, maxiter=200, amg=None, amg_levels=0, backend=
         if amg_levels > 0:
             built = backend.multigrid(mA, levels=amg_levels, block_size=min(m, 64), refreshable=False)
         solver = backend.linear_solver(mA, amg=amg if amg is not None else built, max_cols=m)
-        return solver.solve(b, x0=x0, tol=tol, maxiter=maxiter)
+        if not attached:
+            return solver.solve(b, x0=x0, tol=tol, maxiter=maxiter)
+        # x attached to the graph: what was created here now lives until backward has run or the graph is freed
+        from .grad import _Owned, _solve_attached
+        owned, kept = _Owned(backend, solver, built, made), solver
+        made, built, solver = None, None, None
+        try:
+            return _solve_attached(kept, b, x0, tol, maxiter, structure_A=dA[:2] if dA is not None else None,
+                                   val_A=dA[2] if dA is not None else None, owned=owned)
+        except BaseException:
+            owned.release()
+            raise
     finally:
         if solver is not None:
             solver.close()

@@ -451,6 +451,17 @@ int gcge_hip_csr_spmm  (int nrows, const int *d_rowptr, const int *d_colidx, con
 		const double *d_x, long ldx, double *d_y, long ldy, int ncols, void *stream);
 int gcge_hip_pad8_spmm (int nrows, const int *d_orp, const int *d_pcol, const double *d_pval,
 		const double *d_x, long ldx, double *d_y, long ldy, int ncols, void *stream);
+/*     the sampled outer product on a CSR pattern (csrc/hip/sample_outer.hip): for every stored entry e of row i with column
+ *     j = d_colidx[e]:  d_out[e] = alpha * sum_{c < k} w[c] U[i, c] V[j, c] — what the gradients of eigenvalues and of a solve
+ *     with respect to the matrix values are (gcge_amd/grad.py).  U (nrows rows) and V (a row for every column index) are
+ *     row-major device blocks, ldu, ldv >= k; d_u == d_v is legal; d_w: k doubles on the device, or NULL for all ones; d_out
+ *     in the entry order of the arrays given.  Any k >= 1 and any row lengths; no atomics, and the order of summation is
+ *     fixed by k and by whether 16-byte loads apply (even ldu and ldv, d_u and d_v on 16 bytes), so two runs give the same
+ *     bits.  -1, before anything touches the device, for nrows < 0, k < 1, ldu < k, ldv < k or (nrows > 0) a NULL array other
+ *     than d_w; 0 without a launch for nrows == 0 (rows that are all empty: the launch writes nothing); else a hipError_t.  */
+int gcge_hip_csr_sample_outer (int nrows, const int *d_rowptr, const int *d_colidx,
+		const double *d_u, long ldu, const double *d_v, long ldv, int k,
+		const double *d_w, double alpha, double *d_out, void *stream);
 /* K2  G(k x m, row-major on device, ld m) = Q[:,0:k)^T P[:,0:m)  over nrows rows (MFMA f64) */
 int gcge_hip_gram (int nrows, const double *d_q, long ldq, int k, const double *d_p, long ldp, int m,
 		double *d_g, void *stream);
