@@ -9,9 +9,9 @@ from .lib import (CSR, RunResult, Timing, host_lib, hip_lib, build_libs,
 from .eigsh import EigshResult, NoConvergence, eigsh
 from .solve import SolveResult, solve
 from . import grad
-from .grad import eigenvalue_grads, solve_grads
+from .grad import eigenvalue_grads, eigenvector_grads, solve_grads
 
 __all__ = ["CSR", "RunResult", "Timing", "host_lib", "hip_lib", "build_libs",
            "make_problem", "load_petsc_binary", "load_matrix_market", "HipBackend", "run_gcg",
            "PASResult", "run_pas", "eigsh", "EigshResult", "NoConvergence", "solve", "SolveResult",
-           "grad", "eigenvalue_grads", "solve_grads"]
+           "grad", "eigenvalue_grads", "eigenvector_grads", "solve_grads"]

@@ -1,10 +1,13 @@
 // The three vector sweeps of one step of GCGE_PCGSolve (csrc/host/block_fpcg.c: flexible block CG preconditioned by a BlockAMG
-// V-cycle), each ONE pass over its blocks where the operator table's slots take several:
+// V-cycle) and the shift of GCGE_PCGSolveDeflated's operator, each ONE pass over its blocks where the operator table's slots take
+// several:
 //
 //   pcg_step       x += alpha p ; r -= alpha w ; rr_j = |r_j|^2      4 reads + 2 writes       slots: 2 Axpby per column + 'D' product  4 + 2 + 2
 //   pcg_dots       zr_j = z_j . r_j ; zw_j = z_j . w_j               3 reads                  slots: two 'D' products                  4
 //   pcg_direction  p = z + beta p  (or p = z)                        2 reads + 1 write        slots: 1 Axpby per column                the same
 //                                                                                             streams, but one launch per COLUMN
+//   pcg_shift      w -= shift q ; pw_j = p_j . w_j  (q = B p, or p itself)    3 reads + 1 write        slots: 1 Axpby per column + 'D' product  3 + 1 + 2
+//                                                                         (q == p: 2 + 1)
 // in block streams of the window's width.  Per-column scalars (alpha, beta) and flags come from the host; a column without a flag
 // keeps the bits of everything the sweep writes (a select, not alpha = 0: -0.0 and non-finite neighbours stay what they were).
 //
@@ -225,6 +228,81 @@ __global__ __launch_bounds__(256) void pcg_direction_s(long nrows, const double*
       p[row * ldp + j] = f == 1 ? fma(b, p[row * ldp + j], z[row * ldz + j]) : z[row * ldz + j];
   }
 }
+
+// ---- pcg_shift: w -= shift q ; pw_j = sum p w_new, flagged columns only; QP: q is p (the row is read once) ---------------------------
+template <int UNR, bool QP>
+__global__ __launch_bounds__(256) void pcg_shift_v2(long nrows, const double* __restrict__ p, long ldp, const double* __restrict__ q, long ldq,
+    double* __restrict__ w, long ldw, int m, const double* __restrict__ shift, const int* __restrict__ flag, double* __restrict__ partial,
+    int tpr) {
+  __shared__ double red[256][2];
+  const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
+  const int j = 2 * tx;
+  double s0 = 0.0, s1 = 0.0;
+  const bool mine = j < m;
+  const int f0 = mine ? flag[j] : 0, f1 = mine ? flag[j + 1] : 0;
+  if (mine && (f0 | f1)) {
+    const double a0 = f0 ? shift[j] : 0.0, a1 = f1 ? shift[j + 1] : 0.0;
+    const PcgRows rows = pcg_rows(nrows, tpr, UNR);
+    auto one = [&](long rr, v2d pv, v2d qv, v2d wv) {
+      const v2d wn = {f0 ? fma(-a0, qv.x, wv.x) : wv.x, f1 ? fma(-a1, qv.y, wv.y) : wv.y};
+      __builtin_nontemporal_store(wn, reinterpret_cast<v2d*>(w + rr * ldw + j));
+      if (f0) s0 = fma(pv.x, wn.x, s0);
+      if (f1) s1 = fma(pv.y, wn.y, s1);
+    };
+    long row = rows.first;
+    for (; row + (UNR - 1) * rows.step < rows.end; row += rows.step * UNR) {
+      v2d pv[UNR], qv[UNR], wv[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const long rr = row + u * rows.step;
+        pv[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(p + rr * ldp + j));
+        qv[u] = QP ? pv[u] : __builtin_nontemporal_load(reinterpret_cast<const v2d*>(q + rr * ldq + j));
+        wv[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(w + rr * ldw + j));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) one(row + u * rows.step, pv[u], qv[u], wv[u]);
+    }
+    for (; row < rows.end; row += rows.step) {
+      const v2d pv = *reinterpret_cast<const v2d*>(p + row * ldp + j);
+      one(row, pv, QP ? pv : *reinterpret_cast<const v2d*>(q + row * ldq + j), *reinterpret_cast<const v2d*>(w + row * ldw + j));
+    }
+  }
+  red[threadIdx.x][0] = s0; red[threadIdx.x][1] = s1;
+  __syncthreads();
+  if (ty == 0 && mine) {
+    for (int k = 1; k < rpb; ++k) { s0 += red[k * tpr + tx][0]; s1 += red[k * tpr + tx][1]; }
+    partial[(long)blockIdx.x * m + j] = s0;
+    partial[(long)blockIdx.x * m + j + 1] = s1;
+  }
+}
+
+template <bool QP>
+__global__ __launch_bounds__(256) void pcg_shift_s(long nrows, const double* __restrict__ p, long ldp, const double* __restrict__ q, long ldq,
+    double* __restrict__ w, long ldw, int m, const double* __restrict__ shift, const int* __restrict__ flag, double* __restrict__ partial,
+    long rows_per_block) {
+  __shared__ double red[4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const long r0 = (long)blockIdx.x * rows_per_block;
+  const long r1 = min(nrows, r0 + rows_per_block);
+  for (int c0 = 0; c0 < m; c0 += 64) {
+    const int j = c0 + tx;
+    double s = 0.0;
+    if (j < m && flag[j]) {
+      const double a = shift[j];
+      for (long row = r0 + ty; row < r1; row += 4) {
+        const double pv = p[row * ldp + j];
+        const double wn = fma(-a, QP ? pv : q[row * ldq + j], w[row * ldw + j]);
+        w[row * ldw + j] = wn;
+        s = fma(pv, wn, s);
+      }
+    }
+    red[ty][tx] = s;
+    __syncthreads();
+    if (ty == 0 && j < m) partial[(long)blockIdx.x * m + j] = (red[0][tx] + red[1][tx]) + (red[2][tx] + red[3][tx]);
+    __syncthreads();
+  }
+}
 }  // namespace gcge
 
 using namespace gcge;
@@ -319,6 +397,32 @@ extern "C" int gcge_hip_pcg_direction(int nrows, const double* d_z, long ldz, do
   return (int)hipGetLastError();
 }
 
+extern "C" int gcge_hip_pcg_shift(int nrows, const double* d_p, long ldp, const double* d_q, long ldq, double* d_w, long ldw, int m,
+                                  const double* shift, const int* flag, double* pw, void* stream) {
+  gcge_hip_apply_pending();
+  if (m <= 0) return 0;
+  for (int j = 0; j < m; ++j) pw[j] = 0.0;
+  if (nrows <= 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const CgGrid grid = cg_grid(nrows);
+  const int* d_flag = pcg_upload(m, shift, flag, st);
+  double* part = gcge_hip_partial_ws((size_t)grid.nb * m + m);
+  const bool qp = d_q == d_p && ldq == ldp;
+  const bool vec = m <= 512 && cg_vec_ok(m, {d_p, d_q, d_w}, {ldp, ldq, ldw});
+#define GCGE_PCG_SHIFT_LAUNCH(kernel, last)                                                                                          \
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid.nb), dim3(256), 0, st, (long)nrows, d_p, ldp, d_q, ldq, d_w, ldw, m, (const double*)g_d_sc, \
+                     d_flag, part, last)
+  if (vec && qp) GCGE_PCG_SHIFT_LAUNCH((pcg_shift_v2<4, true>), cg_tpr(m));
+  else if (vec) GCGE_PCG_SHIFT_LAUNCH((pcg_shift_v2<4, false>), cg_tpr(m));
+  else if (qp) GCGE_PCG_SHIFT_LAUNCH(pcg_shift_s<true>, grid.rpb);
+  else GCGE_PCG_SHIFT_LAUNCH(pcg_shift_s<false>, grid.rpb);
+#undef GCGE_PCG_SHIFT_LAUNCH
+  const int rc = (int)hipGetLastError();
+  if (rc != 0) return rc;
+  pcg_sums_to_host(part, grid.nb, m, pw, st);
+  return 0;
+}
+
 // ---- the hooks of the HIP table's back-end record (GCGE_BACKEND, include/gcge_ops.h): the same sweeps on blocks of this back-end ----
 // a window of m columns from column c0 of a block with the rows and the row order of `like`
 static bool window_ok(const GcgeHipMV* v, int c0, int m, const GcgeHipMV* like) {
@@ -360,6 +464,19 @@ static int HIP_PcgDirection(void** z, int z0, void** p, int p0, int m, const dou
   GCGE_REQUIRE(rc == 0, "PCG direction: kernel launch");
   return 1;
 }
+static int HIP_PcgShift(void** p, int p0, void** q, int q0, void** w, int w0, int m, const double* shift, const int* flag, double* pw,
+                        struct OPS_* ops) {
+  (void)ops;
+  GcgeHipMV *vp = (GcgeHipMV*)p, *vq = (GcgeHipMV*)q, *vw = (GcgeHipMV*)w;
+  if (m <= 0 || vw == nullptr || shift == nullptr || flag == nullptr || pw == nullptr) return 0;
+  if (!window_ok(vp, p0, m, vw) || !window_ok(vq, q0, m, vw) || !window_ok(vw, w0, m, vw)) return 0;
+  if (vw == vp || vw == vq) return 0;      // (what is written is no other operand)
+  gcge_hip_enter();
+  SlotTimer tm_("PCG shift (w -= shift q, p.w)", m);
+  const int rc = gcge_hip_pcg_shift(vw->nrows, vp->d + p0, vp->ld, vq->d + q0, vq->ld, vw->d + w0, vw->ld, m, shift, flag, pw, gcge_hip_stream());
+  GCGE_REQUIRE(rc == 0, "PCG shift: kernel launch");
+  return 1;
+}
 // iterations of the fused CG's last call (the solver amg_smoother_setup installs)
 static int bpcg_last_niter(struct OPS_* ops) {
   (void)ops;
@@ -372,5 +489,6 @@ extern "C" void gcge_hip_pcg_backend(GCGE_BACKEND* be) {
   be->pcg_step = HIP_PcgStep;
   be->pcg_dots = HIP_PcgDots;
   be->pcg_direction = HIP_PcgDirection;
+  be->pcg_shift = HIP_PcgShift;
   be->amg_smoother_niter = bpcg_last_niter;
 }

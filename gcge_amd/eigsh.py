@@ -33,7 +33,8 @@ def _device_of(*things):
     return torch.cuda.current_device()
 
 
-def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None):
+def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None,
+          eigenvector_grad=False):
     """The k smallest eigenvalues and their eigenvectors of the symmetric problem A x = lambda M x (M=None: the identity; M positive
     definite) by GCG on the GPU.  The smallest eigenvalues are the only mode.
 
@@ -66,21 +67,51 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
     Gradients: when A (or M) is given as a sparse_csr tensor or a (crow, col, val) triple whose values require grad, and grad mode is
     on, `eigenvalues` comes back attached to the graph and backward gives d loss / d values on the stored entries
     (gcge_amd.grad.eigenvalue_grads: d lambda_c / d A_ij = x_ic x_jc, d lambda_c / d M_ij = -lambda_c x_ic x_jc, one kernel call per
-    matrix); the matrix is created from the detached values.  `eigenvectors` and `residual_norms` are marked non-differentiable:
-    gradients through eigenvectors need deflated solves and are not implemented.  Double backward raises.  With handles, or
-    without a tensor that requires grad, nothing is attached and nothing else changes.
+    matrix); the matrix is created from the detached values.  `eigenvectors` and `residual_norms` are marked non-differentiable.
+    Double backward raises.  With handles, or without a tensor that requires grad, nothing is attached and nothing else changes.
+    eigenvector_grad=True (or a dict of the keywords tol, maxiter, cluster_tol of gcge_amd.grad.eigenvector_grads, whose defaults
+    True takes): `eigenvectors` comes back attached as well, for a loss such as one of the density sum_c f_c x_c^2.  Backward then
+    runs eigenvector_grads with both incoming gradients: the k x k algebra inside the computed space and k deflated, shifted
+    systems (A - lambda_c M) y_c = g_c - M X (X^T g_c) outside it (LinearSolver.solve_deflated; with amg_levels >= 2 preconditioned
+    by a hierarchy on A that backward builds and frees, block min(k, 64); otherwise unpreconditioned), then one rank-2k product per
+    matrix; NoConvergence of those solves propagates from backward.  The gradients are the symmetrised ones (each of the stored
+    entries (i, j) and (j, i) gets its own value; their sum is the derivative along E_ij + E_ji).  The systems are conditioned like
+    1 / (lambda_{k+1} - lambda_c) with lambda_{k+1} the first eigenvalue NOT returned: choose k at a gap.  Eigenvalues closer than
+    cluster_tol (relative, default 1e-8) are a cluster: the terms between its members are dropped, so a loss that depends on the
+    choice of basis inside a cluster has no gradient, while one that weights the members equally gets its own.  The matrices
+    this call created then live until backward has run or the graph is freed.  ValueError: eigenvector_grad with a handle for A
+    or M, or without a tensor that requires grad — a loop over handles calls gcge_amd.eigenvector_grads itself.
 
     Returns EigshResult(eigenvalues (k,), eigenvectors (n, k), converged, iterations, seconds, residual_norms (k,)), tensors float64
     on the device.  Raises NoConvergence, carrying the partial result, when fewer than k pairs converged."""
     import torch
     dA, dM = _differentiable(A), _differentiable(M)
     kw = dict(X0=X0, tol=tol, maxiter=maxiter, nev_max=nev_max, block_size=block_size, amg_levels=amg_levels, gcge_args=gcge_args, amg=amg)
+    if eigenvector_grad and (_is_handle(A) or _is_handle(M) or (dA is None and dM is None)):
+        raise ValueError("eigsh: eigenvector_grad needs A (or M) given as tensors whose values require grad, with grad mode on, and no "
+                         "matrix handle; a loop that keeps handles calls gcge_amd.eigenvector_grads itself")
     if dA is None and dM is None:
         return _eigsh(A, k, M, backend=backend, **kw)
     from .grad import _function
     backend = _backend_for(backend, A, M, X0)
     detached = lambda a, d: a if d is None else (a.detach() if isinstance(a, torch.Tensor) else (a[0], a[1], a[2].detach()) + tuple(a[3:]))
     box = {}
+    if eigenvector_grad:
+        from .grad import _Owned
+        options = dict(eigenvector_grad) if isinstance(eigenvector_grad, dict) else {}
+        if set(options) - {"tol", "maxiter", "cluster_tol"}:
+            raise ValueError("eigsh: eigenvector_grad takes the keywords tol, maxiter, cluster_tol")
+        options["amg_levels"] = int(amg_levels)
+        kept = {}
+
+        def run_kept():
+            box["result"] = _eigsh(detached(A, dA), k, detached(M, dM) if M is not None else None, backend=backend, _keep=kept, **kw)
+            kept["owned"] = _Owned(backend, None, None, kept.pop("made"))
+            return box["result"]
+
+        lam, V, rn = _function(2).apply(dA[2] if dA is not None else None, dM[2] if dM is not None else None, run_kept, backend,
+                                          dA[:2] if dA is not None else None, dM[:2] if dM is not None else None, kept, options)
+        return box["result"]._replace(eigenvalues=lam, eigenvectors=V, residual_norms=rn)
 
     def run():
         box["result"] = _eigsh(detached(A, dA), k, detached(M, dM) if M is not None else None, backend=backend, **kw)
@@ -114,8 +145,10 @@ def _backend_for(backend, *things):
     return backend
 
 
-def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None):
-    """eigsh on detached inputs: see there"""
+def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None,
+           _keep=None):
+    """eigsh on detached inputs: see there.  _keep: a dict that, when all k pairs converged, takes the handles "A" and "M" of the solve
+    and the list "made" of those created here, which are then NOT freed (the caller owns them)"""
     import numpy as np
     import torch
     from .lib import host_lib, run_gcg
@@ -167,7 +200,7 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
         made.append(m)
         return m
 
-    evec = None
+    evec = result = None
     try:
         mA = handle(A)
         mB = handle(M) if M is not None else None
@@ -196,8 +229,11 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
     finally:
         if evec is not None and evec.value:
             backend.ops.mv_destroy(evec, nev_max)
-        for m in made:
-            backend.free_matrix(m)
+        if _keep is not None and result is not None and result.converged >= k:
+            _keep.update(A=mA, M=mB, made=list(made))
+        else:
+            for m in made:
+                backend.free_matrix(m)
     if result.converged < k:
         raise NoConvergence("eigsh: %d of %d pairs converged in %d iterations" % (result.converged, k, result.iterations), result)
     return result

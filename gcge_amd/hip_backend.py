@@ -416,7 +416,8 @@ class LinearSolver:
                 raise ValueError("linear_solver: amg was not built on this matrix handle")
         self.backend, self.A, self.amg, self.max_cols = backend, as_handle(A), amg, max_cols
         self.n = int(backend.g.gcge_hip_mat_nrows(self.A))
-        self._s = self._b = self._x = self.column_iterations = None
+        self._s = self._b = self._x = self._X = self.column_iterations = None
+        self._X_cols = 0
         self._b = backend.ops.mv_create(max_cols, self.A)
         self._x = backend.ops.mv_create(max_cols, self.A)
         try:
@@ -477,8 +478,42 @@ class LinearSolver:
             return _solve_attached(self, b, x0, tol, maxiter)
         return self._solve(b, x0, tol, maxiter)
 
-    def _solve(self, b, x0, tol, maxiter):
-        """solve on a detached b: see there"""
+    def solve_deflated(self, b, X, shifts, M=None, tol=1e-8, maxiter=200):
+        """The deflated, per-column-shifted systems  Q^T (A - shifts[j] M) y_j = Q^T b_j,  y_j in range(Q),  Q = I - X X^T M
+        (GCGE_PCGSolveDeflated): the adjoint systems of eigenvector gradients, with X the (n, k) block of computed, M-orthonormal
+        eigenvectors and shifts their eigenvalues.  b as for solve; X: an (n, k) CUDA tensor (k = 0: no deflation), copied into a
+        block the solver keeps; shifts: m values (a tensor, an array or a sequence); M: a matrix handle of the back-end or None for
+        the identity.  The preconditioner is the solver's V-cycle on A, unchanged (without a hierarchy: none).  The operator is
+        positive definite on range(Q) while every shift is below the first eigenvalue that is not in X, and conditioned like the
+        inverse of that gap.  Returns SolveResult as solve does, residual_norms the TRUE projected residuals
+        |Q^T (b_j - (A - shifts[j] M) y_j)| / |Q^T b_j| (a b_j inside span(M X): y_j = 0, residual 0); raises NoConvergence carrying
+        the result.  Nothing is attached to a graph.  TypeError / ValueError as solve, and ValueError for X of another row count or
+        another number of shifts than columns."""
+        import numpy as np
+        import torch
+        if self._s is None:
+            raise ValueError("the solver is closed")
+        bt, flat = self._block(b.detach() if isinstance(b, torch.Tensor) else b, "b")
+        m = int(bt.shape[1])
+        if not isinstance(X, torch.Tensor) or not X.is_cuda:
+            raise TypeError("solve_deflated: X must be a torch tensor that lives on the GPU")
+        if X.dim() != 2 or X.shape[0] != self.n:
+            raise ValueError("solve_deflated: X is an (n, k) block with the matrix's %d rows" % self.n)
+        sh = np.ascontiguousarray(shifts.detach().cpu().numpy() if isinstance(shifts, torch.Tensor) else shifts, dtype=np.float64).reshape(-1)
+        if sh.size != m:
+            raise ValueError("solve_deflated: %d shifts for %d columns" % (sh.size, m))
+        k = int(X.shape[1])
+        if k > self._X_cols:
+            if self._X is not None:
+                self.backend.ops.mv_destroy(self._X, self._X_cols)
+            self._X, self._X_cols = self.backend.ops.mv_create(k, self.A), k
+        if k > 0:
+            self.backend.mv_from_torch(self.A, X.detach(), mv=self._X, c0=0)
+        as_handle = lambda a: a if isinstance(a, C.c_void_p) or a is None else C.c_void_p(a)
+        return self._solve(bt.reshape(-1) if flat else bt, None, tol, maxiter, deflation=(as_handle(M), k, sh))
+
+    def _solve(self, b, x0, tol, maxiter, deflation=None):
+        """solve on a detached b: see there; deflation = (M handle or None, k, shifts): GCGE_PCGSolveDeflated with the block _X"""
         import time
         import numpy as np
         import torch
@@ -503,13 +538,18 @@ class LinearSolver:
         rel, it = np.zeros(m), np.zeros(m, dtype=np.int32)
         bk.sync()
         t0 = time.perf_counter()
-        rc = bk.h.GCGE_PCGSolve(self._s, self._b, 0, self._x, 0, m, float(tol), int(maxiter), 1 if x0 is None else 0,
-                                rel.ctypes.data_as(C.c_void_p), it.ctypes.data_as(C.c_void_p), bk.ops_handle)
+        tail = (self._b, 0, self._x, 0, m, float(tol), int(maxiter), 1 if x0 is None else 0, rel.ctypes.data_as(C.c_void_p),
+                it.ctypes.data_as(C.c_void_p), bk.ops_handle)
+        if deflation is None:
+            name, rc = "GCGE_PCGSolve", bk.h.GCGE_PCGSolve(self._s, *tail)
+        else:
+            M, k, sh = deflation
+            name, rc = "GCGE_PCGSolveDeflated", bk.h.GCGE_PCGSolveDeflated(self._s, M, self._X, 0, k, sh.ctypes.data_as(C.c_void_p), *tail)
         bk.sync()
         seconds = time.perf_counter() - t0
         self.column_iterations = it.copy()                             # per column: V-cycles (amg=None: the one call's count)
         if rc < 0:
-            raise RuntimeError("GCGE_PCGSolve rc=%d%s" % (rc, " (a communicator is set: single rank only)" if rc == -2 else ""))
+            raise RuntimeError("%s rc=%d%s" % (name, rc, " (a communicator is set: single rank only)" if rc == -2 else ""))
         x = bk.mv_to_torch(self._x, 0, m)
         if flat:
             x = x.reshape(-1)
@@ -523,11 +563,12 @@ class LinearSolver:
         if self._s is not None:
             b.h.GCGE_PCGDestroy(C.byref(self._s), b.ops_handle)
             self._s = None
-        for name in ("_b", "_x"):
+        for name, cols in (("_b", self.max_cols), ("_x", self.max_cols), ("_X", self._X_cols)):
             mv = getattr(self, name)
             if mv is not None and mv.value:
-                b.ops.mv_destroy(mv, self.max_cols)
+                b.ops.mv_destroy(mv, cols)
             setattr(self, name, None)
+        self._X_cols = 0
 
     def __enter__(self):
         return self

@@ -637,20 +637,24 @@ long gcge_hip_gram_sym_launches (void);
 /* K4  Y[:,0:m) = alpha X[:,0:m) + beta Y   (d_x NULL: scale only; beta == 0: no read of Y) */
 int gcge_hip_axpby (int nrows, double alpha, const double *d_x, long ldx, double beta,
 		double *d_y, long ldy, int m, void *stream);
-/*     The three sweeps of one step of GCGE_PCGSolve (gcge_solver.h; GCGE_BACKEND.pcg_step / pcg_dots / pcg_direction of OPS_HIP_Set,
- *     csrc/hip/pcg_sweeps.hip) on raw device pointers, m columns from each pointer; alpha, beta, flag and the sums are HOST arrays of
+/*     The three sweeps of one step of GCGE_PCGSolve and the shift of GCGE_PCGSolveDeflated's operator (gcge_solver.h; GCGE_BACKEND.pcg_step
+ *     / pcg_dots / pcg_direction / pcg_shift of OPS_HIP_Set, csrc/hip/pcg_sweeps.hip) on raw device pointers, m columns from each pointer; alpha, beta, flag and the sums are HOST arrays of
  *     m entries, the sums complete when the call returns (the stream is synchronised).  16-byte lanes when m, the origins and the
  *     leading dimensions are even, scalar lanes otherwise: the same results.  Return 0, or the launch's error.
  *       step       x += p diag(alpha) ; r -= w diag(alpha) ; rr[j] = sum_r r_new[r,j]^2 for flag[j] != 0; other columns keep their
  *                  bits (rr[j] = 0)
  *       dots       zr[j] = sum_r z[r,j] r[r,j] ; zw[j] = sum_r z[r,j] w[r,j] from one read of the three blocks
- *       direction  flag[j] == 1: p = z + p diag(beta) ; == 2: p = z (p is not used) ; == 0: the column keeps its bits               */
+ *       direction  flag[j] == 1: p = z + p diag(beta) ; == 2: p = z (p is not used) ; == 0: the column keeps its bits
+ *       shift      w -= q diag(shift) ; pw[j] = sum_r p[r,j] w_new[r,j] for flag[j] != 0; other columns keep the bits of w (pw[j] = 0);
+ *                  with d_q == d_p and ldq == ldp the row of p is read once                                                        */
 int gcge_hip_pcg_step (int nrows, const double *d_p, long ldp, const double *d_w, long ldw, double *d_x, long ldx, double *d_r, long ldr,
 		int m, const double *alpha, const int *flag, double *rr, void *stream);
 int gcge_hip_pcg_dots (int nrows, const double *d_z, long ldz, const double *d_r, long ldr, const double *d_w, long ldw, int m,
 		double *zr, double *zw, void *stream);
 int gcge_hip_pcg_direction (int nrows, const double *d_z, long ldz, double *d_p, long ldp, int m, const double *beta, const int *flag,
 		void *stream);
+int gcge_hip_pcg_shift (int nrows, const double *d_p, long ldp, const double *d_q, long ldq, double *d_w, long ldw, int m,
+		const double *shift, const int *flag, double *pw, void *stream);
 /*     GCGE_BACKEND.block_moves of OPS_HIP_Set (include/gcge_ops.h) on blocks of this back-end, for tests: V[:, x0..x1) = ritz[:, x0..x1),
  *     V[:, w0 + ..) = the runs of ritz packed, b[:, b0 + ..) = the same times scale (b NULL: none) in one sweep; 0: declined        */
 int gcge_hip_block_moves_mv (void **ritz, void **V, int x0, int x1, const int *runs, int w0, void **b, int b0, const double *scale);

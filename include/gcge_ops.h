@@ -254,7 +254,13 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *                 not read: it may hold anything), and a column with flag[j] == 0 keeps its bits (the slots: one MultiVecAxpby per
  *                 flagged column).  beta, flag: host arrays of m entries.  0 declines, nothing touched.
  *   amg_smoother_niter   the iteration count of the last call of the smoother of amg_smoother_setup (what BlockPCGSolver.niter would
- *                 hold): GCGE_PCGSolve without a hierarchy reports it.  NULL: that solve takes BlockPCG over the slots. */
+ *                 hold): GCGE_PCGSolve without a hierarchy reports it.  NULL: that solve takes BlockPCG over the slots.
+ *   pcg_shift     the shift of GCGE_PCGSolveDeflated's operator on a window of m columns, in one sweep: w[:, w0..) -= q[:, q0..)
+ *                 diag(shift) ;  pw[j] = sum over the LOCAL rows of p[r, j] w_new[r, j] — for the columns with flag[j] != 0 only; a
+ *                 column without a flag keeps the bits of its w (its pw[j] is 0).  q is B p, or p itself (the same block and column:
+ *                 the row is read once).  shift, flag, pw: host arrays of m entries.  The slots take one MultiVecAxpby per flagged
+ *                 column, then MultiVecLocalInnerProd('D'): 3 reads + 1 write + 2 reads in m + 1 launches.  0 declines, nothing
+ *                 touched. */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -272,6 +278,8 @@ typedef int    (*GCGE_PCG_STEP_FN) (void **p, int p0, void **w, int w0, void **x
 		const int *flag, double *rr, struct OPS_ *ops);
 typedef int    (*GCGE_PCG_DOTS_FN) (void **z, int z0, void **r, int r0, void **w, int w0, int m, double *zr, double *zw, struct OPS_ *ops);
 typedef int    (*GCGE_PCG_DIRECTION_FN) (void **z, int z0, void **p, int p0, int m, const double *beta, const int *flag, struct OPS_ *ops);
+typedef int    (*GCGE_PCG_SHIFT_FN) (void **p, int p0, void **q, int q0, void **w, int w0, int m, const double *shift, const int *flag,
+		double *pw, struct OPS_ *ops);
 typedef struct GCGE_BACKEND_ {
 	GCGE_RESIDUAL_FN residual_sq;
 	int inplace_lincomb_cols;
@@ -292,6 +300,7 @@ typedef struct GCGE_BACKEND_ {
 	int  (*multigrid_refresh_check) (void **A_array, void **B_array, void **P_array, int num_levels);
 	GCGE_PCG_STEP_FN pcg_step; GCGE_PCG_DOTS_FN pcg_dots; GCGE_PCG_DIRECTION_FN pcg_direction;
 	int  (*amg_smoother_niter) (struct OPS_ *ops);
+	GCGE_PCG_SHIFT_FN pcg_shift;
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

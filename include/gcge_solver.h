@@ -130,11 +130,29 @@ int  GCGE_AMGRefresh (GCGE_AMG *amg, struct OPS_ *ops);
  * GCGE_PCGCreate: four blocks of max_cols columns created by A (r, z, p, w) and the scalar arrays; NULL on bad arguments, among
  * them a hierarchy whose level 0 is not A.  GCGE_PCGSolve: zero_start != 0 starts from x = 0 whatever x holds; returns the number
  * of columns with rel_res <= tol, -1 on bad arguments (m > max_cols among them), -2 while a communicator of more than one rank is
- * set (single rank only) — nothing is written then.                                                                              */
+ * set (single rank only) — nothing is written then.
+ *
+ * GCGE_PCGSolveDeflated: on the same solver, for m columns, the deflated and per-column-shifted systems
+ *     Q^T (A - shift_j B) y_j = Q^T b_j ,  y_j in range(Q) ,  Q = I - X X^T B      (B == NULL: the identity)
+ * with X = X[:, xc0..xc0+k) B-orthonormal (the computed eigenvectors; the adjoint systems of eigenvector gradients, shift_j their
+ * eigenvalues: positive definite on range(Q) while shift_j is below the first eigenvalue NOT in X, conditioned like the inverse of
+ * that gap).  The same recurrence — flexible beta, per-column alpha and beta, retired columns keep their bits, chunks of
+ * amg->block_size — with the operator  w = A p ; w -= shift_j (B p) ; w -= MX (X^T w)  and the preconditioner  z = V(r) ;
+ * z -= X (MX^T z), V the UNCHANGED V-cycle on A; without a hierarchy z = r (the same loop with the identity: the fused block CG
+ * cannot take this operator).  MX = B X is formed once per call in a work block the solver creates on first use (B == NULL: X
+ * itself), B p in a second one.  The shift and p.w go through GCGE_BACKEND.pcg_shift where it is offered and does not decline, the
+ * projections through the table's MultiVecInnerProd / MultiVecLinearComb.  What is checked and reported is the TRUE projected
+ * residual |Q^T (b_j - (A - shift_j B) y_j)| relative to |Q^T b_j|; a column whose Q^T b_j is at the rounding level of forming it,
+ * |Q^T b_j| <= 2^10 eps |b_j| (b_j inside span(MX)), gets y_j = 0 and rel_res 0.  zero_start == 0: the start is projected into
+ * range(Q) first.  shift: m host doubles.  The table and the published GCGE_LINSOL_ARGS are left as found, and GCGE_PCGSolve on the
+ * same solver is not affected.  Returns as GCGE_PCGSolve: -2 under a communicator of more than one rank, -1 on bad arguments (k < 0,
+ * X the block of b or of y, m > max_cols, ...) with nothing written, else the number of columns with rel_res <= tol.              */
 typedef struct GCGE_PCG_ GCGE_PCG;
 GCGE_PCG *GCGE_PCGCreate (void *A, GCGE_AMG *amg, int max_cols, struct OPS_ *ops);
 int  GCGE_PCGSolve (GCGE_PCG *s, void **b, int b0, void **x, int x0, int m, double tol, int max_iter, int zero_start,
 		double *rel_res, int *col_iters, struct OPS_ *ops);
+int  GCGE_PCGSolveDeflated (GCGE_PCG *s, void *B, void **X, int xc0, int k, const double *shift, void **b, int b0, void **y, int y0,
+		int m, double tol, int max_iter, int zero_start, double *rel_res, int *col_iters, struct OPS_ *ops);
 void GCGE_PCGDestroy (GCGE_PCG **s, struct OPS_ *ops);
 
 /* ---- GCG eigensolver (sets ops->EigenSolver) -------------------------------- */
