@@ -1,0 +1,122 @@
+// The vector sweep of one step of a Chebyshev filter (GCGE_ChebFilter, csrc/host/chfsi.c): with out holding the product A y,
+//
+//   cheb_sweep     out <- alpha (out - c y) - beta z          3 reads + 1 write        slots: 2 Axpby (3 streams each)
+//                                                             (beta == 0: 2 + 1, z is not read)
+// in block streams of the width m, in place on out, in ONE pass.  The step Y_{j+1} = alpha_j (A - c I) Y_j - beta_j Y_{j-1} of the
+// three-term recurrence is then the product (2 streams) and this sweep: 6 streams instead of the 8 of product + two Axpby.
+//
+// Order of operations, the same in both kernels and on every run (no sums, no atomics, every entry computed by one thread from its
+// own three operands):
+//     u   = fma(-c, y, out)                       one rounding
+//     out = fma(alpha, u, -(beta * z))            beta * z rounded, then one rounding            (beta != 0)
+//     out = alpha * u                             one rounding; z may be NULL or hold anything   (beta == 0: a filter's first step)
+// alpha, c and beta are the same for every column: kernel arguments, nothing is staged.
+//
+// Modelled on pcg_shift of pcg_sweeps.hip: 16-byte lanes (v2d, one column pair per thread) with non-temporal loads and stores when
+// the width, the column origins and the leading dimensions are even (cg_vec_ok), a scalar-lane kernel (4 row lanes x 64 columns)
+// otherwise; row groups of 4 with all loads issued before the arithmetic; the grid is cg_grid's.
+//
+// Also here: the device staging of the fused step's scalars (gcge_hip_cheb_step_mv, mat_product.hip), filled by a one-block kernel
+// so that nothing is copied from the host and nothing is waited for.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "gcge_hip.h"
+#include "gcge_hip_internal.h"
+
+namespace gcge {
+
+typedef double v2d __attribute__((ext_vector_type(2)));
+
+template <int UNR, bool HASZ>
+__global__ __launch_bounds__(256) void cheb_sweep_v2(long nrows, double* __restrict__ out, long ldo, const double* __restrict__ y, long ldy,
+    const double* __restrict__ z, long ldz, int m, double alpha, double c, double beta, int tpr) {
+  const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
+  const int j = 2 * tx;
+  if (j >= m) return;
+  // the rows of workgroup blockIdx.x, walked rpb at a time in groups of UNR (pcg_rows of pcg_sweeps.hip)
+  const long group = (long)rpb * UNR;
+  const long slab = (((nrows + gridDim.x - 1) / gridDim.x) + group - 1) / group * group;
+  const long rend = min(nrows, ((long)blockIdx.x + 1) * slab), step = rpb;
+  auto one = [&](long rr, v2d ov, v2d yv, v2d zv) {
+    const v2d u = {fma(-c, yv.x, ov.x), fma(-c, yv.y, ov.y)};
+    const v2d r = HASZ ? v2d{fma(alpha, u.x, -(beta * zv.x)), fma(alpha, u.y, -(beta * zv.y))} : v2d{alpha * u.x, alpha * u.y};
+    __builtin_nontemporal_store(r, reinterpret_cast<v2d*>(out + rr * ldo + j));
+  };
+  long row = (long)blockIdx.x * slab + ty;
+  for (; row + (UNR - 1) * step < rend; row += step * UNR) {
+    v2d ov[UNR], yv[UNR], zv[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const long rr = row + u * step;
+      ov[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(out + rr * ldo + j));
+      yv[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(y + rr * ldy + j));
+      zv[u] = HASZ ? __builtin_nontemporal_load(reinterpret_cast<const v2d*>(z + rr * ldz + j)) : v2d{0.0, 0.0};
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) one(row + u * step, ov[u], yv[u], zv[u]);
+  }
+  for (; row < rend; row += step)
+    one(row, *reinterpret_cast<const v2d*>(out + row * ldo + j), *reinterpret_cast<const v2d*>(y + row * ldy + j),
+        HASZ ? *reinterpret_cast<const v2d*>(z + row * ldz + j) : v2d{0.0, 0.0});
+}
+
+// any width, origin and leading dimension: 4 row lanes x 64 columns, the columns in chunks of 64
+template <bool HASZ>
+__global__ __launch_bounds__(256) void cheb_sweep_s(long nrows, double* __restrict__ out, long ldo, const double* __restrict__ y, long ldy,
+    const double* __restrict__ z, long ldz, int m, double alpha, double c, double beta, long rows_per_block) {
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const long r0 = (long)blockIdx.x * rows_per_block;
+  const long r1 = min(nrows, r0 + rows_per_block);
+  for (int j = tx; j < m; j += 64)
+    for (long row = r0 + ty; row < r1; row += 4) {
+      const double u = fma(-c, y[row * ldy + j], out[row * ldo + j]);
+      out[row * ldo + j] = HASZ ? fma(alpha, u, -(beta * z[row * ldz + j])) : alpha * u;
+    }
+}
+
+// the scalars of one fused step, the same for every column: coef = [al | cb | bp] (3 m doubles), flag = m ones
+__global__ void cheb_scalars_fill(int m, double al, double cb, double bp, double* __restrict__ coef, int* __restrict__ flag) {
+  for (int j = threadIdx.x; j < m; j += blockDim.x) { coef[j] = al; coef[m + j] = cb; coef[2 * m + j] = bp; flag[j] = 1; }
+}
+}  // namespace gcge
+
+using namespace gcge;
+
+extern "C" int gcge_hip_cheb_sweep(long n, double* out, long ldo, const double* y, long ldy, const double* z, long ldz, int m, double alpha,
+                                   double c, double beta, void* stream) {
+  gcge_hip_apply_pending();
+  if (n < 0 || m < 0 || out == nullptr || y == nullptr || (beta != 0.0 && z == nullptr) || out == y || out == z) return -1;
+  if (n == 0 || m == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const CgGrid grid = cg_grid(n);
+  const bool hasz = beta != 0.0;
+  if (!hasz) { z = y; ldz = ldy; }      // (never read; keeps the alignment test below on the operands that are)
+  const bool vec = m <= 512 && cg_vec_ok(m, {out, y, z}, {ldo, ldy, ldz});
+#define GCGE_CHEB_LAUNCH(kernel, last)                                                                                              \
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid.nb), dim3(256), 0, st, n, out, ldo, y, ldy, z, ldz, m, alpha, c, beta, last)
+  if (vec && hasz) GCGE_CHEB_LAUNCH((cheb_sweep_v2<4, true>), cg_tpr(m));
+  else if (vec) GCGE_CHEB_LAUNCH((cheb_sweep_v2<4, false>), cg_tpr(m));
+  else if (hasz) GCGE_CHEB_LAUNCH(cheb_sweep_s<true>, grid.rpb);
+  else GCGE_CHEB_LAUNCH(cheb_sweep_s<false>, grid.rpb);
+#undef GCGE_CHEB_LAUNCH
+  return (int)hipGetLastError();
+}
+
+// The staging area of the fused step: 3 m doubles and m ints on the device, grown on demand, written by a kernel on `stream` (in
+// stream order behind the step that read it last).  d_alpha = -alpha, d_beta = -alpha c - 1, d_betaprev = beta, every flag 1: the
+// mapping of the step onto kernel MODE 7 (mat_product.hip, gcge_hip_cheb_step_mv).
+static double* g_d_cheb = nullptr; static int g_cheb_cap = 0;
+extern "C" void gcge_hip_cheb_scalars(int m, double alpha, double c, double beta, void* stream, const double** d_alpha, const double** d_beta,
+                                      const double** d_betaprev, const int** d_flag) {
+  hipStream_t st = (hipStream_t)stream;
+  if (m > g_cheb_cap) {
+    if (g_d_cheb) { GCGE_HIP_CHECK(hipStreamSynchronize(st)); GCGE_HIP_CHECK(hipFree(g_d_cheb)); }
+    g_cheb_cap = m + 64;
+    GCGE_HIP_CHECK(hipMalloc(&g_d_cheb, 4 * (size_t)g_cheb_cap * sizeof(double)));
+  }
+  int* flag = reinterpret_cast<int*>(g_d_cheb + 3 * (size_t)m);
+  hipLaunchKernelGGL(cheb_scalars_fill, dim3(1), dim3(64), 0, st, m, -alpha, -alpha * c - 1.0, beta, g_d_cheb, flag);
+  *d_alpha = g_d_cheb; *d_beta = g_d_cheb + m; *d_betaprev = g_d_cheb + 2 * (size_t)m; *d_flag = flag;
+}

@@ -149,6 +149,10 @@ void gcge_hip_mg_members_host(const int* agg, int nf, int nc, std::vector<int>& 
 extern "C" void gcge_hip_bpcg_backend(GCGE_BACKEND* be);
 // pcg_sweeps.hip: the three sweeps of GCGE_PCGSolve's step (pcg_step / pcg_dots / pcg_direction) and the fused CG's iteration count
 extern "C" void gcge_hip_pcg_backend(GCGE_BACKEND* be);
+// cheb_sweeps.hip: the scalars of one fused Chebyshev step (gcge_hip_cheb_step_mv) written to a device staging area by a kernel on
+// `stream`; the four pointers (m entries each) stay valid until the next call
+extern "C" void gcge_hip_cheb_scalars(int m, double alpha, double c, double beta, void* stream, const double** d_alpha, const double** d_beta,
+                                      const double** d_betaprev, const int** d_flag);
 // What the block sweeps of block_pcg.hip and pcg_sweeps.hip share.  16-byte lanes (column pairs) need an even width, 16-byte aligned
 // column origins and even leading dimensions; cg_tpr: threads per row of such a sweep (m <= 512)
 #include <initializer_list>

@@ -4,6 +4,7 @@
 //   spmm_rows, star_product, spmm_halo   which K1 form a product (or a fused CG pass: CgPass) takes, whole or in row strips
 //   HIP_MatDotMultiVec, HIP_MatTransDotMultiVec, gcge_hip_spmm_dot*   the product, alone or with the column sums x.y / y.y
 //   gcge_hip_cg_*                        the passes of the fused block CG on a pattern matrix (product formed twice, never stored)
+//   gcge_hip_cheb_step_mv                one step of a Chebyshev filter: the second CG pass with prescribed scalars, or product + sweep
 //   HIP_Amg*, HIP_ResidualSq             the fused sweeps of a V-cycle and the residual norms of Ritz pairs (GCGE_BACKEND)
 //   gcge_hip_profile_*                   HIP events around every K1 launch
 // Runtime state, staging, pool and the multivector slots live in app_hip.hip (shared names: gcge_hip_internal.h); the handle itself
@@ -547,6 +548,50 @@ extern "C" int gcge_hip_cg_pass2i_mv(void* mat, void** p, void** pprev, void** p
   return 0;
 }
 
+// ---- one step of a Chebyshev filter (GCGE_ChebFilter, csrc/host/chfsi.c; GCGE_BACKEND.cheb_step) --------------------------------
+//   out[:, o0..o0+m) = alpha (A y[:, y0..) - c y[:, y0..)) - beta z[:, z0..)          out, y, z: three different blocks
+// Fused: kernel MODE 7 computes pnew = (p - bp pprev - al (A p)) + cb p from per-column device scalars; with p = y, pprev = z,
+// pnew = out and  al = -alpha, bp = beta, cb = -alpha c - 1  that is  y - beta z + alpha A y - alpha c y - y, the step itself: one call
+// of gcge_hip_cg_pass2i_dev with every column flagged, 3 block streams and the matrix, its d_rho ignored.  Only where forming the
+// product inside the sweep pays (gcge_hip_cg_recompute_pays: the reason is written there), on one rank, with beta != 0 (MODE 7 reads
+// pprev) and the three windows on the same even column.  Everything else, and GCGE_CHEB_NO_FUSE=1 (read per call): the ordinary
+// product into out, whatever K1 form the handle has, then gcge_hip_cheb_sweep in place on out — 6 block streams and the matrix.
+static long g_cheb_stats[3] = {0, 0, 0};      // fused, product + sweep, declined
+extern "C" void gcge_hip_cheb_stats(long out[3]) { for (int i = 0; i < 3; ++i) out[i] = g_cheb_stats[i]; }
+extern "C" int gcge_hip_cheb_step_mv(void* mat, void** y, int y0, void** z, int z0, void** out, int o0, int m, double alpha, double c,
+                                     double beta) {
+  GCGE_HIP_MAT_* A = (GCGE_HIP_MAT_*)mat;
+  GcgeHipMV *vy = (GcgeHipMV*)y, *vz = (GcgeHipMV*)z, *vo = (GcgeHipMV*)out;
+  const bool hasz = beta != 0.0;
+  bool ok = A != nullptr && A->rect_ncols == 0 && vy != nullptr && vo != nullptr && m > 0 && vo != vy && (!hasz || (vz != nullptr && vz != vo && vz != vy));
+  ok = ok && y0 >= 0 && y0 + m <= vy->ncols && o0 >= 0 && o0 + m <= vo->ncols && (!hasz || (z0 >= 0 && z0 + m <= vz->ncols));
+  ok = ok && A->nrows == vy->nrows && A->nrows == vo->nrows && A->nrows + A->nghost <= vy->nrows_alloc && (!hasz || A->nrows == vz->nrows);
+  ok = ok && real_perm(vy->perm) == real_perm(A->perm) && real_perm(vo->perm) == real_perm(A->perm) && (!hasz || real_perm(vz->perm) == real_perm(A->perm));
+  if (!ok) { ++g_cheb_stats[2]; return -1; }
+  gcge_hip_enter();
+  if (hasz && A->nghost == 0 && y0 == z0 && y0 == o0 && !(y0 & 1) && getenv("GCGE_CHEB_NO_FUSE") == nullptr &&
+      gcge_hip_cg_fusable(mat, y, m) && gcge_hip_cg_recompute_pays(mat) && pair_ok(vz, z0) && pair_ok(vo, o0)) {
+    SlotTimer tm_("Chebyshev step (fused)", m);
+    const double *d_al, *d_cb, *d_bp; const int* d_flag;
+    gcge_hip_cheb_scalars(m, alpha, c, beta, g_stream, &d_al, &d_cb, &d_bp, &d_flag);
+    GCGE_REQUIRE(gcge_hip_cg_pass2i_dev(mat, y, z, out, y0, m, d_al, d_cb, d_flag, d_bp, gcge_hip_stage_d(6 * (size_t)m)) == 0, "Chebyshev step: fused pass");
+    ++g_cheb_stats[0];
+    return 0;
+  }
+  int start[2] = {y0, o0}, end[2] = {y0 + m, o0 + m};
+  HIP_MatDotMultiVec(mat, y, out, start, end, nullptr);
+  SlotTimer tm_("Chebyshev step (sweep)", m);
+  GCGE_REQUIRE(gcge_hip_cheb_sweep(A->nrows, vo->d + o0, vo->ld, vy->d + y0, vy->ld, hasz ? vz->d + z0 : nullptr, hasz ? vz->ld : 0, m, alpha, c, beta,
+                                   g_stream) == 0, "Chebyshev step: sweep");
+  ++g_cheb_stats[1];
+  return 0;
+}
+static int HIP_ChebStep(void* mat, void** y, int y0, void** z, int z0, void** out, int o0, int m, double alpha, double c, double beta,
+                        struct OPS_* ops) {
+  (void)ops;
+  return gcge_hip_cheb_step_mv(mat, y, y0, z, z0, out, o0, m, alpha, c, beta) == 0 ? 1 : 0;
+}
+
 // ---- the start sweep (kernel MODES 5 / 6): r[:, rc0:rc0+m) = b[:, bc0:bc0+m) - A x[:, xc0:xc0+m), pnew[:, rc0:rc0+m) = r, and the
 // column sums of r^2 over the LOCAL rows into dd (6 m doubles: 3 m of scratch behind the sums when the product is split); fetches the
 // halo rows of x.  vb == NULL: b_j = d_scale[j] x_j is never formed (MODE 6).  Behind gcge_hip_cg_start_mv, gcge_hip_cg_start_scaled_mv
@@ -828,4 +873,5 @@ extern "C" void gcge_hip_product_slots(struct OPS_* ops, GCGE_BACKEND* be) {
   be->amg_residual    = HIP_AmgResidual;          // r = b - A x and x += P e as one sweep each
   be->amg_prolong_add = HIP_AmgProlongAdd;
   be->amg_form_rhs    = HIP_AmgFormRhs;           // b = x diag(scale) in one sweep
+  be->cheb_step       = HIP_ChebStep;             // one step of a Chebyshev filter: fused on pattern matrices, product + one sweep otherwise
 }

@@ -1,0 +1,241 @@
+/* Chebyshev-filtered subspace iteration (Zhou, Saad, Tiago, Chelikowsky, J. Comput. Phys. 219 (2006) 172-184): the smallest
+ * eigenpairs of a symmetric standard problem A x = lambda x without a linear solve — no preconditioner, no hierarchy, no
+ * definiteness.  Written against the operator table only, like gcg.c.
+ *
+ *   GCGE_ChebFilter   X <- p(A) X with the scaled Chebyshev polynomial p of a given degree that is 1 at `lowest` and bounded by 1 in
+ *                     modulus on [lower, upper]: components of the eigenvalues in [lower, upper] are damped, those below `lower` grow
+ *                     relative to them like a Chebyshev polynomial outside its interval.
+ *   GCGE_RunChFSI     upper bound by a few Lanczos steps, then per iteration: filter the unconverged columns, orthonormalise them
+ *                     against the locked ones and among themselves, Rayleigh-Ritz, residuals, lock the leading converged pairs.
+ *
+ * The filter is the three-term recurrence  Y_{j+1} = alpha_j (A - c I) Y_j - beta_j Y_{j-1}.  One step goes through the back-end's
+ * cheb_step (GCGE_BACKEND, gcge_ops.h) where the table offers it and it accepts, else through the slots: MatDotMultiVec into the
+ * output block and two MultiVecAxpby.
+ */
+#include <float.h>
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "gcge_solver.h"
+
+/* out[:, o0..) = alpha (A y[:, y0..) - c y[:, y0..)) - beta z[:, z0..)   (beta == 0: z is not read) */
+static void cheb_step(void *A, void **y, int y0, void **z, int z0, void **out, int o0, int m, double alpha, double c, double beta,
+		const GCGE_BACKEND *be, struct OPS_ *ops)
+{
+	int s[2], e[2];
+	if (be->cheb_step != NULL && be->cheb_step(A, y, y0, z, z0, out, o0, m, alpha, c, beta, ops)) return;
+	s[0] = y0; e[0] = y0 + m; s[1] = o0; e[1] = o0 + m;
+	ops->MatDotMultiVec(A, y, out, s, e, ops);
+	ops->MultiVecAxpby(-alpha * c, y, alpha, out, s, e, ops);                 /* alpha (A y) - alpha c y */
+	if (beta != 0.0) {
+		s[0] = z0; e[0] = z0 + m;
+		ops->MultiVecAxpby(-beta, z, 1.0, out, s, e, ops);
+	}
+}
+
+/* the filter with the work blocks' windows at column w0 (the driver puts them on x's own column: the back-end's fused step wants
+ * the three windows on one column) */
+static int cheb_filter(void *A, void **x, int x0, int m, int degree, double lower, double upper, double lowest,
+		void **work1, void **work2, int w0, struct OPS_ *ops)
+{
+	const GCGE_BACKEND be = GCGE_BackendOf(ops);
+	void **blk[3]; int col[3], i, s[2], e[2];
+	double ee, c, sigma, sigma1, tau;
+	if (A == NULL || x == NULL || work1 == NULL || work2 == NULL || ops == NULL || x0 < 0 || w0 < 0 || m < 0 || degree < 1) return -1;
+	if (!(lower < upper) || !(lowest < lower)) return -1;
+	if (x == work1 || x == work2 || work1 == work2) return -1;
+	if (m == 0) return 0;
+	ee = 0.5 * (upper - lower); c = 0.5 * (upper + lower);
+	sigma1 = ee / (lowest - c); tau = 2.0 / sigma1; sigma = sigma1;
+	blk[0] = x; col[0] = x0; blk[1] = work1; col[1] = w0; blk[2] = work2; col[2] = w0;
+	/* step i reads block (i - 1) % 3 (and (i - 2) % 3) and writes block i % 3 */
+	cheb_step(A, blk[0], col[0], NULL, 0, blk[1], col[1], m, sigma1 / ee, c, 0.0, &be, ops);
+	for (i = 2; i <= degree; ++i) {
+		const double sigma2 = 1.0 / (tau - sigma);
+		const int iy = (i - 1) % 3, iz = (i - 2) % 3, io = i % 3;
+		cheb_step(A, blk[iy], col[iy], blk[iz], col[iz], blk[io], col[io], m, 2.0 * sigma2 / ee, c, sigma * sigma2, &be, ops);
+		sigma = sigma2;
+	}
+	if (degree % 3 != 0) {
+		const int ir = degree % 3;
+		s[0] = col[ir]; e[0] = col[ir] + m; s[1] = x0; e[1] = x0 + m;
+		ops->MultiVecAxpby(1.0, blk[ir], 0.0, x, s, e, ops);
+	}
+	return 0;
+}
+
+int GCGE_ChebFilter(void *A, void **x, int x0, int m, int degree, double lower, double upper, double lowest,
+		void **work1, void **work2, struct OPS_ *ops)
+{
+	return cheb_filter(A, x, x0, m, degree, lower, upper, lowest, work1, work2, 0, ops);
+}
+
+static double col_dot(void **x, int cx, void **y, int cy, struct OPS_ *ops)
+{
+	int s[2], e[2]; double v = 0.0;
+	s[0] = cx; e[0] = cx + 1; s[1] = cy; e[1] = cy + 1;
+	ops->MultiVecInnerProd('D', x, y, 0, s, e, &v, 1, ops);
+	return v;
+}
+static void col_axpby(double a, void **x, int cx, double b, void **y, int cy, struct OPS_ *ops)
+{
+	int s[2], e[2];
+	s[0] = cx; e[0] = cx + 1; s[1] = cy; e[1] = cy + 1;
+	ops->MultiVecAxpby(a, x, b, y, s, e, ops);
+}
+
+/* theta_max(T_k) + |beta_k| after k Lanczos steps from one random column: the safeguarded upper bound of Zhou and Li (Y. Zhou,
+ * R.-C. Li, Linear Algebra Appl. 435 (2011) 480-493).  0 when the start vector vanishes. */
+static double lanczos_upper_bound(void *A, int steps, struct OPS_ *ops)
+{
+	void **v; int j, k = 0, ip = 0, iv = 1, iw = 2, s[2], e[2];
+	double *al, *be, *T, *w, *z, *work, nrm, last = 0.0, upper = 0.0;
+	if (steps < 1) steps = 1;
+	al = (double*)calloc(2 * (size_t)steps + 2 * (size_t)steps * steps + 3 * (size_t)steps, sizeof(double));
+	be = al + steps; T = be + steps; z = T + (size_t)steps * steps; w = z + (size_t)steps * steps; work = w + steps;
+	ops->MultiVecCreateByMat(&v, 3, A, ops);
+	ops->MultiVecSetRandomValue(v, iv, iv + 1, ops);
+	nrm = sqrt(col_dot(v, iv, v, iv, ops));
+	if (nrm > 0.0) {
+		col_axpby(0.0, NULL, 0, 1.0 / nrm, v, iv, ops);
+		for (j = 0; j < steps; ++j) {
+			int t;
+			s[0] = iv; e[0] = iv + 1; s[1] = iw; e[1] = iw + 1;
+			ops->MatDotMultiVec(A, v, v, s, e, ops);
+			al[j] = col_dot(v, iv, v, iw, ops);
+			col_axpby(-al[j], v, iv, 1.0, v, iw, ops);
+			if (j > 0) col_axpby(-be[j - 1], v, ip, 1.0, v, iw, ops);
+			be[j] = sqrt(col_dot(v, iw, v, iw, ops));
+			k = j + 1; last = be[j];
+			if (!(be[j] > DBL_EPSILON * fabs(al[j])) || j + 1 == steps) break;      /* an invariant subspace: T_k's values are exact */
+			col_axpby(0.0, NULL, 0, 1.0 / be[j], v, iw, ops);
+			t = ip; ip = iv; iv = iw; iw = t;
+		}
+		for (j = 0; j < k; ++j) {
+			T[(size_t)k * j + j] = al[j];
+			if (j + 1 < k) T[(size_t)k * j + j + 1] = T[(size_t)k * (j + 1) + j] = be[j];
+		}
+		if (GCGE_SymEigHost('U', k, T, k, w, z, k, work) == 0) upper = w[k - 1] + fabs(last);
+	}
+	ops->MultiVecDestroy(&v, 3, ops);
+	free(al);
+	return upper;
+}
+
+/* Ritz pairs of A on span X[:, c..n): X[:, c..n) <- X[:, c..n) Q, eval[c..n) ascending; `work` a block of n - c columns or more */
+static int rayleigh_ritz(void *A, void **x, int c, int n, double *eval, void **work, double *H, double *Q, double *dws, struct OPS_ *ops)
+{
+	int N = n - c, s[2], e[2];
+	if (N <= 0) return 0;
+	s[0] = c; e[0] = n; s[1] = c; e[1] = n;
+	ops->MultiVecQtAP('S', 'N', x, A, x, 0, s, e, H, N, work, ops);
+	if (GCGE_SymEigFor(ops, 'U', N, H, N, eval + c, Q, N, dws) != 0) return -1;
+	s[0] = c; e[0] = n; s[1] = 0; e[1] = N;
+	ops->MultiVecLinearComb(x, work, 0, s, e, Q, N, NULL, 0, ops);
+	s[0] = 0; e[0] = N; s[1] = c; e[1] = n;
+	ops->MultiVecAxpby(1.0, work, 0.0, x, s, e, ops);
+	return 0;
+}
+
+/* the leading converged pairs among [c, upto) by the rule of gcg.c's CheckConvergence: the new count */
+static int leading_converged(void *A, void **x, int c, int upto, const double *eval, const double tol[2], double *res, struct OPS_ *ops)
+{
+	int idx;
+	if (upto <= c) return c;
+	if (GCGE_ResidualNorms(A, NULL, x, c, upto, eval + c, res, ops) != 0) return c;
+	for (idx = 0; idx < upto - c; ++idx) {
+		const double ev = fabs(eval[c + idx]);
+		const int bad = ev > tol[1] ? (res[idx] > tol[0] || res[idx] > ev * tol[1]) : (res[idx] > tol[0]);
+		if (bad) {
+			ops->Printf("ChFSI: [%d] %6.14e (%6.4e, %6.4e)\n", c + idx, eval[c + idx], res[idx], res[idx] / ev);
+			break;
+		}
+	}
+	return c + idx;
+}
+
+int GCGE_RunChFSI(void *A, int argc, char *argv[], struct OPS_ *ops, double *eval, void **evec, int nevGiven, GCGE_CHFSI_RESULT *res)
+{
+	int nevConv = 30, nevMax, max_niter = 100, degree = 20, lanczos_steps = 10, have_upper, conv = 0, numIter = 0, ncol, given, end, rc = 0, pass;
+	double tol[2] = {1e-1, 1e-8}, upper = 0.0, lower = 0.0, lowest = 0.0, t0, *H, *Q, *dws, *rn, *orth_ws;
+	void **w1, **w2; GCGE_COMM *comm = GCGE_GetComm();
+	void (*orth_before) (void **, int, int *, void *, struct OPS_ *); void *orth_ws_before;
+
+	if (res != NULL) memset(res, 0, sizeof(*res));
+	if (A == NULL || ops == NULL || eval == NULL || evec == NULL || nevGiven < 0) return -1;
+	if (comm != NULL && comm->size > 1) return -2;      /* row slabs: not yet */
+	ops->GetOptionFromCommandLine("-nevConv", 'i', &nevConv, argc, argv, ops);
+	nevMax = 2 * nevConv;
+	ops->GetOptionFromCommandLine("-nevMax", 'i', &nevMax, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_abs_tol", 'f', &tol[0], argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_rel_tol", 'f', &tol[1], argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_max_niter", 'i', &max_niter, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-chfsi_degree", 'i', &degree, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-chfsi_lanczos_steps", 'i', &lanczos_steps, argc, argv, ops);
+	have_upper = ops->GetOptionFromCommandLine("-chfsi_upper_bound", 'f', &upper, argc, argv, ops);
+	if (nevConv < 1 || nevMax < nevConv || nevGiven > nevMax || degree < 1 || max_niter < 0 || lanczos_steps < 1) return -1;
+	if (have_upper && !(upper == upper && fabs(upper) <= DBL_MAX)) return -1;
+
+	t0 = ops->GetWtime();
+	ops->Printf("===============================================\n");
+	ops->Printf("ChFSI Eigen Solver\n");
+	ops->Printf("nevGiven = %d, nevConv = %d, nevMax = %d, degree = %d\n", nevGiven, nevConv, nevMax, degree);
+	srand(0);      /* as the harness: the random columns are the rand() stream after srand(0) where the back-end draws from it */
+	orth_before = ops->MultiVecOrth; orth_ws_before = ops->orth_workspace;
+	ops->MultiVecCreateByMat(&w1, nevMax, A, ops);
+	ops->MultiVecCreateByMat(&w2, nevMax, A, ops);
+	H = (double*)calloc(2 * (size_t)nevMax * nevMax + 3 * (size_t)nevMax + (size_t)nevMax * nevMax + 2 * (size_t)nevMax, sizeof(double));
+	Q = H + (size_t)nevMax * nevMax; dws = Q + (size_t)nevMax * nevMax; rn = dws + 2 * (size_t)nevMax; orth_ws = rn + nevMax;
+
+	ops->MultiVecSetRandomValue(evec, nevGiven, nevMax, ops);      /* (first: the same columns whether a bound is given or not) */
+
+	/* 1. the upper bound */
+	if (!have_upper) upper = lanczos_upper_bound(A, lanczos_steps, ops);
+	ops->Printf("ChFSI: upper bound %6.14e (%s)\n", upper, have_upper ? "given" : "Lanczos");
+
+	/* 2. the start block: the given columns, the rest random, orthonormalised as GCG's InitializeX does by default */
+	MultiVecOrthSetup_ModifiedGramSchmidt(80, 2, 2 * DBL_EPSILON, w2, orth_ws, ops);
+	given = nevGiven;
+	ops->MultiVecOrth(evec, 0, &given, NULL, ops);
+	if (given < nevGiven) ops->MultiVecSetRandomValue(evec, given, nevMax, ops);      /* dependent start vectors were dropped */
+	ncol = nevMax;
+	ops->MultiVecOrth(evec, given, &ncol, NULL, ops);
+	if (ncol < nevConv) rc = -3;      /* the random block has no full rank */
+	if (rc == 0 && rayleigh_ritz(A, evec, 0, ncol, eval, w1, H, Q, dws, ops) != 0) rc = -4;
+	if (rc == 0) conv = leading_converged(A, evec, 0, nevConv, eval, tol, rn, ops);
+
+	/* 3. filter, orthonormalise, Rayleigh-Ritz, test, lock */
+	while (rc == 0 && conv < nevConv && numIter < max_niter) {
+		lowest = eval[0]; lower = eval[ncol - 1];
+		if (!(lower > lowest)) lower = lowest + 0.5 * fabs(upper - lowest);        /* a block of one column */
+		if (!(upper > lower)) {                                                  /* a bound below the block's Ritz values: not a bound */
+			ops->Printf("ChFSI: the upper bound %6.14e is not above the largest Ritz value %6.14e\n", upper, lower);
+			rc = -5; break;
+		}
+		if (cheb_filter(A, evec, conv, ncol - conv, degree, lower, upper, lowest, w1, w2, conv, ops) != 0) { rc = -5; break; }
+		for (pass = 0, end = conv; pass < 3 && end < ncol; ++pass) {             /* (a dropped column is drawn again) */
+			if (pass > 0) ops->MultiVecSetRandomValue(evec, end, ncol, ops);
+			given = end; end = ncol;
+			ops->MultiVecOrth(evec, given, &end, NULL, ops);
+		}
+		if (end < nevConv) { rc = -3; break; }
+		ncol = end;
+		if (rayleigh_ritz(A, evec, conv, ncol, eval, w1, H, Q, dws, ops) != 0) { rc = -4; break; }
+		++numIter;
+		conv = leading_converged(A, evec, conv, nevConv, eval, tol, rn, ops);
+	}
+
+	ops->MultiVecOrth = orth_before; ops->orth_workspace = orth_ws_before;
+	ops->MultiVecDestroy(&w1, nevMax, ops);
+	ops->MultiVecDestroy(&w2, nevMax, ops);
+	free(H);
+	if (res != NULL) {
+		res->nevConv = conv; res->numIter = numIter; res->degree = degree; res->seconds = ops->GetWtime() - t0;
+		res->lower = lower; res->upper = upper;
+	}
+	ops->Printf("numIter = %d, nevConv = %d\n", numIter, conv);
+	ops->Printf("Time is %.3f\n", ops->GetWtime() - t0);
+	return rc;
+}

@@ -34,7 +34,7 @@ def _device_of(*things):
 
 
 def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None,
-          eigenvector_grad=False):
+          eigenvector_grad=False, method="gcg", degree=20, upper_bound=None):
     """The k smallest eigenvalues and their eigenvectors of the symmetric problem A x = lambda M x (M=None: the identity; M positive
     definite) by GCG on the GPU.  The smallest eigenvalues are the only mode.
 
@@ -63,6 +63,19 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
            hierarchy's, a hierarchy of another back-end.
     backend:  a HipBackend (default: one per device, kept for the process).
     gcge_args:  harness options ("-gcge_compW_cg_max_iter", 40, ...), appended as they are; they win over the arguments above.
+    method:  "gcg" (the default), or "chebyshev": Chebyshev-filtered subspace iteration (GCGE_RunChFSI) in place of the harness, for
+           the standard problem only.  It solves no linear system, so it needs no hierarchy, no preconditioner and no definite A: per
+           outer iteration the unconverged columns are filtered by a polynomial of A of the given `degree` (default 20) that damps the
+           spectrum between the block's largest Ritz value and `upper_bound` (None: a bound on the largest eigenvalue from ten Lanczos
+           steps; a value from the caller must be such a bound), orthonormalised, and a Rayleigh-Ritz step follows; `iterations`
+           counts these outer iterations, nev_max is the width of the filtered block.  Everything else — A, X0, the result, the
+           residual norms, NoConvergence, gradients — is as for "gcg".  ValueError: M, amg, amg_levels or block_size given with it, or
+           an unknown method.  A loop over a handle in the manner of real-space electronic-structure codes does ONE filter pass per
+           step of the outer (self-consistency) loop and takes whatever that reaches: maxiter=1 and the .result of NoConvergence,
+               try: r = eigsh(m, k, X0=r.eigenvectors, method="chebyshev", maxiter=1, backend=hip)
+               except NoConvergence as e: r = e.result
+           Measured (profiles/chfsi/README.md: Lap3D 128^3, k = 50) it is 3.6 times SLOWER than GCG with a kept hierarchy, cold and
+           warm: use it for matrices GCG cannot take — an indefinite A, or no hierarchy that can be built or kept — not instead of it.
 
     Gradients: when A (or M) is given as a sparse_csr tensor or a (crow, col, val) triple whose values require grad, and grad mode is
     on, `eigenvalues` comes back attached to the graph and backward gives d loss / d values on the stored entries
@@ -86,7 +99,8 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
     on the device.  Raises NoConvergence, carrying the partial result, when fewer than k pairs converged."""
     import torch
     dA, dM = _differentiable(A), _differentiable(M)
-    kw = dict(X0=X0, tol=tol, maxiter=maxiter, nev_max=nev_max, block_size=block_size, amg_levels=amg_levels, gcge_args=gcge_args, amg=amg)
+    kw = dict(X0=X0, tol=tol, maxiter=maxiter, nev_max=nev_max, block_size=block_size, amg_levels=amg_levels, gcge_args=gcge_args, amg=amg,
+              method=method, degree=degree, upper_bound=upper_bound)
     if eigenvector_grad and (_is_handle(A) or _is_handle(M) or (dA is None and dM is None)):
         raise ValueError("eigsh: eigenvector_grad needs A (or M) given as tensors whose values require grad, with grad mode on, and no "
                          "matrix handle; a loop that keeps handles calls gcge_amd.eigenvector_grads itself")
@@ -146,13 +160,21 @@ def _backend_for(backend, *things):
 
 
 def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None,
-           _keep=None):
+           _keep=None, method="gcg", degree=20, upper_bound=None):
     """eigsh on detached inputs: see there.  _keep: a dict that, when all k pairs converged, takes the handles "A" and "M" of the solve
     and the list "made" of those created here, which are then NOT freed (the caller owns them)"""
     import numpy as np
     import torch
-    from .lib import host_lib, run_gcg
+    from .lib import host_lib, run_chfsi, run_gcg
 
+    if method not in ("gcg", "chebyshev"):
+        raise ValueError("eigsh: method is \"gcg\" or \"chebyshev\"")
+    chebyshev = method == "chebyshev"
+    if chebyshev and (M is not None or amg is not None or amg_levels or block_size is not None):
+        raise ValueError("eigsh: method=\"chebyshev\" is for the standard problem and solves no linear system: M, amg, amg_levels and "
+                         "block_size do not go with it")
+    if chebyshev and int(degree) < 1:
+        raise ValueError("eigsh: degree >= 1 is required")
     k = int(k)
     nev_max = 2 * k if nev_max is None else int(nev_max)
     amg_levels = int(amg_levels)
@@ -182,6 +204,10 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
         own.append(("-blockSize", int(block_size)))
     if amg_levels > 0:
         own.append(("-gcge_amg_levels", amg_levels))
+    if chebyshev:
+        own.append(("-chfsi_degree", int(degree)))
+        if upper_bound is not None:
+            own.append(("-chfsi_upper_bound", repr(float(upper_bound))))
     args = []
     for name, value in own:             # (the harness takes the first occurrence of an option)
         if name not in gcge_args:
@@ -207,10 +233,19 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
         flag = 1 if amg_levels > 0 or amg is not None else 0
         if amg is not None:
             amg.install()
+        shape = None
         if X0 is not None:
             shape = tuple(X0.shape) if hasattr(X0, "shape") else tuple(X0.__cuda_array_interface__["shape"])
             if len(shape) != 2 or shape[1] > nev_max:
                 raise ValueError("eigsh: X0 is an (n, j) block with j <= nev_max")
+        if chebyshev:
+            evec = backend.ops.mv_create(nev_max, mA)
+            if X0 is not None:
+                backend.mv_from_torch(mA, X0, mv=evec, c0=0)
+            ev, res, rc = run_chfsi(backend.ops_handle, mA, args, evec, given=int(shape[1]) if X0 is not None else 0)
+            if rc != 0:
+                raise RuntimeError("GCGE_RunChFSI rc=%d" % rc)
+        elif X0 is not None:
             evec = backend.ops.mv_create(nev_max, mA)
             backend.mv_from_torch(mA, X0, mv=evec, c0=0)
             ev, res = run_gcg(backend.ops_handle, mA, mB, args, flag=flag, given=(evec, int(shape[1])))

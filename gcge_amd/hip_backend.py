@@ -231,6 +231,31 @@ class HipBackendImpl:
             self.g.gcge_hip_mv_from_device(mv, c0, c0 + m, t.data_ptr(), rs, cs)
         return mv
 
+    def chebyshev_filter(self, A, X, degree, lower, upper, lowest):
+        """p(A) X for the matrix handle A and an (n, m) device tensor X, as a new (n, m) float64 tensor (GCGE_ChebFilter): p is the
+        Chebyshev polynomial of the given degree scaled to 1 at `lowest` and bounded by 1 on [lower, upper] — the components of X along
+        eigenvectors with eigenvalues in [lower, upper] are damped relative to those below `lower`.  X goes in through mv_from_torch
+        and out through mv_to_torch; the two work blocks are created and freed here.  Every step is the back-end's cheb_step (fused
+        into one sweep on matrices whose product it can rebuild there, product + one sweep otherwise; lib.cheb_stats counts them).
+        ValueError: degree < 1, lower >= upper, lowest >= lower."""
+        if int(degree) < 1 or not float(lower) < float(upper) or not float(lowest) < float(lower):
+            raise ValueError("chebyshev_filter: degree >= 1 and lowest < lower < upper are required")
+        mx = self.mv_from_torch(A, X)
+        m = self.g.gcge_hip_mv_ncols(mx)
+        w1 = w2 = None
+        try:
+            if m == 0:
+                return self.mv_to_torch(mx, 0, 0)
+            w1, w2 = self.ops.mv_create(m, A), self.ops.mv_create(m, A)
+            rc = self.h.GCGE_ChebFilter(A, mx, 0, m, int(degree), float(lower), float(upper), float(lowest), w1, w2, self.ops_handle)
+            if rc != 0:
+                raise RuntimeError("GCGE_ChebFilter rc=%d" % rc)
+            return self.mv_to_torch(mx, 0, m)
+        finally:
+            for w in (w1, w2, mx):
+                if w is not None:
+                    self.ops.mv_destroy(w, m)
+
     def sample_outer(self, crow, col, U, V, weights=None, alpha=1.0):
         """The rank-k product U diag(weights) V^T on the stored entries of a CSR pattern (gcge_hip_csr_sample_outer): an (nnz,)
         float64 device tensor with out[e] = alpha sum_c weights[c] U[i, c] V[col[e], c] for every entry e of row i, in the entry order

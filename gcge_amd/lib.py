@@ -414,6 +414,31 @@ def run_gcg(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False, given=No
     return ev, res
 
 
+class ChFSIResult(C.Structure):
+    """GCGE_CHFSI_RESULT (include/gcge_solver.h)."""
+    _fields_ = [("nevConv", C.c_int), ("numIter", C.c_int), ("degree", C.c_int), ("seconds", C.c_double), ("lower", C.c_double),
+                ("upper", C.c_double)]
+
+
+def run_chfsi(ops, matA, args, evec, given=0, quiet=True):
+    """GCGE_RunChFSI (Chebyshev-filtered subspace iteration, standard problem) through the operator table `ops`: `evec` is the
+    caller's block of nevMax columns whose first `given` columns are start vectors; the eigenvectors come back in it.  Returns
+    (eval of nevMax entries, ChFSIResult, return code) — the code is 0 for a completed run, converged or not."""
+    h = host_lib()
+    argc, argv, ev = _solver_args(args, quiet)
+    res = ChFSIResult()
+    rc = h.GCGE_RunChFSI(matA, argc, C.cast(argv, C.c_void_p), ops, ev.ctypes.data_as(C.c_void_p), evec, int(given),
+                         C.cast(C.byref(res), C.c_void_p))
+    return ev, res, rc
+
+
+def cheb_stats():
+    """gcge_hip_cheb_stats: (Chebyshev steps taken fused, steps taken as product + sweep, calls declined) since the library was loaded."""
+    out = (C.c_long * 3)()
+    hip_lib().gcge_hip_cheb_stats(out)
+    return tuple(out)
+
+
 def run_pas(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False):
     """GCGE_RunPAS through the operator table `ops`: PAS (the multigrid eigensolver over the back-end's hierarchy), then GCG
     warm-started from PAS's converged vectors unless args hold -gcge_pas_only 1.  Returns (eval, pas_result, gcg_result)

@@ -665,6 +665,28 @@ int gcge_hip_panel_norms_sq_mv (void **y, int start, int end, double *out);
  *     on an odd column (matrix in pattern form, even width, x and r on even columns), out[2] / out[3] the same for the V-cycle's
  *     fused residual                                                                                                              */
 void gcge_hip_sweep_stats (long out[4]);
+/*     One step of a Chebyshev filter (GCGE_ChebFilter, gcge_solver.h; csrc/hip/cheb_sweeps.hip), the sweep on raw device pointers:
+ *         out[r, j] <- alpha (out[r, j] - c y[r, j]) - beta z[r, j]        0 <= r < n, 0 <= j < m
+ *     in place on out, which holds A y on entry; row-major blocks with their leading dimensions, out apart from y and z.
+ *     beta == 0: z is not read (NULL, or any contents).  Rounded as u = fma(-c, y, out), then fma(alpha, u, -(beta z)) (beta == 0:
+ *     alpha u): the same bits on every run and in both kernels (16-byte lanes when m, the origins and the leading dimensions are
+ *     even, scalar lanes otherwise).  Nothing is waited for.  Return 0, the launch's error, or -1 on bad arguments.                */
+int gcge_hip_cheb_sweep (long n, double *out, long ldo, const double *y, long ldy, const double *z, long ldz, int m,
+		double alpha, double c, double beta, void *stream);
+/*     The step on a matrix handle and blocks of this back-end:  out[:, o0..o0+m) = alpha (A y[:, y0..) - c y[:, y0..)) - beta z[:, z0..),
+ *     out, y and z three different blocks (beta == 0: z is not read and may be NULL).  Two paths:
+ *       fused            matrices with a pattern table whose product is bound by HBM (gcge_hip_cg_fusable, gcge_hip_cg_recompute_pays),
+ *                        beta != 0, one rank, an even width and y0 == z0 == o0 even: ONE call of gcge_hip_cg_pass2i_dev (kernel MODE 7)
+ *                        with every column flagged and d_alpha = -alpha, d_betaprev = beta, d_beta = -alpha c - 1 — the product is
+ *                        rebuilt in registers: y and z read, out written, 3 block streams and the matrix;
+ *       product + sweep  everything else: the handle's ordinary product into out (any K1 form), then gcge_hip_cheb_sweep in place:
+ *                        6 block streams and the matrix.  GCGE_CHEB_NO_FUSE=1 in the environment (read per call) forces this path.
+ *     Nothing is waited for.  Returns 0; -1 with nothing written for operands no path takes (aliased blocks, a rectangular handle,
+ *     column ranges outside a block, blocks of another row count or row order).  gcge_hip_cheb_stats: steps taken fused, steps by
+ *     product + sweep, calls that returned -1, since the library was loaded.                                                       */
+int gcge_hip_cheb_step_mv (void *mat, void **y, int y0, void **z, int z0, void **out, int o0, int m,
+		double alpha, double c, double beta);
+void gcge_hip_cheb_stats (long out[3]);
 
 #ifdef __cplusplus
 }

@@ -260,7 +260,12 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *                 column without a flag keeps the bits of its w (its pw[j] is 0).  q is B p, or p itself (the same block and column:
  *                 the row is read once).  shift, flag, pw: host arrays of m entries.  The slots take one MultiVecAxpby per flagged
  *                 column, then MultiVecLocalInnerProd('D'): 3 reads + 1 write + 2 reads in m + 1 launches.  0 declines, nothing
- *                 touched. */
+ *                 touched.
+ *   cheb_step     one step of the three-term recurrence of GCGE_ChebFilter (gcge_solver.h) on a window of m columns:
+ *                 out[:, o0..) = alpha (A y[:, y0..) - c y[:, y0..)) - beta z[:, z0..), out, y and z three different blocks; beta == 0:
+ *                 z is not read and may be NULL (a filter's first step).  Nothing is waited for.  The slots take MatDotMultiVec into
+ *                 out and two MultiVecAxpby: 2 + 3 + 3 block streams; the HIP back-end 3 on matrices whose product it can rebuild
+ *                 inside the sweep, 6 otherwise.  1 taken, 0 declines with nothing touched. */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -280,6 +285,8 @@ typedef int    (*GCGE_PCG_DOTS_FN) (void **z, int z0, void **r, int r0, void **w
 typedef int    (*GCGE_PCG_DIRECTION_FN) (void **z, int z0, void **p, int p0, int m, const double *beta, const int *flag, struct OPS_ *ops);
 typedef int    (*GCGE_PCG_SHIFT_FN) (void **p, int p0, void **q, int q0, void **w, int w0, int m, const double *shift, const int *flag,
 		double *pw, struct OPS_ *ops);
+typedef int    (*GCGE_CHEB_STEP_FN) (void *A, void **y, int y0, void **z, int z0, void **out, int o0, int m, double alpha, double c,
+		double beta, struct OPS_ *ops);
 typedef struct GCGE_BACKEND_ {
 	GCGE_RESIDUAL_FN residual_sq;
 	int inplace_lincomb_cols;
@@ -301,6 +308,7 @@ typedef struct GCGE_BACKEND_ {
 	GCGE_PCG_STEP_FN pcg_step; GCGE_PCG_DOTS_FN pcg_dots; GCGE_PCG_DIRECTION_FN pcg_direction;
 	int  (*amg_smoother_niter) (struct OPS_ *ops);
 	GCGE_PCG_SHIFT_FN pcg_shift;
+	GCGE_CHEB_STEP_FN cheb_step;
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

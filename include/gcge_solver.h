@@ -243,6 +243,37 @@ int GCGE_RunGCGGiven (void *A, void *B, int flag, int argc, char *argv[], struct
  * end - start columns created for the call.  Returns 0, -1 on bad arguments.                                                      */
 int GCGE_ResidualNorms (void *A, void *B, void **evec, int start, int end, const double *eval, double *out, struct OPS_ *ops);
 
+/* ---- Chebyshev-filtered subspace iteration (csrc/host/chfsi.c): the smallest eigenpairs of a STANDARD problem without a linear
+ * solve — no preconditioner, no hierarchy, and A need not be definite.  Single rank.
+ * GCGE_ChebFilter: x[:, x0..x0+m) <- p(A) x[:, x0..x0+m) in place, p the Chebyshev polynomial of the given degree scaled to 1 at
+ * `lowest` and bounded by 1 on [lower, upper] (so nothing overflows at any degree), by the three-term recurrence with
+ *     e = (upper - lower) / 2,  c = (upper + lower) / 2,  sigma_1 = e / (lowest - c),  tau = 2 / sigma_1
+ *     step 1:       Y_1 = (sigma_1 / e) (A - c) X
+ *     step i >= 2:  sigma' = 1 / (tau - sigma) ;  Y_i = (2 sigma' / e) (A - c) Y_{i-1} - sigma sigma' Y_{i-2} ;  sigma = sigma'
+ * over x and the two work blocks (windows [0, m) of work1 and work2, m columns or more each; three different blocks), the result
+ * copied back into x when it ends elsewhere.  One step is the back-end's cheb_step (GCGE_BACKEND, gcge_ops.h) where it is offered
+ * and accepts, else MatDotMultiVec and two MultiVecAxpby.  Returns 0; -1 on bad arguments (degree < 1, lower >= upper, lowest >=
+ * lower, aliased blocks) with nothing written.
+ * GCGE_RunChFSI: options in harness style: -nevConv (30), -nevMax (2 nevConv), -gcge_abs_tol / -gcge_rel_tol (1e-1 / 1e-8, tested
+ * by the rule of the GCG driver's convergence check), -gcge_max_niter (100), -chfsi_degree (20), -chfsi_lanczos_steps (10),
+ * -chfsi_upper_bound (unset: theta_max + |beta_k| of that many Lanczos steps on one random column, the safeguarded bound of Zhou
+ * and Li).  evec: the caller's block of nevMax columns whose first nevGiven columns are start vectors (the rest is drawn by
+ * MultiVecSetRandomValue); eval: nevMax doubles.  The start block is orthonormalised as GCG's initial block is by default and
+ * tested after a Rayleigh-Ritz step, so a converged start returns with numIter == 0.  Per iteration: lower = the block's largest
+ * Ritz value, lowest = its smallest; the columns behind the locked ones are filtered, orthonormalised against the locked ones and
+ * among themselves, Rayleigh-Ritz, residual norms (GCGE_ResidualNorms), the count of LEADING converged pairs advances.  ops->MultiVecOrth
+ * and its workspace are put back before it returns.  Returns 0 for a completed run, converged or not (res->nevConv says);
+ * -1 bad arguments and -2 a communicator of more than one rank, both with evec untouched; -3 the block lost rank; -4 the dense
+ * eigensolver failed; -5 the upper bound is not above the block's Ritz values.                                                    */
+typedef struct GCGE_CHFSI_RESULT_ {
+	int nevConv, numIter, degree;
+	double seconds, lower, upper;      /* the last filter's lower end; the upper bound used */
+} GCGE_CHFSI_RESULT;
+int GCGE_ChebFilter (void *A, void **x, int x0, int m, int degree, double lower, double upper, double lowest,
+		void **work1, void **work2, struct OPS_ *ops);
+int GCGE_RunChFSI (void *A, int argc, char *argv[], struct OPS_ *ops, double *eval, void **evec, int nevGiven,
+		GCGE_CHFSI_RESULT *res);
+
 /* ---- PAS eigensolver (sets ops->EigenSolver; reference src/ops_eig_sol_pas.h) -------------------------------------
  * Rayleigh-Ritz on the coarsest level H = num_levels - 1, then per iteration: prolongate X one level (down to level 0),
  * smooth A X = Lambda B X by BlockAMG from that level down, make X B-orthogonal to range(P_H) and B-orthonormal, solve the
