@@ -7,6 +7,8 @@
  *                     relative to them like a Chebyshev polynomial outside its interval.
  *   GCGE_RunChFSI     upper bound by a few Lanczos steps, then per iteration: filter the unconverged columns, orthonormalise them
  *                     against the locked ones and among themselves, Rayleigh-Ritz, residuals, lock the leading converged pairs.
+ *   GCGE_ChebBandFilter, GCGE_RunChFSIBand   (at the end of the file) the eigenpairs INSIDE an interval [a, b]: the filter is the
+ *                     Jackson-damped Chebyshev expansion of the interval's indicator, a sum of the recurrence's iterates.
  *
  * The filter is the three-term recurrence  Y_{j+1} = alpha_j (A - c I) Y_j - beta_j Y_{j-1}.  One step goes through the back-end's
  * cheb_step (GCGE_BACKEND, gcge_ops.h) where the table offers it and it accepts, else through the slots: MatDotMultiVec into the
@@ -87,11 +89,12 @@ static void col_axpby(double a, void **x, int cx, double b, void **y, int cy, st
 }
 
 /* theta_max(T_k) + |beta_k| after k Lanczos steps from one random column: the safeguarded upper bound of Zhou and Li (Y. Zhou,
- * R.-C. Li, Linear Algebra Appl. 435 (2011) 480-493).  0 when the start vector vanishes. */
-static double lanczos_upper_bound(void *A, int steps, struct OPS_ *ops)
+ * R.-C. Li, Linear Algebra Appl. 435 (2011) 480-493), and theta_min(T_k) - |beta_k|, the same at the other end, from the same run
+ * (either pointer may be NULL).  Returns 0; -1, with 0 in both, when the start vector vanishes or the dense eigensolver fails. */
+static int lanczos_bounds(void *A, int steps, struct OPS_ *ops, double *lower_out, double *upper_out)
 {
 	void **v; int j, k = 0, ip = 0, iv = 1, iw = 2, s[2], e[2];
-	double *al, *be, *T, *w, *z, *work, nrm, last = 0.0, upper = 0.0;
+	double *al, *be, *T, *w, *z, *work, nrm, last = 0.0, upper = 0.0, lower = 0.0; int rc = -1;
 	if (steps < 1) steps = 1;
 	al = (double*)calloc(2 * (size_t)steps + 2 * (size_t)steps * steps + 3 * (size_t)steps, sizeof(double));
 	be = al + steps; T = be + steps; z = T + (size_t)steps * steps; w = z + (size_t)steps * steps; work = w + steps;
@@ -117,11 +120,20 @@ static double lanczos_upper_bound(void *A, int steps, struct OPS_ *ops)
 			T[(size_t)k * j + j] = al[j];
 			if (j + 1 < k) T[(size_t)k * j + j + 1] = T[(size_t)k * (j + 1) + j] = be[j];
 		}
-		if (GCGE_SymEigHost('U', k, T, k, w, z, k, work) == 0) upper = w[k - 1] + fabs(last);
+		if (GCGE_SymEigHost('U', k, T, k, w, z, k, work) == 0) { upper = w[k - 1] + fabs(last); lower = w[0] - fabs(last); rc = 0; }
 	}
 	ops->MultiVecDestroy(&v, 3, ops);
 	free(al);
-	return upper;
+	if (lower_out != NULL) *lower_out = lower;
+	if (upper_out != NULL) *upper_out = upper;
+	return rc;
+}
+
+int GCGE_LanczosBounds(void *A, int steps, double *lmin, double *lmax, struct OPS_ *ops)
+{
+	GCGE_COMM *comm = GCGE_GetComm();
+	if (A == NULL || ops == NULL || steps < 1 || (comm != NULL && comm->size > 1)) return -1;
+	return lanczos_bounds(A, steps, ops, lmin, lmax);
 }
 
 /* Ritz pairs of A on span X[:, c..n): X[:, c..n) <- X[:, c..n) Q, eval[c..n) ascending; `work` a block of n - c columns or more */
@@ -192,7 +204,7 @@ int GCGE_RunChFSI(void *A, int argc, char *argv[], struct OPS_ *ops, double *eva
 	ops->MultiVecSetRandomValue(evec, nevGiven, nevMax, ops);      /* (first: the same columns whether a bound is given or not) */
 
 	/* 1. the upper bound */
-	if (!have_upper) upper = lanczos_upper_bound(A, lanczos_steps, ops);
+	if (!have_upper) lanczos_bounds(A, lanczos_steps, ops, NULL, &upper);
 	ops->Printf("ChFSI: upper bound %6.14e (%s)\n", upper, have_upper ? "given" : "Lanczos");
 
 	/* 2. the start block: the given columns, the rest random, orthonormalised as GCG's InitializeX does by default */
@@ -236,6 +248,240 @@ int GCGE_RunChFSI(void *A, int argc, char *argv[], struct OPS_ *ops, double *eva
 		res->lower = lower; res->upper = upper;
 	}
 	ops->Printf("numIter = %d, nevConv = %d\n", numIter, conv);
+	ops->Printf("Time is %.3f\n", ops->GetWtime() - t0);
+	return rc;
+}
+
+/* ---- eigenpairs inside an interval: a band-pass filter, a SUM of Chebyshev terms ------------------------------------------------
+ * p(t) = sum_j mu_j T_j(t), t = (lambda - c) / e, the Jackson-damped Chebyshev expansion of the indicator of [a, b] (A. Weisse,
+ * G. Wellein, A. Alvermann, H. Fehske, Rev. Mod. Phys. 78 (2006) 275-306; E. Di Napoli, E. Polizzi, Y. Saad, Numer. Linear Algebra
+ * Appl. 23 (2016) 674-692): about 1 inside, about 0 outside, 1/2 at the ends, monotone across each end. */
+int GCGE_ChebBandCoefficients(int degree, double a, double b, double lmin, double lmax, double *mu)
+{
+	const double pi = 3.14159265358979323846;
+	double c, e, ta, tb, tha, thb, al;
+	int j;
+	if (mu == NULL || degree < 2 || !(lmin < lmax) || !(a < b) || !(a <= lmax) || !(b >= lmin)) return -1;
+	c = 0.5 * (lmax + lmin); e = 0.5 * (lmax - lmin);
+	ta = (a - c) / e; if (ta < -1.0) ta = -1.0;
+	tb = (b - c) / e; if (tb > 1.0) tb = 1.0;
+	tha = acos(ta); thb = acos(tb);
+	al = pi / (degree + 2);
+	for (j = 0; j <= degree; ++j) {
+		const double gamma = j == 0 ? (tha - thb) / pi : 2.0 * (sin(j * tha) - sin(j * thb)) / (j * pi);
+		const double g = ((degree + 2 - j) * cos(j * al) + sin(j * al) * (cos(al) / sin(al))) / (degree + 2);
+		mu[j] = gamma * g;
+	}
+	return 0;
+}
+
+/* p at lambda by the recurrence, lambda clamped to [lmin, lmax] (an end outside the bounds has no eigenvalue near it) */
+static double band_poly(int degree, const double *mu, double c, double e, double lambda)
+{
+	double t = (lambda - c) / e, t0 = 1.0, t1, p;
+	int j;
+	if (t < -1.0) t = -1.0;
+	if (t > 1.0) t = 1.0;
+	t1 = t; p = mu[0] + mu[1] * t;
+	for (j = 2; j <= degree; ++j) {
+		const double t2 = 2.0 * t * t1 - t0;
+		p += mu[j] * t2; t0 = t1; t1 = t2;
+	}
+	return p;
+}
+
+/* acc[:, a0..) = [acc +] mu_a ta[:, ta0..) + mu_b tb[:, tb0..)   (tb == NULL: one term; init: acc is not read) */
+static void cheb_accum(void **acc, int a0, void **ta, int ta0, double mu_a, void **tb, int tb0, double mu_b, int m, int init,
+		struct OPS_ *ops)
+{
+	int s[2], e[2];
+	s[0] = ta0; e[0] = ta0 + m; s[1] = a0; e[1] = a0 + m;
+	ops->MultiVecAxpby(mu_a, ta, init ? 0.0 : 1.0, acc, s, e, ops);
+	if (tb != NULL) {
+		s[0] = tb0; e[0] = tb0 + m;
+		ops->MultiVecAxpby(mu_b, tb, 1.0, acc, s, e, ops);
+	}
+}
+
+/* x[:, x0..) <- sum_j mu[j] T_j((A - c) / e) x[:, x0..): the ring of three blocks of cheb_filter (block 0 is x itself, the work
+ * blocks' windows at column w0), the iterates added to acc[:, w0..) in pairs while both are live (the order a one-pass kernel for
+ * two terms would take: init on (T_0, T_1), then (T_2, T_3), ...), acc copied into x at the end (and left holding the result). */
+static void cheb_band_filter(void *A, void **x, int x0, int m, int degree, const double *mu, double c, double ee,
+		void **work1, void **work2, void **acc, int w0, struct OPS_ *ops)
+{
+	const GCGE_BACKEND be = GCGE_BackendOf(ops);
+	void **blk[3]; int col[3], i, s[2], e[2];
+	blk[0] = x; col[0] = x0; blk[1] = work1; col[1] = w0; blk[2] = work2; col[2] = w0;
+	/* step i reads block (i - 1) % 3 (and (i - 2) % 3) and writes T_i into block i % 3 */
+	cheb_step(A, blk[0], col[0], NULL, 0, blk[1], col[1], m, 1.0 / ee, c, 0.0, &be, ops);
+	cheb_accum(acc, w0, blk[0], col[0], mu[0], blk[1], col[1], mu[1], m, 1, ops);
+	for (i = 2; i <= degree; ++i) {
+		const int iy = (i - 1) % 3, iz = (i - 2) % 3, io = i % 3;
+		cheb_step(A, blk[iy], col[iy], blk[iz], col[iz], blk[io], col[io], m, 2.0 / ee, c, 1.0, &be, ops);
+		if (i & 1) cheb_accum(acc, w0, blk[iy], col[iy], mu[i - 1], blk[io], col[io], mu[i], m, 0, ops);
+		else if (i == degree) cheb_accum(acc, w0, blk[io], col[io], mu[i], NULL, 0, 0.0, m, 0, ops);
+	}
+	s[0] = w0; e[0] = w0 + m; s[1] = x0; e[1] = x0 + m;
+	ops->MultiVecAxpby(1.0, acc, 0.0, x, s, e, ops);
+}
+
+int GCGE_ChebBandFilter(void *A, void **x, int x0, int m, int degree, double a, double b, double lmin, double lmax,
+		void **work1, void **work2, void **acc, struct OPS_ *ops)
+{
+	double *mu;
+	if (A == NULL || x == NULL || work1 == NULL || work2 == NULL || acc == NULL || ops == NULL || x0 < 0 || m < 0 || degree < 2) return -1;
+	if (x == work1 || x == work2 || work1 == work2 || acc == x || acc == work1 || acc == work2) return -1;
+	mu = (double*)malloc(((size_t)degree + 1) * sizeof(double));
+	if (mu == NULL) return -1;
+	if (GCGE_ChebBandCoefficients(degree, a, b, lmin, lmax, mu) != 0) { free(mu); return -1; }
+	if (m > 0) cheb_band_filter(A, x, x0, m, degree, mu, 0.5 * (lmax + lmin), 0.5 * (lmax - lmin), work1, work2, acc, 0, ops);
+	free(mu);
+	return 0;
+}
+
+static int pair_passes(double eval, double rn, const double tol[2])
+{
+	const double ev = fabs(eval);
+	return ev > tol[1] ? !(rn > tol[0] || rn > ev * tol[1]) : !(rn > tol[0]);      /* (leading_converged's rule) */
+}
+
+int GCGE_RunChFSIBand(void *A, int argc, char *argv[], struct OPS_ *ops, double *eval, void **evec, int nevGiven, GCGE_CHFSI_BAND_RESULT *res)
+{
+	int nevMax = 0, max_niter = 100, degree = 0, lanczos_steps = 10, have_a, have_b, have_n, have_lo, have_up, have_deg;
+	int numIter = 0, ncol = 0, given, end, rc = 0, pass, i, j, ngen = 0, nspur = 0, converged = 0, *kind, s[2], e[2];
+	double tol[2] = {1e-1, 1e-8}, a = 0.0, b = 0.0, lmin = 0.0, lmax = 0.0, edge = 0.0, c, ee, t0, *H, *Q, *dws, *rn, *rho, *ev2, *orth_ws, *mu = NULL;
+	void **w1, **w2, **acc, **xc; GCGE_COMM *comm = GCGE_GetComm();
+	void (*orth_before) (void **, int, int *, void *, struct OPS_ *); void *orth_ws_before;
+
+	if (res != NULL) memset(res, 0, sizeof(*res));
+	if (A == NULL || ops == NULL || eval == NULL || evec == NULL || nevGiven < 0) return -1;
+	if (comm != NULL && comm->size > 1) return -2;      /* row slabs: not yet */
+	have_a = ops->GetOptionFromCommandLine("-chfsi_band_lo", 'f', &a, argc, argv, ops);
+	have_b = ops->GetOptionFromCommandLine("-chfsi_band_hi", 'f', &b, argc, argv, ops);
+	have_n = ops->GetOptionFromCommandLine("-nevMax", 'i', &nevMax, argc, argv, ops);
+	have_deg = ops->GetOptionFromCommandLine("-chfsi_degree", 'i', &degree, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_abs_tol", 'f', &tol[0], argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_rel_tol", 'f', &tol[1], argc, argv, ops);
+	ops->GetOptionFromCommandLine("-gcge_max_niter", 'i', &max_niter, argc, argv, ops);
+	ops->GetOptionFromCommandLine("-chfsi_lanczos_steps", 'i', &lanczos_steps, argc, argv, ops);
+	have_lo = ops->GetOptionFromCommandLine("-chfsi_lower_bound", 'f', &lmin, argc, argv, ops);
+	have_up = ops->GetOptionFromCommandLine("-chfsi_upper_bound", 'f', &lmax, argc, argv, ops);
+	if (!have_a || !have_b || !have_n || !(a < b) || !(fabs(a) <= DBL_MAX) || !(fabs(b) <= DBL_MAX)) return -1;
+	if (nevMax < 1 || nevGiven > nevMax || (have_deg && degree < 2) || max_niter < 0 || lanczos_steps < 1) return -1;
+	if ((have_lo && !(fabs(lmin) <= DBL_MAX)) || (have_up && !(fabs(lmax) <= DBL_MAX))) return -1;
+	if (have_lo && have_up && (!(lmin < lmax) || !(a <= lmax) || !(b >= lmin))) return -1;
+
+	t0 = ops->GetWtime();
+	ops->Printf("===============================================\n");
+	ops->Printf("ChFSI Eigen Solver, interval [%6.14e, %6.14e]\n", a, b);
+	srand(0);      /* as GCGE_RunChFSI */
+	orth_before = ops->MultiVecOrth; orth_ws_before = ops->orth_workspace;
+	ops->MultiVecCreateByMat(&w1, nevMax, A, ops);
+	ops->MultiVecCreateByMat(&w2, nevMax, A, ops);
+	ops->MultiVecCreateByMat(&acc, nevMax, A, ops);
+	ops->MultiVecCreateByMat(&xc, nevMax, A, ops);
+	H = (double*)calloc(2 * (size_t)nevMax * nevMax + 3 * (size_t)nevMax + (size_t)nevMax * nevMax + 2 * (size_t)nevMax + 3 * (size_t)nevMax, sizeof(double));
+	Q = H + (size_t)nevMax * nevMax; dws = Q + (size_t)nevMax * nevMax; rn = dws + 2 * (size_t)nevMax; orth_ws = rn + nevMax;
+	rho = orth_ws + (size_t)nevMax * nevMax + 2 * (size_t)nevMax; ev2 = rho + nevMax;
+	kind = (int*)calloc((size_t)nevMax, sizeof(int));      /* of a pair inside [a, b]: 1 genuine, 2 spurious; 0 outside */
+
+	ops->MultiVecSetRandomValue(evec, nevGiven, nevMax, ops);
+
+	/* 1. the bounds: one Lanczos run gives whichever the caller left out */
+	if (!have_lo || !have_up) {
+		double lo = 0.0, up = 0.0;
+		if (lanczos_bounds(A, lanczos_steps, ops, &lo, &up) != 0) rc = -5;
+		if (!have_lo) lmin = lo;
+		if (!have_up) lmax = up;
+	}
+	ops->Printf("ChFSI: bounds %6.14e (%s), %6.14e (%s)\n", lmin, have_lo ? "given" : "Lanczos", lmax, have_up ? "given" : "Lanczos");
+	if (rc == 0 && (!(lmin < lmax) || !(a <= lmax) || !(b >= lmin))) rc = -5;      /* the interval misses the bounds */
+	c = 0.5 * (lmax + lmin); ee = 0.5 * (lmax - lmin);
+	if (rc == 0 && !have_deg) {
+		const double d = ceil(GCGE_CHFSI_BAND_DEGREE_FACTOR * (lmax - lmin) / (b - a));
+		degree = d < 20.0 ? 20 : d > 1000.0 ? 1000 : (int)d;
+	}
+	if (rc == 0) {
+		mu = (double*)malloc(((size_t)degree + 1) * sizeof(double));
+		if (mu == NULL || GCGE_ChebBandCoefficients(degree, a, b, lmin, lmax, mu) != 0) rc = -5;
+	}
+	if (rc == 0) {
+		const double pa = band_poly(degree, mu, c, ee, a), pb = band_poly(degree, mu, c, ee, b);
+		edge = pa < pb ? pa : pb;
+		ops->Printf("ChFSI: degree %d, p(a) = %6.14e, p(b) = %6.14e\n", degree, pa, pb);
+	}
+
+	/* 2. the start block, as GCGE_RunChFSI */
+	if (rc == 0) {
+		MultiVecOrthSetup_ModifiedGramSchmidt(80, 2, 2 * DBL_EPSILON, w2, orth_ws, ops);
+		given = nevGiven;
+		ops->MultiVecOrth(evec, 0, &given, NULL, ops);
+		if (given < nevGiven) ops->MultiVecSetRandomValue(evec, given, nevMax, ops);
+		ncol = nevMax;
+		ops->MultiVecOrth(evec, given, &ncol, NULL, ops);
+		if (ncol < 1) rc = -3;
+	}
+	if (rc == 0 && rayleigh_ritz(A, evec, 0, ncol, eval, w1, H, Q, dws, ops) != 0) rc = -4;
+
+	/* 3. residuals of the Ritz vectors, filter (their rho comes out of it), decide on THOSE vectors; else orthonormalise, Rayleigh-Ritz */
+	while (rc == 0) {
+		int all_pass = 1;
+		if (GCGE_ResidualNorms(A, NULL, evec, 0, ncol, eval, rn, ops) != 0) { rc = -4; break; }
+		s[0] = 0; e[0] = ncol; s[1] = 0; e[1] = ncol;
+		ops->MultiVecAxpby(1.0, evec, 0.0, xc, s, e, ops);                              /* the Ritz vectors, kept */
+		cheb_band_filter(A, evec, 0, ncol, degree, mu, c, ee, w1, w2, acc, 0, ops);
+		ops->MultiVecInnerProd('D', xc, evec, 0, s, e, rho, 1, ops);                    /* rho_i = x_i^T p(A) x_i */
+		ngen = nspur = 0;
+		for (i = 0; i < ncol; ++i) {
+			kind[i] = 0;
+			if (!(eval[i] >= a && eval[i] <= b)) continue;
+			if (rho[i] >= edge) {
+				kind[i] = 1; ++ngen;
+				if (!pair_passes(eval[i], rn[i], tol)) {
+					if (all_pass) ops->Printf("ChFSI: [%d] %6.14e (%6.4e, rho %6.4e)\n", i, eval[i], rn[i], rho[i]);
+					all_pass = 0;
+				}
+			} else { kind[i] = 2; ++nspur; }
+		}
+		if (numIter >= 2 && ngen == ncol) rc = -6;                                    /* every column holds a wanted pair: the block is too small */
+		else if (ngen > 0 && all_pass) converged = 1;
+		if (converged || rc != 0 || numIter >= max_niter) {
+			/* the Ritz vectors back from xc, the genuine pairs first (ascending, as they are), the others behind them: one block
+			 * copy when the genuine pairs already lead, column by column otherwise */
+			for (i = 0; i < ncol && (kind[i] == 1) == (i < ngen); ++i) ;
+			if (i == ncol) {
+				s[0] = 0; e[0] = ncol; s[1] = 0; e[1] = ncol;
+				ops->MultiVecAxpby(1.0, xc, 0.0, evec, s, e, ops);
+				break;
+			}
+			for (pass = 1, j = 0; pass >= 0; --pass)
+				for (i = 0; i < ncol; ++i)
+					if ((kind[i] == 1) == pass) { col_axpby(1.0, xc, i, 0.0, evec, j, ops); ev2[j] = eval[i]; ++j; }
+			memcpy(eval, ev2, (size_t)ncol * sizeof(double));
+			break;
+		}
+		for (pass = 0, end = 0; pass < 3 && end < ncol; ++pass) {                     /* (a dropped column is drawn again) */
+			if (pass > 0) ops->MultiVecSetRandomValue(evec, end, ncol, ops);
+			given = end; end = ncol;
+			ops->MultiVecOrth(evec, given, &end, NULL, ops);
+		}
+		if (end < 1) { rc = -3; break; }
+		ncol = end;
+		if (rayleigh_ritz(A, evec, 0, ncol, eval, w1, H, Q, dws, ops) != 0) { rc = -4; break; }
+		++numIter;
+	}
+
+	ops->MultiVecOrth = orth_before; ops->orth_workspace = orth_ws_before;
+	ops->MultiVecDestroy(&w1, nevMax, ops);
+	ops->MultiVecDestroy(&w2, nevMax, ops);
+	ops->MultiVecDestroy(&acc, nevMax, ops);
+	ops->MultiVecDestroy(&xc, nevMax, ops);
+	free(H); free(kind); free(mu);
+	if (res != NULL) {
+		res->nevConv = ngen; res->numIter = numIter; res->degree = degree; res->spurious = nspur; res->converged = converged;
+		res->seconds = ops->GetWtime() - t0; res->lmin = lmin; res->lmax = lmax; res->edge = edge;
+	}
+	ops->Printf("numIter = %d, inside = %d, spurious = %d\n", numIter, ngen, nspur);
 	ops->Printf("Time is %.3f\n", ops->GetWtime() - t0);
 	return rc;
 }

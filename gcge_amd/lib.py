@@ -432,6 +432,34 @@ def run_chfsi(ops, matA, args, evec, given=0, quiet=True):
     return ev, res, rc
 
 
+class ChFSIBandResult(C.Structure):
+    """GCGE_CHFSI_BAND_RESULT (include/gcge_solver.h)."""
+    _fields_ = [("nevConv", C.c_int), ("numIter", C.c_int), ("degree", C.c_int), ("spurious", C.c_int), ("converged", C.c_int),
+                ("seconds", C.c_double), ("lmin", C.c_double), ("lmax", C.c_double), ("edge", C.c_double)]
+
+
+def run_chfsi_band(ops, matA, args, evec, given=0, quiet=True):
+    """GCGE_RunChFSIBand (every eigenpair inside [-chfsi_band_lo, -chfsi_band_hi]) through the operator table `ops`: `evec` is the
+    caller's block of -nevMax columns whose first `given` columns are start vectors; the pairs inside the interval come back in its
+    first res.nevConv columns, ascending.  Returns (eval of nevMax entries, ChFSIBandResult, return code) — the code is 0 for a
+    completed run (res.converged says whether the test passed), -6 for a block that is too small."""
+    h = host_lib()
+    argc, argv, ev = _solver_args(args, quiet)
+    res = ChFSIBandResult()
+    rc = h.GCGE_RunChFSIBand(matA, argc, C.cast(argv, C.c_void_p), ops, ev.ctypes.data_as(C.c_void_p), evec, int(given),
+                             C.cast(C.byref(res), C.c_void_p))
+    return ev, res, rc
+
+
+def band_coefficients(degree, a, b, lmin, lmax):
+    """GCGE_ChebBandCoefficients: the degree + 1 coefficients of the band filter as a numpy array; ValueError when it refuses."""
+    import numpy as np
+    mu = np.zeros(max(int(degree), 0) + 1)
+    if host_lib().GCGE_ChebBandCoefficients(int(degree), float(a), float(b), float(lmin), float(lmax), mu.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("band_coefficients: lmin < lmax, a < b, [a, b] meeting [lmin, lmax] and degree >= 2 are required")
+    return mu
+
+
 def cheb_stats():
     """gcge_hip_cheb_stats: (Chebyshev steps taken fused, steps taken as product + sweep, calls declined) since the library was loaded."""
     out = (C.c_long * 3)()

@@ -274,6 +274,53 @@ int GCGE_ChebFilter (void *A, void **x, int x0, int m, int degree, double lower,
 int GCGE_RunChFSI (void *A, int argc, char *argv[], struct OPS_ *ops, double *eval, void **evec, int nevGiven,
 		GCGE_CHFSI_RESULT *res);
 
+/* ---- Eigenpairs INSIDE an interval [a, b] (csrc/host/chfsi.c): spectrum slicing with a band-pass Chebyshev filter.  For interior
+ * pairs (the states round a gap, the modes of a frequency band) and indefinite matrices; NOT for the smallest pairs of a definite
+ * matrix, which GCG with a kept hierarchy finds several times faster.  Single rank.  The ends a and b belong in gaps of the
+ * spectrum: an eigenvalue AT an end sits at rho = p(end) and may be counted either way.
+ * GCGE_ChebBandCoefficients: mu[0..degree] of p(t) = sum_j mu_j T_j(t), t = (lambda - c) / e, c = (lmax + lmin) / 2,
+ * e = (lmax - lmin) / 2: with t_a = max(-1, (a - c) / e), t_b = min(1, (b - c) / e), theta = acos t,
+ *     gamma_0 = (theta_a - theta_b) / pi,   gamma_j = 2 (sin j theta_a - sin j theta_b) / (j pi),
+ *     mu_j = gamma_j g_j,   g_j = ((p + 2 - j) cos(j alpha) + sin(j alpha) cot alpha) / (p + 2),   alpha = pi / (p + 2), p = degree
+ * (the Jackson factors: p is then monotone across each end, within [0, 1], about 1/2 at the ends).  -1 unless lmin < lmax, a < b,
+ * [a, b] meets [lmin, lmax] and degree >= 2.
+ * GCGE_ChebBandFilter: x[:, x0..x0+m) <- sum_j mu_j T_j((A - c) / e) x[:, x0..x0+m).  T_1 is the back-end's cheb_step with alpha = 1 / e,
+ * beta = 0, T_{j+1} with alpha = 2 / e, beta = 1, over x and the windows [0, m) of work1 and work2 in a ring of three as in
+ * GCGE_ChebFilter; the iterates are added to the window [0, m) of acc (a fourth block) in PAIRS while both are live — init on
+ * (T_0, T_1), then (T_2, T_3), ... after each odd step, a last single term at an even degree — by MultiVecAxpby(mu_a, T_a,
+ * init ? 0 : 1, acc) and MultiVecAxpby(mu_b, T_b, 1, acc); acc is copied into x at the end and keeps the result.
+ * Returns 0; -1 on bad arguments (those of the coefficients, aliased blocks) with nothing written.
+ * GCGE_RunChFSIBand: every eigenpair with a <= lambda <= b.  Options in harness style: -chfsi_band_lo, -chfsi_band_hi and -nevMax
+ * (the block width) are required; -chfsi_degree (unset: ceil(GCGE_CHFSI_BAND_DEGREE_FACTOR (lmax - lmin) / (b - a)) within
+ * [20, 1000]), -gcge_abs_tol / -gcge_rel_tol, -gcge_max_niter (100), -chfsi_lanczos_steps (10), -chfsi_lower_bound /
+ * -chfsi_upper_bound (taken as they are; what is unset comes from ONE Lanczos run: theta_min - |beta_k|, theta_max + |beta_k|).
+ * The start block is made as in GCGE_RunChFSI.  Per iteration, on all columns (no locking: p >= p(end) inside the interval, so
+ * converged vectors stay): residual norms of the Ritz vectors X, Y = p(A) X, rho_i = x_i^T y_i.  A Ritz pair with theta_i in [a, b]
+ * is GENUINE when rho_i >= edge = min(p(a), p(b)), else spurious (a mixture of outside eigenvectors: its rho is a convex
+ * combination of values of p below the edge value).  The run has converged when at least one pair is genuine and every genuine
+ * pair passes GCGE_RunChFSI's residual test; otherwise Y is orthonormalised, Rayleigh-Ritz, and on.  So a run of numIter iterations
+ * applies numIter + 1 filters.  On return the genuine pairs stand first in evec / eval, ascending, res->nevConv of them, the
+ * other Ritz pairs behind them.  Returns 0 for a completed run (res->converged says whether the test passed; an interval that
+ * holds nothing ends after max_niter with 0 pairs); -1 / -2 as GCGE_RunChFSI with evec untouched; -3, -4 as there; -5 bounds that
+ * are not bounds for the interval; -6 the block is too small: after two iterations every column held a genuine pair
+ * (res->nevConv = the columns), so more pairs may lie inside than the block can hold.
+ * Memory: beside evec the run holds FOUR blocks of nevMax columns (the ring's two work blocks, the accumulator, the copy of the
+ * Ritz vectors), five in all.
+ * GCGE_LanczosBounds: the Lanczos bounds alone, -1 when they fail.  The start column is drawn by MultiVecSetRandomValue from the
+ * random stream as it stands: the two drivers seed it (srand(0)) before they draw, a caller who wants the same bounds on every
+ * call does the same.                                                                                                            */
+#define GCGE_CHFSI_BAND_DEGREE_FACTOR 6.0      /* the fewest matrix products among 2, 3, 4, 6: profiles/chfsi_band/README.md */
+typedef struct GCGE_CHFSI_BAND_RESULT_ {
+	int nevConv, numIter, degree, spurious, converged;      /* genuine pairs; outer iterations; -; inside pairs rejected at the end; the test passed */
+	double seconds, lmin, lmax, edge;                       /* the bounds used; min(p(a), p(b)) */
+} GCGE_CHFSI_BAND_RESULT;
+int GCGE_LanczosBounds (void *A, int steps, double *lmin, double *lmax, struct OPS_ *ops);
+int GCGE_ChebBandCoefficients (int degree, double a, double b, double lmin, double lmax, double *mu);
+int GCGE_ChebBandFilter (void *A, void **x, int x0, int m, int degree, double a, double b, double lmin, double lmax,
+		void **work1, void **work2, void **acc, struct OPS_ *ops);
+int GCGE_RunChFSIBand (void *A, int argc, char *argv[], struct OPS_ *ops, double *eval, void **evec, int nevGiven,
+		GCGE_CHFSI_BAND_RESULT *res);
+
 /* ---- PAS eigensolver (sets ops->EigenSolver; reference src/ops_eig_sol_pas.h) -------------------------------------
  * Rayleigh-Ritz on the coarsest level H = num_levels - 1, then per iteration: prolongate X one level (down to level 0),
  * smooth A X = Lambda B X by BlockAMG from that level down, make X B-orthogonal to range(P_H) and B-orthonormal, solve the
