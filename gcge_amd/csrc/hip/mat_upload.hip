@@ -251,7 +251,7 @@ static GCGE_HIP_MAT* mat_create_local(int nrows, int ncols_local, int nglobal, i
     if (S != nullptr) {
       void* D = gcge_hip_dense_build_rows(nrows, ncols_local, H->rem_rowptr.data(), H->rem_col.data(), H->rem_val.data(),
                                           (const unsigned char*)H->clean.data(), keep_maps);   // (its pad-8 part lists the other rows only)
-      if (D != nullptr) { A->star = S; A->star_rem = D; } else gcge_hip_star_free(S);   // (no blocks among the other rows: the forms below)
+      if (D != nullptr) { A->star = S; A->star_rem = D; } else gcge_hip_star_free(S);   // (the block form switched off, gcge_hip_spmm_dense_mode(-1): the forms below)
       if (D != nullptr && keep_maps) A->star_maps = gcge_hip_star_maps_create(H, A->nnz);
       delete H;
       phase("blocks + listed rows");

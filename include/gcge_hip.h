@@ -497,7 +497,8 @@ long gcge_hip_dense_selfcheck (int nrows, int ncols_local, const int *rowptr, co
  *     ONE star stencil of arm length <= 6 with a diagonal of their own (the finite-difference Laplacian + local potential of
  *     real-space DFT Hamiltonians): those rows leave the CSR arrays and are multiplied by a plane sweep (z-neighbours in
  *     registers, x / y arms from LDS, 2.5 X rows fetched per row, no matrix stream), the other rows keep all their entries
- *     and take the block form.  Needs blocks among the other rows.  Row slabs (one process per GPU) keep the form when
+ *     and take the block form where they hold blocks, a listed remainder otherwise; a matrix whose rows are ALL such stars keeps
+ *     the form with an empty remainder (at least half of the rows must be).  Row slabs (one process per GPU) keep the form when
  *     they are whole grid planes: the planes below / above come from the halo rows, and with a split exchange the planes that
  *     need none are swept while the halo is in flight (reference: app/app_phg.c:307-357).  mode: 0 automatic, -1 never   */
 void gcge_hip_spmm_star_mode (int mode);

@@ -1490,8 +1490,10 @@ def test_star_sweep_spmm_vs_oracle(both, case, form):
     """K1, grid path (spmm_star.hip: rows that are exactly a star stencil leave the CSR arrays and are multiplied by a plane
     sweep — z-neighbours in registers, x / y arms from LDS; the other rows keep every entry and take the block form) against
     the CPU oracle, scipy and the pad-8 kernel on the whole matrix: grids that are no multiple of the 16 x 16 patch, arm
-    lengths 3 and 6 with different coefficients per axis, a diagonal of its own in every row, z ranges split over
-    workgroups, widths from 2 to 130 columns (more than one 8-column pass, a last pass of 2), column offsets.  form 3: the third
+    lengths 3 and 6 with different coefficients per axis, a diagonal of its own in every row, widths from 2 to 130 columns (more
+    than one 8-column pass, a last pass of 2), column offsets.  Every grid here has fewer than 48 planes, so each launch is ONE
+    z range: several ranges, the XCD-aware workgroup order, the other arm lengths, short plane counts and row slabs are pinned on
+    exact data in tests/test_star_rows.py.  form 3: the third
     form of the sweep (default); form 2: the second form on a grid with ONE coefficient set, which nothing but the switch and
     planes too large for the third form select (the box_* cases have per-axis coefficients and take the second form anyway)."""
     from helpers import csr_from_scipy
