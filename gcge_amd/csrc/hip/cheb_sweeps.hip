@@ -16,6 +16,11 @@
 // the width, the column origins and the leading dimensions are even (cg_vec_ok), a scalar-lane kernel (4 row lanes x 64 columns)
 // otherwise; row groups of 4 with all loads issued before the arithmetic; the grid is cg_grid's.
 //
+// Beside it, in the same shape, the sums of the band-pass filter (GCGE_ChebBandFilter):
+//
+//   cheb_accum     acc <- [acc +] mu_a ta + mu_b tb                3 reads + 1 write        slots: 2 Axpby (3 streams each)
+//                                                                  (init: 2 + 1, acc is not read; one term: tb is not read)
+//
 // Also here: the device staging of the fused step's scalars (gcge_hip_cheb_step_mv, mat_product.hip), filled by a one-block kernel
 // so that nothing is copied from the host and nothing is waited for.
 #include <hip/hip_runtime.h>
@@ -76,6 +81,57 @@ __global__ __launch_bounds__(256) void cheb_sweep_s(long nrows, double* __restri
     }
 }
 
+// ---- the sums of a band-pass filter (GCGE_ChebBandFilter): acc <- [acc +] mu_a ta + mu_b tb, two iterates of the recurrence in ONE
+// pass: 3 reads + 1 write (INIT: acc is not read, 2 + 1; !HASB: one term, tb is not read) where the slots take two Axpby of 3 streams
+// each.  s = fma(mu_a, ta, acc) (INIT: mu_a * ta), then acc = fma(mu_b, tb, s) (one term: acc = s): every entry by one thread from
+// its own operands, the same bits in both kernels and on every run.  The launch shape is cheb_sweep's.
+template <int UNR, bool INIT, bool HASB>
+__global__ __launch_bounds__(256) void cheb_accum_v2(long nrows, double* __restrict__ acc, long lda, const double* __restrict__ ta, long ldta,
+    const double* __restrict__ tb, long ldtb, int m, double mu_a, double mu_b, int tpr) {
+  const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
+  const int j = 2 * tx;
+  if (j >= m) return;
+  const long group = (long)rpb * UNR;
+  const long slab = (((nrows + gridDim.x - 1) / gridDim.x) + group - 1) / group * group;
+  const long rend = min(nrows, ((long)blockIdx.x + 1) * slab), step = rpb;
+  const v2d zero = {0.0, 0.0};
+  auto one = [&](long rr, v2d cv, v2d av, v2d bv) {
+    const v2d s = INIT ? v2d{mu_a * av.x, mu_a * av.y} : v2d{fma(mu_a, av.x, cv.x), fma(mu_a, av.y, cv.y)};
+    const v2d r = HASB ? v2d{fma(mu_b, bv.x, s.x), fma(mu_b, bv.y, s.y)} : s;
+    __builtin_nontemporal_store(r, reinterpret_cast<v2d*>(acc + rr * lda + j));
+  };
+  long row = (long)blockIdx.x * slab + ty;
+  for (; row + (UNR - 1) * step < rend; row += step * UNR) {
+    v2d cv[UNR], av[UNR], bv[UNR];
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      const long rr = row + u * step;
+      cv[u] = INIT ? zero : __builtin_nontemporal_load(reinterpret_cast<const v2d*>(acc + rr * lda + j));
+      av[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(ta + rr * ldta + j));
+      bv[u] = HASB ? __builtin_nontemporal_load(reinterpret_cast<const v2d*>(tb + rr * ldtb + j)) : zero;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) one(row + u * step, cv[u], av[u], bv[u]);
+  }
+  for (; row < rend; row += step)
+    one(row, INIT ? zero : *reinterpret_cast<const v2d*>(acc + row * lda + j), *reinterpret_cast<const v2d*>(ta + row * ldta + j),
+        HASB ? *reinterpret_cast<const v2d*>(tb + row * ldtb + j) : zero);
+}
+
+template <bool INIT, bool HASB>
+__global__ __launch_bounds__(256) void cheb_accum_s(long nrows, double* __restrict__ acc, long lda, const double* __restrict__ ta, long ldta,
+    const double* __restrict__ tb, long ldtb, int m, double mu_a, double mu_b, long rows_per_block) {
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const long r0 = (long)blockIdx.x * rows_per_block;
+  const long r1 = min(nrows, r0 + rows_per_block);
+  for (int j = tx; j < m; j += 64)
+    for (long row = r0 + ty; row < r1; row += 4) {
+      const double s = INIT ? mu_a * ta[row * ldta + j] : fma(mu_a, ta[row * ldta + j], acc[row * lda + j]);
+      acc[row * lda + j] = HASB ? fma(mu_b, tb[row * ldtb + j], s) : s;
+    }
+}
+
 // the scalars of one fused step, the same for every column: coef = [al | cb | bp] (3 m doubles), flag = m ones
 __global__ void cheb_scalars_fill(int m, double al, double cb, double bp, double* __restrict__ coef, int* __restrict__ flag) {
   for (int j = threadIdx.x; j < m; j += blockDim.x) { coef[j] = al; coef[m + j] = cb; coef[2 * m + j] = bp; flag[j] = 1; }
@@ -101,6 +157,29 @@ extern "C" int gcge_hip_cheb_sweep(long n, double* out, long ldo, const double* 
   else if (hasz) GCGE_CHEB_LAUNCH(cheb_sweep_s<true>, grid.rpb);
   else GCGE_CHEB_LAUNCH(cheb_sweep_s<false>, grid.rpb);
 #undef GCGE_CHEB_LAUNCH
+  return (int)hipGetLastError();
+}
+
+extern "C" int gcge_hip_cheb_accum(long n, double* acc, long lda, const double* ta, long ldta, double mu_a, const double* tb, long ldtb,
+                                   double mu_b, int m, int init, void* stream) {
+  gcge_hip_apply_pending();
+  if (n < 0 || m < 0 || acc == nullptr || ta == nullptr || acc == ta || acc == tb) return -1;
+  if (n == 0 || m == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const CgGrid grid = cg_grid(n);
+  const bool hasb = tb != nullptr;
+  if (!hasb) { tb = ta; ldtb = ldta; mu_b = 0.0; }      // (never read; keeps the alignment test below on the operands that are)
+  const bool vec = m <= 512 && cg_vec_ok(m, {acc, ta, tb}, {lda, ldta, ldtb});
+#define GCGE_ACCUM_LAUNCH(kernel, last)                                                                                             \
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid.nb), dim3(256), 0, st, n, acc, lda, ta, ldta, tb, ldtb, m, mu_a, mu_b, last)
+#define GCGE_ACCUM_FORMS(V2, S)                                                                                                     \
+  do { if (vec) GCGE_ACCUM_LAUNCH(V2, cg_tpr(m)); else GCGE_ACCUM_LAUNCH(S, grid.rpb); } while (0)
+  if (init && hasb) GCGE_ACCUM_FORMS((cheb_accum_v2<4, true, true>), (cheb_accum_s<true, true>));
+  else if (init) GCGE_ACCUM_FORMS((cheb_accum_v2<4, true, false>), (cheb_accum_s<true, false>));
+  else if (hasb) GCGE_ACCUM_FORMS((cheb_accum_v2<4, false, true>), (cheb_accum_s<false, true>));
+  else GCGE_ACCUM_FORMS((cheb_accum_v2<4, false, false>), (cheb_accum_s<false, false>));
+#undef GCGE_ACCUM_FORMS
+#undef GCGE_ACCUM_LAUNCH
   return (int)hipGetLastError();
 }
 

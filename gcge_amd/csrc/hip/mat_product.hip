@@ -5,7 +5,8 @@
 //   HIP_MatDotMultiVec, HIP_MatTransDotMultiVec, gcge_hip_spmm_dot*   the product, alone or with the column sums x.y / y.y
 //   gcge_hip_cg_*                        the passes of the fused block CG on a pattern matrix (product formed twice, never stored)
 //   gcge_hip_cheb_step_mv                one step of a Chebyshev filter: the second CG pass with prescribed scalars, or product + sweep
-//   HIP_Amg*, HIP_ResidualSq             the fused sweeps of a V-cycle and the residual norms of Ritz pairs (GCGE_BACKEND)
+//   gcge_hip_cheb_accum_mv               the sums of a band-pass filter on blocks (no matrix: it sits beside the step it follows)
+//   HIP_Amg*, HIP_ResidualSq       the fused sweeps of a V-cycle and the residual norms of Ritz pairs (GCGE_BACKEND)
 //   gcge_hip_profile_*                   HIP events around every K1 launch
 // Runtime state, staging, pool and the multivector slots live in app_hip.hip (shared names: gcge_hip_internal.h); the handle itself
 // is built by mat_upload.hip.  These wrappers run several times per CG iteration on levels bound by launch latency: helpers are
@@ -592,6 +593,32 @@ static int HIP_ChebStep(void* mat, void** y, int y0, void** z, int z0, void** ou
   return gcge_hip_cheb_step_mv(mat, y, y0, z, z0, out, o0, m, alpha, c, beta) == 0 ? 1 : 0;
 }
 
+// ---- the sums of a band-pass filter (GCGE_ChebBandFilter, csrc/host/chfsi.c; GCGE_BACKEND.cheb_accum) ----------------------------
+//   acc[:, a0..a0+m) = [acc[:, a0..) +] mu_a ta[:, ta0..) + mu_b tb[:, tb0..)         acc, ta, tb: three different blocks
+// one call of gcge_hip_cheb_accum (cheb_sweeps.hip) on g_stream: 4 block streams for two terms where two MultiVecAxpby take 6.
+// tb == NULL: one term; init: acc is not read.
+static long g_cheb_accum_stats[3] = {0, 0, 0};      // two-term calls, one-term calls, declined
+extern "C" void gcge_hip_cheb_accum_stats(long out[3]) { for (int i = 0; i < 3; ++i) out[i] = g_cheb_accum_stats[i]; }
+extern "C" int gcge_hip_cheb_accum_mv(void** acc, int a0, void** ta, int ta0, double mu_a, void** tb, int tb0, double mu_b, int m, int init) {
+  GcgeHipMV *vc = (GcgeHipMV*)acc, *va = (GcgeHipMV*)ta, *vb = (GcgeHipMV*)tb;
+  const bool hasb = vb != nullptr;
+  bool ok = vc != nullptr && va != nullptr && m > 0 && vc != va && (!hasb || (vb != vc && vb != va));
+  ok = ok && a0 >= 0 && a0 + m <= vc->ncols && ta0 >= 0 && ta0 + m <= va->ncols && (!hasb || (tb0 >= 0 && tb0 + m <= vb->ncols));
+  ok = ok && vc->nrows == va->nrows && (!hasb || vc->nrows == vb->nrows);
+  ok = ok && real_perm(va->perm) == real_perm(vc->perm) && (!hasb || real_perm(vb->perm) == real_perm(vc->perm));
+  if (!ok) { ++g_cheb_accum_stats[2]; return -1; }
+  gcge_hip_enter();
+  SlotTimer tm_("Chebyshev sum", m);
+  GCGE_REQUIRE(gcge_hip_cheb_accum(vc->nrows, vc->d + a0, vc->ld, va->d + ta0, va->ld, mu_a, hasb ? vb->d + tb0 : nullptr, hasb ? vb->ld : 0, mu_b, m,
+                                   init, g_stream) == 0, "Chebyshev sum: sweep");
+  ++g_cheb_accum_stats[hasb ? 0 : 1];
+  return 0;
+}
+static int HIP_ChebAccum(void** acc, int a0, void** ta, int ta0, double mu_a, void** tb, int tb0, double mu_b, int m, int init, struct OPS_* ops) {
+  (void)ops;
+  return gcge_hip_cheb_accum_mv(acc, a0, ta, ta0, mu_a, tb, tb0, mu_b, m, init) == 0 ? 1 : 0;
+}
+
 // ---- the start sweep (kernel MODES 5 / 6): r[:, rc0:rc0+m) = b[:, bc0:bc0+m) - A x[:, xc0:xc0+m), pnew[:, rc0:rc0+m) = r, and the
 // column sums of r^2 over the LOCAL rows into dd (6 m doubles: 3 m of scratch behind the sums when the product is split); fetches the
 // halo rows of x.  vb == NULL: b_j = d_scale[j] x_j is never formed (MODE 6).  Behind gcge_hip_cg_start_mv, gcge_hip_cg_start_scaled_mv
@@ -874,4 +901,5 @@ extern "C" void gcge_hip_product_slots(struct OPS_* ops, GCGE_BACKEND* be) {
   be->amg_prolong_add = HIP_AmgProlongAdd;
   be->amg_form_rhs    = HIP_AmgFormRhs;           // b = x diag(scale) in one sweep
   be->cheb_step       = HIP_ChebStep;             // one step of a Chebyshev filter: fused on pattern matrices, product + one sweep otherwise
+  be->cheb_accum      = HIP_ChebAccum;            // two iterates of a band-pass filter added to its sum in one sweep
 }

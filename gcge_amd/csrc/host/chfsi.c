@@ -12,7 +12,7 @@
  *
  * The filter is the three-term recurrence  Y_{j+1} = alpha_j (A - c I) Y_j - beta_j Y_{j-1}.  One step goes through the back-end's
  * cheb_step (GCGE_BACKEND, gcge_ops.h) where the table offers it and it accepts, else through the slots: MatDotMultiVec into the
- * output block and two MultiVecAxpby.
+ * output block and two MultiVecAxpby.  The band filter's sums go the same way: the back-end's cheb_accum, else two MultiVecAxpby.
  */
 #include <float.h>
 #include <math.h>
@@ -290,11 +290,13 @@ static double band_poly(int degree, const double *mu, double c, double e, double
 	return p;
 }
 
-/* acc[:, a0..) = [acc +] mu_a ta[:, ta0..) + mu_b tb[:, tb0..)   (tb == NULL: one term; init: acc is not read) */
+/* acc[:, a0..) = [acc +] mu_a ta[:, ta0..) + mu_b tb[:, tb0..)   (tb == NULL: one term; init: acc is not read): the back-end's
+ * cheb_accum (one sweep) where the table offers it and it accepts, else two MultiVecAxpby */
 static void cheb_accum(void **acc, int a0, void **ta, int ta0, double mu_a, void **tb, int tb0, double mu_b, int m, int init,
-		struct OPS_ *ops)
+		const GCGE_BACKEND *be, struct OPS_ *ops)
 {
 	int s[2], e[2];
+	if (be->cheb_accum != NULL && be->cheb_accum(acc, a0, ta, ta0, mu_a, tb, tb0, mu_b, m, init, ops)) return;
 	s[0] = ta0; e[0] = ta0 + m; s[1] = a0; e[1] = a0 + m;
 	ops->MultiVecAxpby(mu_a, ta, init ? 0.0 : 1.0, acc, s, e, ops);
 	if (tb != NULL) {
@@ -314,12 +316,12 @@ static void cheb_band_filter(void *A, void **x, int x0, int m, int degree, const
 	blk[0] = x; col[0] = x0; blk[1] = work1; col[1] = w0; blk[2] = work2; col[2] = w0;
 	/* step i reads block (i - 1) % 3 (and (i - 2) % 3) and writes T_i into block i % 3 */
 	cheb_step(A, blk[0], col[0], NULL, 0, blk[1], col[1], m, 1.0 / ee, c, 0.0, &be, ops);
-	cheb_accum(acc, w0, blk[0], col[0], mu[0], blk[1], col[1], mu[1], m, 1, ops);
+	cheb_accum(acc, w0, blk[0], col[0], mu[0], blk[1], col[1], mu[1], m, 1, &be, ops);
 	for (i = 2; i <= degree; ++i) {
 		const int iy = (i - 1) % 3, iz = (i - 2) % 3, io = i % 3;
 		cheb_step(A, blk[iy], col[iy], blk[iz], col[iz], blk[io], col[io], m, 2.0 / ee, c, 1.0, &be, ops);
-		if (i & 1) cheb_accum(acc, w0, blk[iy], col[iy], mu[i - 1], blk[io], col[io], mu[i], m, 0, ops);
-		else if (i == degree) cheb_accum(acc, w0, blk[io], col[io], mu[i], NULL, 0, 0.0, m, 0, ops);
+		if (i & 1) cheb_accum(acc, w0, blk[iy], col[iy], mu[i - 1], blk[io], col[io], mu[i], m, 0, &be, ops);
+		else if (i == degree) cheb_accum(acc, w0, blk[io], col[io], mu[i], NULL, 0, 0.0, m, 0, &be, ops);
 	}
 	s[0] = w0; e[0] = w0 + m; s[1] = x0; e[1] = x0 + m;
 	ops->MultiVecAxpby(1.0, acc, 0.0, x, s, e, ops);

@@ -70,7 +70,8 @@ void **GCGE_GetRealignedRhs(int *b0) { if (b0 != NULL) *b0 = g_realigned_b0; ret
  *   GCGE_NO_PANEL_NORMS      panel_norms_sq                                 (column norms by a sweep of their own)
  *   GCGE_NO_START_IN_PLACE   start_in_place                                 (the W start vectors and b moved before the solve)
  *   GCGE_NO_PCG_SWEEPS       pcg_step, pcg_dots, pcg_direction, pcg_shift   (GCGE_PCGSolve's sweeps through the slots)
- *   GCGE_NO_CHEB_STEP        cheb_step                                      (GCGE_ChebFilter's steps through the slots) */
+ *   GCGE_NO_CHEB_STEP        cheb_step                                      (GCGE_ChebFilter's steps through the slots)
+ *   GCGE_NO_CHEB_ACCUM       cheb_accum                                     (GCGE_ChebBandFilter's sums by two MultiVecAxpby) */
 static GCGE_BACKEND g_backend; static void *g_backend_matvec = NULL, *g_backend_lincomb = NULL;
 void GCGE_SetBackend(struct OPS_ *ops, const GCGE_BACKEND *backend)
 {
@@ -97,6 +98,7 @@ GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
 	if (getenv("GCGE_NO_START_IN_PLACE") != NULL) b.start_in_place = 0;
 	if (getenv("GCGE_NO_PCG_SWEEPS") != NULL) { b.pcg_step = NULL; b.pcg_dots = NULL; b.pcg_direction = NULL; b.pcg_shift = NULL; }
 	if (getenv("GCGE_NO_CHEB_STEP") != NULL) b.cheb_step = NULL;
+	if (getenv("GCGE_NO_CHEB_ACCUM") != NULL) b.cheb_accum = NULL;
 	return b;
 }
 

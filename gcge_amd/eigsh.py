@@ -33,8 +33,46 @@ def _device_of(*things):
     return torch.cuda.current_device()
 
 
-def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None,
-          eigenvector_grad=False, method="gcg", degree=20, upper_bound=None):
+def _check_method(k, M, nev_max, block_size, amg_levels, amg, method, degree, lower_bound, interval, eigenvector_grad=False):
+    """the ValueErrors of eigsh that depend on method, degree, interval and k alone: raised before anything touches the device"""
+    import math
+    if method not in ("gcg", "chebyshev"):
+        raise ValueError("eigsh: method is \"gcg\" or \"chebyshev\"")
+    chebyshev = method == "chebyshev"
+    if interval is not None and not chebyshev:
+        raise ValueError("eigsh: interval requires method=\"chebyshev\" (the band-pass filter is the only solver for interior pairs)")
+    if chebyshev and (M is not None or amg is not None or amg_levels or block_size is not None):
+        raise ValueError("eigsh: method=\"chebyshev\" is for the standard problem and solves no linear system: M, amg, amg_levels and "
+                         "block_size do not go with it")
+    if interval is None:
+        if k is None:
+            raise ValueError("eigsh: k is required (k=None goes with interval=(a, b) only)")
+        if lower_bound is not None:
+            raise ValueError("eigsh: lower_bound goes with interval only (the low-pass filter takes its lower end from the Ritz values)")
+        if chebyshev and degree is not None and int(degree) < 1:
+            raise ValueError("eigsh: degree >= 1 is required")
+        return
+    if k is not None:
+        raise ValueError("eigsh: interval requires k=None (every pair inside the interval is returned; nev_max is the block's width)")
+    if nev_max is None:
+        raise ValueError("eigsh: interval requires nev_max, the width of the filtered block (more than the eigenvalues inside)")
+    if int(nev_max) < 1:
+        raise ValueError("eigsh: nev_max >= 1 is required")
+    try:
+        a, b = (float(v) for v in interval)
+    except (TypeError, ValueError):
+        raise ValueError("eigsh: interval is a pair (a, b) of numbers") from None
+    if not (math.isfinite(a) and math.isfinite(b) and a < b):
+        raise ValueError("eigsh: interval=(a, b) requires a < b, both finite")
+    if degree is not None and int(degree) < 2:
+        raise ValueError("eigsh: interval requires degree >= 2 (or None: the driver's choice)")
+    if eigenvector_grad:
+        raise ValueError("eigsh: eigenvector_grad does not go with interval: the pairs below the interval are not in the computed space, "
+                         "so the deflated systems (A - lambda_c) y = g would be indefinite")
+
+
+def eigsh(A, k=None, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None,
+          eigenvector_grad=False, method="gcg", degree=None, upper_bound=None, lower_bound=None, interval=None):
     """The k smallest eigenvalues and their eigenvectors of the symmetric problem A x = lambda M x (M=None: the identity; M positive
     definite) by GCG on the GPU.  The smallest eigenvalues are the only mode.
 
@@ -76,6 +114,28 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
                except NoConvergence as e: r = e.result
            Measured (profiles/chfsi/README.md: Lap3D 128^3, k = 50) it is 3.6 times SLOWER than GCG with a kept hierarchy, cold and
            warm: use it for matrices GCG cannot take — an indefinite A, or no hierarchy that can be built or kept — not instead of it.
+           degree=None means 20 here.
+    interval:  (a, b), a < b, both finite, with method="chebyshev", k=None and nev_max given: EVERY eigenpair with a <= lambda <= b
+           (GCGE_RunChFSIBand) — the states round a gap, the modes of a frequency band, an indefinite A — in place of the k smallest.
+           Per outer iteration all nev_max columns are filtered by the Jackson-damped Chebyshev expansion of the interval's indicator
+           (about 1 inside, about 0 outside, 1/2 at the ends), orthonormalised, and a Rayleigh-Ritz step follows; Ritz values inside
+           the interval that are mixtures of outside eigenvectors are told from genuine pairs by x^T p(A) x.  nev_max is the width
+           of the filtered block and must EXCEED the number of eigenvalues inside (twice it is a good choice); `degree` (>= 2) is the
+           expansion's, None: the driver's 6 (lmax - lmin) / (b - a) within [20, 1000]; `lower_bound`, `upper_bound`: bounds of the
+           whole spectrum, each taken as it is, what is left out comes from one Lanczos run (given bounds that hug the spectrum need
+           fewer iterations than Lanczos's safeguarded ones).  Put a and b in GAPS of the spectrum: an eigenvalue at an end may be
+           counted either way, and one close to an end converges slowly.  Do NOT use this for the smallest pairs of a definite
+           matrix: GCG with a kept hierarchy finds those several times faster.
+           The result holds the j genuine pairs inside, ascending: eigenvalues (j,), eigenvectors (n, j), residual_norms (j,),
+           converged = j; `iterations` outer iterations (iterations + 1 filters were applied).  X0, tol, maxiter, gcge_args, backend
+           and the forms of A are as for the other methods; a warm start from the eigenvectors of a nearby operator is the loop
+               r = eigsh(m, interval=(a, b), nev_max=N, X0=r.eigenvectors, method="chebyshev", backend=hip)
+           NoConvergence, with what the run reached in .result: the run ended (maxiter) before every genuine pair passed tol, or
+           every column of the block held a wanted pair — more pairs may lie inside than the block can hold: raise nev_max.
+           ValueError: another method, k given, no nev_max, a >= b or an end that is not finite, degree < 2, M, amg, amg_levels or
+           block_size, eigenvector_grad.  The eigenvalues take gradients as below (the sum over the returned pairs, however many);
+           eigenvector_grad is refused: its deflated systems (A - lambda_c) y = g would be INDEFINITE, because the pairs below the
+           interval are not in the computed space — call gcge_amd.eigenvector_grads on a space that holds them.
 
     Gradients: when A (or M) is given as a sparse_csr tensor or a (crow, col, val) triple whose values require grad, and grad mode is
     on, `eigenvalues` comes back attached to the graph and backward gives d loss / d values on the stored entries
@@ -96,11 +156,13 @@ def eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_siz
     or M, or without a tensor that requires grad — a loop over handles calls gcge_amd.eigenvector_grads itself.
 
     Returns EigshResult(eigenvalues (k,), eigenvectors (n, k), converged, iterations, seconds, residual_norms (k,)), tensors float64
-    on the device.  Raises NoConvergence, carrying the partial result, when fewer than k pairs converged."""
+    on the device (with interval: the j pairs inside in place of k).  Raises NoConvergence, carrying the partial result, when fewer
+    than k pairs converged (with interval: see there)."""
+    _check_method(k, M, nev_max, block_size, amg_levels, amg, method, degree, lower_bound, interval, eigenvector_grad)
     import torch
     dA, dM = _differentiable(A), _differentiable(M)
     kw = dict(X0=X0, tol=tol, maxiter=maxiter, nev_max=nev_max, block_size=block_size, amg_levels=amg_levels, gcge_args=gcge_args, amg=amg,
-              method=method, degree=degree, upper_bound=upper_bound)
+              method=method, degree=degree, upper_bound=upper_bound, lower_bound=lower_bound, interval=interval)
     if eigenvector_grad and (_is_handle(A) or _is_handle(M) or (dA is None and dM is None)):
         raise ValueError("eigsh: eigenvector_grad needs A (or M) given as tensors whose values require grad, with grad mode on, and no "
                          "matrix handle; a loop that keeps handles calls gcge_amd.eigenvector_grads itself")
@@ -160,26 +222,24 @@ def _backend_for(backend, *things):
 
 
 def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_size=None, amg_levels=0, backend=None, gcge_args=(), amg=None,
-           _keep=None, method="gcg", degree=20, upper_bound=None):
+           _keep=None, method="gcg", degree=None, upper_bound=None, lower_bound=None, interval=None):
     """eigsh on detached inputs: see there.  _keep: a dict that, when all k pairs converged, takes the handles "A" and "M" of the solve
     and the list "made" of those created here, which are then NOT freed (the caller owns them)"""
     import numpy as np
     import torch
-    from .lib import host_lib, run_chfsi, run_gcg
+    from .lib import host_lib, run_chfsi, run_chfsi_band, run_gcg
 
-    if method not in ("gcg", "chebyshev"):
-        raise ValueError("eigsh: method is \"gcg\" or \"chebyshev\"")
-    chebyshev = method == "chebyshev"
-    if chebyshev and (M is not None or amg is not None or amg_levels or block_size is not None):
-        raise ValueError("eigsh: method=\"chebyshev\" is for the standard problem and solves no linear system: M, amg, amg_levels and "
-                         "block_size do not go with it")
-    if chebyshev and int(degree) < 1:
-        raise ValueError("eigsh: degree >= 1 is required")
-    k = int(k)
-    nev_max = 2 * k if nev_max is None else int(nev_max)
+    _check_method(k, M, nev_max, block_size, amg_levels, amg, method, degree, lower_bound, interval)
+    chebyshev, band = method == "chebyshev", interval is not None
+    if band:
+        k = 0                          # (the count comes out of the run)
+        nev_max = int(nev_max)
+    else:
+        k = int(k)
+        nev_max = 2 * k if nev_max is None else int(nev_max)
+        if k < 1 or nev_max < k:
+            raise ValueError("eigsh: 1 <= k <= nev_max is required")
     amg_levels = int(amg_levels)
-    if k < 1 or nev_max < k:
-        raise ValueError("eigsh: 1 <= k <= nev_max is required")
     if amg_levels == 1 or amg_levels < 0:
         raise ValueError("eigsh: amg_levels is 0 (no hierarchy) or at least 2")
     if amg is not None:
@@ -197,7 +257,7 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
             block_size = amg.block_size
     backend = _backend_for(backend, A, M, X0)
     gcge_args = [str(a) for a in gcge_args]
-    own = [("-nevConv", k), ("-nevMax", nev_max), ("-gcge_rel_tol", repr(float(tol)))]
+    own = ([] if band else [("-nevConv", k)]) + [("-nevMax", nev_max), ("-gcge_rel_tol", repr(float(tol)))]
     if maxiter is not None:
         own.append(("-gcge_max_niter", int(maxiter)))
     if block_size is not None:
@@ -205,7 +265,12 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
     if amg_levels > 0:
         own.append(("-gcge_amg_levels", amg_levels))
     if chebyshev:
-        own.append(("-chfsi_degree", int(degree)))
+        if band:
+            own += [("-chfsi_band_lo", repr(float(interval[0]))), ("-chfsi_band_hi", repr(float(interval[1])))]
+        if degree is not None or not band:                 # (the band's None is the driver's own choice)
+            own.append(("-chfsi_degree", 20 if degree is None else int(degree)))
+        if lower_bound is not None:
+            own.append(("-chfsi_lower_bound", repr(float(lower_bound))))
         if upper_bound is not None:
             own.append(("-chfsi_upper_bound", repr(float(upper_bound))))
     args = []
@@ -238,13 +303,16 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
             shape = tuple(X0.shape) if hasattr(X0, "shape") else tuple(X0.__cuda_array_interface__["shape"])
             if len(shape) != 2 or shape[1] > nev_max:
                 raise ValueError("eigsh: X0 is an (n, j) block with j <= nev_max")
+        band_rc = 0
         if chebyshev:
             evec = backend.ops.mv_create(nev_max, mA)
             if X0 is not None:
                 backend.mv_from_torch(mA, X0, mv=evec, c0=0)
-            ev, res, rc = run_chfsi(backend.ops_handle, mA, args, evec, given=int(shape[1]) if X0 is not None else 0)
-            if rc != 0:
-                raise RuntimeError("GCGE_RunChFSI rc=%d" % rc)
+            ev, res, rc = (run_chfsi_band if band else run_chfsi)(backend.ops_handle, mA, args, evec, given=int(shape[1]) if X0 is not None else 0)
+            if band and rc in (0, -6):                     # (-6: every column holds a wanted pair; the columns are what the run reached)
+                band_rc, k = rc, int(res.nevConv)
+            elif rc != 0:
+                raise RuntimeError("%s rc=%d" % ("GCGE_RunChFSIBand" if band else "GCGE_RunChFSI", rc))
         elif X0 is not None:
             evec = backend.ops.mv_create(nev_max, mA)
             backend.mv_from_torch(mA, X0, mv=evec, c0=0)
@@ -255,7 +323,7 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
         lam = np.ascontiguousarray(ev[:k], dtype=np.float64)
         rn = np.zeros(k)
         rc = h.GCGE_ResidualNorms(mA, mB, evec, 0, k, lam.ctypes.data_as(C.POINTER(C.c_double)), rn.ctypes.data_as(C.POINTER(C.c_double)),
-                                  backend.ops_handle)
+                                  backend.ops_handle) if k > 0 else 0
         if rc != 0:
             raise RuntimeError("GCGE_ResidualNorms rc=%d" % rc)
         V = backend.mv_to_torch(evec, 0, k)
@@ -264,11 +332,19 @@ def _eigsh(A, k, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, block_si
     finally:
         if evec is not None and evec.value:
             backend.ops.mv_destroy(evec, nev_max)
-        if _keep is not None and result is not None and result.converged >= k:
+        if _keep is not None and result is not None and not band and result.converged >= k:
             _keep.update(A=mA, M=mB, made=list(made))
         else:
             for m in made:
                 backend.free_matrix(m)
+    if band:
+        if band_rc == -6:
+            raise NoConvergence("eigsh: all %d columns hold eigenpairs inside [%r, %r] after %d iterations: more may lie inside than the block "
+                                "can hold; raise nev_max" % (result.converged, float(interval[0]), float(interval[1]), result.iterations), result)
+        if not res.converged:
+            raise NoConvergence("eigsh: the %d pairs found inside [%r, %r] did not all converge in %d iterations"
+                                % (result.converged, float(interval[0]), float(interval[1]), result.iterations), result)
+        return result
     if result.converged < k:
         raise NoConvergence("eigsh: %d of %d pairs converged in %d iterations" % (result.converged, k, result.iterations), result)
     return result

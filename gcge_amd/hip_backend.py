@@ -256,6 +256,32 @@ class HipBackendImpl:
                 if w is not None:
                     self.ops.mv_destroy(w, m)
 
+    def chebyshev_band_filter(self, A, X, degree, a, b, lmin, lmax):
+        """p(A) X for the matrix handle A and an (n, m) device tensor X, as a new (n, m) float64 tensor (GCGE_ChebBandFilter): p is the
+        Jackson-damped Chebyshev expansion of the given degree of the indicator of [a, b] over the bounds [lmin, lmax] of A's spectrum
+        — about 1 inside the interval, about 0 outside, 1/2 at its ends (lib.band_coefficients gives its coefficients).  X goes in
+        through mv_from_torch and out through mv_to_torch; the two work blocks and the accumulator are created and freed here.
+        Every step is the back-end's cheb_step, every sum of a pair of iterates its cheb_accum (one sweep; lib.cheb_stats and
+        lib.cheb_accum_stats count them).  ValueError: degree < 2, a >= b, lmin >= lmax, an interval that misses the bounds."""
+        degree, a, b, lmin, lmax = int(degree), float(a), float(b), float(lmin), float(lmax)
+        if degree < 2 or not a < b or not lmin < lmax or not a <= lmax or not b >= lmin:
+            raise ValueError("chebyshev_band_filter: degree >= 2, a < b, lmin < lmax and an interval [a, b] that meets [lmin, lmax] are required")
+        mx = self.mv_from_torch(A, X)
+        m = self.g.gcge_hip_mv_ncols(mx)
+        w1 = w2 = acc = None
+        try:
+            if m == 0:
+                return self.mv_to_torch(mx, 0, 0)
+            w1, w2, acc = self.ops.mv_create(m, A), self.ops.mv_create(m, A), self.ops.mv_create(m, A)
+            rc = self.h.GCGE_ChebBandFilter(A, mx, 0, m, degree, a, b, lmin, lmax, w1, w2, acc, self.ops_handle)
+            if rc != 0:
+                raise RuntimeError("GCGE_ChebBandFilter rc=%d" % rc)
+            return self.mv_to_torch(mx, 0, m)
+        finally:
+            for w in (w1, w2, acc, mx):
+                if w is not None:
+                    self.ops.mv_destroy(w, m)
+
     def sample_outer(self, crow, col, U, V, weights=None, alpha=1.0):
         """The rank-k product U diag(weights) V^T on the stored entries of a CSR pattern (gcge_hip_csr_sample_outer): an (nnz,)
         float64 device tensor with out[e] = alpha sum_c weights[c] U[i, c] V[col[e], c] for every entry e of row i, in the entry order

@@ -467,6 +467,14 @@ def cheb_stats():
     return tuple(out)
 
 
+def cheb_accum_stats():
+    """gcge_hip_cheb_accum_stats: (two-term sums of a band filter taken in one sweep, one-term sums, calls declined) since the library
+    was loaded."""
+    out = (C.c_long * 3)()
+    hip_lib().gcge_hip_cheb_accum_stats(out)
+    return tuple(out)
+
+
 def run_pas(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False):
     """GCGE_RunPAS through the operator table `ops`: PAS (the multigrid eigensolver over the back-end's hierarchy), then GCG
     warm-started from PAS's converged vectors unless args hold -gcge_pas_only 1.  Returns (eval, pas_result, gcg_result)

@@ -688,6 +688,23 @@ int gcge_hip_cheb_sweep (long n, double *out, long ldo, const double *y, long ld
 int gcge_hip_cheb_step_mv (void *mat, void **y, int y0, void **z, int z0, void **out, int o0, int m,
 		double alpha, double c, double beta);
 void gcge_hip_cheb_stats (long out[3]);
+/*     The sums of a band-pass filter (GCGE_ChebBandFilter, gcge_solver.h; csrc/hip/cheb_sweeps.hip) on raw device pointers, in ONE pass:
+ *         acc[r, j] <- [acc[r, j] +] mu_a ta[r, j] + mu_b tb[r, j]        0 <= r < n, 0 <= j < m
+ *     row-major blocks with their leading dimensions, acc apart from ta and tb: 3 reads + 1 write.  init != 0: acc is NOT read and
+ *     may hold anything (2 reads + 1 write).  tb == NULL: one term, mu_b is ignored and nothing of tb is read.  Rounded as
+ *     s = fma(mu_a, ta, acc) (init: mu_a ta), then fma(mu_b, tb, s) (one term: s): the same bits on every run and in both kernels
+ *     (16-byte lanes when m, the origins and the leading dimensions are even, scalar lanes otherwise).  Nothing is waited for.
+ *     Return 0 (also for n == 0 or m == 0), the launch's error, or -1 with nothing written on bad arguments (n < 0, m < 0, NULL acc
+ *     or ta, acc == ta or acc == tb).                                                                                              */
+int gcge_hip_cheb_accum (long n, double *acc, long lda, const double *ta, long ldta, double mu_a,
+		const double *tb, long ldtb, double mu_b, int m, int init, void *stream);
+/*     The same on blocks of this back-end (GCGE_BACKEND.cheb_accum of OPS_HIP_Set):  acc[:, a0..a0+m) = [acc[:, a0..) +]
+ *     mu_a ta[:, ta0..) + mu_b tb[:, tb0..), acc, ta and tb three different blocks (tb == NULL: one term), on the back-end's stream;
+ *     nothing is waited for.  Returns 0; -1 with nothing written for aliased blocks, column ranges outside a block, blocks of
+ *     different row counts or row orders, m <= 0.  gcge_hip_cheb_accum_stats: two-term calls, one-term calls, calls that returned
+ *     -1, since the library was loaded.                                                                                            */
+int gcge_hip_cheb_accum_mv (void **acc, int a0, void **ta, int ta0, double mu_a, void **tb, int tb0, double mu_b, int m, int init);
+void gcge_hip_cheb_accum_stats (long out[3]);
 
 #ifdef __cplusplus
 }

@@ -265,7 +265,13 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *                 out[:, o0..) = alpha (A y[:, y0..) - c y[:, y0..)) - beta z[:, z0..), out, y and z three different blocks; beta == 0:
  *                 z is not read and may be NULL (a filter's first step).  Nothing is waited for.  The slots take MatDotMultiVec into
  *                 out and two MultiVecAxpby: 2 + 3 + 3 block streams; the HIP back-end 3 on matrices whose product it can rebuild
- *                 inside the sweep, 6 otherwise.  1 taken, 0 declines with nothing touched. */
+ *                 inside the sweep, 6 otherwise.  1 taken, 0 declines with nothing touched.
+ *   cheb_accum    the sums of GCGE_ChebBandFilter (gcge_solver.h) on a window of m columns, in one sweep:
+ *                 acc[:, a0..) = [acc[:, a0..) +] mu_a ta[:, ta0..) + mu_b tb[:, tb0..), acc, ta and tb three different blocks;
+ *                 init != 0: acc is not read and may hold anything; tb == NULL: one term, mu_b is ignored.  Nothing is waited for.
+ *                 The slots take two MultiVecAxpby (one for one term): 3 + 3 block streams; the HIP back-end 4 (init: 3).  Rounded
+ *                 as s = fma(mu_a, ta, acc) (init: mu_a ta), then fma(mu_b, tb, s): not the bits of the two Axpby.  1 taken, 0
+ *                 declines with nothing touched. */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -287,6 +293,8 @@ typedef int    (*GCGE_PCG_SHIFT_FN) (void **p, int p0, void **q, int q0, void **
 		double *pw, struct OPS_ *ops);
 typedef int    (*GCGE_CHEB_STEP_FN) (void *A, void **y, int y0, void **z, int z0, void **out, int o0, int m, double alpha, double c,
 		double beta, struct OPS_ *ops);
+typedef int    (*GCGE_CHEB_ACCUM_FN) (void **acc, int a0, void **ta, int ta0, double mu_a, void **tb, int tb0, double mu_b, int m,
+		int init, struct OPS_ *ops);
 typedef struct GCGE_BACKEND_ {
 	GCGE_RESIDUAL_FN residual_sq;
 	int inplace_lincomb_cols;
@@ -309,6 +317,7 @@ typedef struct GCGE_BACKEND_ {
 	int  (*amg_smoother_niter) (struct OPS_ *ops);
 	GCGE_PCG_SHIFT_FN pcg_shift;
 	GCGE_CHEB_STEP_FN cheb_step;
+	GCGE_CHEB_ACCUM_FN cheb_accum;
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

@@ -287,8 +287,10 @@ int GCGE_RunChFSI (void *A, int argc, char *argv[], struct OPS_ *ops, double *ev
  * GCGE_ChebBandFilter: x[:, x0..x0+m) <- sum_j mu_j T_j((A - c) / e) x[:, x0..x0+m).  T_1 is the back-end's cheb_step with alpha = 1 / e,
  * beta = 0, T_{j+1} with alpha = 2 / e, beta = 1, over x and the windows [0, m) of work1 and work2 in a ring of three as in
  * GCGE_ChebFilter; the iterates are added to the window [0, m) of acc (a fourth block) in PAIRS while both are live — init on
- * (T_0, T_1), then (T_2, T_3), ... after each odd step, a last single term at an even degree — by MultiVecAxpby(mu_a, T_a,
- * init ? 0 : 1, acc) and MultiVecAxpby(mu_b, T_b, 1, acc); acc is copied into x at the end and keeps the result.
+ * (T_0, T_1), then (T_2, T_3), ... after each odd step, a last single term at an even degree — by the back-end's cheb_accum
+ * (GCGE_BACKEND, gcge_ops.h: one sweep, 4 block streams for a pair) where it is offered and accepts, else by MultiVecAxpby(mu_a, T_a,
+ * init ? 0 : 1, acc) and MultiVecAxpby(mu_b, T_b, 1, acc) (6 streams; over a table without the slot the bits are those of these two
+ * calls); acc is copied into x at the end and keeps the result.
  * Returns 0; -1 on bad arguments (those of the coefficients, aliased blocks) with nothing written.
  * GCGE_RunChFSIBand: every eigenpair with a <= lambda <= b.  Options in harness style: -chfsi_band_lo, -chfsi_band_hi and -nevMax
  * (the block width) are required; -chfsi_degree (unset: ceil(GCGE_CHFSI_BAND_DEGREE_FACTOR (lmax - lmin) / (b - a)) within
