@@ -8,10 +8,12 @@ from .lib import (CSR, RunResult, Timing, host_lib, hip_lib, build_libs,
                   PASResult, run_pas)
 from .eigsh import EigshResult, NoConvergence, eigsh
 from .solve import SolveResult, solve
+from .kpm import CountResult, count_from_moments, eigenvalue_count, spectral_density
 from . import grad
 from .grad import eigenvalue_grads, eigenvector_grads, solve_grads
 
 __all__ = ["CSR", "RunResult", "Timing", "host_lib", "hip_lib", "build_libs",
            "make_problem", "load_petsc_binary", "load_matrix_market", "HipBackend", "run_gcg",
            "PASResult", "run_pas", "eigsh", "EigshResult", "NoConvergence", "solve", "SolveResult",
-           "grad", "eigenvalue_grads", "eigenvector_grads", "solve_grads"]
+           "grad", "eigenvalue_grads", "eigenvector_grads", "solve_grads",
+           "CountResult", "count_from_moments", "eigenvalue_count", "spectral_density"]

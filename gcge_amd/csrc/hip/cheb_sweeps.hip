@@ -21,10 +21,19 @@
 //   cheb_accum     acc <- [acc +] mu_a ta + mu_b tb                3 reads + 1 write        slots: 2 Axpby (3 streams each)
 //                                                                  (init: 2 + 1, acc is not read; one term: tb is not read)
 //
+// And the sweep that also returns the inner products of the kernel polynomial method (GCGE_ChebMoments), with the sums alone beside it:
+//
+//   cheb_sweep_dots   cheb_sweep, and oo_j = sum_r out_new[r, j]^2, oy_j = sum_r out_new[r, j] y[r, j]      3 reads + 1 write
+//                                                                  slots: the sweep, then two 'D' products (3 to 4 more reads)
+//   cheb_dots         tt_j = sum_r t[r, j]^2, ty_j = sum_r t[r, j] y[r, j]                                  2 reads
+// per-workgroup partial sums in gcge_hip_partial_ws, added by reduce_partials in a fixed order as in pcg_sweeps.hip: no atomics, the
+// same bits on every run; the sums come back to the host, so these two wait for the stream.
+//
 // Also here: the device staging of the fused step's scalars (gcge_hip_cheb_step_mv, mat_product.hip), filled by a one-block kernel
 // so that nothing is copied from the host and nothing is waited for.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "gcge_hip.h"
 #include "gcge_hip_internal.h"
@@ -132,6 +141,158 @@ __global__ __launch_bounds__(256) void cheb_accum_s(long nrows, double* __restri
     }
 }
 
+// ---- the step's sweep WITH the two column sums of the kernel polynomial method (GCGE_ChebMoments): cheb_sweep's arithmetic, entry by
+// entry the same expressions, so out gets the same bits; from the value r it stores each thread also adds r^2 and r y into its own
+// sums (fma, rows in ascending order), the workgroup adds its row lanes in LDS in ascending lane order and leaves
+//     partial[b * 2m + j] = sum r^2,   partial[b * 2m + m + j] = sum r y        (pcg_dots' layout)
+// for reduce_partials: a fixed order, no atomics, the same bits on every run.  3 reads + 1 write (!HASZ: 2 + 1), as the sweep alone.
+template <int UNR, bool HASZ>
+__global__ __launch_bounds__(256) void cheb_sweep_dots_v2(long nrows, double* __restrict__ out, long ldo, const double* __restrict__ y, long ldy,
+    const double* __restrict__ z, long ldz, int m, double alpha, double c, double beta, double* __restrict__ partial, int tpr) {
+  __shared__ double red[256][4];
+  const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
+  const int j = 2 * tx;
+  double s0 = 0.0, s1 = 0.0, t0 = 0.0, t1 = 0.0;
+  const bool mine = j < m;
+  if (mine) {
+    const long group = (long)rpb * UNR;
+    const long slab = (((nrows + gridDim.x - 1) / gridDim.x) + group - 1) / group * group;
+    const long rend = min(nrows, ((long)blockIdx.x + 1) * slab), step = rpb;
+    auto one = [&](long rr, v2d ov, v2d yv, v2d zv) {
+      const v2d u = {fma(-c, yv.x, ov.x), fma(-c, yv.y, ov.y)};
+      const v2d r = HASZ ? v2d{fma(alpha, u.x, -(beta * zv.x)), fma(alpha, u.y, -(beta * zv.y))} : v2d{alpha * u.x, alpha * u.y};
+      __builtin_nontemporal_store(r, reinterpret_cast<v2d*>(out + rr * ldo + j));
+      s0 = fma(r.x, r.x, s0); s1 = fma(r.y, r.y, s1);
+      t0 = fma(r.x, yv.x, t0); t1 = fma(r.y, yv.y, t1);
+    };
+    long row = (long)blockIdx.x * slab + ty;
+    for (; row + (UNR - 1) * step < rend; row += step * UNR) {
+      v2d ov[UNR], yv[UNR], zv[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const long rr = row + u * step;
+        ov[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(out + rr * ldo + j));
+        yv[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(y + rr * ldy + j));
+        zv[u] = HASZ ? __builtin_nontemporal_load(reinterpret_cast<const v2d*>(z + rr * ldz + j)) : v2d{0.0, 0.0};
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) one(row + u * step, ov[u], yv[u], zv[u]);
+    }
+    for (; row < rend; row += step)
+      one(row, *reinterpret_cast<const v2d*>(out + row * ldo + j), *reinterpret_cast<const v2d*>(y + row * ldy + j),
+          HASZ ? *reinterpret_cast<const v2d*>(z + row * ldz + j) : v2d{0.0, 0.0});
+  }
+  red[threadIdx.x][0] = s0; red[threadIdx.x][1] = s1; red[threadIdx.x][2] = t0; red[threadIdx.x][3] = t1;
+  __syncthreads();
+  if (ty == 0 && mine) {
+    for (int k = 1; k < rpb; ++k) {
+      s0 += red[k * tpr + tx][0]; s1 += red[k * tpr + tx][1]; t0 += red[k * tpr + tx][2]; t1 += red[k * tpr + tx][3];
+    }
+    double* p = partial + (long)blockIdx.x * 2 * m;
+    p[j] = s0; p[j + 1] = s1; p[m + j] = t0; p[m + j + 1] = t1;
+  }
+}
+
+template <bool HASZ>
+__global__ __launch_bounds__(256) void cheb_sweep_dots_s(long nrows, double* __restrict__ out, long ldo, const double* __restrict__ y, long ldy,
+    const double* __restrict__ z, long ldz, int m, double alpha, double c, double beta, double* __restrict__ partial, long rows_per_block) {
+  __shared__ double red[2][4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const long r0 = (long)blockIdx.x * rows_per_block;
+  const long r1 = min(nrows, r0 + rows_per_block);
+  for (int c0 = 0; c0 < m; c0 += 64) {
+    const int j = c0 + tx;
+    double s = 0.0, t = 0.0;
+    if (j < m)
+      for (long row = r0 + ty; row < r1; row += 4) {
+        const double yv = y[row * ldy + j];
+        const double u = fma(-c, yv, out[row * ldo + j]);
+        const double r = HASZ ? fma(alpha, u, -(beta * z[row * ldz + j])) : alpha * u;
+        out[row * ldo + j] = r;
+        s = fma(r, r, s);
+        t = fma(r, yv, t);
+      }
+    red[0][ty][tx] = s; red[1][ty][tx] = t;
+    __syncthreads();
+    if (ty == 0 && j < m) {
+      partial[(long)blockIdx.x * 2 * m + j] = (red[0][0][tx] + red[0][1][tx]) + (red[0][2][tx] + red[0][3][tx]);
+      partial[(long)blockIdx.x * 2 * m + m + j] = (red[1][0][tx] + red[1][1][tx]) + (red[1][2][tx] + red[1][3][tx]);
+    }
+    __syncthreads();
+  }
+}
+
+// ---- the same two sums of an iterate that is in memory already (behind the fused step): tt = sum t^2, ty = sum t y from ONE read of
+// t and y, 2 reads; the launch shape and the partials' layout are cheb_sweep_dots'.
+template <int UNR>
+__global__ __launch_bounds__(256) void cheb_dots_v2(long nrows, const double* __restrict__ t, long ldt, const double* __restrict__ y, long ldy, int m,
+    double* __restrict__ partial, int tpr) {
+  __shared__ double red[256][4];
+  const int tx = threadIdx.x % tpr, ty = threadIdx.x / tpr, rpb = 256 / tpr;
+  const int j = 2 * tx;
+  double s0 = 0.0, s1 = 0.0, t0 = 0.0, t1 = 0.0;
+  const bool mine = j < m;
+  if (mine) {
+    const long group = (long)rpb * UNR;
+    const long slab = (((nrows + gridDim.x - 1) / gridDim.x) + group - 1) / group * group;
+    const long rend = min(nrows, ((long)blockIdx.x + 1) * slab), step = rpb;
+    auto one = [&](v2d tv, v2d yv) {
+      s0 = fma(tv.x, tv.x, s0); s1 = fma(tv.y, tv.y, s1);
+      t0 = fma(tv.x, yv.x, t0); t1 = fma(tv.y, yv.y, t1);
+    };
+    long row = (long)blockIdx.x * slab + ty;
+    for (; row + (UNR - 1) * step < rend; row += step * UNR) {
+      v2d tv[UNR], yv[UNR];
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) {
+        const long rr = row + u * step;
+        tv[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(t + rr * ldt + j));
+        yv[u] = __builtin_nontemporal_load(reinterpret_cast<const v2d*>(y + rr * ldy + j));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < UNR; ++u) one(tv[u], yv[u]);
+    }
+    for (; row < rend; row += step)
+      one(*reinterpret_cast<const v2d*>(t + row * ldt + j), *reinterpret_cast<const v2d*>(y + row * ldy + j));
+  }
+  red[threadIdx.x][0] = s0; red[threadIdx.x][1] = s1; red[threadIdx.x][2] = t0; red[threadIdx.x][3] = t1;
+  __syncthreads();
+  if (ty == 0 && mine) {
+    for (int k = 1; k < rpb; ++k) {
+      s0 += red[k * tpr + tx][0]; s1 += red[k * tpr + tx][1]; t0 += red[k * tpr + tx][2]; t1 += red[k * tpr + tx][3];
+    }
+    double* p = partial + (long)blockIdx.x * 2 * m;
+    p[j] = s0; p[j + 1] = s1; p[m + j] = t0; p[m + j + 1] = t1;
+  }
+}
+
+__global__ __launch_bounds__(256) void cheb_dots_s(long nrows, const double* __restrict__ t, long ldt, const double* __restrict__ y, long ldy, int m,
+    double* __restrict__ partial, long rows_per_block) {
+  __shared__ double red[2][4][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const long r0 = (long)blockIdx.x * rows_per_block;
+  const long r1 = min(nrows, r0 + rows_per_block);
+  for (int c0 = 0; c0 < m; c0 += 64) {
+    const int j = c0 + tx;
+    double s = 0.0, q = 0.0;
+    if (j < m)
+      for (long row = r0 + ty; row < r1; row += 4) {
+        const double tv = t[row * ldt + j];
+        s = fma(tv, tv, s);
+        q = fma(tv, y[row * ldy + j], q);
+      }
+    red[0][ty][tx] = s; red[1][ty][tx] = q;
+    __syncthreads();
+    if (ty == 0 && j < m) {
+      partial[(long)blockIdx.x * 2 * m + j] = (red[0][0][tx] + red[0][1][tx]) + (red[0][2][tx] + red[0][3][tx]);
+      partial[(long)blockIdx.x * 2 * m + m + j] = (red[1][0][tx] + red[1][1][tx]) + (red[1][2][tx] + red[1][3][tx]);
+    }
+    __syncthreads();
+  }
+}
+
 // the scalars of one fused step, the same for every column: coef = [al | cb | bp] (3 m doubles), flag = m ones
 __global__ void cheb_scalars_fill(int m, double al, double cb, double bp, double* __restrict__ coef, int* __restrict__ flag) {
   for (int j = threadIdx.x; j < m; j += blockDim.x) { coef[j] = al; coef[m + j] = cb; coef[2 * m + j] = bp; flag[j] = 1; }
@@ -158,6 +319,60 @@ extern "C" int gcge_hip_cheb_sweep(long n, double* out, long ldo, const double* 
   else GCGE_CHEB_LAUNCH(cheb_sweep_s<false>, grid.rpb);
 #undef GCGE_CHEB_LAUNCH
   return (int)hipGetLastError();
+}
+
+// the 2 m sums nb workgroups left in part come back to the host, added in reduce_partials' fixed order (one stream synchronisation)
+static void cheb_sums_to_host(double* part, long nb, int m, double* first, double* second, hipStream_t st) {
+  double* h = gcge_hip_stage_h(2 * (size_t)m);
+  gcge_hip_reduce_partials(part, (int)nb, 2 * m, part + (size_t)nb * 2 * m, st);
+  GCGE_HIP_CHECK(hipMemcpyAsync(h, part + (size_t)nb * 2 * m, 2 * (size_t)m * sizeof(double), hipMemcpyDeviceToHost, st));
+  GCGE_HIP_CHECK(hipStreamSynchronize(st));
+  memcpy(first, h, m * sizeof(double));
+  memcpy(second, h + m, m * sizeof(double));
+}
+
+extern "C" int gcge_hip_cheb_sweep_dots(long n, double* out, long ldo, const double* y, long ldy, const double* z, long ldz, int m, double alpha,
+                                        double c, double beta, double* oo, double* oy, void* stream) {
+  gcge_hip_apply_pending();
+  if (n < 0 || m < 0 || out == nullptr || y == nullptr || (beta != 0.0 && z == nullptr) || out == y || out == z || oo == nullptr || oy == nullptr)
+    return -1;
+  for (int j = 0; j < m; ++j) oo[j] = oy[j] = 0.0;
+  if (n == 0 || m == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const CgGrid grid = cg_grid(n);
+  const bool hasz = beta != 0.0;
+  if (!hasz) { z = y; ldz = ldy; }      // (never read; keeps the alignment test below on the operands that are)
+  const bool vec = m <= 512 && cg_vec_ok(m, {out, y, z}, {ldo, ldy, ldz});
+  double* part = gcge_hip_partial_ws((size_t)grid.nb * 2 * m + 2 * m);
+#define GCGE_CHEB_LAUNCH(kernel, last)                                                                                              \
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid.nb), dim3(256), 0, st, n, out, ldo, y, ldy, z, ldz, m, alpha, c, beta, part, last)
+  if (vec && hasz) GCGE_CHEB_LAUNCH((cheb_sweep_dots_v2<4, true>), cg_tpr(m));
+  else if (vec) GCGE_CHEB_LAUNCH((cheb_sweep_dots_v2<4, false>), cg_tpr(m));
+  else if (hasz) GCGE_CHEB_LAUNCH(cheb_sweep_dots_s<true>, grid.rpb);
+  else GCGE_CHEB_LAUNCH(cheb_sweep_dots_s<false>, grid.rpb);
+#undef GCGE_CHEB_LAUNCH
+  const int rc = (int)hipGetLastError();
+  if (rc != 0) return rc;
+  cheb_sums_to_host(part, grid.nb, m, oo, oy, st);
+  return 0;
+}
+
+extern "C" int gcge_hip_cheb_dots(long n, const double* t, long ldt, const double* y, long ldy, int m, double* tt, double* ty, void* stream) {
+  gcge_hip_apply_pending();
+  if (n < 0 || m < 0 || t == nullptr || y == nullptr || tt == nullptr || ty == nullptr) return -1;
+  for (int j = 0; j < m; ++j) tt[j] = ty[j] = 0.0;
+  if (n == 0 || m == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const CgGrid grid = cg_grid(n);
+  double* part = gcge_hip_partial_ws((size_t)grid.nb * 2 * m + 2 * m);
+  if (m <= 512 && cg_vec_ok(m, {t, y}, {ldt, ldy}))
+    hipLaunchKernelGGL(cheb_dots_v2<4>, dim3((unsigned)grid.nb), dim3(256), 0, st, n, t, ldt, y, ldy, m, part, cg_tpr(m));
+  else
+    hipLaunchKernelGGL(cheb_dots_s, dim3((unsigned)grid.nb), dim3(256), 0, st, n, t, ldt, y, ldy, m, part, grid.rpb);
+  const int rc = (int)hipGetLastError();
+  if (rc != 0) return rc;
+  cheb_sums_to_host(part, grid.nb, m, tt, ty, st);
+  return 0;
 }
 
 extern "C" int gcge_hip_cheb_accum(long n, double* acc, long lda, const double* ta, long ldta, double mu_a, const double* tb, long ldtb,

@@ -6,6 +6,7 @@
 //   gcge_hip_cg_*                        the passes of the fused block CG on a pattern matrix (product formed twice, never stored)
 //   gcge_hip_cheb_step_mv                one step of a Chebyshev filter: the second CG pass with prescribed scalars, or product + sweep
 //   gcge_hip_cheb_accum_mv               the sums of a band-pass filter on blocks (no matrix: it sits beside the step it follows)
+//   gcge_hip_cheb_step_dots_mv           the step with the two column sums of the kernel polynomial method
 //   HIP_Amg*, HIP_ResidualSq       the fused sweeps of a V-cycle and the residual norms of Ritz pairs (GCGE_BACKEND)
 //   gcge_hip_profile_*                   HIP events around every K1 launch
 // Runtime state, staging, pool and the multivector slots live in app_hip.hip (shared names: gcge_hip_internal.h); the handle itself
@@ -559,8 +560,10 @@ extern "C" int gcge_hip_cg_pass2i_mv(void* mat, void** p, void** pprev, void** p
 // product into out, whatever K1 form the handle has, then gcge_hip_cheb_sweep in place on out — 6 block streams and the matrix.
 static long g_cheb_stats[3] = {0, 0, 0};      // fused, product + sweep, declined
 extern "C" void gcge_hip_cheb_stats(long out[3]) { for (int i = 0; i < 3; ++i) out[i] = g_cheb_stats[i]; }
-extern "C" int gcge_hip_cheb_step_mv(void* mat, void** y, int y0, void** z, int z0, void** out, int o0, int m, double alpha, double c,
-                                     double beta) {
+// one step, with the two sums of GCGE_BACKEND.cheb_step_dots when oo != NULL (then oy != NULL as well): the same checks and the same
+// choice of path either way; `stats` counts it
+static int cheb_step_any(void* mat, void** y, int y0, void** z, int z0, void** out, int o0, int m, double alpha, double c, double beta,
+                         double* oo, double* oy, long* stats) {
   GCGE_HIP_MAT_* A = (GCGE_HIP_MAT_*)mat;
   GcgeHipMV *vy = (GcgeHipMV*)y, *vz = (GcgeHipMV*)z, *vo = (GcgeHipMV*)out;
   const bool hasz = beta != 0.0;
@@ -568,7 +571,7 @@ extern "C" int gcge_hip_cheb_step_mv(void* mat, void** y, int y0, void** z, int 
   ok = ok && y0 >= 0 && y0 + m <= vy->ncols && o0 >= 0 && o0 + m <= vo->ncols && (!hasz || (z0 >= 0 && z0 + m <= vz->ncols));
   ok = ok && A->nrows == vy->nrows && A->nrows == vo->nrows && A->nrows + A->nghost <= vy->nrows_alloc && (!hasz || A->nrows == vz->nrows);
   ok = ok && real_perm(vy->perm) == real_perm(A->perm) && real_perm(vo->perm) == real_perm(A->perm) && (!hasz || real_perm(vz->perm) == real_perm(A->perm));
-  if (!ok) { ++g_cheb_stats[2]; return -1; }
+  if (!ok) { ++stats[2]; return -1; }
   gcge_hip_enter();
   if (hasz && A->nghost == 0 && y0 == z0 && y0 == o0 && !(y0 & 1) && getenv("GCGE_CHEB_NO_FUSE") == nullptr &&
       gcge_hip_cg_fusable(mat, y, m) && gcge_hip_cg_recompute_pays(mat) && pair_ok(vz, z0) && pair_ok(vo, o0)) {
@@ -576,16 +579,42 @@ extern "C" int gcge_hip_cheb_step_mv(void* mat, void** y, int y0, void** z, int 
     const double *d_al, *d_cb, *d_bp; const int* d_flag;
     gcge_hip_cheb_scalars(m, alpha, c, beta, g_stream, &d_al, &d_cb, &d_bp, &d_flag);
     GCGE_REQUIRE(gcge_hip_cg_pass2i_dev(mat, y, z, out, y0, m, d_al, d_cb, d_flag, d_bp, gcge_hip_stage_d(6 * (size_t)m)) == 0, "Chebyshev step: fused pass");
-    ++g_cheb_stats[0];
+    if (oo != nullptr)      // the sums from one read of what the pass wrote and of y: 2 more block streams
+      GCGE_REQUIRE(gcge_hip_cheb_dots(A->nrows, vo->d + o0, vo->ld, vy->d + y0, vy->ld, m, oo, oy, g_stream) == 0, "Chebyshev step: sums");
+    ++stats[0];
     return 0;
   }
   int start[2] = {y0, o0}, end[2] = {y0 + m, o0 + m};
   HIP_MatDotMultiVec(mat, y, out, start, end, nullptr);
   SlotTimer tm_("Chebyshev step (sweep)", m);
-  GCGE_REQUIRE(gcge_hip_cheb_sweep(A->nrows, vo->d + o0, vo->ld, vy->d + y0, vy->ld, hasz ? vz->d + z0 : nullptr, hasz ? vz->ld : 0, m, alpha, c, beta,
-                                   g_stream) == 0, "Chebyshev step: sweep");
-  ++g_cheb_stats[1];
+  if (oo != nullptr)
+    GCGE_REQUIRE(gcge_hip_cheb_sweep_dots(A->nrows, vo->d + o0, vo->ld, vy->d + y0, vy->ld, hasz ? vz->d + z0 : nullptr, hasz ? vz->ld : 0, m, alpha, c,
+                                          beta, oo, oy, g_stream) == 0, "Chebyshev step: sweep with sums");
+  else
+    GCGE_REQUIRE(gcge_hip_cheb_sweep(A->nrows, vo->d + o0, vo->ld, vy->d + y0, vy->ld, hasz ? vz->d + z0 : nullptr, hasz ? vz->ld : 0, m, alpha, c, beta,
+                                     g_stream) == 0, "Chebyshev step: sweep");
+  ++stats[1];
   return 0;
+}
+extern "C" int gcge_hip_cheb_step_mv(void* mat, void** y, int y0, void** z, int z0, void** out, int o0, int m, double alpha, double c,
+                                     double beta) {
+  return cheb_step_any(mat, y, y0, z, z0, out, o0, m, alpha, c, beta, nullptr, nullptr, g_cheb_stats);
+}
+// The step with the sums of the kernel polynomial method (GCGE_ChebMoments, csrc/host/chfsi.c; GCGE_BACKEND.cheb_step_dots):
+// gcge_hip_cheb_step_mv's decisions, and oo[j] = sum out[r, j]^2, oy[j] = sum out[r, j] y[r, j] over the local rows on the host.  Fused:
+// the MODE-7 pass, then gcge_hip_cheb_dots (3 + 2 block streams); otherwise the product, then gcge_hip_cheb_sweep_dots (6 streams, as
+// the step without sums).  The slots would add two MultiVecLocalInnerProd('D') to either: 3 to 4 more reads, two launches, two drains.
+static long g_cheb_step_dots_stats[3] = {0, 0, 0};      // fused, product + sweep, declined
+extern "C" void gcge_hip_cheb_step_dots_stats(long out[3]) { for (int i = 0; i < 3; ++i) out[i] = g_cheb_step_dots_stats[i]; }
+extern "C" int gcge_hip_cheb_step_dots_mv(void* mat, void** y, int y0, void** z, int z0, void** out, int o0, int m, double alpha, double c,
+                                          double beta, double* oo, double* oy) {
+  if (oo == nullptr || oy == nullptr) { ++g_cheb_step_dots_stats[2]; return -1; }
+  return cheb_step_any(mat, y, y0, z, z0, out, o0, m, alpha, c, beta, oo, oy, g_cheb_step_dots_stats);
+}
+static int HIP_ChebStepDots(void* mat, void** y, int y0, void** z, int z0, void** out, int o0, int m, double alpha, double c, double beta,
+                            double* oo, double* oy, struct OPS_* ops) {
+  (void)ops;
+  return gcge_hip_cheb_step_dots_mv(mat, y, y0, z, z0, out, o0, m, alpha, c, beta, oo, oy) == 0 ? 1 : 0;
 }
 static int HIP_ChebStep(void* mat, void** y, int y0, void** z, int z0, void** out, int o0, int m, double alpha, double c, double beta,
                         struct OPS_* ops) {
@@ -902,4 +931,5 @@ extern "C" void gcge_hip_product_slots(struct OPS_* ops, GCGE_BACKEND* be) {
   be->amg_form_rhs    = HIP_AmgFormRhs;           // b = x diag(scale) in one sweep
   be->cheb_step       = HIP_ChebStep;             // one step of a Chebyshev filter: fused on pattern matrices, product + one sweep otherwise
   be->cheb_accum      = HIP_ChebAccum;            // two iterates of a band-pass filter added to its sum in one sweep
+  be->cheb_step_dots  = HIP_ChebStepDots;         // the step with the two column sums of the kernel polynomial method, no pass of their own
 }

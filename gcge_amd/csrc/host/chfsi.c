@@ -9,6 +9,8 @@
  *                     against the locked ones and among themselves, Rayleigh-Ritz, residuals, lock the leading converged pairs.
  *   GCGE_ChebBandFilter, GCGE_RunChFSIBand   (at the end of the file) the eigenpairs INSIDE an interval [a, b]: the filter is the
  *                     Jackson-damped Chebyshev expansion of the interval's indicator, a sum of the recurrence's iterates.
+ *   GCGE_ChebMoments, GCGE_ChebCountFromMoments   (behind them) what that solve needs to know in advance — how many eigenvalues lie in
+ *                     an interval, where the gaps are — from the Chebyshev moments of a few probe vectors (the kernel polynomial method).
  *
  * The filter is the three-term recurrence  Y_{j+1} = alpha_j (A - c I) Y_j - beta_j Y_{j-1}.  One step goes through the back-end's
  * cheb_step (GCGE_BACKEND, gcge_ops.h) where the table offers it and it accepts, else through the slots: MatDotMultiVec into the
@@ -486,4 +488,98 @@ int GCGE_RunChFSIBand(void *A, int argc, char *argv[], struct OPS_ *ops, double 
 	ops->Printf("numIter = %d, inside = %d, spurious = %d\n", numIter, ngen, nspur);
 	ops->Printf("Time is %.3f\n", ops->GetWtime() - t0);
 	return rc;
+}
+
+/* ---- eigenvalue counts and the density of states from Chebyshev moments: the kernel polynomial method (Weisse et al., cited above;
+ * L. Lin, Y. Saad, C. Yang, SIAM Rev. 58 (2016) 34-65; E. Di Napoli, E. Polizzi, Y. Saad, cited above, for the counts) ---------------
+ * mu_j = v^T T_j(At) v, At = (A - c) / e, for every column v of a block of probes.  With t_k = T_k(At) v and T_2k = 2 T_k^2 - 1,
+ * T_{2k+1} = 2 T_{k+1} T_k - T_1 (A symmetric: v^T T_k T_l v = t_k . t_l),
+ *     mu_2k = 2 t_k . t_k - mu_0 ,   mu_{2k-1} = 2 t_k . t_{k-1} - mu_1 :
+ * two column sums per step of the recurrence, ceil(degree / 2) steps and as many products, no second block of vectors. */
+
+/* the sums every rank holds over its own rows, added over the ranks: lin_sol.c's rule for sums that came out of
+ * MultiVecLocalInnerProd (a back-end may have reduced them already); a slot's sums are local whatever that switch says */
+static void sum_over_ranks(double *v, int n, int from_slot)
+{
+	GCGE_COMM *c = GCGE_GetComm();
+	if (!from_slot && GCGE_GetLocalInnerProdReduces()) return;
+	if (c != NULL && n > 0) c->allreduce_sum(v, n, c->ctx);
+}
+
+static void local_col_dots(void **x, int x0, void **y, int y0, int m, double *out, struct OPS_ *ops)
+{
+	int s[2], e[2];
+	s[0] = x0; e[0] = x0 + m; s[1] = y0; e[1] = y0 + m;
+	ops->MultiVecLocalInnerProd('D', x, y, 0, s, e, out, 1, ops);
+}
+
+/* cheb_step, and dots[j] = out_j . out_j, dots[m + j] = out_j . y_j over all ranks: ONE call of the back-end's cheb_step_dots where
+ * the table offers it and it accepts, else the step and two MultiVecLocalInnerProd('D') */
+static void cheb_step_dots(void *A, void **y, int y0, void **z, int z0, void **out, int o0, int m, double alpha, double c, double beta,
+		double *dots, const GCGE_BACKEND *be, struct OPS_ *ops)
+{
+	if (be->cheb_step_dots != NULL && be->cheb_step_dots(A, y, y0, z, z0, out, o0, m, alpha, c, beta, dots, dots + m, ops)) {
+		sum_over_ranks(dots, 2 * m, 1);
+		return;
+	}
+	cheb_step(A, y, y0, z, z0, out, o0, m, alpha, c, beta, be, ops);
+	local_col_dots(out, o0, out, o0, m, dots, ops);
+	local_col_dots(out, o0, y, y0, m, dots + m, ops);
+	sum_over_ranks(dots, 2 * m, 0);
+}
+
+int GCGE_ChebMoments(void *A, void **v, int v0, int m, int degree, double lmin, double lmax, void **w1, void **w2, void **w3,
+		double *moments, struct OPS_ *ops)
+{
+	void **ring[3]; double *dots, c, ee; int k, col, steps;
+	if (A == NULL || v == NULL || w1 == NULL || w2 == NULL || w3 == NULL || moments == NULL || ops == NULL) return -1;
+	if (v0 < 0 || m < 1 || degree < 1 || !(lmin < lmax)) return -1;
+	if (v == w1 || v == w2 || v == w3 || w1 == w2 || w1 == w3 || w2 == w3) return -1;
+	dots = (double*)malloc(2 * (size_t)m * sizeof(double));
+	if (dots == NULL) return -1;
+	{
+		const GCGE_BACKEND be = GCGE_BackendOf(ops);
+		ring[0] = w1; ring[1] = w2; ring[2] = w3;
+		c = 0.5 * (lmax + lmin); ee = 0.5 * (lmax - lmin);
+		steps = (degree + 1) / 2;
+		local_col_dots(v, v0, v, v0, m, moments, ops);                               /* mu_0 = v . v */
+		sum_over_ranks(moments, m, 0);
+		/* step k writes t_k into ring[(k - 1) % 3] from t_{k-1} and t_{k-2} (t_0 is v itself, read only) */
+		for (k = 1; k <= steps; ++k) {
+			void **out = ring[(k - 1) % 3], **y = k == 1 ? v : ring[(k - 2) % 3], **z = k == 1 ? NULL : k == 2 ? v : ring[k % 3];
+			cheb_step_dots(A, y, k == 1 ? v0 : 0, z, k == 2 ? v0 : 0, out, 0, m, k == 1 ? 1.0 / ee : 2.0 / ee, c, k == 1 ? 0.0 : 1.0,
+					dots, &be, ops);
+			for (col = 0; col < m; ++col) {
+				moments[(size_t)(2 * k - 1) * m + col] = k == 1 ? dots[m + col] : 2.0 * dots[m + col] - moments[m + col];
+				if (2 * k <= degree) moments[(size_t)(2 * k) * m + col] = 2.0 * dots[col] - moments[col];
+			}
+		}
+	}
+	free(dots);
+	return 0;
+}
+
+int GCGE_ChebCountFromMoments(const double *moments, int m, int degree, double a, double b, double lmin, double lmax,
+		double *count, double *stderr_, double *per_probe)
+{
+	double *mu, mean = 0.0, var = 0.0; int j, col;
+	if (moments == NULL || count == NULL || stderr_ == NULL || m < 1 || degree < 2) return -1;
+	mu = (double*)malloc(((size_t)degree + 1 + (size_t)m) * sizeof(double));
+	if (mu == NULL) return -1;
+	if (GCGE_ChebBandCoefficients(degree, a, b, lmin, lmax, mu) != 0) { free(mu); return -1; }
+	{
+		double *pp = mu + degree + 1;
+		for (col = 0; col < m; ++col) {
+			double s = 0.0;
+			for (j = 0; j <= degree; ++j) s += mu[j] * moments[(size_t)j * m + col];
+			pp[col] = s; mean += s;
+		}
+		mean /= m;
+		for (col = 0; col < m; ++col) var += (pp[col] - mean) * (pp[col] - mean);
+		*count = mean;
+		*stderr_ = m > 1 ? sqrt(var / (m - 1)) / sqrt((double)m) : 0.0;
+		if (per_probe != NULL) memcpy(per_probe, pp, (size_t)m * sizeof(double));
+	}
+	free(mu);
+	return 0;
 }

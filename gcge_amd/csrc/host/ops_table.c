@@ -71,7 +71,8 @@ void **GCGE_GetRealignedRhs(int *b0) { if (b0 != NULL) *b0 = g_realigned_b0; ret
  *   GCGE_NO_START_IN_PLACE   start_in_place                                 (the W start vectors and b moved before the solve)
  *   GCGE_NO_PCG_SWEEPS       pcg_step, pcg_dots, pcg_direction, pcg_shift   (GCGE_PCGSolve's sweeps through the slots)
  *   GCGE_NO_CHEB_STEP        cheb_step                                      (GCGE_ChebFilter's steps through the slots)
- *   GCGE_NO_CHEB_ACCUM       cheb_accum                                     (GCGE_ChebBandFilter's sums by two MultiVecAxpby) */
+ *   GCGE_NO_CHEB_ACCUM       cheb_accum                                     (GCGE_ChebBandFilter's sums by two MultiVecAxpby)
+ *   GCGE_NO_CHEB_STEP_DOTS   cheb_step_dots                                 (GCGE_ChebMoments' steps by cheb_step and two inner products) */
 static GCGE_BACKEND g_backend; static void *g_backend_matvec = NULL, *g_backend_lincomb = NULL;
 void GCGE_SetBackend(struct OPS_ *ops, const GCGE_BACKEND *backend)
 {
@@ -99,6 +100,7 @@ GCGE_BACKEND GCGE_BackendOf(struct OPS_ *ops)
 	if (getenv("GCGE_NO_PCG_SWEEPS") != NULL) { b.pcg_step = NULL; b.pcg_dots = NULL; b.pcg_direction = NULL; b.pcg_shift = NULL; }
 	if (getenv("GCGE_NO_CHEB_STEP") != NULL) b.cheb_step = NULL;
 	if (getenv("GCGE_NO_CHEB_ACCUM") != NULL) b.cheb_accum = NULL;
+	if (getenv("GCGE_NO_CHEB_STEP_DOTS") != NULL) b.cheb_step_dots = NULL;
 	return b;
 }
 

@@ -120,7 +120,8 @@ def eigsh(A, k=None, M=None, X0=None, tol=1e-8, maxiter=None, nev_max=None, bloc
            Per outer iteration all nev_max columns are filtered by the Jackson-damped Chebyshev expansion of the interval's indicator
            (about 1 inside, about 0 outside, 1/2 at the ends), orthonormalised, and a Rayleigh-Ritz step follows; Ritz values inside
            the interval that are mixtures of outside eigenvectors are told from genuine pairs by x^T p(A) x.  nev_max is the width
-           of the filtered block and must EXCEED the number of eigenvalues inside (twice it is a good choice); `degree` (>= 2) is the
+           of the filtered block and must EXCEED the number of eigenvalues inside (twice it is a good choice;
+           gcge_amd.eigenvalue_count estimates that number, suggests an nev_max and shows the gaps before anything is solved); `degree` (>= 2) is the
            expansion's, None: the driver's 6 (lmax - lmin) / (b - a) within [20, 1000]; `lower_bound`, `upper_bound`: bounds of the
            whole spectrum, each taken as it is, what is left out comes from one Lanczos run (given bounds that hug the spectrum need
            fewer iterations than Lanczos's safeguarded ones).  Put a and b in GAPS of the spectrum: an eigenvalue at an end may be

@@ -282,6 +282,33 @@ class HipBackendImpl:
                 if w is not None:
                     self.ops.mv_destroy(w, m)
 
+    def chebyshev_moments(self, A, V, degree, lmin, lmax):
+        """The Chebyshev moments mu[j, col] = v_col^T T_j((A - c) / e) v_col, j = 0 .. degree, of the columns of an (n, m) device tensor V
+        for the matrix handle A, c and e the centre and half width of the bounds [lmin, lmax] of A's spectrum, as a (degree + 1, m)
+        float64 device tensor (GCGE_ChebMoments: ceil(degree / 2) steps of the recurrence, each ONE call of the back-end's
+        cheb_step_dots, which returns the step's two inner products with it; lib.cheb_step_dots_stats counts them).  V goes in
+        through mv_from_torch and is not changed; the three work blocks are created and freed here.  ValueError: degree < 1,
+        lmin >= lmax, a V without columns."""
+        import torch
+        degree, lmin, lmax = int(degree), float(lmin), float(lmax)
+        if degree < 1 or not lmin < lmax:
+            raise ValueError("chebyshev_moments: degree >= 1 and lmin < lmax are required")
+        if not hasattr(V, "shape") or len(V.shape) != 2 or int(V.shape[1]) < 1:
+            raise ValueError("chebyshev_moments: V is an (n, m) block with m >= 1")
+        mv = self.mv_from_torch(A, V)
+        m = self.g.gcge_hip_mv_ncols(mv)
+        work = []
+        try:
+            work = [self.ops.mv_create(m, A) for _ in range(3)]
+            mom = np.zeros((degree + 1, m))
+            rc = self.h.GCGE_ChebMoments(A, mv, 0, m, degree, lmin, lmax, work[0], work[1], work[2], mom.ctypes.data_as(C.c_void_p), self.ops_handle)
+            if rc != 0:
+                raise RuntimeError("GCGE_ChebMoments rc=%d" % rc)
+            return torch.from_numpy(mom).to(self.torch_device())
+        finally:
+            for w in work + [mv]:
+                self.ops.mv_destroy(w, m)
+
     def sample_outer(self, crow, col, U, V, weights=None, alpha=1.0):
         """The rank-k product U diag(weights) V^T on the stored entries of a CSR pattern (gcge_hip_csr_sample_outer): an (nnz,)
         float64 device tensor with out[e] = alpha sum_c weights[c] U[i, c] V[col[e], c] for every entry e of row i, in the entry order

@@ -475,6 +475,32 @@ def cheb_accum_stats():
     return tuple(out)
 
 
+def cheb_step_dots_stats():
+    """gcge_hip_cheb_step_dots_stats: (steps with sums taken fused, taken as product + sweep, calls declined) since the library was
+    loaded."""
+    out = (C.c_long * 3)()
+    hip_lib().gcge_hip_cheb_step_dots_stats(out)
+    return tuple(out)
+
+
+def count_from_moments(moments, lower_bound, upper_bound, interval):
+    """GCGE_ChebCountFromMoments on a (degree + 1, m) numpy array of Chebyshev moments taken over [lower_bound, upper_bound]:
+    (count, stderr, per_probe) for interval = (a, b); ValueError when the library refuses (degree < 2, a >= b, lower_bound >=
+    upper_bound, an interval that misses the bounds)."""
+    import numpy as np
+    mom = np.ascontiguousarray(moments, dtype=np.float64)
+    if mom.ndim != 2 or mom.shape[0] < 3 or mom.shape[1] < 1:
+        raise ValueError("count_from_moments: a (degree + 1, m) array with degree >= 2 and m >= 1 is required")
+    a, b = (float(v) for v in interval)
+    count, err, per = C.c_double(), C.c_double(), np.zeros(mom.shape[1])
+    rc = host_lib().GCGE_ChebCountFromMoments(mom.ctypes.data_as(C.c_void_p), mom.shape[1], mom.shape[0] - 1, a, b, float(lower_bound),
+                                              float(upper_bound), C.cast(C.byref(count), C.c_void_p), C.cast(C.byref(err), C.c_void_p),
+                                              per.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise ValueError("count_from_moments: a < b, lower_bound < upper_bound and an interval that meets the bounds are required")
+    return count.value, err.value, per
+
+
 def run_pas(ops, matA, matB, args, flag=0, quiet=True, keep_evec=False):
     """GCGE_RunPAS through the operator table `ops`: PAS (the multigrid eigensolver over the back-end's hierarchy), then GCG
     warm-started from PAS's converged vectors unless args hold -gcge_pas_only 1.  Returns (eval, pas_result, gcg_result)

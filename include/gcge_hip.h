@@ -705,6 +705,30 @@ int gcge_hip_cheb_accum (long n, double *acc, long lda, const double *ta, long l
  *     -1, since the library was loaded.                                                                                            */
 int gcge_hip_cheb_accum_mv (void **acc, int a0, void **ta, int ta0, double mu_a, void **tb, int tb0, double mu_b, int m, int init);
 void gcge_hip_cheb_accum_stats (long out[3]);
+/*     The step's sweep with the two column sums of the kernel polynomial method (GCGE_ChebMoments, gcge_solver.h; csrc/hip/cheb_sweeps.hip):
+ *     gcge_hip_cheb_sweep with the same operation order — out gets the bits gcge_hip_cheb_sweep writes — and, from the values it stores,
+ *         oo[j] = sum_r out_new[r, j]^2 ,   oy[j] = sum_r out_new[r, j] y[r, j]        0 <= j < m
+ *     in the same pass: 3 reads + 1 write (beta == 0: 2 + 1), nothing more than the sweep alone.  oo, oy: HOST arrays of m doubles;
+ *     the call waits for the stream, as gcge_hip_pcg_dots does.  Every thread adds its rows in ascending order by fma, a workgroup
+ *     its row lanes in a fixed order, and the workgroups' partial sums are added in a fixed order: no atomics, the same bits on
+ *     every run.  Return 0 (also for n == 0 or m == 0: the sums are 0), the launch's error, or -1 with nothing written on
+ *     gcge_hip_cheb_sweep's bad arguments or a NULL oo or oy.
+ *     gcge_hip_cheb_dots: the same two sums of a block t that is in memory, tt[j] = sum_r t[r, j]^2, ty[j] = sum_r t[r, j] y[r, j], from
+ *     ONE read of t and y (2 reads; t and y may be the same block); -1 on n < 0, m < 0 or a NULL pointer.                          */
+int gcge_hip_cheb_sweep_dots (long n, double *out, long ldo, const double *y, long ldy, const double *z, long ldz, int m,
+		double alpha, double c, double beta, double *oo, double *oy, void *stream);
+int gcge_hip_cheb_dots (long n, const double *t, long ldt, const double *y, long ldy, int m, double *tt, double *ty, void *stream);
+/*     The step on a matrix handle with the sums (GCGE_BACKEND.cheb_step_dots of OPS_HIP_Set): gcge_hip_cheb_step_mv's operands, checks
+ *     and decisions, out bit for bit what it writes, and oo[j] = sum out[r, o0 + j]^2, oy[j] = sum out[r, o0 + j] y[r, y0 + j] over
+ *     the LOCAL rows in host arrays of m doubles (the call waits for them):
+ *       fused            the MODE-7 pass, then gcge_hip_cheb_dots on what it wrote: 3 + 2 block streams and the matrix;
+ *       product + sweep  the product into out, then gcge_hip_cheb_sweep_dots in place: 6 block streams and the matrix.
+ *     Returns 0; -1 with nothing written for the operands gcge_hip_cheb_step_mv refuses and for a NULL oo or oy.
+ *     gcge_hip_cheb_step_dots_stats: steps taken fused, steps by product + sweep, calls that returned -1, since the library was
+ *     loaded (gcge_hip_cheb_stats does not count these calls).                                                                      */
+int gcge_hip_cheb_step_dots_mv (void *mat, void **y, int y0, void **z, int z0, void **out, int o0, int m,
+		double alpha, double c, double beta, double *oo, double *oy);
+void gcge_hip_cheb_step_dots_stats (long out[3]);
 
 #ifdef __cplusplus
 }

@@ -271,7 +271,14 @@ void     **GCGE_GetRealignedRhs (int *b0);
  *                 init != 0: acc is not read and may hold anything; tb == NULL: one term, mu_b is ignored.  Nothing is waited for.
  *                 The slots take two MultiVecAxpby (one for one term): 3 + 3 block streams; the HIP back-end 4 (init: 3).  Rounded
  *                 as s = fma(mu_a, ta, acc) (init: mu_a ta), then fma(mu_b, tb, s): not the bits of the two Axpby.  1 taken, 0
- *                 declines with nothing touched. */
+ *                 declines with nothing touched.
+ *   cheb_step_dots   cheb_step, and additionally the two LOCAL column sums the kernel polynomial method takes from every step
+ *                 (GCGE_ChebMoments, gcge_solver.h):  oo[j] = sum over the LOCAL rows of out[r, o0 + j]^2 ,  oy[j] = the same of
+ *                 out[r, o0 + j] y[r, y0 + j],  j < m, of the out it has just written; oo, oy: host arrays of m entries, so the call
+ *                 waits for them.  out is bit for bit what cheb_step writes for the same operands.  The slots take cheb_step (or its
+ *                 slot sequence) and two MultiVecLocalInnerProd('D'): 3 to 4 more block reads in two launches with two drains; the HIP
+ *                 back-end forms the sums inside the step's sweep (6 block streams, as the step alone) or, behind the fused step, from
+ *                 one read of out and y (3 + 2).  1 taken, 0 declines with nothing touched. */
 typedef int    (*GCGE_RESIDUAL_FN) (void *A, void *B, void **x, int start, int end, const double *lambda, double *res_sq);
 typedef int    (*GCGE_SYMEIG_FN) (char uplo, int n, const double *a, int lda, double *w, double *z, int ldz);
 typedef void   (*GCGE_SMOOTHER_SETUP_FN) (int max_iter, double rate, double tol, const char *tol_type, struct OPS_ *ops);
@@ -295,6 +302,8 @@ typedef int    (*GCGE_CHEB_STEP_FN) (void *A, void **y, int y0, void **z, int z0
 		double beta, struct OPS_ *ops);
 typedef int    (*GCGE_CHEB_ACCUM_FN) (void **acc, int a0, void **ta, int ta0, double mu_a, void **tb, int tb0, double mu_b, int m,
 		int init, struct OPS_ *ops);
+typedef int    (*GCGE_CHEB_STEP_DOTS_FN) (void *A, void **y, int y0, void **z, int z0, void **out, int o0, int m, double alpha, double c,
+		double beta, double *oo, double *oy, struct OPS_ *ops);
 typedef struct GCGE_BACKEND_ {
 	GCGE_RESIDUAL_FN residual_sq;
 	int inplace_lincomb_cols;
@@ -318,6 +327,7 @@ typedef struct GCGE_BACKEND_ {
 	GCGE_PCG_SHIFT_FN pcg_shift;
 	GCGE_CHEB_STEP_FN cheb_step;
 	GCGE_CHEB_ACCUM_FN cheb_accum;
+	GCGE_CHEB_STEP_DOTS_FN cheb_step_dots;
 } GCGE_BACKEND;
 void       GCGE_SetBackend (struct OPS_ *ops, const GCGE_BACKEND *backend);
 GCGE_BACKEND GCGE_BackendOf (struct OPS_ *ops);

@@ -323,6 +323,28 @@ int GCGE_ChebBandFilter (void *A, void **x, int x0, int m, int degree, double a,
 int GCGE_RunChFSIBand (void *A, int argc, char *argv[], struct OPS_ *ops, double *eval, void **evec, int nevGiven,
 		GCGE_CHFSI_BAND_RESULT *res);
 
+/* ---- Counting before solving (csrc/host/chfsi.c): the kernel polynomial method.  GCGE_RunChFSIBand wants a block wider than the
+ * number of eigenvalues inside, ends in gaps of the spectrum and a degree; these two routines estimate all three from the Chebyshev
+ * moments of a few probe vectors, for the price of ceil(degree / 2) products with a block of m columns.
+ * GCGE_ChebMoments: moments[j * m + col] = v_col^T T_j((A - c) / e) v_col, j = 0 .. degree, for the columns v[:, v0..v0+m), with
+ * c = (lmax + lmin) / 2, e = (lmax - lmin) / 2 and [lmin, lmax] bounds of the spectrum (GCGE_LanczosBounds).  With t_k = T_k v:
+ *     mu_0 = v . v ,  mu_1 = t_1 . v ,  mu_2k = 2 t_k . t_k - mu_0 ,  mu_{2k-1} = 2 t_k . t_{k-1} - mu_1
+ * so the recurrence runs ceil(degree / 2) steps, t_k into the window [0, m) of w1, w2, w3 in turn (three different blocks of m columns
+ * or more, none of them v); v is read only.  Each step is ONE call of the back-end's cheb_step_dots (GCGE_BACKEND, gcge_ops.h: the
+ * step and both sums) where it is offered and accepts, else cheb_step (or its slot sequence) followed by two
+ * MultiVecLocalInnerProd('D').  The local sums are added over the communicator (lin_sol.c's rule), so row slabs work.  moments:
+ * (degree + 1) m doubles.  Returns 0; -1 on bad arguments (degree < 1, m < 1, lmin >= lmax, aliased blocks) with nothing written.
+ * GCGE_ChebCountFromMoments: per_probe[col] = sum_j mu_j moments[j * m + col] with mu = GCGE_ChebBandCoefficients(degree, a, b, lmin,
+ * lmax): the probe's estimate of tr p(A), p the band-pass polynomial of [a, b] — for probes with v^T v = n and independent entries of
+ * mean 0 (Rademacher +-1 columns), whose expectation of v^T p(A) v is tr p(A) = sum_i p(lambda_i), about the number of eigenvalues
+ * inside when a and b lie in gaps.  *count = the mean over the probes, *stderr_ = the sample standard deviation / sqrt(m) (0 for
+ * m == 1); per_probe: m doubles, or NULL.  No matrix: another interval is recounted from the same moments.  -1 on the coefficients'
+ * bad arguments (degree < 2 among them), m < 1 or a NULL pointer, with nothing written.                                              */
+int GCGE_ChebMoments (void *A, void **v, int v0, int m, int degree, double lmin, double lmax,
+		void **w1, void **w2, void **w3, double *moments, struct OPS_ *ops);
+int GCGE_ChebCountFromMoments (const double *moments, int m, int degree, double a, double b, double lmin, double lmax,
+		double *count, double *stderr_, double *per_probe);
+
 /* ---- PAS eigensolver (sets ops->EigenSolver; reference src/ops_eig_sol_pas.h) -------------------------------------
  * Rayleigh-Ritz on the coarsest level H = num_levels - 1, then per iteration: prolongate X one level (down to level 0),
  * smooth A X = Lambda B X by BlockAMG from that level down, make X B-orthogonal to range(P_H) and B-orthonormal, solve the
